@@ -5,6 +5,7 @@ BASELINE.json configs[2]) on a human-like synthetic reference, one process per G
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: starts N ranks by itself, see launch_ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py ... --dump-outputs DIR                 (+ what the last timed step computed, as .npy files: dump_outputs)
 
 A "step" is one pass of the whole hot path (k_prep -> k_parts/k_exact -> frontier search -> k_verify ->
 k_traceback -> k_fmocc -> k_filter, results copied back to the host)
@@ -51,6 +52,30 @@ GROUP_KERNELS = {"k_prep": ["k_prep", "k_match_words"], "k_partition": ["k_parts
                  "k_dfs": ["k_bfs_start", "k_bfs_pass", "k_bfs_finish", "k_hbfs"],
                  "k_verify": ["k_verify"], "k_verify_edit": ["k_verify_stage"], "k_traceback": ["k_traceback"],
                  "k_fmocc": ["k_fm_keys", "k_fm_unique", "k_fmocc"], "k_filter": ["k_pack_keys", "k_filter_segments", "k_filter_mark", "k_filter_write"]}
+
+
+DUMP_READS = 1 << 18         # --dump-outputs: reads of the batch whose occurrences are written (a fixed, seeded sample)
+DUMP_OCCURRENCES = 1 << 20   # ... and at most this many of their occurrences (4 fields x 8 B: 32 MB)
+
+
+def dump_outputs(path, occ, occ_offs, cnt):
+    """--dump-outputs DIR: what a caller of the timed path received from its last step (Batch.results / MoveBatch.results), as
+    float64 .npy files — integers below 2^53, exact there.  counters: every counter in ca.COUNTER_NAMES order; totals: reads,
+    occurrences; read_ids: a sample of DUMP_READS reads (np.random.default_rng(0), sorted; every read of a smaller batch);
+    occurrences_per_read: theirs; occ_<field>: their occurrences in read order, the first DUMP_OCCURRENCES of them.  < 40 MB."""
+    n_reads = occ_offs.shape[0] - 1
+    ids = np.arange(n_reads) if n_reads <= DUMP_READS else np.sort(np.random.default_rng(0).choice(n_reads, DUMP_READS, replace=False))
+    lo = occ_offs[ids].astype(np.int64)
+    per_read = occ_offs[ids + 1].astype(np.int64) - lo
+    starts = np.cumsum(per_read) - per_read
+    rows = (np.repeat(lo - starts, per_read) + np.arange(int(per_read.sum())))[:DUMP_OCCURRENCES]
+    arrays = {"counters": [cnt[kn] for kn in ca.COUNTER_NAMES], "totals": [n_reads, len(occ)], "read_ids": ids,
+              "occurrences_per_read": per_read}
+    for f in occ.dtype.names:
+        arrays["occ_" + f] = occ[f][rows]
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float64))
+    log(f"[bench] outputs of the last timed step ({len(rows)} occurrences of {len(ids)} reads, counters) written to {path}")
 
 
 def launch_ranks(n: int) -> int:
@@ -357,6 +382,8 @@ def main_rlc(args):
             kern[kname] = kern.get(kname, 0.0) + ms
     sync()
     elapsed = time.perf_counter() - tstart
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *batch.results())
     steps = max(args.steps, 1)
     per_rank_ms = [round(elapsed / steps * 1e3, 3)]
     concurrent = {kn: round(v / steps, 3) for kn, v in kern.items()}  # busy ms per step, summed over the chunk's concurrent halves
@@ -642,7 +669,14 @@ def main():
                          "node on a one-GPU box; the line's host_cpu field shows what a step costs the host")
     ap.add_argument("--no-rlc", action="store_true",
                     help="skip the bounded BASELINE configs[4] leg (`rlc`: b-move index, 250 bp, k = 6) of the default one-GPU line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (rank 0's batch: counters and the occurrences of a "
+                         "fixed, seeded sample of the reads) as DIR/<name>.npy in float64, for output-for-output comparison of two builds")
     args = ap.parse_args()
+    if args.dump_outputs:
+        if args.steps < 1:
+            ap.error("--dump-outputs needs at least one timed step (--steps >= 1)")
+        os.makedirs(args.dump_outputs, exist_ok=True)
     if args.config == "rlc":
         if "--reads" not in " ".join(sys.argv):
             args.reads = 1_000_000
@@ -726,6 +760,8 @@ def main():
     sync()
     elapsed = time.perf_counter() - tstart
     host_cpu_ms = [round((host_cpu_seconds() - cpu0) / max(args.steps, 1) * 1e3, 2)] # CPU time the host spent per step, this rank
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *batch.results())
     per_rank_ms = [round(elapsed / max(args.steps, 1) * 1e3, 3)]
     if dist is not None:
         cdev = "cpu" if dist.get_backend() == "gloo" else dev

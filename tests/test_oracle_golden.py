@@ -71,20 +71,22 @@ def test_fixture_is_what_the_reference_prints_today():
     assert res == outs
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/search_schemes"), reason="build container only")
 def test_scheme_fixtures_are_the_reference_data():
-    """tests/golden/search_schemes/ is a verbatim copy of the reference's data directory."""
-    import filecmp
-    ref = "/root/reference/search_schemes"
-    n = 0
-    for root, _d, files in os.walk(ref):
-        for fn in files:
-            a = os.path.join(root, fn)
-            b = os.path.join(GOLD, "search_schemes", os.path.relpath(a, ref))
-            assert os.path.exists(b), b
-            assert filecmp.cmp(a, b, shallow=False), b
-            n += 1
-    assert n > 150
+    """tests/golden/search_schemes/ is a verbatim copy of the reference's data directory: it holds exactly the files of
+    tests/golden/search_schemes.sha256, the checksums of that directory (`find . -type f | LC_ALL=C sort | xargs -d '\\n' sha256sum`
+    run inside it), each with its listed content."""
+    import hashlib
+    copy = os.path.join(GOLD, "search_schemes")
+    listed = {}
+    for line in open(os.path.join(GOLD, "search_schemes.sha256")).read().splitlines():
+        digest, name = line.split("  ", 1)
+        listed[os.path.normpath(name)] = digest
+    present = {os.path.relpath(os.path.join(root, fn), copy) for root, _d, files in os.walk(copy) for fn in files}
+    assert present == set(listed)
+    for name, digest in listed.items():
+        with open(os.path.join(copy, name), "rb") as f:
+            assert hashlib.sha256(f.read()).hexdigest() == digest, name
+    assert len(listed) > 150
 
 
 def test_sparse_sa_files_of_the_reference_load(tmp_path):
