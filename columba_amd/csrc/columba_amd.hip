@@ -671,6 +671,12 @@ struct cmb_batch {
 static int batchCreateOne(cmb_index* idx, const cmb_strategy* st, uint32_t max_distance, const char* seqs,
                           const uint64_t* offs, uint32_t n_reads, cmb_batch** out);
 constexpr uint32_t MAX_SUB_READS = 1u << 23; // reads per sub-batch (keys: kernels.hpp k_pack_keys, packVerifyKey)
+// bits of the group (the read, or read x strand when every strand is filtered by itself) in the filter keys of a
+// sub-batch: 24 in layouts 0 and 1, 22 in the wide layout 2 (dev_search.hpp: keyBits)
+static uint32_t groupBits(const cmb_batch* b) {
+    const uint32_t layout = b->metric == CMB_METRIC_HAMMING ? 1u : b->wideEdit ? 2u : 0u;
+    return 64u - keyBits(layout).group;
+}
 
 extern "C" int cmb_batch_create(cmb_index* idx, const cmb_strategy* st, uint32_t max_distance, const char* seqs,
                                 const uint64_t* offs, uint32_t n_reads, cmb_batch** out) {
@@ -683,6 +689,8 @@ extern "C" int cmb_batch_create(cmb_index* idx, const cmb_strategy* st, uint32_t
     if (getenv("CMB_SUBBATCHES")) S = (uint32_t)std::max(1, atoi(getenv("CMB_SUBBATCHES")));
     // a sub-batch holds fewer than 2^24 reads (24-bit read number of the filter key, 25 bits of read x strand in the
     // verification key): larger batches are cut into more sub-batches up front, never refused after the work is done
+    // (a sub-batch made larger than its keys hold by CMB_SUBBATCH_SPLIT is refused here, or by cmb_batch_filter_per_strand
+    // when read x strand would not fit: both before any work)
     // (22 group bits in the wide filter keys; from 11 errors on the frontier of a read can hold millions of nodes on a large reference —
     // 20 000 reads at 12 errors on 3 Gbp overflowed pools of 2^32 slots —, so those sub-batches are small and run three at a time)
     const uint32_t maxSub = st->metric != CMB_METRIC_EDIT || max_distance <= 7 ? MAX_SUB_READS : max_distance <= MX_MAX_ED ? (1u << 20) : (1u << 11);
@@ -772,6 +780,8 @@ static int batchCreateOne(cmb_index* idx, const cmb_strategy* st, uint32_t max_d
                 return fail(CMB_ERR_INVALID, e.what());
             }
         }
+        if ((uint64_t)n_reads >= (1ull << groupBits(b.get()))) // (wide keys: 22 group bits)
+            return fail(CMB_ERR_UNSUPPORTED, "more than 2^" + std::to_string(groupBits(b.get())) + " reads in one sub-batch at this distance");
         uint32_t maxLen = 1, minLen = ~0u;
         for (uint32_t i = 0; i < n_reads; i++) {
             if (offs[i + 1] < offs[i]) return fail(CMB_ERR_INVALID, "read offsets must be non-decreasing");
@@ -1423,8 +1433,9 @@ static int batchRunOne(cmb_batch* b) {
                 // one read seeding the same alignment) are performed once: k_verify only locates and emits a key per
                 // candidate, the keys are sorted and run-length encoded, k_verify_edit verifies the distinct ones and
                 // scales the counters by the multiplicities.
-                // (25 key bits for read x strand; 21 in the key layout of batches at 8 ... 13 errors, whose sub-batches hold at most 2^20 reads)
-                const bool dedup = b->metric == CMB_METRIC_EDIT && b->k > 0 && 2ull * nReads < (b->wideEdit ? (1ull << 21) : (1ull << 25));
+                // (25 key bits for read x strand; 23 in the key layout of batches at 8 ... 13 errors — 64 - VKW_RS — whose sub-batches
+                // hold at most 2^20 reads: the sorted bits below end at VKW_RS + rsBits <= 64)
+                const bool dedup = b->metric == CMB_METRIC_EDIT && b->k > 0 && 2ull * nReads < (b->wideEdit ? (1ull << (64u - VKW_RS)) : (1ull << 25));
                 if (b->wideEdit && !dedup) return fail(CMB_ERR_INTERNAL, "a sub-batch beyond 7 errors holds more reads than its verification keys number");
                 const uint32_t tbCap = (uint32_t)std::min<size_t>(b->tbq.n, 0xFFFFFFF0u);
                 const char* vGroup = "k_verify";
@@ -1680,7 +1691,8 @@ static int batchRunOne(cmb_batch* b) {
         b->cnts[1] += naiveSurvivors; // reported once more, as text occurrences of the read (indexinterface.cpp:1333, :1378)
         // groups of the filter: reads, or read x strand when every strand is filtered by itself
         const uint32_t nGroups = b->perStrand ? 2u * nReads : nReads;
-        if (nGroups >= (1u << (64u - groupShift))) return fail(CMB_ERR_UNSUPPORTED, "more filter groups in one sub-batch than the keys number");
+        // (group numbers 0 ... nGroups - 1: 2^24 groups fit the 24 bits of layouts 0 and 1 — a BEST sub-batch of 2^23 reads)
+        if (nGroups > (1u << (64u - groupShift))) return fail(CMB_ERR_UNSUPPORTED, "more filter groups in one sub-batch than the keys number");
         {
             tm.begin();
             if (b->keysA.n < nText) {
@@ -1905,6 +1917,13 @@ extern "C" int cmb_batch_results(const cmb_batch* b, cmb_occ* out, uint64_t out_
 }
 extern "C" int cmb_batch_filter_per_strand(cmb_batch* b, int on) {
     if (!b) return fail(CMB_ERR_INVALID, "null argument");
+    // the group of a key becomes read x strand: a sub-batch of more than 2^(group bits - 1) reads (only reachable
+    // through CMB_SUBBATCH_SPLIT) would overflow it in k_pack_keys after the search — refused before any work instead
+    if (on)
+        for (const cmb_batch* c : b->subs.empty() ? std::vector<const cmb_batch*>{b} : std::vector<const cmb_batch*>(b->subs.begin(), b->subs.end()))
+            if ((uint64_t)c->nReads > (1ull << (groupBits(c) - 1)))
+                return fail(CMB_ERR_UNSUPPORTED, "a sub-batch of more than 2^" + std::to_string(groupBits(c) - 1) +
+                                                     " reads cannot filter every strand by itself (read x strand does not fit the filter key)");
     b->perStrand = on != 0;
     for (cmb_batch* c : b->subs) c->perStrand = on != 0;
     b->done = false;

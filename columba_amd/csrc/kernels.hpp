@@ -850,6 +850,12 @@ __device__ __forceinline__ uint32_t forwardPass(const DevIndex& ix, const MFull&
 // are scaled by the multiplicities), so the radix sort only covers the bits from the low VK_LOW bits of the start
 // upwards — five 8-bit passes for a sub-batch of 2^22 reads instead of eight.
 constexpr uint32_t VK_LOW = 10;
+// last text position of an in-text verification window, start + m - 1 clamped to maxEnd: summed in 64 bits (at the end of a
+// text near 2^32 characters start + m passes 2^32, and a 32-bit sum wraps to an empty window)
+__host__ __device__ __forceinline__ uint32_t windowEnd(uint32_t maxEnd, uint32_t start, uint32_t m) {
+    const unsigned long long e = (unsigned long long)start + m - 1ull;
+    return e < maxEnd ? (uint32_t)e : maxEnd;
+}
 __host__ __device__ __forceinline__ unsigned long long packVerifyKey(uint32_t rs, uint32_t start, uint32_t maxED,
                                                                      uint32_t minED, uint32_t fixed) {
     return ((unsigned long long)rs << 39) | ((unsigned long long)(maxED & 7u) << 36) | ((unsigned long long)(minED & 7u) << 33) |
@@ -885,7 +891,7 @@ __device__ __forceinline__ bool verifyEdit(const DevIndex& ix, const uint64_t* o
     g.Wh = maxED;
     g.m = max(g.Wv + g.n, g.Wv + g.Wh + 1u); // (bitparallelmatrix.cpp:98-103: reads shorter than the band)
     const uint32_t maxEnd = ix.n - 1;
-    const uint32_t hEnd = limitEnd ? min(maxEnd, limitEnd) : min(maxEnd, start + g.m - 1);
+    const uint32_t hEnd = limitEnd ? min(maxEnd, limitEnd) : windowEnd(maxEnd, start, g.m);
     const uint32_t size = hEnd > start ? hEnd - start : 0;
     if (!g.inFinalColumn(size)) return false;
     uint32_t mask = 0, rows = 0;
@@ -1005,7 +1011,7 @@ k_verify(DevIndex ix, const uint64_t* __restrict__ offs, uint32_t maxLen, uint32
                 const uint32_t lengthBefore = a;
                 const uint32_t Tb = pos > lengthBefore ? pos - lengthBefore : 0;
                 const uint32_t Te = Tb + len;
-                if (Te <= ix.n) {
+                if ((unsigned long long)Tb + len <= ix.n) { // (64 bits: Tb + len can pass 2^32 at the end of the text)
                     uint32_t score = 0;
                     for (uint32_t j = 0; j < len; j += 16) { // 16 characters per step
                         const uint32_t nC = min(16u, len - j);
@@ -1183,7 +1189,7 @@ k_wide_filter(DevIndex ix, const uint64_t* __restrict__ offs, const uint32_t* __
                             start = verifyKeyStart(key);
                             len = (uint32_t)(offs[(rs >> 1) + 1] - offs[rs >> 1]);
                             g = wideGeom(len, maxED, nZeros);
-                            const uint32_t maxEnd = ix.n - 1, hEnd = min(maxEnd, start + g.m - 1);
+                            const uint32_t maxEnd = ix.n - 1, hEnd = windowEnd(maxEnd, start, g.m);
                             size = hEnd > start ? hEnd - start : 0;
                             if (!g.inFinalColumn(size)) { // (indexhelpers.cpp:527): started, nothing computed
                                 cStarted += mult;
@@ -1316,7 +1322,7 @@ k_verify_wide(DevIndex ix, const uint64_t* __restrict__ offs, uint32_t maxLen, c
         if (active) {
             cStarted += mult;
             const uint32_t maxEnd = ix.n - 1;
-            const uint32_t hEnd = limitEnd ? min(maxEnd, limitEnd) : min(maxEnd, start + g.m - 1); // (limitEnd: inTextVerificationOneString)
+            const uint32_t hEnd = limitEnd ? min(maxEnd, limitEnd) : windowEnd(maxEnd, start, g.m); // (limitEnd: inTextVerificationOneString)
             const uint32_t size = hEnd > start ? hEnd - start : 0;
             if (!g.inFinalColumn(size)) { // (indexhelpers.cpp:527)
                 active = false;
@@ -1487,7 +1493,7 @@ k_verify_stage(DevIndex ix, const uint64_t* __restrict__ offs, MFull mf,
         uint32_t size = 0;
         if (key != ~0ull) {
             const uint32_t maxEnd = ix.n - 1;
-            const uint32_t hEnd = min(maxEnd, start + g.m - 1);
+            const uint32_t hEnd = windowEnd(maxEnd, start, g.m);
             size = hEnd > start ? hEnd - start : 0;
             alive = g.inFinalColumn(size); // indexhelpers.cpp:527 (candidates that cannot reach it do nothing)
             if (FIRST && alive) {

@@ -109,6 +109,13 @@ def _sort_big(key: torch.Tensor):
     return k2, i2
 
 
+def doubling_key_fits(n: int) -> bool:
+    """whether every doubling key of `suffix_array` on n symbols fits an int64: ranks are 1 ... n, the rank h
+    positions further on 0 ... n (0 = beyond the end), so the keys run from (1 - n/2)(n+1) to (n - n/2)(n+1) + n"""
+    half = n // 2
+    return -(2 ** 63) <= (1 - half) * (n + 1) and (n - half) * (n + 1) + n < 2 ** 63
+
+
 def suffix_array(codes: torch.Tensor) -> torch.Tensor:
     """SA of the sequence ``codes`` (uint8, values 0..4), where a suffix that is a proper prefix of
     another sorts first (end-of-string smallest).  Prefix doubling with radix sorts (torch.sort).
@@ -121,7 +128,7 @@ def suffix_array(codes: torch.Tensor) -> torch.Tensor:
         return torch.zeros(0, dtype=torch.int64, device=dev)
     # doubling key = (rank[i] - n/2) * (n+1) + rank[i+h]: centred so that texts up to 2^32 fit an int64
     half = n // 2
-    assert (half + 2) * (n + 2) < 2 ** 63, "text too long for single-key prefix doubling"
+    assert doubling_key_fits(n), "text too long for single-key prefix doubling"
     rdt = torch.int32 if n < 2 ** 31 - 2 else torch.int64
     h = 20  # initial key: first 20 symbols, 3 bits each (values 1..5, 0 = beyond the end)
     cp = torch.zeros(n + h, dtype=torch.uint8, device=dev)
@@ -177,7 +184,9 @@ def _popcount_words(bits: torch.Tensor) -> torch.Tensor:
 
 def _rank_counts(pc: torch.Tensor, nblk: int, n_words: int):
     """L1 (absolute) and packed L2 (seven 9-bit partial sums) per 8-word block."""
-    within = torch.cumsum(pc.reshape(nblk, 8), dim=1)
+    # (chunked: a cumsum along the rows of 2^23 or more blocks — texts near 2^32 — fails to launch on the GPU)
+    pcb = pc.reshape(nblk, 8)
+    within = torch.cat([torch.cumsum(pcb[o:o + _CHUNK // 64], dim=1) for o in range(0, nblk, _CHUNK // 64)])
     blocktot = within[:, 7]
     l1 = torch.cumsum(blocktot, 0) - blocktot
     l2 = torch.zeros(nblk, dtype=torch.int64, device=pc.device)

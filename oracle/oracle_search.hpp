@@ -825,7 +825,8 @@ template <class IX> class MatcherT {
         counters.inc(IN_TEXT_STARTED, startPos.size());
         for (len_t start : startPos) {
             len_t maxEnd = index.textLength - 1;
-            len_t hEnd = std::min(maxEnd, start + nRows - 1);
+            // (64 bits: start + nRows passes 2^32 at the end of a text near 2^32 characters, and a 32-bit sum wraps to an empty window)
+            len_t hEnd = (len_t)std::min<uint64_t>(maxEnd, (uint64_t)start + nRows - 1);
             Substring ref((const char*)index.text, index.textLength, start, hEnd);
             len_t refBegin = ref.begin();
             len_t i;
@@ -1110,7 +1111,7 @@ template <class IX> class MatcherT {
             counters.inc(IN_TEXT_STARTED);
             Tb = (Tb > lengthBefore) ? Tb - lengthBefore : 0;
             len_t Te = Tb + pSize;
-            if (Te > index.textLength) continue;
+            if ((uint64_t)Tb + pSize > index.textLength) continue; // (64 bits, as above)
             len_t score = 0;
             for (len_t j = 0; j < pSize; j++) {
                 counters.inc(TEXT_BYTES);
