@@ -903,8 +903,8 @@ def plcp_runs(plcp: np.ndarray):
 
 
 class MoveIndex:
-    """Device-resident b-move index (cmb_move_index) over the arrays of columba_amd.movebuild.build_move, or any object
-    with the same members read from the reference's files."""
+    """Device-resident b-move index (cmb_move_index) over the arrays of columba_amd.movebuild.build_move (a MoveArrays,
+    whatever fills it)."""
 
     def __init__(self, mv, device: int = 0, with_locate: bool = True, length_bits: int = 64, _handle=None):
         L = lib()
@@ -922,7 +922,7 @@ class MoveIndex:
         d.length_bits = length_bits
         d.samples_first, d.samples_last, d.rev_samples_first, d.rev_samples_last = (a.ctypes.data for a in keep[2:6])
         if with_locate:
-            pos, sm = plcp_runs(mv.plcp)
+            pos, sm = mv.plcp_run_form()
             loc = [np.ascontiguousarray(a, dtype=np.uint64) for a in (mv.pred_first, mv.first_to_run, mv.pred_last, mv.last_to_run, pos, sm)]
             keep += loc
             d.pred_first, d.first_to_run, d.pred_last, d.last_to_run, d.plcp_pos, d.plcp_sum = (a.ctypes.data for a in loc)

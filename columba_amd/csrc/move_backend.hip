@@ -28,6 +28,14 @@ using namespace cmb;
         if (_e != hipSuccess) throw std::runtime_error(std::string(#expr) + ": " + hipGetErrorString(_e)); \
     } while (0)
 
+// hipcub takes its element counts as int: a count of 2^31 or more is refused here instead of being truncated by the cast
+#define MV_CUB_COUNT(n, what)                                                                                                  \
+    do {                                                                                                                       \
+        if ((uint64_t)(n) >= (1ull << 31))                                                                                     \
+            return failWith(CMB_ERR_UNSUPPORTED, std::string(what) + ": " + std::to_string((uint64_t)(n)) + " elements, hipcub " \
+                                                                  "takes 2^31 - 1 at most");                                   \
+    } while (0)
+
 namespace {
 
 // a growing host array in PAGE-LOCKED memory (the occurrence records of a batch: 10^6 reads of BASELINE configs[4] leave 1.15 GB — into
@@ -477,6 +485,7 @@ extern "C" int cmb_move_match_exact(const cmb_move_index* idx, const char* reads
         MV_HIPCHK(hipEventRecord(ev[1], 0));
         // offsets of the tasks' occurrences: exclusive prefix sum over nTasks + 1 widths (the last one is zero)
         size_t tmpBytes = 0;
+        MV_CUB_COUNT(nTasks + 1, "exact-match tasks"); // (below 2^31: 2^30 reads per call at most)
         MV_HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmpBytes, dWidth.p, dTaskOff.p, (int)(nTasks + 1)));
         MvBuf<uint8_t> tmp;
         tmp.alloc(tmpBytes);
@@ -977,7 +986,8 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
             uint64_t nOcc = 0, c2[2] = {0, 0};
             std::vector<cmb_move_occ> tmp((size_t)nReads * 8 + 1024);
             int rc = cmb_move_match_exact(ix, (const char*)b->hostReads.data(), b->hostOffs.data(), nReads, tmp.data(), tmp.size(), b->occOffs.data(), &nOcc, c2);
-            if (rc == CMB_ERR_OVERFLOW) {
+            if (rc == CMB_ERR_OVERFLOW) { // (nOcc: the number needed; nothing of that size has been allocated yet)
+                if (nOcc >= (1ull << 31)) return failWith(CMB_ERR_UNSUPPORTED, "2^31 and more text positions in one b-move batch");
                 tmp.resize(nOcc);
                 rc = cmb_move_match_exact(ix, (const char*)b->hostReads.data(), b->hostOffs.data(), nReads, tmp.data(), tmp.size(), b->occOffs.data(), &nOcc, c2);
             }
@@ -1315,6 +1325,7 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
             }
             hipLaunchKernelGGL(k_mvs_fm_keys, dim3(gridFor(nFm)), dim3(256), 0, s, b->fm.p, nFm, b->keysA.p, b->fmIdxA.p);
             size_t tb = 0;
+            MV_CUB_COUNT((uint64_t)nFm + 1, "in-index occurrences of one slice"); // (2^31 records of 96 bytes would not fit the HBM)
             MV_HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, b->keysA.p, b->keysB.p, b->fmIdxA.p, b->fmIdxB.p, (int)nFm, 0, 64, s));
             if (b->sortTmp.n < tb) b->sortTmp.alloc(tb + tb / 4);
             MV_HIPCHK(hipcub::DeviceRadixSort::SortPairs(b->sortTmp.p, tb, b->keysA.p, b->keysB.p, b->fmIdxA.p, b->fmIdxB.p, (int)nFm, 0, 64, s));
@@ -1335,6 +1346,7 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                                    b->locMeta.p, b->locWidths.p);
                 MV_HIPCHK(hipMemsetAsync(b->locWidths.p + nUniq, 0, sizeof(uint64_t), s));
                 tb = 0;
+                MV_CUB_COUNT((uint64_t)nUniq + 1, "distinct in-index occurrences of one slice"); // (nUniq <= nFm)
                 MV_HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, b->locWidths.p, b->locOff.p, (int)(nUniq + 1), s));
                 if (b->sortTmp.n < tb) b->sortTmp.alloc(tb + tb / 4);
                 MV_HIPCHK(hipcub::DeviceScan::ExclusiveSum(b->sortTmp.p, tb, b->locWidths.p, b->locOff.p, (int)(nUniq + 1), s));
@@ -1361,7 +1373,10 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
         uint64_t nOut = 0, nNaiveKept = 0;
         const uint32_t window = b->metric == CMB_METRIC_EDIT ? b->k : 0u;
         const uint32_t uniqueOnly = b->metric == CMB_METRIC_EDIT ? 0u : 1u; // (getTextOccHamming, indexinterface.cpp:1331-1371: no redundancy filter)
-        auto sortAndFilter = [&](uint64_t nKeys, uint32_t nGroups, MvBuf<MoveOccOut>& dst, uint64_t& kept) {
+        auto sortAndFilter = [&](uint64_t nKeys, uint32_t nGroups, MvBuf<MoveOccOut>& dst, uint64_t& kept) -> int {
+            // (nKeys < 2^31: the refusals of 2^31 text positions per slice; nGroups <= 2^24: 2^23 reads per batch)
+            MV_CUB_COUNT(nKeys, "text occurrences of one slice");
+            MV_CUB_COUNT((uint64_t)nGroups + 1, "filter groups of one slice");
             size_t tb = 0;
             MV_HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, b->keysA.p, b->keysB.p, b->vals.p, b->valsB.p, (int)nKeys, 0, 64, s));
             if (b->sortTmp.n < tb) b->sortTmp.alloc(tb + tb / 4);
@@ -1379,12 +1394,13 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
             if (kept)
                 hipLaunchKernelGGL(k_mvs_filter<true>, dim3(gridFor(nGroups)), dim3(256), 0, s, b->keysB.p, b->valsB.p, nKeys, nGroups, window, b->readCnt.p,
                                    b->readOff.p, dst.p, uniqueOnly);
+            return CMB_OK;
         };
         if (totalPos) {
             if (hasNaive) { // the naive path's own filter pass, per read x strand (indexinterface.cpp:1137, :1205)
                 hipLaunchKernelGGL(k_mvs_text_keys, dim3(gridFor(totalPos)), dim3(256), 0, s, b->positions.p, b->locOff.p, nUniq, totalPos, b->locMeta.p,
                                    b->keysA.p, b->vals.p, b->bad.p, (const uint8_t*)b->psel.p, 1);
-                sortAndFilter(totalPos, 2 * nReads, b->naiveOut, nNaiveKept);
+                if (const int rc = sortAndFilter(totalPos, 2 * nReads, b->naiveOut, nNaiveKept); rc != CMB_OK) return rc;
                 if (b->naiveOff.n < (size_t)2 * nReads + 1) b->naiveOff.alloc((size_t)2 * nReads + 1);
                 MV_HIPCHK(hipMemcpyAsync(b->naiveOff.p, b->readOff.p, ((size_t)2 * nReads + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
                 const uint64_t need = totalPos + nNaiveKept;
@@ -1403,7 +1419,7 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
             // (the previous slice's records may still be on their way out of b->out: this stream waits for them before the buffer is
             // written or enlarged — sortAndFilter synchronises the stream before it allocates)
             if (b->copyPending) MV_HIPCHK(hipStreamWaitEvent(s, b->copyDone, 0));
-            sortAndFilter(totalPos + nNaiveKept, perStrand ? 2 * nReads : nReads, b->out, nOut);
+            if (const int rc = sortAndFilter(totalPos + nNaiveKept, perStrand ? 2 * nReads : nReads, b->out, nOut); rc != CMB_OK) return rc;
             if (perStrand) { // per read again: the two strands of a read are neighbouring groups
                 if (b->rsOff.n < (size_t)2 * nReads + 1) b->rsOff.alloc((size_t)2 * nReads + 1);
                 MV_HIPCHK(hipMemcpyAsync(b->rsOff.p, b->readOff.p, ((size_t)2 * nReads + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
