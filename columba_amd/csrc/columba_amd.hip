@@ -93,6 +93,7 @@ struct cmb_index {
     DevIndex d{};
     DevBuf<uint4> blkF, blkR; // 32-byte rank blocks
     DevBuf<uint32_t> saSamples;
+    DevBuf<uint32_t> saDense; // derived at creation / validation (buildDenseSA), not replicated; empty: the sparse walk
     DevBuf<uint8_t> text;
     DevBuf<uint32_t> text2;
     DevBuf<uint4> kmer;
@@ -156,11 +157,47 @@ static int probeIndex(cmb_index* ix) {
                                          " LF steps (wrong sparseness, or bit vectors / samples / BWT of different texts)");
     return CMB_OK;
 }
+// The dense suffix array (DevIndex::saDense): every locate becomes one 4-byte load instead of the sparse walk's ~(s + 3) / 2 rank
+// blocks and a sample.  It is a speed-up, so it must not take the memory read batches need: it is built only if at least
+// min(128 GiB, half the device) stays free after it — a batch of the headline's 10^7 reads holds ~10 KB per read (~93 GiB), and two
+// ranks sharing one device hold half as many reads each (CMB_TEST_SA_MIN_FREE_GB overrides the 128 GiB for tests).  CMB_SA_SPARSE=1
+// keeps the walk.  An index whose walks do not all take SA[row] % sparseness steps (the LF counter of locateRow relies on it) keeps
+// the walk too.  The index's DevIndex must be bound to its arrays; ix->bytes follows the array.
+static void buildDenseSA(cmb_index* ix) {
+    ix->bytes -= ix->saDense.bytes();
+    ix->saDense.release();
+    ix->d.saDense = nullptr;
+    const uint64_t n = ix->d.n;
+    if (getenv("CMB_SA_SPARSE") || n == 0 || ix->saSparseness == 0 || !ix->saSamples.p || !ix->d.fwd.blk) return;
+    size_t freeB = 0, totalB = 0;
+    HIPCHK(hipMemGetInfo(&freeB, &totalB));
+    uint64_t minFree = std::min<uint64_t>(128ull << 30, totalB / 2);
+    if (const char* e = getenv("CMB_TEST_SA_MIN_FREE_GB")) minFree = (uint64_t)(atof(e) * (double)(1ull << 30));
+    if (freeB < n * sizeof(uint32_t) || freeB - n * sizeof(uint32_t) < minFree) return;
+    ix->saDense.alloc(n);
+    DevBuf<uint32_t> bad;
+    bad.alloc(1);
+    HIPCHK(hipMemset(bad.p, 0, sizeof(uint32_t)));
+    const uint32_t nSamples = (uint32_t)std::min<size_t>(ix->saSamples.n, 0xFFFFFFFFu);
+    hipLaunchKernelGGL(k_dense_sa, dim3((unsigned)std::min<uint64_t>((n + 255) / 256, 1u << 16)), dim3(256), 0, 0, ix->d, nSamples,
+                       ix->saDense.p, bad.p);
+    HIPCHK(hipGetLastError());
+    uint32_t hb = 0;
+    HIPCHK(hipMemcpy(&hb, bad.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (hb) {
+        ix->saDense.release();
+        return;
+    }
+    ix->d.saDense = ix->saDense.p;
+    ix->bytes += ix->saDense.bytes();
+}
 extern "C" int cmb_index_validate(cmb_index* idx) {
     if (!idx) return fail(CMB_ERR_INVALID, "null argument");
     try {
         useDevice(idx->device);
-        return probeIndex(idx);
+        if (int rc = probeIndex(idx)) return rc;
+        buildDenseSA(idx); // (each replica derives its own: the array is not one of the broadcast ones)
+        return CMB_OK;
     } catch (const std::exception& e) {
         return fail(CMB_ERR_DEVICE, e.what());
     }
@@ -238,6 +275,7 @@ extern "C" int cmb_index_create(const cmb_index_desc* desc, int device, cmb_inde
         d.fwd = DevBWT{ix->blkF.p, (uint32_t)desc->dollar_pos_fwd};
         d.rev = DevBWT{ix->blkR.p, (uint32_t)desc->dollar_pos_rev};
         d.saSamples = ix->saSamples.p;
+        d.saSparseness = ix->saSparseness;
         d.text = ix->text.p;
         d.text2 = packedOk ? ix->text2.p : nullptr;
         d.kmer = ix->kmer.p;
@@ -249,6 +287,7 @@ extern "C" int cmb_index_create(const cmb_index_desc* desc, int device, cmb_inde
         HIPCHK(hipDeviceSynchronize());
         if (int rc = probeIndex(ix.get())) return rc; // the arrays must belong together, or findSA would never end
         ix->bytes = ix->blkF.bytes() + ix->blkR.bytes() + ix->saSamples.bytes() + ix->text.bytes() + ix->text2.bytes() + ix->kmer.bytes();
+        buildDenseSA(ix.get());
         ix->uploadSeqStarts();
         *out = ix.release();
         return CMB_OK;
@@ -277,6 +316,8 @@ inline void bindDevIndex(cmb_index* ix) { // DevIndex pointers from the owning b
     d.fwd.blk = ix->blkF.p;
     d.rev.blk = ix->blkR.p;
     d.saSamples = ix->saSamples.p;
+    d.saDense = ix->saDense.n ? ix->saDense.p : nullptr;
+    d.saSparseness = ix->saSparseness;
     d.text = ix->text.p;
     d.text2 = ix->text2.n ? ix->text2.p : nullptr;
     d.kmer = ix->kmer.p;

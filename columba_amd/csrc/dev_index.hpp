@@ -42,6 +42,8 @@ struct DevIndex {
     uint32_t counts[5];
     DevBWT fwd, rev;
     const uint32_t* saSamples;
+    const uint32_t* saDense; // the whole suffix array, one word per row (nullptr: locate by the sparse walk, findSA)
+    uint32_t saSparseness;
     const uint8_t* text;
     const uint32_t* text2; // 2 bits per character, 16 per word (nullptr if the text holds non-ACGT characters before '$')
     const uint4* kmer; // 4^kmerSize entries {sa.b, sa.e, rev.b, rev.e}
@@ -276,17 +278,35 @@ __device__ __forceinline__ uint32_t findLF(const DevIndex& ix, uint32_t k) {
 }
 
 // findSA (fmindex.cpp:53-60); *lf accumulates the number of LF steps.  One 32-byte sector per visited row.
-__device__ __forceinline__ uint32_t findSA(const DevIndex& ix, uint32_t row, uint32_t* lf) {
+// CHECKED (k_dense_sa walks EVERY row of an index whose arrays only passed the probe): a walk longer than the sparseness, a row
+// past the text or a sample index past the nSamples samples returns 0xFFFFFFFF instead of looping on or reading past an array.
+template <bool CHECKED = false>
+__device__ __forceinline__ uint32_t findSA(const DevIndex& ix, uint32_t row, uint32_t* lf, uint32_t nSamples = 0) {
     uint32_t l = 0;
     RankChunks ch;
     loadRankChunks(ix.fwd, row, ch);
     while (!rowSampled(ch)) {
+        if (CHECKED && l == ix.saSparseness) return 0xFFFFFFFFu;
         row = lfFromChunks(ix, ch, row);
+        if (CHECKED && row >= ix.n) return 0xFFFFFFFFu;
         loadRankChunks(ix.fwd, row, ch);
         l++;
     }
+    if (CHECKED && sampleIndex(ch) >= nSamples) return 0xFFFFFFFFu;
     if (lf) *lf += l;
     return ix.saSamples[sampleIndex(ch)] + l;
+}
+
+// SA[row] for every locate of the search: one word of the dense suffix array where the index holds it (cmb_index_create), else the
+// walk.  *lf gets the steps the walk takes, SA[row] % sparseness (the sampling rule, suffixArray.h:163, checked for every row when the
+// dense array was built), so the LF counter does not depend on the layout.
+__device__ __forceinline__ uint32_t locateRow(const DevIndex& ix, uint32_t row, uint32_t* lf) {
+    if (ix.saDense) {
+        const uint32_t p = ix.saDense[row];
+        if (lf) *lf += p & (ix.saSparseness - 1u);
+        return p;
+    }
+    return findSA(ix, row, lf);
 }
 
 } // namespace cmb

@@ -102,8 +102,23 @@ __global__ void k_locate(DevIndex ix, const uint32_t* __restrict__ rows, uint64_
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     uint32_t lf = 0;
-    out[i] = findSA(ix, rows[i], &lf);
+    out[i] = locateRow(ix, rows[i], &lf);
     if (lf) atomicAdd(lfTotal, (unsigned long long)lf);
+}
+
+// The dense suffix array (DevIndex::saDense) from the sparse one: findSA on every row, so the array holds exactly what the walk
+// returns.  Every row's walk must take SA[row] % sparseness steps (the sampling rule, suffixArray.h:163) — what locateRow adds to the
+// LF counter instead of walking; `bad` counts the rows that break it (the index then stays on the walk).  ix.saDense must be null.
+__global__ void __launch_bounds__(256) k_dense_sa(DevIndex ix, uint32_t nSamples, uint32_t* __restrict__ sa, uint32_t* __restrict__ bad) {
+    uint32_t nBad = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; row < ix.n; row += stride) {
+        uint32_t l = 0;
+        const uint32_t p = findSA<true>(ix, (uint32_t)row, &l, nSamples);
+        sa[row] = p;
+        nBad += (p >= ix.n || l != (p & (ix.saSparseness - 1u))) ? 1u : 0u;
+    }
+    if (nBad) atomicAdd(bad, nBad);
 }
 
 // Consistency probe at index creation: findSA terminates because every LF walk reaches a sampled row within
@@ -934,9 +949,10 @@ __device__ __forceinline__ uint32_t mismatch16(const uint4& t, const uint4& r, u
 }
 
 // KEYS: edit-distance candidates only get their verification key (the batch path; the matrix runs in
-// k_verify_stage) — that instance carries no matrix code and keeps twice the wavefronts in flight for the locate.
+// k_verify_stage) — that instance carries no matrix code and keeps twice the wavefronts in flight for the locate (8 per SIMD: stated, as
+// hipcc's scalar registers alone would otherwise cost it one).
 template <bool KEYS>
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(256, KEYS ? 8 : 1)
 k_verify(DevIndex ix, const uint64_t* __restrict__ offs, uint32_t maxLen, uint32_t gw,
          const uint8_t* __restrict__ seq, MFull mf, const uint4* __restrict__ items,
          uint32_t nItems, uint4* __restrict__ tbq, uint32_t tbCap, unsigned long long* __restrict__ vkeys, Queues q,
@@ -973,7 +989,7 @@ k_verify(DevIndex ix, const uint64_t* __restrict__ offs, uint32_t maxLen, uint32
                 pos = row;
             } else {
                 cLoc++;
-                pos = findSA(ix, row, &cLF);
+                pos = locateRow(ix, row, &cLF);
             }
             if (kind == ITEM_EXACT) { // verifyInTextExact (indexinterface.cpp:918-943)
                 if (fixed) {
@@ -1294,7 +1310,7 @@ k_verify_wide(DevIndex ix, const uint64_t* __restrict__ offs, uint32_t maxLen, c
                 uint32_t pos = item.y;
                 if (!direct) {
                     cLoc++;
-                    pos = findSA(ix, item.y, &cLF);
+                    pos = locateRow(ix, item.y, &cLF);
                 }
                 const uint32_t startDiff = direct ? 0u : item.z;
                 limitEnd = direct ? item.z : 0u;
@@ -1885,6 +1901,22 @@ k_fmocc(DevIndex ix, const FMOccRec* __restrict__ recs, uint32_t n, Queues q) {
         const uint32_t o = waveAppend(&q.cnt[2], w, total);
         if (o + w > q.textCap) {
             if (w) flags |= FLAG_TEXT_OVERFLOW;
+            continue;
+        }
+        if (ix.saDense) { // the rows of a range are consecutive words: four loads in flight before their records are written
+            for (uint32_t t = 0; t < w; t += 4) {
+                uint32_t sa[4];
+#pragma unroll
+                for (uint32_t j = 0; j < 4; j++) sa[j] = t + j < w ? ix.saDense[f.b + t + j] : 0u;
+#pragma unroll
+                for (uint32_t j = 0; j < 4; j++) {
+                    if (t + j >= w) break;
+                    cLF += sa[j] & (ix.saSparseness - 1u); // (locateRow)
+                    const uint32_t p = sa[j] + f.shift;
+                    q.text[o + t + j] = TextOccRec{f.rsId, p, p + f.depth, f.dist};
+                }
+            }
+            cLoc += w;
             continue;
         }
         for (uint32_t t = 0; t < w; t++) {

@@ -70,6 +70,9 @@ typedef struct {
     uint32_t in_text_switch;      /* in-text verification switch point (default 4, alignparameters.h:90) */
 } cmb_index_desc;
 
+/* Besides the arrays of desc, the index derives a dense suffix array on the device (4 bytes per text character, counted in
+ * cmb_index_device_bytes) when min(128 GiB, half the device) stays free after it; locates are then single loads.  CMB_SA_SPARSE=1
+ * in the environment keeps the sparse walk. */
 int cmb_index_create(const cmb_index_desc* desc, int device, cmb_index** out);
 void cmb_index_destroy(cmb_index* idx);
 /* bytes of HBM held by the index */
@@ -98,7 +101,9 @@ int cmb_index_create_empty(const cmb_index_layout* layout, const uint32_t* seq_s
 int cmb_index_create_text_only(const char* text, uint64_t n, const uint32_t* seq_starts, uint32_t n_seqs, int device, cmb_index** out);
 int cmb_index_device_arrays(cmb_index* idx, void** ptrs /* [CMB_DEV_ARRAYS] */, uint64_t* bytes /* [CMB_DEV_ARRAYS] */);
 /* after the arrays of an empty twin have been filled: the consistency probe cmb_index_create runs (every probed row of the
- * suffix array reaches a sampled row within sa_sparseness LF steps, FMIndex::findSA, src/fmindex/fmindex.cpp:53-60) */
+ * suffix array reaches a sampled row within sa_sparseness LF steps, FMIndex::findSA, src/fmindex/fmindex.cpp:53-60); then the
+ * replica derives its own dense suffix array under cmb_index_create's rule (it is not one of the CMB_DEV_ARRAYS; an index that
+ * was not validated locates by the sparse walk) */
 int cmb_index_validate(cmb_index* idx);
 /* copy the device k-mer table (4^kmer_size x {sa.b,sa.e,rev.b,rev.e}) to host: test hook for
  * IndexInterface::populateTable (indexinterface.cpp:294-335) */
