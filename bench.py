@@ -6,6 +6,7 @@ BASELINE.json configs[2]) on a human-like synthetic reference, one process per G
     python bench.py --gpus N --steps K --warmup W          (N > 1: starts N ranks by itself, see launch_ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py ... --dump-outputs DIR                 (+ what the last timed step computed, as .npy files: dump_outputs)
+    python bench.py ... --full                             (+ everything beyond the headline figure, see below)
 
 A "step" is one pass of the whole hot path (k_prep -> k_parts/k_exact -> frontier search -> k_verify ->
 k_traceback -> k_fmocc -> k_filter, results copied back to the host)
@@ -14,6 +15,12 @@ rank matches `--reads` reads against a full replica of the index; no collective 
 (rank 0 builds the index and broadcasts its DEVICE layout over RCCL, read shards are scattered once, both
 before the timed region; after it the occurrence lists are gathered on rank 0 and the counters all-reduced,
 timed apart as `result_gather_ms`).  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline figure needs: it sets up (reference, index, reads), warms up, times the steps, writes
+--dump-outputs and prints the line.  `--full` adds what takes runs or work of its own after the timed region: the kernel table of
+extra steps with serial sub-batches and the `roofline` built on it, the oracle's `cpu_baseline` and its comparison with the GPU's
+occurrences, the `streaming` and `rlc` legs, and for N > 1 ranks the result gather (`result_gather_ms`).  Without it those fields are
+null.  `--config rlc` splits the same way (kernel table, `roofline`, `cpu_baseline`).
 """
 from __future__ import annotations
 
@@ -76,6 +83,97 @@ def dump_outputs(path, occ, occ_offs, cnt):
     for name, a in arrays.items():
         np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float64))
     log(f"[bench] outputs of the last timed step ({len(rows)} occurrences of {len(ids)} reads, counters) written to {path}")
+
+
+def _nonzero(mask):
+    """torch.nonzero of a 1-D mask of any length (one call is limited to INT_MAX elements)"""
+    c = 1 << 29
+    return torch.cat([torch.nonzero(mask[o:o + c]).flatten() + o for o in range(0, int(mask.numel()), c)])
+
+
+def suffix_array(codes):
+    """indexbuild.suffix_array (the same first 20-symbol sort, the same centred doubling keys), but every doubling round re-sorts
+    only the suffixes whose group is not settled yet (Larsson-Sadakane), where indexbuild sorts all n again each time: 6.5 instead
+    of 22 s for both suffix arrays and the rest of the 3 Gbp index on one MI355X.  Ranks are group heads: 1 + the SA slot of the first
+    suffix of the group.  The suffix array is unique, so the arrays built on it are those of indexbuild.build_index."""
+    dev = codes.device
+    n = int(codes.numel())
+    half = n // 2
+    assert n > 0 and ib.doubling_key_fits(n), "text too long for single-key prefix doubling"
+    h = 20
+    cp = torch.zeros(n + h, dtype=torch.uint8, device=dev)
+    cp[:n] = codes.to(torch.uint8) + 1
+    key = torch.zeros(n, dtype=torch.int64, device=dev)
+    for j in range(h):
+        key <<= 3
+        key |= cp[j:j + n]
+    del cp
+    skey, sa = ib._sort_big(key)
+    del key
+    rank = torch.zeros(n + 1, dtype=torch.int64, device=dev)  # rank[n] = 0: beyond the end
+    slots, pos = None, sa  # (the first round covers every slot)
+    while True:
+        # groups of the sorted keys: rank = 1 + slot of the group's head; a group of one is settled
+        first = torch.ones(skey.numel() + 1, dtype=torch.bool, device=dev)
+        first[1:-1] = skey[1:] != skey[:-1]
+        del skey
+        heads = _nonzero(first[:-1])
+        if slots is not None:
+            heads = slots[heads]
+        heads += 1
+        gid = torch.cumsum(first[:-1], 0)
+        gid -= 1
+        rank[pos] = heads[gid]
+        del heads, gid
+        open_ = _nonzero(~(first[:-1] & first[1:]))
+        del first
+        slots = open_ if slots is None else slots[open_]
+        del open_
+        if slots.numel() == 0:
+            return sa
+        # next round: the open suffixes by (own group, group of the suffix h further on); groups stay on their slots
+        pos = sa[slots]
+        key = (rank[pos] - half) * (n + 1) + rank[torch.clamp(pos + h, max=n)]
+        skey, perm = ib._sort_big(key)
+        del key
+        pos = pos[perm]
+        del perm
+        sa[slots] = pos
+        h *= 2
+
+
+def build_fm_index(text, seq_starts, sparseness, device, with_bwt):
+    """indexbuild.build_index of the bench's reference (an ACGT tensor on the device) with the suffix arrays of suffix_array above:
+    every array is built by the same indexbuild steps, so the index is the same (tests/test_bench_index.py compares the two)"""
+    dev = torch.device(device)
+    tt = torch.cat([text.to(dev), torch.tensor([ord("$")], dtype=torch.uint8, device=dev)])
+    n = int(tt.numel())
+    lut = torch.from_numpy(ib.CODE).to(dev)
+    tc = torch.cat([lut[tt[o:o + (1 << 28)].long()] for o in range(0, n, 1 << 28)])
+    if bool((tc[:-1] == 0).any()) or bool((tc == 255).any()):
+        raise ValueError("text must consist of A,C,G,T")
+    sa = suffix_array(tc)
+    prev = sa - 1
+    prev = torch.where(prev < 0, n - 1, prev)
+    bwt = tc[prev]
+    del prev
+    bv_fwd, cnt_fwd, dpos_f = ib.build_bitvec_intl(bwt)
+    sa_bv, sa_cnt, samples = ib.build_sparse_sa(sa, sparseness)
+    del sa
+    bwt_words = ib.encode_bwt(bwt) if with_bwt else np.zeros(1, np.uint64)
+    del bwt
+    rsa = suffix_array(torch.flip(tc, dims=[0]))
+    idx = torch.where(rsa == 0, 0, n - rsa)
+    del rsa
+    bv_rev, cnt_rev, dpos_r = ib.build_bitvec_intl(tc[idx])
+    del idx
+    cc = sum(torch.bincount(tc[o:o + (1 << 28)].long(), minlength=5) for o in range(0, n, 1 << 28)).cpu().numpy().astype(np.uint64)
+    counts = np.zeros(5, dtype=np.uint64)
+    counts[1:] = np.cumsum(cc)[:-1]
+    return ib.IndexArrays(text=tt.cpu().numpy(), counts=counts, dollar_pos_fwd=dpos_f, bv_fwd=bv_fwd, cnt_fwd=cnt_fwd,
+                          dollar_pos_rev=dpos_r, bv_rev=bv_rev, cnt_rev=cnt_rev, bwt_words=bwt_words, sa_bv=sa_bv,
+                          sa_bv_counts=sa_cnt, sa_samples=samples, sparseness=sparseness,
+                          seq_starts=np.asarray(seq_starts, dtype=np.uint32), seq_names=[f"seq{i}" for i in range(len(seq_starts) - 1)])
 
 
 def launch_ranks(n: int) -> int:
@@ -185,6 +283,23 @@ def move_source_digest() -> str:
         with open(os.path.join(d, fn), "rb") as f:
             h.update(fn.encode() + b"\0" + f.read())
     return h.hexdigest()[:16]
+
+
+def serial_kernel_table(batch):
+    """kernel table of the FM batch (--full): SERIAL_TABLE_STEPS extra steps with the sub-batches run one after the other
+    (CMB_SERIAL_SUBBATCHES), so that every kernel has the device to itself (in the timed steps they overlap, which is where
+    15 % of the throughput comes from, but a kernel's duration then depends on what happens to run beside it); the median
+    per kernel group (one sample moved by 3 ms between otherwise identical runs)"""
+    os.environ["CMB_SERIAL_SUBBATCHES"] = "1"
+    runs = []
+    try:
+        for _ in range(SERIAL_TABLE_STEPS):
+            batch.run()
+            torch.cuda.synchronize()
+            runs.append(dict(batch.timings()))
+    finally:
+        del os.environ["CMB_SERIAL_SUBBATCHES"]
+    return {kn: float(np.median([r.get(kn, 0.0) for r in runs])) for kn in runs[0]}
 
 
 def serial_move_table(batch, n: int = 1):
@@ -387,7 +502,7 @@ def main_rlc(args):
     steps = max(args.steps, 1)
     per_rank_ms = [round(elapsed / steps * 1e3, 3)]
     concurrent = {kn: round(v / steps, 3) for kn, v in kern.items()}  # busy ms per step, summed over the chunk's concurrent halves
-    serial = serial_move_table(batch, 1)
+    serial = serial_move_table(batch, 1) if args.full else None
     occ, occ_offs, cnt = batch.results()
     total_occ = len(occ)
     if dist is not None:
@@ -407,59 +522,60 @@ def main_rlc(args):
         dist.barrier()
         dist.destroy_process_group()
         return
-    avg = serial
-    dominant = max(avg, key=avg.get)
-    # algorithmic bytes: one move-table row fetched = 16 B (an aligned 16-byte row here; the reference reads the
-    # same 16 bytes with one unaligned 128-bit load per row access, moverepr.cpp:36-47).  Rows are counted on the device where
-    # they are loaded: run scans, LF rows, fast-forward steps, run-index searches.
-    alg = {"k_partition": 16.0 * (cnt["TABLE_ROWS"] - cnt["DFS_TABLE_ROWS"]), "k_dfs": 16.0 * cnt["DFS_TABLE_ROWS"]}
-    per_kernel = {}
-    for kname, ms in avg.items():
-        gbs = alg[kname] / (ms * 1e-3) / 1e9 if ms > 0 and kname in alg else None
-        per_kernel[kname] = {"ms": round(ms, 3), "algorithmic_GBps": None if gbs is None else round(gbs, 1),
-                             "frac_of_hbm_peak": None if gbs is None else round(gbs / HBM_PEAK_GBS, 4)}
-    achieved = per_kernel[dominant]["algorithmic_GBps"] or 0.0
-    passes = None
-    traffic, traffic_source = load_rlc_traffic(R, L, k) if dominant == "k_dfs" else (None, None)
-    roofline = {"bound": "hbm", "kernel": dominant, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_source, "kernel_src_sha": move_source_digest(),
-                "traffic_note": "GB per step of the frontier kernels, 2 x FETCH_SIZE + WRITE_SIZE (separate rocprofv3 --pmc passes of this command, two-step "
-                                "minus one-step run: tools/profile_rlc.sh -> profiles/*_rlc_pmc_traffic.json)",
-                "avg_launch_ms": round(avg[dominant], 3),
-                "timing_note": "kernel times (HIP events on the batch's streams) are those of one extra step with the chunk's halves run one after "
-                               "the other; in the timed steps the halves overlap (busy ms per step there: see concurrent_ms)",
-                "concurrent_ms": concurrent,
-                "overlap": {"serial_sum_ms": round(sum(avg.values()), 3), "step_over_serial_sum": round(elapsed / steps * 1e3 / max(sum(avg.values()), 1e-9), 4)},
-                "unit_note": "16 B per move-table row fetched (TABLE_ROWS counted on the device); "
-                             f"{cnt['DFS_TABLE_ROWS'] / max(cnt['DFS_EXPANSIONS'], 1):.1f} rows per node expansion of the search",
-                "per_kernel": per_kernel}
-    cpu = None
-    if not args.no_cpu_baseline and world == 1:
-        sys.path.insert(0, os.path.join(ROOT, "oracle"))
-        import oracle_py as op
-        import schemes_py as sp
-        ns = min(args.cpu_sample if args.cpu_sample != 1_000_000 else 20_000, R)
-        cores = effective_cpus()
-        oidx = op.OracleMoveIndex(mv)
-        oidx.prepare(args.kmer_size)   # (the k-mer table: index loading, not matching)
-        ost = op.OracleStrategy(sp.MULTIPLE_OPT, "edit", "dynamic")
-        packed = (np.ascontiguousarray(buf[:ns * L]), offs[:ns + 1].copy())
-        tc = time.perf_counter()
-        o_occ, o_off, o_cnt = oidx.match_batch(ost, k, threads=cores, word_size=args.kmer_size, packed=packed)
-        dt = time.perf_counter() - tc
-        m = int(occ_offs[ns])
-        same = (len(o_occ) == m and np.array_equal(o_occ["begin"].astype(np.uint64), occ["begin"][:m]) and
-                np.array_equal(o_occ["end"].astype(np.uint64), occ["end"][:m]) and
-                np.array_equal(o_occ["distance"], occ["distance"][:m]))
-        cpu = {"value": round(ns / dt, 1), "unit": "reads/s", "cores": cores, "kind": "port",
-               "sample": f"first {ns} reads of the GPU batch, oracle/ (C++ restatement of the RUN_LENGTH_COMPRESSION flavour) with {cores} "
-                         f"threads, {dt:.1f} s (reads packed and k-mer table built before the clock); occurrences identical to the GPU's: "
-                         f"{bool(same)}; table rows stepped over by the reference's walks on the sample: {o_cnt['ROW_STEPS']}"}
+    roofline = cpu = None
+    if args.full:
+        avg = serial
+        dominant = max(avg, key=avg.get)
+        # algorithmic bytes: one move-table row fetched = 16 B (an aligned 16-byte row here; the reference reads the
+        # same 16 bytes with one unaligned 128-bit load per row access, moverepr.cpp:36-47).  Rows are counted on the device where
+        # they are loaded: run scans, LF rows, fast-forward steps, run-index searches.
+        alg = {"k_partition": 16.0 * (cnt["TABLE_ROWS"] - cnt["DFS_TABLE_ROWS"]), "k_dfs": 16.0 * cnt["DFS_TABLE_ROWS"]}
+        per_kernel = {}
+        for kname, ms in avg.items():
+            gbs = alg[kname] / (ms * 1e-3) / 1e9 if ms > 0 and kname in alg else None
+            per_kernel[kname] = {"ms": round(ms, 3), "algorithmic_GBps": None if gbs is None else round(gbs, 1),
+                                 "frac_of_hbm_peak": None if gbs is None else round(gbs / HBM_PEAK_GBS, 4)}
+        achieved = per_kernel[dominant]["algorithmic_GBps"] or 0.0
+        passes = None
+        traffic, traffic_source = load_rlc_traffic(R, L, k) if dominant == "k_dfs" else (None, None)
+        roofline = {"bound": "hbm", "kernel": dominant, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_source, "kernel_src_sha": move_source_digest(),
+                    "traffic_note": "GB per step of the frontier kernels, 2 x FETCH_SIZE + WRITE_SIZE (separate rocprofv3 --pmc passes of this command, two-step "
+                                    "minus one-step run: tools/profile_rlc.sh -> profiles/*_rlc_pmc_traffic.json)",
+                    "avg_launch_ms": round(avg[dominant], 3),
+                    "timing_note": "kernel times (HIP events on the batch's streams) are those of one extra step with the chunk's halves run one after "
+                                   "the other; in the timed steps the halves overlap (busy ms per step there: see concurrent_ms)",
+                    "concurrent_ms": concurrent,
+                    "overlap": {"serial_sum_ms": round(sum(avg.values()), 3), "step_over_serial_sum": round(elapsed / steps * 1e3 / max(sum(avg.values()), 1e-9), 4)},
+                    "unit_note": "16 B per move-table row fetched (TABLE_ROWS counted on the device); "
+                                 f"{cnt['DFS_TABLE_ROWS'] / max(cnt['DFS_EXPANSIONS'], 1):.1f} rows per node expansion of the search",
+                    "per_kernel": per_kernel}
+        if not args.no_cpu_baseline and world == 1:
+            sys.path.insert(0, os.path.join(ROOT, "oracle"))
+            import oracle_py as op
+            import schemes_py as sp
+            ns = min(args.cpu_sample if args.cpu_sample != 1_000_000 else 20_000, R)
+            cores = effective_cpus()
+            oidx = op.OracleMoveIndex(mv)
+            oidx.prepare(args.kmer_size)   # (the k-mer table: index loading, not matching)
+            ost = op.OracleStrategy(sp.MULTIPLE_OPT, "edit", "dynamic")
+            packed = (np.ascontiguousarray(buf[:ns * L]), offs[:ns + 1].copy())
+            tc = time.perf_counter()
+            o_occ, o_off, o_cnt = oidx.match_batch(ost, k, threads=cores, word_size=args.kmer_size, packed=packed)
+            dt = time.perf_counter() - tc
+            m = int(occ_offs[ns])
+            same = (len(o_occ) == m and np.array_equal(o_occ["begin"].astype(np.uint64), occ["begin"][:m]) and
+                    np.array_equal(o_occ["end"].astype(np.uint64), occ["end"][:m]) and
+                    np.array_equal(o_occ["distance"], occ["distance"][:m]))
+            cpu = {"value": round(ns / dt, 1), "unit": "reads/s", "cores": cores, "kind": "port",
+                   "sample": f"first {ns} reads of the GPU batch, oracle/ (C++ restatement of the RUN_LENGTH_COMPRESSION flavour) with {cores} "
+                             f"threads, {dt:.1f} s (reads packed and k-mer table built before the clock); occurrences identical to the GPU's: "
+                             f"{bool(same)}; table rows stepped over by the reference's walks on the sample: {o_cnt['ROW_STEPS']}"}
     line = {
         "metric": "reads/sec (250bp, k=6 edit, pan-genome RLC b-move index)",
         "value": round(world * R * steps / elapsed, 1), "unit": "reads/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(elapsed / steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "u64", "data": "synthetic", "rccl_ranks": rccl_ranks, "per_rank_ms_per_step": per_rank_ms,
+        "dtype": "u64", "data": "synthetic", "full": args.full, "rccl_ranks": rccl_ranks, "per_rank_ms_per_step": per_rank_ms,
         "index_broadcast_ms": None if broadcast_ms is None else round(broadcast_ms, 1), "host_affinity": affinity,
         "config": {"workload": f"BASELINE configs[4] stand-in: {args.haplotypes} haplotypes x {args.base_mbp} Mbp with {args.snp} SNPs "
                                f"({mv.n / 1e6:.0f} Mbp, r = {mv.runs_fwd}, n/r = {mv.n / mv.runs_fwd:.1f}) under the b-move index, {R} x {L} bp "
@@ -563,7 +679,7 @@ def streaming_leg(index, strategy, k, buf, R, L, steps, rank, dev, dist, world):
 
 
 def rlc_leg(args, dev, local):
-    """BASELINE configs[4] (b-move index, 250 bp, k = 6) as a bounded leg of the DEFAULT line, after the headline's timed region: the
+    """BASELINE configs[4] (b-move index, 250 bp, k = 6) as a bounded leg of the --full line, after the headline's timed region: the
     stand-in of `--config rlc` (64 haplotypes x 4 Mbp, 0.5 % SNPs) with 10^6 reads, one warm-up and two timed steps, the oracle's RLC
     flavour on the first 10 000 reads beside it.  `python bench.py --config rlc` is the full-length version of this leg."""
     from columba_amd import movebuild
@@ -657,18 +773,22 @@ def main():
                          "100 M reads over 8 GPUs = 12.5 M per GPU); default 0 = weak scaling with --reads per GPU")
     ap.add_argument("--read-len", type=int, default=150)
     ap.add_argument("--k", type=int, default=4)
-    ap.add_argument("--cpu-sample", type=int, default=1_000_000, help="reads timed on the CPU oracle (bounded sample)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-gather", action="store_true", help="skip the (untimed) gather of the results on rank 0")
-    ap.add_argument("--include-upload", action="store_true", help="kept for older command lines: the streaming leg is part of the default line")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, everything else the benchmark measures and checks after the timed steps: the kernel "
+                         "table of extra serial steps and the roofline built on it, the CPU baseline and its comparison with the GPU's "
+                         "occurrences, the streaming and rlc legs, the result gather of N > 1 ranks (off: those fields are null)")
+    ap.add_argument("--cpu-sample", type=int, default=1_000_000, help="reads timed on the CPU oracle (bounded sample; --full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-gather", action="store_true", help="with --full: skip the (untimed) gather of the results on rank 0")
+    ap.add_argument("--include-upload", action="store_true", help="kept for older command lines: the streaming leg is part of the --full line")
     ap.add_argument("--no-streaming", action="store_true",
-                    help="skip the `streaming` leg (steps that take FRESH reads from page-locked host memory and hand their results to the "
-                         "host; reported beside `value`, never as `value`)")
+                    help="with --full: skip the `streaming` leg (steps that take FRESH reads from page-locked host memory and hand their "
+                         "results to the host; reported beside `value`, never as `value`)")
     ap.add_argument("--cpus-per-rank", type=int, default=0,
                     help="confine every rank to this many CPUs (set before anything touches the GPU): a rehearsal of a CPU-starved 8-rank "
                          "node on a one-GPU box; the line's host_cpu field shows what a step costs the host")
     ap.add_argument("--no-rlc", action="store_true",
-                    help="skip the bounded BASELINE configs[4] leg (`rlc`: b-move index, 250 bp, k = 6) of the default one-GPU line")
+                    help="with --full: skip the bounded BASELINE configs[4] leg (`rlc`: b-move index, 250 bp, k = 6) of the one-GPU line")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last of them computed (rank 0's batch: counters and the occurrences of a "
                          "fixed, seeded sample of the reads) as DIR/<name>.npy in float64, for output-for-output comparison of two builds")
@@ -703,7 +823,8 @@ def main():
     ix = None
     if rank == 0:
         g, starts = synth.genome_human_like(n, seed=2025, device=dev)
-        ix = ib.build_index(g, sparseness=args.sparseness, seq_starts=starts, device=dev, with_bwt=(world == 1 and not args.no_cpu_baseline))
+        ix = build_fm_index(g, starts, args.sparseness, dev,
+                            with_bwt=(args.full and world == 1 and not args.no_cpu_baseline))  # (the 3-bit BWT is the oracle's alone)
         del g
         torch.cuda.empty_cache()
         log(f"[bench] index for {n / 1e6:.0f} Mbp built in {time.time() - t0:.1f} s "
@@ -775,19 +896,7 @@ def main():
         te = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
         elapsed = float(te.item())
-    # kernel table: one extra step with the sub-batches of the batch run one after the other, so that every kernel
-    # has the device to itself (in the timed steps above they overlap, which is where 15 % of the throughput
-    # comes from, but a kernel's duration then depends on what happens to run beside it)
-    os.environ["CMB_SERIAL_SUBBATCHES"] = "1"
-    serial_runs = []
-    try:
-        for _ in range(SERIAL_TABLE_STEPS):  # (three such steps, the median per kernel group: one sample moved by 3 ms between otherwise identical runs)
-            batch.run()
-            torch.cuda.synchronize()
-            serial_runs.append(dict(batch.timings()))
-    finally:
-        del os.environ["CMB_SERIAL_SUBBATCHES"]
-    kern_serial = {kn: float(np.median([r.get(kn, 0.0) for r in serial_runs])) for kn in serial_runs[0]}
+    kern_serial = serial_kernel_table(batch) if args.full else None
     occ, occ_offs, cnt = batch.results()
     total_occ = len(occ)
     gather_ms = None
@@ -795,7 +904,7 @@ def main():
         tt = torch.tensor([total_occ], dtype=torch.int64, device="cpu" if dist.get_backend() == "gloo" else dev)
         dist.all_reduce(tt)
         total_occ = int(tt.item())
-        if not args.no_gather:
+        if args.full and not args.no_gather:
             # result path of the sharded job: gatherv of the occurrence lists on rank 0 + all-reduce of the counters
             # (SURVEY.md §8e).  Not part of a step: one rank's host link would carry every rank's results.
             sync()
@@ -811,10 +920,10 @@ def main():
                     f"NODE_COUNTER of the job {cnt_all['NODE_COUNTER']}")
                 del g_occ, g_offs
 
-    streaming = None
-    if rank == 0:
-        steps = max(args.steps, 1)
-        value = world * R * steps / elapsed
+    streaming = roofline = cpu = None
+    steps = max(args.steps, 1)
+    value = world * R * steps / elapsed
+    if rank == 0 and args.full:
         avg_concurrent = {k: v / steps for k, v in kern.items()}
         avg = kern_serial
         dominant = max(avg, key=avg.get)
@@ -872,7 +981,6 @@ def main():
                     "overlap": {"serial_sum_ms": round(sum(avg.values()), 3), "step_over_serial_sum": round(elapsed / steps * 1e3 / max(sum(avg.values()), 1e-9), 4)},
                     "line_rate": line_rate, "valu": valu,
                     "per_kernel": per_kernel}
-        cpu = None
         if world == 1 and not args.no_cpu_baseline:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import oracle_py as op
@@ -899,11 +1007,11 @@ def main():
     del occ, occ_offs
     torch.cuda.empty_cache()
     rlc = None
-    if not args.no_streaming:
+    if args.full and not args.no_streaming:
         streaming = streaming_leg(index, strategy, args.k, buf, R, L, min(max(args.steps, 1), 8), rank, dev, dist, world)
         if streaming is not None and rank == 0:
             streaming["frac_of_resident"] = round(streaming["value"] / (world * R * max(args.steps, 1) / elapsed), 4)
-    if rank == 0 and world == 1 and not args.no_rlc:
+    if args.full and rank == 0 and world == 1 and not args.no_rlc:
         torch.cuda.empty_cache()
         try:
             rlc = rlc_leg(args, dev, local)
@@ -914,7 +1022,7 @@ def main():
             "metric": "reads/sec (150bp, k=4 edit, human ref)",
             "value": round(value, 1), "unit": "reads/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(elapsed / steps * 1e3, 3), "higher_is_better": True,
-            "scaling": "strong" if args.total_reads else "weak", "vs_baseline": None, "dtype": "u64", "data": "synthetic",
+            "scaling": "strong" if args.total_reads else "weak", "vs_baseline": None, "dtype": "u64", "data": "synthetic", "full": args.full,
             "rccl_ranks": rccl_ranks, "per_rank_ms_per_step": per_rank_ms, "index_broadcast_ms": None if broadcast_ms is None else round(broadcast_ms, 1),
             "host_affinity": affinity,
             # what a step costs the HOST: CPU time (all threads of the rank: three sub-batch workers + the Python thread) per step and

@@ -1,5 +1,5 @@
 """tools/pmc_traffic.py turns the rocprofv3 --pmc passes of tools/profile_round.sh into the per-STEP table bench.py reads back as
-`roofline.traffic`.  The passes run `bench.py --steps 1 --warmup 0`, which goes through the hot path 1 + SERIAL_TABLE_STEPS times; the
+`roofline.traffic`.  The passes run `bench.py --full --steps 1 --warmup 0`, which goes through the hot path 1 + SERIAL_TABLE_STEPS times; the
 divisor once stayed at 2 when the kernel table became a median of three steps (round 4: traffic reported twice too large) — the tool now
 takes the constant from bench.py and checks it against the launches of k_parts."""
 import csv

@@ -3,7 +3,7 @@
     python tools/pmc_traffic.py <bench_line.json> <dir of the FETCH_SIZE pass> <dir of the WRITE_SIZE pass> [steps run]  > *_pmc_traffic.json
 
 FETCH_SIZE / WRITE_SIZE are collected in separate passes (they do not fit one pass, MI355X_MICROARCH.md) of
-`bench.py --steps 1 --warmup 0`, which runs the hot path 1 + SERIAL_TABLE_STEPS times (one timed step + the serial steps its
+`bench.py --full --steps 1 --warmup 0`, which runs the hot path 1 + SERIAL_TABLE_STEPS times (one timed step + the serial steps its
 kernel table is the median of; the constant is read from bench.py): the sums over all dispatches of a kernel are divided by the
 number of steps run, and the division is checked against the dispatch count of k_parts (one launch per sub-batch and step).  Units: KiB.
 bench.py (load_traffic) applies the gfx950 correction (FETCH_SIZE x 2) when it reports `roofline.traffic`."""
@@ -30,7 +30,7 @@ steps_run = float(sys.argv[4]) if len(sys.argv) > 4 and not os.path.isdir(sys.ar
 sq_dir = next((a for a in sys.argv[4:] if os.path.isdir(a)), None)  # the SQ_* pass (wave-instructions per kernel)
 out = {"workload": {k: line["config"][k] for k in ("genome_bp", "reads_per_gpu", "read_len", "k")},
        "kernel_src_sha": source_digest(),
-       "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, one pass each, bench.py --steps 1 --warmup 0 "
+       "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, one pass each, bench.py --full --steps 1 --warmup 0 "
                  "(sub-batches one after the other); per step",
        "kernels": collections.defaultdict(dict)}
 for d, name in ((sys.argv[2], "FETCH_SIZE"), (sys.argv[3], "WRITE_SIZE")):

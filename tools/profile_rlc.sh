@@ -8,7 +8,7 @@ OUT=$R/gpurun_out/profiles_${ROUND}_rlc
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 ARGS="--config rlc $@"
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rlc_stats -- python3 $R/bench.py $ARGS --no-cpu-baseline --no-streaming --no-rlc > $OUT/bench_under_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rlc_stats -- python3 $R/bench.py $ARGS --full --no-cpu-baseline --no-streaming --no-rlc > $OUT/bench_under_rocprof.log 2>&1
 python3 - <<PY > $OUT/kernel_stats.csv
 import csv, glob
 rows = []
@@ -23,9 +23,9 @@ PY
 # HBM traffic counters: every run starts with a warm-up that sizes the pools, so one step = (two timed steps) - (one timed step)
 for C in FETCH_SIZE WRITE_SIZE; do
   for N in 1 2; do
-    rocprofv3 --pmc $C --kernel-include-regex 'k_mvs|k_move' --output-format csv -d /tmp/rlc_${C}_$N -- python3 $R/bench.py $ARGS --steps $N --warmup 1 --no-cpu-baseline --no-streaming --no-rlc > $OUT/pmc_${C}_$N.log 2>&1
+    rocprofv3 --pmc $C --kernel-include-regex 'k_mvs|k_move' --output-format csv -d /tmp/rlc_${C}_$N -- python3 $R/bench.py $ARGS --full --steps $N --warmup 1 --no-cpu-baseline --no-streaming --no-rlc > $OUT/pmc_${C}_$N.log 2>&1
   done
 done
-cd $R && python3 bench.py $ARGS > $OUT/bench_line.json 2> $OUT/bench_stderr.log
+cd $R && python3 bench.py $ARGS --full > $OUT/bench_line.json 2> $OUT/bench_stderr.log
 python3 $R/tools/pmc_traffic_rlc.py $OUT/bench_line.json /tmp/rlc_FETCH_SIZE_1 /tmp/rlc_FETCH_SIZE_2 /tmp/rlc_WRITE_SIZE_1 /tmp/rlc_WRITE_SIZE_2 > $OUT/pmc_traffic.json
 ls -la $OUT
