@@ -48,7 +48,7 @@ EXPORTS = [
     "cmb_sam_pe", "cmb_sam_unpaired", "cmb_sam_unmapped_pe", "cmb_pair_sam", "cmb_pair_infer",
     "cmb_pair_best_create", "cmb_pair_best_set_trim", "cmb_pair_best_cutoff", "cmb_pair_best_seed", "cmb_pair_best_advance", "cmb_pair_best_supply", "cmb_pair_best_sam",
     "cmb_pair_best_destroy",
-    "cmb_read_prepare", "cmb_batch_sam", "cmb_batch_filter_per_strand", "cmb_match_best", "cmb_best_sizes", "cmb_best_results",
+    "cmb_read_prepare", "cmb_batch_sam", "cmb_batch_sam_device", "cmb_sam_device_mapq", "cmb_batch_filter_per_strand", "cmb_match_best", "cmb_best_sizes", "cmb_best_results",
     "cmb_best_destroy",
     "cmb_move_create", "cmb_move_destroy", "cmb_move_device_bytes", "cmb_move_info", "cmb_move_complete_range", "cmb_move_rows",
     "cmb_move_extend_batch", "cmb_move_extend_bench", "cmb_move_locate_batch", "cmb_move_match_exact", "cmb_move_last_timings", "cmb_move_kmer_table",
@@ -187,6 +187,12 @@ def pair_infer(samples) -> "PairInferred":
     return out
 
 
+class SamInputs(C.Structure):
+    """cmb_sam_inputs"""
+    _fields_ = [("seqs", C.c_void_p), ("ids", C.c_void_p), ("id_offs", C.c_void_p), ("quals", C.c_void_p), ("qual_offs", C.c_void_p),
+                ("seq_names", C.c_void_p), ("seq_name_offs", C.c_void_p), ("n_seqs", C.c_uint32)]
+
+
 class SamHit(C.Structure):
     """cmb_sam_hit"""
     _fields_ = [("seq_name", C.c_char_p), ("pos0", C.c_uint32), ("distance", C.c_uint32), ("revcomp", C.c_uint32),
@@ -273,6 +279,8 @@ def lib():
         L.cmb_read_prepare.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, vp, vp, vp, vp]
         L.cmb_batch_sam.restype = C.c_int64
         L.cmb_batch_sam.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, u64]
+        L.cmb_batch_sam_device.argtypes = [vp, C.POINTER(SamInputs), i32, i32, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
+        L.cmb_sam_device_mapq.argtypes = [u32, vp]
         L.cmb_batch_filter_per_strand.argtypes = [vp, i32]
         L.cmb_trim_occurrence.argtypes = [vp, vp, u32, u32, i32, vp, vp, vp, u32, C.POINTER(u32), C.POINTER(i32)]
         L.cmb_batch_allow_unsupported.argtypes = [vp, i32]
@@ -737,6 +745,40 @@ def pack_reads(reads: Sequence[bytes]) -> Tuple[np.ndarray, np.ndarray]:
     return buf, offs
 
 
+def pack_fields(fields) -> Tuple[np.ndarray, np.ndarray]:
+    """SAM fields (identifiers, qualities, sequence names) one after the other as cmb_sam_inputs takes them: (bytes, offsets[n + 1]).
+    Entries are str or bytes, empty ones included; SAM fields are ASCII, anything else is refused.  A (bytes, offsets) pair that
+    is packed already passes through."""
+    if isinstance(fields, tuple) and len(fields) == 2 and isinstance(fields[1], np.ndarray):
+        return np.ascontiguousarray(fields[0], np.uint8), np.ascontiguousarray(fields[1], np.uint64)
+    raw = fields if isinstance(fields, list) else list(fields)
+    try:
+        blob = b"".join(raw)  # (all bytes: no per-entry work beyond the join and len)
+    except TypeError:
+        raw = [f.encode("ascii") if isinstance(f, str) else bytes(f) for f in raw]
+        blob = b"".join(raw)
+    offs = np.zeros(len(raw) + 1, np.uint64)
+    if raw:
+        offs[1:] = np.cumsum(np.fromiter(map(len, raw), np.uint64, len(raw)))
+    buf = np.frombuffer(blob, dtype=np.uint8)
+    if buf.size and int(buf.max()) > 127:
+        raise ValueError("SAM fields are ASCII")
+    return (buf if buf.size else np.zeros(1, np.uint8)), offs
+
+
+def unpack_fields(buf: np.ndarray, offs: np.ndarray):
+    """the entries of pack_fields as bytes"""
+    b = buf.tobytes()
+    return [b[int(offs[i]):int(offs[i + 1])] for i in range(offs.shape[0] - 1)]
+
+
+def sam_device_mapq(n: int) -> np.ndarray:
+    """test hook: the MAPQ the device path prints for 1 ... n occurrences of minimal distance"""
+    out = np.zeros(max(n, 1), np.uint32)
+    _chk(lib().cmb_sam_device_mapq(n, _p(out)))
+    return out[:n]
+
+
 class Batch:
     """A batch of reads resident in HBM (handle of ``cmb_batch_*``)."""
 
@@ -750,13 +792,15 @@ class Batch:
         self.h = h
 
     def run(self):
-        # a run consumes the staged chunk (cmb_batch_run waits for its copy first): from here on the batch's reads ARE that
-        # chunk — sam() must see them — and the chunk before it may still be the source of nothing
-        staged = getattr(self, "_staged", None)
-        if staged is not None:
-            self._retired = self._packed  # (one more generation alive: its upload finished before this run started)
-            self._packed = staged
-            self._staged = None
+        # a run matches the chunk whose upload the run BEFORE it started (cmb_batch_run waits for that copy first) and starts the
+        # upload of the chunk registered since: stage(c1); run() still matches the batch's own chunk while c1 travels, the next
+        # run() matches c1.  _packed is the chunk the results belong to — sam() and sam_device() must see its characters.
+        inflight = getattr(self, "_inflight", None)
+        if inflight is not None:
+            self._retired = self._packed  # (one more generation alive)
+            self._packed = inflight
+        self._inflight = getattr(self, "_staged", None)
+        self._staged = None
         _chk(lib().cmb_batch_run(self.h))
 
     def stage(self, packed):
@@ -823,6 +867,26 @@ class Batch:
         out = C.create_string_buffer(int(n) + 1)
         lib().cmb_batch_sam(self.h, _p(buf), ai, aq, an, int(unmapped), int(xa), out, int(n) + 1)
         return out.value.decode()
+
+    def sam_device_bytes(self, ids, quals, seq_names, unmapped: bool = True, xa: bool = False):
+        """the same text written on the device (cmb_batch_sam_device): (bytes, number of reads the host formatted — those with an
+        occurrence over the end of its sequence).  ids / quals / seq_names: sequences of str or bytes, or (bytes, offsets) pairs
+        packed with pack_fields; quals=None: no qualities."""
+        bi, oi = pack_fields(ids)
+        bn, on = pack_fields(seq_names)
+        bq, oq = pack_fields(quals) if quals is not None else (None, None)
+        if oi.shape[0] - 1 != self.n_reads or (oq is not None and oq.shape[0] - 1 != self.n_reads):
+            raise ValueError("one identifier and one quality per read")
+        inp = SamInputs(_p(self._packed[0]), _p(bi), _p(oi), _p(bq) if bq is not None else None, _p(oq) if oq is not None else None,
+                        _p(bn), _p(on), on.shape[0] - 1)
+        text, n, host = C.c_void_p(), C.c_uint64(), C.c_uint64()
+        _chk(lib().cmb_batch_sam_device(self.h, C.byref(inp), int(unmapped), int(xa), C.byref(text), C.byref(n), C.byref(host)))
+        return C.string_at(text.value, n.value) if n.value else b"", int(host.value)
+
+    def sam_device(self, ids, quals, seq_names, unmapped: bool = True, xa: bool = False):
+        """(SAM text, number of host-formatted reads): sam_device_bytes, decoded"""
+        t, host = self.sam_device_bytes(ids, quals, seq_names, unmapped, xa)
+        return t.decode(), host
 
     def timings(self) -> Dict[str, float]:
         names = (C.c_char_p * 16)()

@@ -3,6 +3,7 @@
 #include "host_sam.hpp"
 #include "host_schemes.hpp"
 #include "kernels.hpp"
+#include "dev_sam.hpp"
 
 #include <chrono>
 #include <cstring>
@@ -668,6 +669,14 @@ struct cmb_batch {
     uint32_t alnStride = 0;
     PinnedBuf<uint16_t> hAlnOps;
     PinnedBuf<AlnRec> hAlnRec;
+    // cmb_batch_sam_device (dev_sam.hpp): the chunk's packed identifiers, qualities and sequence names, the plan and the
+    // position of every read in the text, the text of the reads the host formatted, the sub-batch's text; samOut: the
+    // finished text of the whole batch in page-locked memory (the composite's own, or the single batch's)
+    DevBuf<uint8_t> samIds, samQuals, samNames, samSide, samText;
+    DevBuf<uint64_t> samIdOffs, samQualOffs, samNameOffs, samLen, samOffs, samSideOffs;
+    DevBuf<SamPlan> samPlan;
+    DevBuf<uint32_t> samHostList, samSideReads;
+    PinnedBuf<char> samOut;
     // cmb_verify_batch_staged: candidates given by the caller take the place of the search's in-text items, and the
     // raw text occurrences (before the filter) are what is handed back
     std::vector<uint4> presetItems;
@@ -2616,6 +2625,22 @@ static void samOfRead(std::string& text, cmb_index* idx, uint32_t k, int metric,
     }
 }
 
+// the occurrences of read i of a (sub-)batch with their alignments, as the run left them on the host
+static std::vector<BestOcc> occsOfBatchRead(const cmb_batch* c, uint32_t i) {
+    std::vector<BestOcc> occs;
+    const uint64_t q0 = c->occOffs.data()[c->perStrand ? 2 * (size_t)i : i], q1 = c->occOffs.data()[c->perStrand ? 2 * (size_t)i + 2 : i + 1];
+    for (uint64_t q2 = q0; q2 < q1; q2++) {
+        BestOcc o;
+        o.occ = c->occs.data()[q2];
+        const AlnRec& ar = c->hAlnRec.data()[q2];
+        o.aln = cmb_aln{ar.seqId, ar.seqBegin, 0, (uint16_t)ar.nOps, (uint16_t)ar.spans, 0};
+        const uint16_t* src = c->hAlnOps.data() + q2 * c->alnStride;
+        for (uint32_t j = 0; j < ar.nOps; j++) o.ops.push_back(src[ar.nOps - 1 - j]);
+        occs.push_back(std::move(o));
+    }
+    return occs;
+}
+
 extern "C" int64_t cmb_batch_sam(const cmb_batch* b, const char* seqs, const char* const* read_ids, const char* const* quals,
                                  const char* const* seq_names, int unmapped_records, int xa_tag, char* out, uint64_t cap) {
     if (!b || !seqs || !read_ids || !seq_names) return fail(CMB_ERR_INVALID, "null argument");
@@ -2636,23 +2661,190 @@ extern "C" int64_t cmb_batch_sam(const cmb_batch* b, const char* seqs, const cha
                 const std::string read = cleanReadSeq(std::string(seqs + o0, seqs + o1)), revC = revComplWithN(read);
                 const std::string sid = cleanSeqID(read_ids[gi]);
                 const std::string qual = quals && quals[gi] ? quals[gi] : "*";
-                std::vector<BestOcc> occs;
-                const uint64_t q0 = c->occOffs.data()[c->perStrand ? 2 * (size_t)i : i], q1 = c->occOffs.data()[c->perStrand ? 2 * (size_t)i + 2 : i + 1];
-                for (uint64_t q2 = q0; q2 < q1; q2++) {
-                    BestOcc o;
-                    o.occ = c->occs.data()[q2];
-                    const AlnRec& ar = c->hAlnRec.data()[q2];
-                    o.aln = cmb_aln{ar.seqId, ar.seqBegin, 0, (uint16_t)ar.nOps, (uint16_t)ar.spans, 0};
-                    const uint16_t* src = c->hAlnOps.data() + q2 * c->alnStride;
-                    for (uint32_t j = 0; j < ar.nOps; j++) o.ops.push_back(src[ar.nOps - 1 - j]);
-                    occs.push_back(std::move(o));
-                }
+                std::vector<BestOcc> occs = occsOfBatchRead(c, i);
                 samOfRead(text, idx, c->k, c->metric, read, revC, sid, qual, occs, seq_names, unmapped_records, xa_tag);
             }
             readBase += c->nReads;
             charBase += c->hostOffs[c->nReads];
         }
         return putString(text, out, cap);
+    } catch (const std::exception& e) {
+        return fail(CMB_ERR_DEVICE, e.what());
+    }
+}
+
+// The same text written on the device (dev_sam.hpp): plan -> lengths of the host-formatted reads -> scan -> write, every sub-batch on
+// its own stream, the finished text in one page-locked buffer of the batch.  Reads with an occurrence that runs over the end of its
+// sequence (AlnRec::spans == 1) go through samOfRead on the host — findSeqName trims them and may drop them — and their bytes are
+// copied into place by the write kernel; nothing else is formatted on the host.
+template <typename T> static void growTo(DevBuf<T>& d, size_t count) {
+    if (d.n < count || !d.p) d.alloc(count + count / 8 + 256);
+}
+extern "C" int cmb_batch_sam_device(cmb_batch* b, const cmb_sam_inputs* in, int unmapped_records, int xa_tag, const char** text,
+                                    uint64_t* length, uint64_t* host_reads) {
+    if (!b || !in || !text || !length || !in->seqs || !in->ids || !in->id_offs || (in->quals && !in->qual_offs) ||
+        (in->n_seqs && (!in->seq_names || !in->seq_name_offs)))
+        return fail(CMB_ERR_INVALID, "null argument");
+    if (!b->done) return fail(CMB_ERR_INVALID, "batch has not been run");
+    if (!b->wantAln) return fail(CMB_ERR_INVALID, "alignments were not requested (cmb_batch_want_alignments)");
+    try {
+        std::vector<cmb_batch*> parts;
+        if (b->subs.empty()) parts.push_back(b);
+        else parts = b->subs;
+        cmb_index* idx = b->ix;
+        useDevice(idx->device);
+        const size_t P = parts.size();
+        const uint64_t nameBytes = in->n_seqs ? in->seq_name_offs[in->n_seqs] : 0;
+        const bool verbose = getenv("CMB_VERBOSE") != nullptr;
+        auto t0 = std::chrono::steady_clock::now();
+        auto lap = [&](const char* what) {
+            if (!verbose) return;
+            auto t1 = std::chrono::steady_clock::now();
+            fprintf(stderr, "[host] sam: %-28s %7.3f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count());
+            t0 = t1;
+        };
+        std::vector<uint64_t> readBase(P + 1, 0), charBase(P + 1, 0), partBytes(P, 0);
+        std::vector<uint32_t> nHost(P, 0);
+        std::vector<SamCtx> ctx(P);
+        for (size_t j = 0; j < P; j++) {
+            readBase[j + 1] = readBase[j] + parts[j]->nReads;
+            charBase[j + 1] = charBase[j] + (parts[j]->nReads ? parts[j]->hostOffs[parts[j]->nReads] : 0);
+        }
+        // ---- plan: inputs up, one wavefront per read
+        for (size_t j = 0; j < P; j++) {
+            cmb_batch* c = parts[j];
+            const uint32_t n = c->nReads;
+            if (!n) continue;
+            hipStream_t s = c->stream;
+            const uint64_t r0 = readBase[j];
+            const uint64_t idLo = in->id_offs[r0], idHi = in->id_offs[r0 + n];
+            if (idHi < idLo) return fail(CMB_ERR_INVALID, "identifier offsets must be non-decreasing");
+            growTo(c->samIds, idHi - idLo + 1); // (+ 1: the cleaned identifier starts at byte 1, also of an empty line)
+            growTo(c->samIdOffs, (size_t)n + 1);
+            if (idHi > idLo) HIPCHK(hipMemcpyAsync(c->samIds.p, in->ids + idLo, idHi - idLo, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(c->samIdOffs.p, in->id_offs + r0, ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+            uint64_t qLo = 0;
+            if (in->quals) {
+                qLo = in->qual_offs[r0];
+                const uint64_t qHi = in->qual_offs[r0 + n];
+                if (qHi < qLo) return fail(CMB_ERR_INVALID, "quality offsets must be non-decreasing");
+                growTo(c->samQuals, qHi - qLo);
+                growTo(c->samQualOffs, (size_t)n + 1);
+                if (qHi > qLo) HIPCHK(hipMemcpyAsync(c->samQuals.p, in->quals + qLo, qHi - qLo, hipMemcpyHostToDevice, s));
+                HIPCHK(hipMemcpyAsync(c->samQualOffs.p, in->qual_offs + r0, ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+            }
+            growTo(c->samNames, nameBytes);
+            growTo(c->samNameOffs, (size_t)in->n_seqs + 1);
+            if (nameBytes) HIPCHK(hipMemcpyAsync(c->samNames.p, in->seq_names, nameBytes, hipMemcpyHostToDevice, s));
+            if (in->n_seqs)
+                HIPCHK(hipMemcpyAsync(c->samNameOffs.p, in->seq_name_offs, ((size_t)in->n_seqs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+            growTo(c->samPlan, n);
+            growTo(c->samLen, (size_t)n + 1);
+            growTo(c->samOffs, (size_t)n + 1);
+            growTo(c->samHostList, (size_t)n + 1);
+            HIPCHK(hipMemsetAsync(c->samLen.p + n, 0, sizeof(uint64_t), s));
+            HIPCHK(hipMemsetAsync(c->samHostList.p, 0, sizeof(uint32_t), s));
+            SamCtx& cx = ctx[j];
+            cx = SamCtx{c->reads.p, c->offs.p, c->foffs.p, c->perStrand ? 2u : 1u, c->fout.p, c->alnRec.p, c->alnOps.p, c->alnStride,
+                        c->samIds.p, c->samIdOffs.p, idLo, in->quals ? c->samQuals.p : nullptr, c->samQualOffs.p, qLo,
+                        c->samNames.p, c->samNameOffs.p, in->n_seqs, n, unmapped_records ? 1u : 0u, xa_tag ? 1u : 0u};
+            hipLaunchKernelGGL(k_sam_plan, dim3((n + 3u) / 4u), dim3(256), 0, s, cx, c->samPlan.p, c->samLen.p, c->samHostList.p);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(&nHost[j], c->samHostList.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        }
+        lap("inputs up, plan started");
+        // ---- the reads the host formats, then the position of every read in its sub-batch's text
+        std::vector<std::string> names;
+        std::vector<const char*> namePtrs;
+        uint64_t nHostAll = 0;
+        for (size_t j = 0; j < P; j++) {
+            cmb_batch* c = parts[j];
+            const uint32_t n = c->nReads;
+            if (!n) continue;
+            hipStream_t s = c->stream;
+            HIPCHK(hipStreamSynchronize(s));
+            if (nHost[j]) {
+                if (names.empty())
+                    for (uint32_t q = 0; q < in->n_seqs; q++)
+                        names.emplace_back(in->seq_names + in->seq_name_offs[q], in->seq_names + in->seq_name_offs[q + 1]);
+                if (namePtrs.empty())
+                    for (const std::string& nm : names) namePtrs.push_back(nm.c_str());
+                std::vector<uint32_t> list(nHost[j]);
+                HIPCHK(hipMemcpy(list.data(), c->samHostList.p + 1, (size_t)nHost[j] * sizeof(uint32_t), hipMemcpyDeviceToHost));
+                std::sort(list.begin(), list.end());
+                std::string side;
+                std::vector<uint64_t> sideOffs(list.size() + 1, 0);
+                for (size_t q = 0; q < list.size(); q++) {
+                    const uint32_t i = list[q];
+                    const uint64_t gi = readBase[j] + i;
+                    const uint64_t o0 = charBase[j] + c->hostOffs[i], o1 = charBase[j] + c->hostOffs[i + 1];
+                    const std::string read = cleanReadSeq(std::string(in->seqs + o0, in->seqs + o1)), revC = revComplWithN(read);
+                    const std::string sid = cleanSeqID(std::string(in->ids + in->id_offs[gi], in->ids + in->id_offs[gi + 1]));
+                    const std::string qual = in->quals ? std::string(in->quals + in->qual_offs[gi], in->quals + in->qual_offs[gi + 1]) : "*";
+                    std::vector<BestOcc> occs = occsOfBatchRead(c, i);
+                    samOfRead(side, idx, c->k, c->metric, read, revC, sid, qual, occs, namePtrs.data(), unmapped_records, xa_tag);
+                    sideOffs[q + 1] = side.size();
+                }
+                growTo(c->samSide, side.size());
+                growTo(c->samSideOffs, sideOffs.size());
+                growTo(c->samSideReads, list.size());
+                if (!side.empty()) HIPCHK(hipMemcpy(c->samSide.p, side.data(), side.size(), hipMemcpyHostToDevice));
+                HIPCHK(hipMemcpy(c->samSideOffs.p, sideOffs.data(), sideOffs.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+                HIPCHK(hipMemcpy(c->samSideReads.p, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+                hipLaunchKernelGGL(k_sam_override, dim3((nHost[j] + 255u) / 256u), dim3(256), 0, s, c->samSideReads.p, c->samSideOffs.p, nHost[j],
+                                   c->samPlan.p, c->samLen.p);
+                HIPCHK(hipGetLastError());
+                nHostAll += nHost[j];
+            }
+            size_t scanBytes = 0;
+            HIPCHK(rocprim::exclusive_scan(nullptr, scanBytes, c->samLen.p, c->samOffs.p, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), s));
+            if (c->scanTmp.n < scanBytes) c->scanTmp.alloc(scanBytes + 256);
+            HIPCHK(rocprim::exclusive_scan(c->scanTmp.p, scanBytes, c->samLen.p, c->samOffs.p, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), s));
+            HIPCHK(hipMemcpyAsync(&partBytes[j], c->samOffs.p + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        }
+        uint64_t total = 0;
+        for (size_t j = 0; j < P; j++) {
+            if (parts[j]->nReads) HIPCHK(hipStreamSynchronize(parts[j]->stream));
+            total += partBytes[j];
+        }
+        lap("plan, host reads, scan");
+        // ---- write: every sub-batch its piece, copied to its place in the batch's text
+        b->samOut.resize((size_t)total + 1);
+        b->samOut.p[total] = '\0';
+        uint64_t at = 0;
+        for (size_t j = 0; j < P; j++) {
+            cmb_batch* c = parts[j];
+            const uint32_t n = c->nReads;
+            if (!n || !partBytes[j]) continue;
+            growTo(c->samText, (size_t)partBytes[j] + 16);
+            hipLaunchKernelGGL(k_sam_write, dim3((n + SAM_READS_PER_WAVE - 1u) / SAM_READS_PER_WAVE), dim3(64), 0, c->stream, ctx[j], c->samPlan.p,
+                               c->samOffs.p, c->samSide.p, c->samText.p);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(b->samOut.p + at, c->samText.p, (size_t)partBytes[j], hipMemcpyDeviceToHost, c->stream));
+            at += partBytes[j];
+        }
+        for (size_t j = 0; j < P; j++)
+            if (parts[j]->nReads && partBytes[j]) HIPCHK(hipStreamSynchronize(parts[j]->stream));
+        lap("write, text down");
+        *text = b->samOut.p;
+        *length = total;
+        if (host_reads) *host_reads = nHostAll;
+        return CMB_OK;
+    } catch (const std::exception& e) {
+        return fail(CMB_ERR_DEVICE, e.what());
+    }
+}
+// test hook: the MAPQ the device path prints for 1 ... n occurrences of minimal distance (dev_sam.hpp: samMapQ)
+extern "C" int cmb_sam_device_mapq(uint32_t n, uint32_t* out) {
+    if (!out && n) return fail(CMB_ERR_INVALID, "null argument");
+    try {
+        if (!n) return CMB_OK;
+        DevBuf<uint32_t> d;
+        d.alloc(n);
+        hipLaunchKernelGGL(k_sam_mapq, dim3((n + 255u) / 256u), dim3(256), 0, 0, n, d.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpy(out, d.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        return CMB_OK;
     } catch (const std::exception& e) {
         return fail(CMB_ERR_DEVICE, e.what());
     }

@@ -41,6 +41,21 @@ __device__ __forceinline__ uint32_t waveInclusiveScanDpp(uint32_t v) {
     return x;
 }
 __device__ __forceinline__ uint32_t waveLastLane(uint32_t x) { return (uint32_t)__builtin_amdgcn_readlane((int)x, 63); }
+// wave-wide minimum and sum of 64-bit values, the result in every lane (all 64 lanes must call).  A minimum over
+// (key << 32 | index) is the FIRST lane-strided element of minimal key (dev_sam.hpp: the primary occurrence of a read)
+__device__ __forceinline__ unsigned long long waveMin64(unsigned long long v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const unsigned long long y = __shfl_xor(v, d);
+        v = y < v ? y : v;
+    }
+    return v;
+}
+__device__ __forceinline__ unsigned long long waveSum64(unsigned long long v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
 
 // one atomic per wavefront: returns this lane's first slot for its `n` records in a queue
 __device__ __forceinline__ uint32_t waveAppend(uint32_t* counter, uint32_t n, uint32_t& total) {

@@ -414,6 +414,37 @@ int cmb_pair_infer(const cmb_pair_sample* samples, uint64_t n, cmb_pair_inferred
  * seq_names = names of the reference sequences.  Returns the length of the text (written if cap is larger). */
 int64_t cmb_batch_sam(const cmb_batch* b, const char* seqs, const char* const* read_ids, const char* const* quals,
                       const char* const* seq_names, int unmapped_records, int xa_tag, char* out, uint64_t cap);
+/* The same text, byte for byte, assembled ON THE DEVICE from what the run left there (occurrences, CIGARs, sequence assignment,
+ * the reads) and handed over as ONE finished buffer: no per-read strings, nothing formatted or copied twice.  The inputs are
+ * PACKED (an array of 10^6 - 10^7 char* is a host bottleneck of its own): seqs = the read characters the batch was created /
+ * staged with; ids = the raw identifier lines one after the other, read i = ids[id_offs[i], id_offs[i + 1]) (cleaned as
+ * Read::cleanUpRecord does, src/reads.h:43-52: first character dropped, cut at the first space); quals likewise, quals == NULL:
+ * every quality prints as "*" (an entry that is to print as "*" is packed as "*"); seq_names / seq_name_offs[n_seqs + 1] = the
+ * names of the reference sequences.  All offsets count bytes and are non-decreasing; lengths are 64-bit throughout (the text of a
+ * chunk can exceed 4 GB).
+ * *text (library-owned, page-locked, *length bytes + a terminating 0) stays valid until the next cmb_batch_run,
+ * cmb_batch_sam_device or cmb_batch_destroy on that batch.  *host_reads (may be NULL): how many reads were formatted by the host
+ * path instead — exactly those with an occurrence that runs over the end of its sequence (cmb_aln.spans == 1), which
+ * IndexInterface::findSeqName (src/indexinterface.cpp:833-899) trims, verifies again and may drop; their bytes are spliced into
+ * the text at their place.  Preconditions and error codes as cmb_batch_sam (run, alignments requested).  Composite batches format
+ * every sub-batch on its own stream; the text is in read order.  MAPQ (TextOcc::getMapQ, src/indexhelpers.h:378-388) comes from
+ * a table on the device: 60, 3, 2, then 1 up to nine and 0 from ten occurrences of minimal distance on.
+ * ALL mode, single-end reads, FM-index batches only: BEST mode (cmb_match_best), read pairs (cmb_pair_sam) and the b-move
+ * flavour (cmb_sam_chunk on caller-held records) keep the host formatter. */
+typedef struct {
+    const char* seqs;
+    const char* ids;
+    const uint64_t* id_offs; /* [n_reads + 1] */
+    const char* quals;       /* NULL: no qualities */
+    const uint64_t* qual_offs;
+    const char* seq_names;
+    const uint64_t* seq_name_offs; /* [n_seqs + 1] */
+    uint32_t n_seqs;
+} cmb_sam_inputs;
+int cmb_batch_sam_device(cmb_batch* b, const cmb_sam_inputs* in, int unmapped_records, int xa_tag, const char** text,
+                         uint64_t* length, uint64_t* host_reads);
+/* test hook: out[i] = the MAPQ the device path prints for i + 1 occurrences of minimal distance, evaluated on the device */
+int cmb_sam_device_mapq(uint32_t n, uint32_t* out);
 /* the same for occurrences and alignments the caller holds — cmb_batch_results + cmb_batch_alignments, or cmb_move_batch_results
  * (begin / end narrowed to 32 bits) + cmb_move_batch_alignments with the text-only index of cmb_move_text_index: occ_offs[n_reads + 1],
  * aln[i].cigar_off / cigar_len into cigar_ops.  `idx` serves the trimming of occurrences that run over a sequence end. */

@@ -26,6 +26,7 @@
 #include <array>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <stdexcept>
@@ -275,6 +276,30 @@ class SearchStrategy {
         } guard{b};
         check(cmb_batch_want_alignments(b, 1));
         check(cmb_batch_run(b));
+        if (const char* e = getenv("CMB_SAM_HOST"); !e || atoi(e) == 0) { // the text is written on the device (cmb_batch_sam_device)
+            const size_t nReads = offs.size() - 1;
+            const bool noQuals = quals.empty() || !quals.data();
+            std::string idBuf, qualBuf, nameBuf;
+            std::vector<uint64_t> idOffs(nReads + 1, 0), qualOffs(nReads + 1, 0), nameOffs(seqNames.size() + 1, 0);
+            for (size_t i = 0; i < nReads; i++) {
+                idBuf += ids[i];
+                idOffs[i + 1] = idBuf.size();
+                if (!noQuals) {
+                    qualBuf += quals[i] ? quals[i] : "*";
+                    qualOffs[i + 1] = qualBuf.size();
+                }
+            }
+            for (size_t i = 0; i < seqNames.size(); i++) {
+                nameBuf += seqNames[i];
+                nameOffs[i + 1] = nameBuf.size();
+            }
+            const cmb_sam_inputs in{seqs.data(),    idBuf.data(),    idOffs.data(),           noQuals ? nullptr : qualBuf.data(),
+                                    qualOffs.data(), nameBuf.data(), nameOffs.data(), (uint32_t)seqNames.size()};
+            const char* text = nullptr;
+            uint64_t length = 0;
+            check(cmb_batch_sam_device(b, &in, unmappedRecords, xaTag, &text, &length, nullptr));
+            return std::string(text, (size_t)length);
+        }
         const int64_t n = cmb_batch_sam(b, seqs.data(), ids.data(), quals.data(), seqNames.data(), unmappedRecords, xaTag, nullptr, 0);
         if (n < 0) check((int)n);
         std::string text((size_t)n + 1, '\0');
