@@ -618,7 +618,7 @@ struct cmb_batch {
     hipStream_t stream = nullptr;
     DevBuf<uint8_t> reads, seq;
     DevBuf<uint32_t> rec; // read records for k_parts / k_exact (k_prep)
-    DevBuf<uint4> exr;    // exact-match range pair of every part: [part][read x strand] (k_parts -> k_exact)
+    DevBuf<ExactTask> exq; // searches with further exact phases (k_parts -> k_exact)
     DevBuf<uint8_t> psel; // selected scheme per read x strand (bit 7: nothing to search)
     uint32_t recW = 0;
     DevBuf<uint64_t> offs;
@@ -861,8 +861,12 @@ static int batchCreateOne(cmb_index* idx, const cmb_strategy* st, uint32_t max_d
             b->strat.upload(&b->hostStrat, 1);
             b->parts.alloc((size_t)2 * n_reads);
         }
-        b->dfs.alloc((size_t)n_reads * 2 + 4096);
-        b->items.alloc((size_t)n_reads * 64 + 4096);
+        // first guesses; a queue that turns out too small grows and the search runs again (CMB_TEST_SMALL_POOLS starts the queues of
+        // the prologue from almost nothing so that tests exercise that path)
+        const bool smallPools = getenv("CMB_TEST_SMALL_POOLS") != nullptr;
+        b->dfs.alloc(smallPools ? 64 : (size_t)n_reads * 2 + 4096);
+        b->items.alloc(smallPools ? 64 : (size_t)n_reads * 64 + 4096);
+        b->exq.alloc(smallPools ? 16 : 65536);
         b->fm.alloc((size_t)n_reads * 8 + 4096);
         b->text.alloc((size_t)n_reads * 48 + 4096);
         b->cnt.alloc(8);
@@ -1124,13 +1128,10 @@ static int batchRunOne(cmb_batch* b) {
             const uint32_t pParts = b->k ? b->sNumParts : 1;
             const uint32_t stratBytes = (uint32_t)(((b->wide ? sizeof(DevStrategyKT<MAXP_WIDE>) : sizeof(DevStrategyK)) + 15) / 16 * 16);
             const uint32_t rdWords = 2 * ((b->maxLen + 31) / 32);
-            uint32_t nSlots = 1; // k = 0: one exact search per read x strand
             const bool longReads = b->maxLen > 256;
+            const uint32_t exCap = (uint32_t)std::min<size_t>(b->exq.n, 0xFFFFFFF0u);
             if (b->k) {
-                if (b->exr.n < (size_t)pParts * tasks) {
-                    b->exr.alloc((size_t)pParts * tasks);
-                    b->psel.alloc(tasks);
-                }
+                if (b->psel.n < tasks) b->psel.alloc(tasks);
                 const size_t pLds = stratBytes + (5 * pParts + rdWords) * 256 * sizeof(uint32_t);
                 if (b->wide) {
                     constexpr int W = MAXP_WIDE;
@@ -1138,27 +1139,27 @@ static int batchRunOne(cmb_batch* b) {
                                         : (b->sPartition == 0 ? k_parts<0, false, W> : b->sPartition == 1 ? k_parts<1, false, W> : k_parts<2, false, W>);
                     if (pLds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void*)kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pLds));
                     hipLaunchKernelGGL(kp, dim3(pSlots / 256), dim3(256), pLds, s, ix->d, b->stratW.p, nReads, b->k, b->maxLen, b->seq.p,
-                                       (const uint4*)b->rec.p, b->recW / 4, b->partsW.p, b->exr.p, b->psel.p, q);
+                                       (const uint4*)b->rec.p, b->recW / 4, b->partsW.p, b->psel.p, b->dfs.p, dfsCap, b->exq.p, exCap, q);
                 } else {
                     auto kp = longReads ? (b->sPartition == 0 ? k_parts<0, true> : b->sPartition == 1 ? k_parts<1, true> : k_parts<2, true>)
                                         : (b->sPartition == 0 ? k_parts<0, false> : b->sPartition == 1 ? k_parts<1, false> : k_parts<2, false>);
                     hipLaunchKernelGGL(kp, dim3(pSlots / 256), dim3(256), pLds, s, ix->d, b->strat.p, nReads,
-                                   b->k, b->maxLen, b->seq.p, (const uint4*)b->rec.p, b->recW / 4, b->parts.p, b->exr.p,
-                                   b->psel.p, q);
+                                   b->k, b->maxLen, b->seq.p, (const uint4*)b->rec.p, b->recW / 4, b->parts.p, b->psel.p,
+                                   b->dfs.p, dfsCap, b->exq.p, exCap, q);
                 }
-                nSlots = b->sMaxSearches + 1; // + the part-level pre-verification
             }
-            const uint64_t eTasks = (uint64_t)tasks * nSlots;
-            const uint32_t eSlots = (uint32_t)std::min<uint64_t>(((eTasks + 255) / 256) * 256, 256ull * 4096ull);
+            // k_exact: k = 0 one lane per read x strand; otherwise the ExactTasks k_parts left — their number is on the device, a small
+            // grid loops over them (none in the common case: every search of the multiple_opt schemes has one exact phase)
+            const uint32_t eSlots = b->k ? 256u * 256u : (uint32_t)std::min<uint64_t>((((uint64_t)tasks + 255) / 256) * 256, 256ull * 4096ull);
             const size_t eLds = stratBytes + (pParts + rdWords) * 256 * sizeof(uint32_t);
             if (b->wide)
                 hipLaunchKernelGGL((longReads ? k_exact<true, MAXP_WIDE> : k_exact<false, MAXP_WIDE>), dim3(eSlots / 256), dim3(256), eLds, s, ix->d,
-                                   b->stratW.p, nReads, b->k, b->maxLen, nSlots, b->seq.p, (const uint4*)b->rec.p, b->recW / 4, b->partsW.p,
-                                   b->exr.p, b->psel.p, b->dfs.p, dfsCap, q);
+                                   b->stratW.p, nReads, b->k, b->maxLen, b->seq.p, (const uint4*)b->rec.p, b->recW / 4, b->partsW.p,
+                                   b->exq.p, exCap, b->dfs.p, dfsCap, q);
             else
                 hipLaunchKernelGGL(longReads ? k_exact<true> : k_exact<false>, dim3(eSlots / 256), dim3(256), eLds,
-                               s, ix->d, b->strat.p, nReads, b->k, b->maxLen, nSlots, b->seq.p, (const uint4*)b->rec.p,
-                               b->recW / 4, b->parts.p, b->exr.p, b->psel.p, b->dfs.p, dfsCap, q);
+                               s, ix->d, b->strat.p, nReads, b->k, b->maxLen, b->seq.p, (const uint4*)b->rec.p,
+                               b->recW / 4, b->parts.p, b->exq.p, exCap, b->dfs.p, dfsCap, q);
             tm.end("k_partition");
             HIPCHK(hipGetLastError());
             HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
@@ -1219,7 +1220,8 @@ static int batchRunOne(cmb_batch* b) {
                             "for the seeding positions of this search strategy at this read length (the reference caps "
                             "the k-mer size, e.g. at 4 for kuch2 and 01*0: alignparameters.cpp:1070-1114, :1275-1278)");
             const uint32_t nDfs = hcnt[5];
-            if (!(flags & (FLAG_ITEM_OVERFLOW | FLAG_DFS_OVERFLOW)) && nDfs) {
+            if (verbose && b->k) fprintf(stderr, "[prologue] %u items, %u search tasks, %u searches with further exact phases\n", hcnt[0], nDfs, hcnt[4]);
+            if (!(flags & (FLAG_ITEM_OVERFLOW | FLAG_DFS_OVERFLOW | FLAG_EXACT_OVERFLOW)) && nDfs) {
                 tm.begin();
                 if (b->metric == CMB_METRIC_EDIT) {
                     // ---- frontier search: start pass, then (expand, events) per level until both queues drain
@@ -1421,14 +1423,18 @@ static int batchRunOne(cmb_batch* b) {
             }
             if (flags & FLAG_CAPACITY)
                 return fail(CMB_ERR_INTERNAL, "device search capacity exceeded (band width / descendants / stack)");
-            if (flags & (FLAG_ITEM_OVERFLOW | FLAG_FMOCC_OVERFLOW | FLAG_DFS_OVERFLOW)) {
+            if (flags & (FLAG_ITEM_OVERFLOW | FLAG_FMOCC_OVERFLOW | FLAG_DFS_OVERFLOW | FLAG_EXACT_OVERFLOW)) {
                 if (attempt >= 60) return fail(CMB_ERR_INTERNAL, "work queues keep overflowing");
+                if (verbose)
+                    fprintf(stderr, "[retry] queues too small:%s%s%s%s\n", hcnt[0] > q.itemCap ? " items" : "", hcnt[1] > q.fmCap ? " occurrences" : "",
+                            hcnt[5] > dfsCap ? " tasks" : "", hcnt[4] > exCap ? " exact" : "");
                 // (a search that stopped at the overflow has only counted what it needed up to there: the naive search of very
                 // short reads, which match all over the text, asks for orders of magnitude more than the first guess)
                 const size_t grow = b->hasNaive ? 8 : 2;
                 if (hcnt[0] > q.itemCap) b->items.alloc((size_t)hcnt[0] * grow + 1024);
                 if (hcnt[1] > q.fmCap) b->fm.alloc((size_t)hcnt[1] * grow + 1024);
                 if (hcnt[5] > dfsCap) b->dfs.alloc((size_t)hcnt[5] + hcnt[5] / 8 + 1024);
+                if (hcnt[4] > exCap) b->exq.alloc((size_t)hcnt[4] + hcnt[4] / 8 + 1024);
                 continue;
             }
             break;

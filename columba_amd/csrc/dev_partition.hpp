@@ -3,12 +3,15 @@
 // kernels whose loop bodies are small:
 //   k_parts  one lane per read x strand, PartMachine below: partitioning — uniform / static
 //            (calculateExactMatchRanges :158-190) or dynamic (seed :381-419 + greedy extension :299-379) —
-//            and the dynamic scheme selection (src/searchstrategy.h:2505-2537).  Output: the parts, the
-//            exact-match range pair of every part, the selected scheme.
-//   k_exact  one lane per (read x strand, search of the selected scheme) + one per read x strand for the
-//            part-level in-text pre-verification (:464-476): the exact phases of doRecSearch (:1181-1254) and
-//            the entry decision of recApproxMatchEditEntry (src/indexinterface.cpp:1306-1325); for k = 0
-//            one lane per read x strand runs exactMatchesOutput (src/indexinterface.cpp:947-1014).
+//            and the dynamic scheme selection (src/searchstrategy.h:2505-2537).  With the parts, their exact-match
+//            range pairs and the selected scheme still in LDS, the lane then starts the searches of its read x
+//            strand: the part-level in-text pre-verification (:464-476) and, per search, the entry of doRecSearch
+//            (:1181-1254) — the first part is the one just matched, so a search whose second phase is approximate
+//            becomes a DfsTask right here (recApproxMatchEditEntry, src/indexinterface.cpp:1306-1325).  Output:
+//            the parts and the selected scheme (the frontier reads them), work items, DfsTasks, and an ExactTask
+//            for every search that has further exact phases.
+//   k_exact  one lane per ExactTask: the remaining exact phases of doRecSearch, then items or a DfsTask; for
+//            k = 0 one lane per read x strand runs exactMatchesOutput (src/indexinterface.cpp:947-1014).
 // Both follow the same rule: every lane of a wavefront is at the SAME program point when it touches memory
 // (one "memory step" per loop iteration: rank blocks of an extension, k-mer table entries, or a record),
 // whatever logical phase its read is in.  What needs the irregular DFS is emitted as a compact DfsTask for
@@ -24,6 +27,15 @@ struct DfsTask {
     RangePair r;                      // start range (after the exact phases)
     uint32_t depth;                   // exact length matched so far
 };
+
+// a search with exact phases beyond its first part (k_parts -> k_exact); rsId = 0xFFFFFFFF: a hole
+struct alignas(16) ExactTask {
+    uint32_t rsId;
+    uint8_t scheme, search, pad[2];
+    uint32_t pad2[2];
+    RangePair r; // exact range pair of the search's first part
+};
+static_assert(sizeof(ExactTask) == 32, "k_exact loads an ExactTask as two 16-byte words");
 
 template <int MP> struct PartOutT { // per read x strand: the parts, needed again by k_dfs
     uint16_t pb[MP], pe[MP];
@@ -72,7 +84,7 @@ struct PartMachine {
         return e <= b ? 0u : e - b;
     }
     // counters
-    uint32_t cNode = 0, cExp = 0, flags = 0;
+    uint32_t cNode = 0, cExp = 0, cImm = 0, cStart = 0, flags = 0;
     // machine state
     int phase = PH_DONE;
     int numParts = 0;
@@ -381,9 +393,9 @@ struct PartMachine {
         }
     }
 
-    // partitioning done: select the scheme (MultipleSchemes::createSearches, searchstrategy.h:2505-2537) and
-    // hand parts, exact ranges and selection to k_exact
-    __device__ void finish(PartOutT<MP>* parts, uint4* exr, uint8_t* psel, uint32_t total) {
+    // partitioning done: select the scheme (MultipleSchemes::createSearches, searchstrategy.h:2505-2537) and write
+    // parts and selection for the frontier; returns the selected scheme
+    __device__ int finish(PartOutT<MP>* parts, uint8_t* psel) {
         int sel = 0;
         if (st.nSchemes > 1) {
             uint32_t tot = 0;
@@ -406,19 +418,56 @@ struct PartMachine {
             po.pe[i] = i < numParts ? (uint16_t)PE(i) : (uint16_t)0;
         }
         parts[rsId] = po;
-        for (int i = 0; i < numParts; i++) {
-            const RangePair r = EX(i);
-            exr[(size_t)i * total + rsId] = make_uint4(r.sa.b, r.sa.e, r.rev.b, r.rev.e);
-        }
         psel[rsId] = (uint8_t)sel;
         phase = PH_DONE;
+        return sel;
+    }
+
+    // The start of every search of scheme `sel` (doRecSearch, searchstrategy.cpp:1181-1254), one bit per search:
+    //   dfsMask   its approximate matching starts now — on the complete range (U[0] > 0) or, the first part being
+    //             the exact phase just matched, on that part's range (U[1] > 0);
+    //   exactMask it has further exact phases (U[1] == 0): k_exact goes on from the first part's range.
+    // A search whose first part is no wider than the in-text switch is covered by the part-level pre-verification.
+    __device__ void startSearches(int sel, uint32_t& dfsMask, uint32_t& exactMask) const {
+        const DevSchemeT<MP>& sch = st.sch[sel];
+        uint32_t dfs = 0, exact = 0; // (plain values: OR-ing into one of two references made the compiler address them in scratch)
+        for (uint32_t slot = 0; slot < sch.nSearches; slot++) {
+            const DevSearchT<MP>& s = sch.s[slot];
+            const bool whole = s.U[0] > 0;
+            const bool live = whole || EXW(s.order[0]) > ix.switchPoint;
+            const bool approx = whole || s.U[1] > 0;
+            const uint32_t bit = live ? 1u << slot : 0u;
+            dfs |= approx ? bit : 0u;
+            exact |= approx ? 0u : bit;
+        }
+        dfsMask = dfs;
+        exactMask = exact;
+    }
+    __device__ DfsTask dfsTask(int sel, uint32_t slot) const {
+        const DevSearchT<MP>& s = st.sch[sel].s[slot];
+        const bool whole = s.U[0] > 0; // recApproxMatchEditEntry on the complete range
+        const int f = s.order[0];
+        DfsTask t;
+        t.rsId = rsId;
+        t.scheme = (uint8_t)sel;
+        t.search = (uint8_t)slot;
+        t.idx = whole ? 0 : 1;
+        t.pad = 0;
+        t.r = whole ? RangePair{{0, ix.n}, {0, ix.n}} : EX(f);
+        t.depth = whole ? 0u : PE(f) - PB(f);
+        return t;
+    }
+    // part-level pre-verification (searchstrategy.cpp:464-476): the items of part i, none unless its range is 1 ...
+    // switchPoint wide
+    __device__ __forceinline__ uint32_t narrowWidth(int i) const {
+        const uint32_t w = EXW(i);
+        return w <= ix.switchPoint ? w : 0u;
     }
 };
 
-// ---- k_exact: one lane per (read x strand, slot) -----------------------------------------------------
-// slot < nSlots - 1 : search `slot` of the selected scheme (exact phases, then items or a DFS task);
-// slot = nSlots - 1 : the part-level in-text pre-verification (searchstrategy.cpp:464-476);
-// k = 0            : one lane per read x strand, exactMatchesOutput (indexinterface.cpp:947-1014).
+// ---- k_exact: one lane per ExactTask of k_parts --------------------------------------------------------
+// k > 0 : the exact phases of the search after its first part, then items or a DFS task;
+// k = 0 : one lane per read x strand, exactMatchesOutput (indexinterface.cpp:947-1014).
 enum : int { EX_IDLE = 0, EX_HDR, EX_LOAD, EX_RUN, EX_K0 };
 
 template <int MP = MAXP>
@@ -497,15 +546,11 @@ struct ExactLane {
         }
     }
 
-    // the search starts from the exact range of its first part (doRecSearch, searchstrategy.cpp:1181-1254)
-    __device__ void startSearch(const RangePair& first) {
-        const DevSearchT<MP>& s = st.sch[sel].s[slot];
+    // the search goes on from the exact range of its first part (doRecSearch, searchstrategy.cpp:1181-1254), which
+    // k_parts found wider than the in-text switch
+    __device__ void continueSearch(const RangePair& first) {
+        const int f = st.sch[sel].s[slot].order[0];
         cur = first;
-        if (cur.width() <= ix.switchPoint) { // covered by the part-level pre-verification
-            phase = EX_IDLE;
-            return;
-        }
-        const int f = s.order[0];
         partInSearch = 1;
         exactLength = PE(f) - PB(f);
         ci = 0;

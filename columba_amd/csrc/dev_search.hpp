@@ -78,10 +78,13 @@ enum : uint32_t { FLAG_ITEM_OVERFLOW = 1, FLAG_FMOCC_OVERFLOW = 2, FLAG_TEXT_OVE
                   // naive backtracking (dev_bfs_naive.hpp): its node queue
                   FLAG_NAIVE_Q = 8192,
                   // a phase whose first column does not fit the 32-bit in-index matrix (dev_bfs_edit.hpp: GeoN32): the batch re-runs on GeoN
-                  FLAG_NARROW_MATRIX = 16384 };
+                  FLAG_NARROW_MATRIX = 16384,
+                  // the list of searches with further exact phases (k_parts -> k_exact)
+                  FLAG_EXACT_OVERFLOW = 32768 };
 constexpr uint32_t FLAG_BITS[] = {FLAG_ITEM_OVERFLOW, FLAG_FMOCC_OVERFLOW, FLAG_TEXT_OVERFLOW, FLAG_CAPACITY,
                                   FLAG_UNSUPPORTED_READ, FLAG_DFS_OVERFLOW, FLAG_TRACE_RULE, FLAG_BFS_Q, FLAG_BFS_EV,
-                                  FLAG_BFS_F, FLAG_BFS_CTX, FLAG_BFS_ARENA, FLAG_SEED_OVERLAP, FLAG_NAIVE_Q, FLAG_NARROW_MATRIX};
+                                  FLAG_BFS_F, FLAG_BFS_CTX, FLAG_BFS_ARENA, FLAG_SEED_OVERLAP, FLAG_NAIVE_Q, FLAG_NARROW_MATRIX,
+                                  FLAG_EXACT_OVERFLOW};
 constexpr bool flagBitsDisjoint() {
     uint32_t seen = 0;
     for (uint32_t b : FLAG_BITS) {
@@ -109,7 +112,7 @@ struct Queues {
     uint32_t fmCap;
     TextOccRec* text;
     uint32_t textCap;
-    uint32_t* cnt; // [0] items, [1] fm, [2] text, [3] flags, [5] search tasks, [7] traceback tasks
+    uint32_t* cnt; // [0] items, [1] fm, [2] text, [3] flags, [4] searches with further exact phases, [5] search tasks, [7] traceback tasks
     unsigned long long* counters; // CMB_CNT_MAX
 };
 

@@ -300,7 +300,7 @@ __global__ void k_bfs_finish(BfsBufs B, Queues q) { // one block: per-block coun
 }
 
 
-// first approximate phase of every task (k_exact's DfsTask queue) -> frontier of pass 0
+// first approximate phase of every task (the DfsTask queue of k_parts and k_exact) -> frontier of pass 0
 template <class Geo = GeoN>
 __global__ void __launch_bounds__(256)
 k_bfs_start(DevIndex ix, const DevStrategyKT<Geo::MP>* __restrict__ stp, BfsBufs B, const DfsTask* __restrict__ tasks, uint32_t nTasks,
@@ -357,11 +357,16 @@ __device__ __forceinline__ bool takeExtend(const DevIndex& ix, int mode, const R
 // (the partitioning of every read costs about the same).  Every loop iteration has ONE memory step: each lane
 // issues the loads of its request — the two rank blocks of an extension (4 x 16 B from 2 sectors), the k-mer
 // table entries of its seeds, or its read record — before any reply is consumed.
+// When the last lane of a batch has its parts, the wavefront is converged again and every lane starts the searches
+// of its read x strand from what it holds in LDS: the items of the part-level pre-verification, a DfsTask per search
+// whose approximate matching begins at once, an ExactTask per search with further exact phases.  Queue space is
+// taken once per batch and queue for the whole wavefront, exactly as much as the batch needs (no holes).
 template <int PARTITION, bool LONG, int MP = MAXP>
 __global__ void __launch_bounds__(256, MP == MAXP ? 4 : 2)
 k_parts(DevIndex ix, const DevStrategyKT<MP>* __restrict__ stp, uint32_t nReads, uint32_t k, uint32_t maxLen,
         const uint8_t* __restrict__ seq, const uint4* __restrict__ rec, uint32_t recQ, PartOutT<MP>* __restrict__ parts,
-        uint4* __restrict__ exr, uint8_t* __restrict__ psel, Queues q) {
+        uint8_t* __restrict__ psel, DfsTask* __restrict__ dfsQ, uint32_t dfsCap, ExactTask* __restrict__ exQ, uint32_t exCap,
+        Queues q) {
     typedef DevStrategyKT<MP> DevStrategyK; // (the instance's table size)
     // LDS: a copy of the strategy tables, then per lane 5 x numParts partition words and 2 x ceil(maxLen/32)
     // read words
@@ -374,6 +379,11 @@ k_parts(DevIndex ix, const DevStrategyKT<MP>* __restrict__ stp, uint32_t nReads,
     PartMachine<PARTITION, MP> m(ix, lst, partLds + STRAT_WORDS, threadIdx.x, blockDim.x);
     m.setReadWords(maxLen);
     const uint32_t total = 2 * nReads;
+    bool ovI = false, ovD = false, ovE = false;
+    WaveChunk chI, chD, chE;
+    auto holeI = [&](uint32_t i) { q.items[i] = make_uint4(0xFFFFFFFFu, 0, 0, 0); };
+    auto holeD = [&](uint32_t i) { dfsQ[i].rsId = 0xFFFFFFFFu; };
+    auto holeE = [&](uint32_t i) { exQ[i].rsId = 0xFFFFFFFFu; };
     // Lock-step batches: every lane of the wavefront takes one read x strand, all load their read records, all
     // fetch their seeds, then all run the extension loop (one extension per iteration, the memory step in the
     // middle) until the last one has assigned every character.  Reads of one batch need about the same number of
@@ -412,24 +422,85 @@ k_parts(DevIndex ix, const DevStrategyKT<MP>* __restrict__ stp, uint32_t nReads,
                 m.resume(ok, child);
             }
         }
-        if (m.phase == PH_FIN) m.finish(parts, exr, psel, total);
+        // ---- the searches of the batch start here (all 64 lanes take part in the allocations; lanes without parts ask for nothing)
+        const bool fin = m.phase == PH_FIN;
+        int sel = 0;
+        uint32_t dfsMask = 0, exactMask = 0, nItems = 0;
+        if (fin) {
+            sel = m.finish(parts, psel);
+            m.startSearches(sel, dfsMask, exactMask);
+            for (int i = 0; i < m.numParts; i++) nItems += m.narrowWidth(i);
+        }
+        { // part-level pre-verification (searchstrategy.cpp:464-476): one item group per narrow part
+            uint32_t o = chI.alloc(&q.cnt[0], q.itemCap, nItems, 1u, ovI, holeI);
+            if (nItems) {
+                for (int i = 0; i < m.numParts; i++) {
+                    const uint32_t n = m.narrowWidth(i);
+                    if (!n) continue;
+                    const uint32_t bg = m.PB(i), row = m.EX(i).sa.b;
+                    uint32_t a, meta;
+                    if (lst.metric == 1) {
+                        m.cImm++; // verifyExactPartialMatchInText (fmindex.cpp:253)
+                        a = bg == 0 ? 0 : bg + k;
+                        meta = packMeta(0, k, 0, bg == 0, ITEM_EDIT);
+                    } else {
+                        a = bg;
+                        meta = packMeta(0, k, 0, 0, ITEM_HAMMING);
+                    }
+                    if (o != 0xFFFFFFFFu)
+                        for (uint32_t t = 0; t < n; t++) q.items[o++] = make_uint4(m.rsId, row + t, a, meta);
+                }
+            }
+        }
+        { // searches whose approximate matching starts now
+            uint32_t o = chD.alloc(&q.cnt[5], dfsCap, (uint32_t)__popc(dfsMask), 1u, ovD, holeD);
+            if (lst.metric == 1) m.cStart += (uint32_t)__popc(dfsMask);
+            if (o != 0xFFFFFFFFu)
+                for (uint32_t mk = dfsMask; mk; mk &= mk - 1u) dfsQ[o++] = m.dfsTask(sel, (uint32_t)__ffs((int)mk) - 1u);
+        }
+        { // searches with further exact phases: k_exact goes on from the range of their first part
+            uint32_t o = chE.alloc(&q.cnt[4], exCap, (uint32_t)__popc(exactMask), 1u, ovE, holeE);
+            if (o != 0xFFFFFFFFu)
+                for (uint32_t mk = exactMask; mk; mk &= mk - 1u) {
+                    const uint32_t slot = (uint32_t)__ffs((int)mk) - 1u;
+                    ExactTask t;
+                    t.rsId = m.rsId;
+                    t.scheme = (uint8_t)sel;
+                    t.search = (uint8_t)slot;
+                    t.pad[0] = t.pad[1] = 0;
+                    t.pad2[0] = t.pad2[1] = 0;
+                    t.r = m.EX(lst.sch[sel].s[slot].order[0]);
+                    exQ[o++] = t;
+                }
+        }
     }
-    const uint32_t local[2] = {m.cNode, m.cExp};
-    const int which[2] = {0, 7};
-    flushCounters(q, local, which, 2);
+    chI.fill(holeI);
+    chD.fill(holeD);
+    chE.fill(holeE);
+    if (ovI) m.flags |= FLAG_ITEM_OVERFLOW;
+    if (ovD) m.flags |= FLAG_DFS_OVERFLOW;
+    if (ovE) m.flags |= FLAG_EXACT_OVERFLOW;
+    const uint32_t local[4] = {m.cNode, m.cExp, m.cImm, m.cStart};
+    const int which[4] = {0, 7, 5, 6};
+    flushCounters(q, local, which, 4);
     if (m.flags) atomicOr(&q.cnt[3], m.flags);
 }
 
-// Exact phases of the searches + part-level pre-verification (dev_partition.hpp: ExactLane); k = 0: the whole
-// exact search.  One lane per (read x strand, slot), static round-robin; same one-memory-step loop.
+// The exact phases that remain after the first part of a search (dev_partition.hpp: ExactLane), for the ExactTasks
+// k_parts left (their number is on the device: a fixed grid loops over them); k = 0: the whole exact search, one lane
+// per read x strand.  Static round-robin; same one-memory-step loop.
 template <bool LONG, int MP = MAXP>
 __global__ void __launch_bounds__(256, MP == MAXP ? 4 : 2)
 k_exact(DevIndex ix, const DevStrategyKT<MP>* __restrict__ stp, uint32_t nReads, uint32_t k, uint32_t maxLen,
-        uint32_t nSlots, const uint8_t* __restrict__ seq, const uint4* __restrict__ rec, uint32_t recQ,
-        const PartOutT<MP>* __restrict__ parts, const uint4* __restrict__ exr, const uint8_t* __restrict__ psel,
+        const uint8_t* __restrict__ seq, const uint4* __restrict__ rec, uint32_t recQ,
+        const PartOutT<MP>* __restrict__ parts, const ExactTask* __restrict__ exQ, uint32_t exCap,
         DfsTask* __restrict__ dfsQ, uint32_t dfsCap, Queues q) {
     typedef DevStrategyKT<MP> DevStrategyK; // (the instance's table size)
-    typedef DevSchemeT<MP> DevScheme;
+    uint64_t nTasks = 2ull * nReads;
+    if (k != 0) {
+        nTasks = q.cnt[4];
+        if (nTasks == 0 || nTasks > exCap) return; // nothing goes on / the list overflowed (flagged by k_parts: the batch runs again)
+    }
     extern __shared__ uint32_t partLds[]; // strategy tables, then per lane numParts + 2 x ceil(maxLen/32) words
     constexpr uint32_t STRAT_WORDS = (uint32_t)((sizeof(DevStrategyK) + 15) / 16 * 4);
     for (uint32_t i = threadIdx.x; i < sizeof(DevStrategyK) / 4; i += blockDim.x)
@@ -437,23 +508,24 @@ k_exact(DevIndex ix, const DevStrategyKT<MP>* __restrict__ stp, uint32_t nReads,
     __syncthreads();
     const DevStrategyK& lst = *reinterpret_cast<const DevStrategyK*>(partLds);
     ExactLane<MP> m(ix, lst, partLds + STRAT_WORDS, threadIdx.x, blockDim.x, maxLen);
-    const uint32_t total = 2 * nReads;
-    const uint64_t nTasks = (uint64_t)total * nSlots;
     uint64_t nextT = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t task = 0;
     const int numParts = lst.numParts;
-    const uint32_t sw = ix.switchPoint;
     bool done = false, ovI = false, ovD = false;
     WaveChunk chI, chD;
     auto holeI = [&](uint32_t i) { q.items[i] = make_uint4(0xFFFFFFFFu, 0, 0, 0); };
     auto holeD = [&](uint32_t i) { dfsQ[i].rsId = 0xFFFFFFFFu; };
+    constexpr int NV = MP > 5 + MP / 4 ? MP : 5 + MP / 4; // an extension's rank blocks, or a read record and the parts
     for (;;) {
-        // (1) an idle lane takes its next (read x strand, slot)
+        // (1) an idle lane takes its next task
         if (!done && m.phase == EX_IDLE && !m.req) {
             if (nextT >= nTasks) done = true;
             else {
-                m.rsId = (uint32_t)(nextT / nSlots);
-                m.slot = (uint32_t)(nextT % nSlots);
-                m.seq = seq + (size_t)m.rsId * maxLen;
+                task = (uint32_t)nextT;
+                if (k == 0) {
+                    m.rsId = task;
+                    m.seq = seq + (size_t)m.rsId * maxLen;
+                }
                 m.phase = k == 0 ? EX_LOAD : EX_HDR;
                 nextT += (uint64_t)gridDim.x * blockDim.x;
             }
@@ -464,27 +536,22 @@ k_exact(DevIndex ix, const DevStrategyKT<MP>* __restrict__ stp, uint32_t nReads,
             else if (m.phase == EX_K0) m.advanceK0();
         }
         // (3) the memory step
-        uint4 v[MP];
-        uint32_t hdr = 0;
+        uint4 v[NV];
         const int ph = done ? EX_IDLE : m.phase;
-        const bool isPost = m.slot == nSlots - 1;
         if (m.req) {
             issueExtend(ix, m.reqMode, m.cur, v);
-        } else if (ph == EX_HDR) { // scheme selection + parts
-            hdr = psel[m.rsId];
-            const uint4* pp = reinterpret_cast<const uint4*>(parts + m.rsId);
+        } else if (ph == EX_HDR) { // the task
+            const uint4* pt = reinterpret_cast<const uint4*>(exQ + task);
+            v[0] = pt[0];
+            v[1] = pt[1];
+        } else if (ph == EX_LOAD) { // read record (+ parts)
 #pragma unroll
-            for (int j = 0; j < MP / 4; j++) v[j] = pp[j]; // (pb[MP], pe[MP]: 4 MP bytes)
-        } else if (ph == EX_LOAD) {
-            if (k == 0 || !isPost) { // read record (+ exact range of the first part of the search)
+            for (uint32_t j = 0; j < 5; j++)
+                if (j < recQ) v[j] = rec[(size_t)m.rsId * recQ + j];
+            if (k != 0) {
+                const uint4* pp = reinterpret_cast<const uint4*>(parts + m.rsId);
 #pragma unroll
-                for (uint32_t j = 0; j < 5; j++)
-                    if (j < recQ) v[j] = rec[(size_t)m.rsId * recQ + j];
-                if (k != 0) v[5] = exr[(size_t)lst.sch[m.sel].s[m.slot].order[0] * total + m.rsId];
-            } else { // exact ranges of all parts
-#pragma unroll
-                for (int i = 0; i < MP; i++)
-                    if (i < numParts) v[i] = exr[(size_t)i * total + m.rsId];
+                for (int j = 0; j < MP / 4; j++) v[5 + j] = pp[j]; // (pb[MP], pe[MP]: 4 MP bytes)
             }
         }
         if (m.req) {
@@ -493,64 +560,27 @@ k_exact(DevIndex ix, const DevStrategyKT<MP>* __restrict__ stp, uint32_t nReads,
             m.req = false;
             m.resume(ok, child);
         } else if (ph == EX_HDR) {
-            m.sel = (int)(hdr & 0x7Fu);
-            const uint16_t* pv = reinterpret_cast<const uint16_t*>(v);
-#pragma unroll
-            for (int i = 0; i < MP; i++)
-                if (i < numParts) m.PBE(i) = (uint32_t)pv[i] | ((uint32_t)pv[MP + i] << 16);
-            m.phase = EX_LOAD;
-            if (hdr & 0x80u) m.phase = EX_IDLE; // unsupported read (reported by k_parts)
-            else if (!isPost) {
-                const DevScheme& sch = lst.sch[m.sel];
-                if (m.slot >= sch.nSearches) m.phase = EX_IDLE;
-                else if (sch.s[m.slot].U[0] > 0) { // recApproxMatchEditEntry on the complete range
-                    if (lst.metric == 1) m.cStart++;
-                    m.emitDfs(0, RangePair{{0, ix.n}, {0, ix.n}}, 0);
-                    m.phase = EX_IDLE;
-                }
-            }
+            m.rsId = v[0].x;
+            m.sel = (int)(v[0].y & 0xFFu);
+            m.slot = (v[0].y >> 8) & 0xFFu;
+            m.cur = RangePair{{v[1].x, v[1].y}, {v[1].z, v[1].w}};
+            m.seq = seq + (size_t)m.rsId * maxLen;
+            m.phase = m.rsId == 0xFFFFFFFFu ? EX_IDLE : EX_LOAD; // (a hole)
         } else if (ph == EX_LOAD) {
+            m.template takeRecord<LONG>(v, rec, recQ);
             if (k == 0) {
-                m.template takeRecord<LONG>(v, rec, recQ);
                 m.cur = RangePair{{0, ix.n}, {0, 0}};
                 m.k0i = m.len;
                 m.phase = m.len == 0 ? EX_IDLE : EX_K0;
-            } else if (!isPost) {
-                m.template takeRecord<LONG>(v, rec, recQ);
-                m.startSearch(RangePair{{v[5].x, v[5].y}, {v[5].z, v[5].w}});
             } else {
-                m.phase = EX_IDLE;
-            }
-        }
-        // (4) part-level pre-verification (searchstrategy.cpp:464-476): one item group per narrow part
-        if (__ballot(ph == EX_LOAD && k != 0 && isPost) != 0ull) {
-            const bool mine = ph == EX_LOAD && k != 0 && isPost;
+                const uint16_t* pv = reinterpret_cast<const uint16_t*>(v + 5);
 #pragma unroll
-            for (int i = 0; i < MP; i++) {
-                if (i >= numParts) break;
-                uint32_t n = 0, a = 0, meta = 0;
-                if (mine) {
-                    const uint32_t width = v[i].y > v[i].x ? v[i].y - v[i].x : 0u;
-                    if (width != 0 && width <= sw) {
-                        n = width;
-                        const uint32_t bg = m.PB(i);
-                        if (lst.metric == 1) {
-                            m.cImm++; // verifyExactPartialMatchInText (fmindex.cpp:253)
-                            a = bg == 0 ? 0 : bg + k;
-                            meta = packMeta(0, k, 0, bg == 0, ITEM_EDIT);
-                        } else {
-                            a = bg;
-                            meta = packMeta(0, k, 0, 0, ITEM_HAMMING);
-                        }
-                    }
-                }
-                if (__ballot(n > 0) == 0ull) continue;
-                const uint32_t o = chI.alloc(&q.cnt[0], q.itemCap, n, 256u, ovI, holeI);
-                if (n && o != 0xFFFFFFFFu)
-                    for (uint32_t t = 0; t < n; t++) q.items[o + t] = make_uint4(m.rsId, v[i].x + t, a, meta);
+                for (int i = 0; i < MP; i++)
+                    if (i < numParts) m.PBE(i) = (uint32_t)pv[i] | ((uint32_t)pv[MP + i] << 16);
+                m.continueSearch(m.cur);
             }
         }
-        // (5) queue what the searches staged
+        // (4) queue what the searches staged
         if (__ballot(m.stN > 0) != 0ull) {
             const uint32_t o = chI.alloc(&q.cnt[0], q.itemCap, m.stN, 256u, ovI, holeI);
             if (m.stN && o != 0xFFFFFFFFu)
