@@ -49,7 +49,7 @@ EXPORTS = [
     "cmb_pair_best_create", "cmb_pair_best_set_trim", "cmb_pair_best_cutoff", "cmb_pair_best_seed", "cmb_pair_best_advance", "cmb_pair_best_supply", "cmb_pair_best_sam",
     "cmb_pair_best_destroy",
     "cmb_read_prepare", "cmb_batch_sam", "cmb_batch_sam_device", "cmb_sam_device_mapq", "cmb_batch_filter_per_strand", "cmb_match_best", "cmb_best_sizes", "cmb_best_results",
-    "cmb_best_destroy",
+    "cmb_best_destroy", "cmb_match_best_device", "cmb_best_host_reads", "cmb_best_sam_device", "cmb_best_timings",
     "cmb_move_create", "cmb_move_destroy", "cmb_move_device_bytes", "cmb_move_info", "cmb_move_complete_range", "cmb_move_rows",
     "cmb_move_extend_batch", "cmb_move_extend_bench", "cmb_move_locate_batch", "cmb_move_match_exact", "cmb_move_last_timings", "cmb_move_kmer_table",
     "cmb_move_layout_of", "cmb_move_create_empty", "cmb_move_device_arrays", "cmb_move_validate",
@@ -286,6 +286,10 @@ def lib():
         L.cmb_batch_allow_unsupported.argtypes = [vp, i32]
         L.cmb_batch_read_status.argtypes = [vp, vp, C.POINTER(u32)]
         L.cmb_match_best.argtypes = [vp, vp, u32, u32, vp, vp, u32, C.POINTER(vp)]
+        L.cmb_match_best_device.argtypes = [vp, vp, u32, u32, vp, vp, u32, C.POINTER(vp)]
+        L.cmb_best_host_reads.argtypes = [vp, vp, C.POINTER(u32)]
+        L.cmb_best_timings.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), u32]
+        L.cmb_best_sam_device.argtypes = [vp, C.POINTER(SamInputs), i32, i32, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
         L.cmb_best_sizes.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
         L.cmb_best_results.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp, vp, vp]
         L.cmb_best_destroy.argtypes = [vp]
@@ -913,6 +917,21 @@ def match_batch(index: Index, strategy: SearchStrategy, max_distance: int, reads
         b.close()
 
 
+def _best_results(h, n_reads: int):
+    n, nops = C.c_uint64(), C.c_uint64()
+    _chk(lib().cmb_best_sizes(h, C.byref(n), C.byref(nops)))
+    occ = np.zeros(max(int(n.value), 1), OCC_DTYPE)
+    aln = np.zeros(max(int(n.value), 1), ALN_DTYPE)
+    ops = np.zeros(max(int(nops.value), 1), np.uint16)
+    o = np.zeros(n_reads + 1, np.uint64)
+    best = np.zeros(max(n_reads, 1), np.uint32)
+    hits = np.zeros(max(n_reads, 1), np.uint32)
+    cnt = np.zeros(len(COUNTER_NAMES), np.uint64)
+    _chk(lib().cmb_best_results(h, _p(occ), _p(aln), occ.shape[0], _p(ops), ops.shape[0], _p(o), _p(best), _p(hits), _p(cnt)))
+    return (occ[:n.value], aln[:n.value], ops[:nops.value], o, best[:n_reads], hits[:n_reads],
+            dict(zip(COUNTER_NAMES, cnt.tolist())))
+
+
 def match_best(index, strategy: SearchStrategy, reads: Sequence[bytes], x: int = 0, min_identity: int = 95, kmer_size: int = 10):
     """``SearchStrategy::matchApproxBestPlusX`` for a whole chunk (the reference's default mode): returns
     (occurrences, alignments, CIGAR operations, per-read offsets, best distance per read, hits at that distance, counters).
@@ -924,20 +943,86 @@ def match_best(index, strategy: SearchStrategy, reads: Sequence[bytes], x: int =
     else:
         _chk(lib().cmb_match_best(index.h, strategy.h, x, min_identity, _p(buf), _p(offs), len(reads), C.byref(h)))
     try:
-        n, nops = C.c_uint64(), C.c_uint64()
-        _chk(lib().cmb_best_sizes(h, C.byref(n), C.byref(nops)))
-        occ = np.zeros(max(int(n.value), 1), OCC_DTYPE)
-        aln = np.zeros(max(int(n.value), 1), ALN_DTYPE)
-        ops = np.zeros(max(int(nops.value), 1), np.uint16)
-        o = np.zeros(len(reads) + 1, np.uint64)
-        best = np.zeros(max(len(reads), 1), np.uint32)
-        hits = np.zeros(max(len(reads), 1), np.uint32)
-        cnt = np.zeros(len(COUNTER_NAMES), np.uint64)
-        _chk(lib().cmb_best_results(h, _p(occ), _p(aln), occ.shape[0], _p(ops), ops.shape[0], _p(o), _p(best), _p(hits), _p(cnt)))
-        return (occ[:n.value], aln[:n.value], ops[:nops.value], o, best[:len(reads)], hits[:len(reads)],
-                dict(zip(COUNTER_NAMES, cnt.tolist())))
+        return _best_results(h, len(reads))
     finally:
         lib().cmb_best_destroy(h)
+
+
+class BestDevice:
+    """A BEST-mode result whose lists stay on the device (cmb_match_best_device): ``results()`` downloads them, ``sam_device()``
+    writes the chunk's SAM text from them on the device (cmb_best_sam_device).  FM-index flavour, single-end reads."""
+
+    def __init__(self, index: "Index", strategy: SearchStrategy, reads: Sequence[bytes], x: int = 0, min_identity: int = 95):
+        self._packed = pack_reads(reads)
+        self.n_reads = len(reads)
+        self.index = index
+        self.h = C.c_void_p()
+        _chk(lib().cmb_match_best_device(index.h, strategy.h, x, min_identity, _p(self._packed[0]), _p(self._packed[1]), self.n_reads,
+                                         C.byref(self.h)))
+
+    def results(self):
+        """the tuple of ``match_best``"""
+        return _best_results(self.h, self.n_reads)
+
+    def host_reads(self) -> np.ndarray:
+        """per read: 1 where the bookkeeping went through the host (an occurrence over a sequence end under edit distance)"""
+        status = np.zeros(max(self.n_reads, 1), np.uint8)
+        n = C.c_uint32()
+        _chk(lib().cmb_best_host_reads(self.h, _p(status), C.byref(n)))
+        assert int(status[:self.n_reads].sum()) == n.value
+        return status[:self.n_reads]
+
+    def timings(self) -> Dict[str, float]:
+        """where the matching call spent its time, in ms (cmb_best_timings)"""
+        names = (C.c_char_p * 64)()
+        ms = (C.c_float * 64)()
+        n = lib().cmb_best_timings(self.h, names, ms, 64)
+        return {names[i].decode(): float(ms[i]) for i in range(n)}
+
+    def sam_device_bytes(self, ids, quals, seq_names, unmapped: bool = True, xa: bool = False):
+        """(the SAM text of the chunk as bytes, number of reads the host formatted); inputs as ``Batch.sam_device_bytes``"""
+        bi, oi = pack_fields(ids)
+        bn, on = pack_fields(seq_names)
+        bq, oq = pack_fields(quals) if quals is not None else (None, None)
+        if oi.shape[0] - 1 != self.n_reads or (oq is not None and oq.shape[0] - 1 != self.n_reads):
+            raise ValueError("one identifier and one quality per read")
+        inp = SamInputs(_p(self._packed[0]), _p(bi), _p(oi), _p(bq) if bq is not None else None, _p(oq) if oq is not None else None,
+                        _p(bn), _p(on), on.shape[0] - 1)
+        text, n, host = C.c_void_p(), C.c_uint64(), C.c_uint64()
+        _chk(lib().cmb_best_sam_device(self.h, C.byref(inp), int(unmapped), int(xa), C.byref(text), C.byref(n), C.byref(host)))
+        return C.string_at(text.value, n.value) if n.value else b"", int(host.value)
+
+    def sam_device(self, ids, quals, seq_names, unmapped: bool = True, xa: bool = False):
+        t, host = self.sam_device_bytes(ids, quals, seq_names, unmapped, xa)
+        return t.decode(), host
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.cmb_best_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+
+def match_best_device(index: "Index", strategy: SearchStrategy, reads: Sequence[bytes], x: int = 0, min_identity: int = 95):
+    """``match_best`` with the strata bookkeeping on the device (cmb_match_best_device): the tuple of ``match_best`` plus the per-read
+    host-read status (``BestDevice.host_reads``)"""
+    b = BestDevice(index, strategy, reads, x, min_identity)
+    try:
+        return b.results() + (b.host_reads(),)
+    finally:
+        b.close()
+
+
+def best_sam_device(index: "Index", strategy: SearchStrategy, reads: Sequence[bytes], ids, quals, seq_names, x: int = 0,
+                    min_identity: int = 95, unmapped: bool = True, xa: bool = False):
+    """(SAM text of a chunk in BEST mode written on the device, number of host-formatted reads); ids / quals / seq_names: lists or
+    packed (bytes, offsets) pairs, as ``Batch.sam_device``"""
+    b = BestDevice(index, strategy, reads, x, min_identity)
+    try:
+        return b.sam_device(ids, quals, seq_names, unmapped, xa)
+    finally:
+        b.close()
 
 
 def shard_bounds(n_reads: int, world_size: int, rank: int) -> Tuple[int, int]:

@@ -4,6 +4,7 @@
 #include "host_schemes.hpp"
 #include "kernels.hpp"
 #include "dev_sam.hpp"
+#include "dev_best.hpp"
 
 #include <chrono>
 #include <cstring>
@@ -2903,6 +2904,40 @@ struct cmb_best {
     std::vector<uint64_t> offs;
     std::vector<uint32_t> best, nHits;
     uint64_t cnts[CMB_CNT_MAX];
+    // cmb_match_best_device: the final lists in HBM, in the layout k_sam_write reads (SamCtx: occurrences as uint4, AlnRec, CIGAR runs
+    // at BEST_OPS_STRIDE stored end to begin, 64-bit offsets per read); occ / aln / ops above are filled from them on first use
+    bool onDevice = false, fetched = false;
+    cmb_index* ix = nullptr;
+    int metric = 1;
+    uint32_t nReads = 0, x = 0;
+    uint64_t nOcc = 0;
+    DevBuf<uint4> dOcc;
+    DevBuf<AlnRec> dAln;
+    DevBuf<uint16_t> dOps;
+    DevBuf<uint64_t> dOffs;
+    DevBuf<uint32_t> dBest, dHits;
+    std::vector<uint8_t> hostRead; // reads whose bookkeeping went through the host (an occurrence over a sequence end, edit distance)
+    uint32_t nHostReads = 0;
+    // cmb_best_sam_device: the chunk's raw reads and packed inputs, the plan, the text
+    DevBuf<uint8_t> samReads, samIds, samQuals, samNames, samSide, samText, scanTmp;
+    DevBuf<uint64_t> samReadOffs, samIdOffs, samQualOffs, samNameOffs, samLen, samOffs, samSideOffs;
+    DevBuf<SamPlan> samPlan;
+    DevBuf<uint32_t> samSideReads;
+    DevBuf<uint8_t> samHostFlag;
+    PinnedBuf<char> samOut;
+    std::vector<uint64_t> readOffs; // the chunk's read offsets, as given to cmb_match_best_device
+    // cmb_best_timings: host time per phase of the call (every phase ends in a synchronise) and, summed over the strata, the
+    // device time of the batches' kernels as cmb_batch_timings names them
+    std::vector<std::pair<std::string, double>> times;
+    void addTime(const std::string& name, double ms) {
+        for (auto& t : times)
+            if (t.first == name) {
+                t.second += ms;
+                return;
+            }
+        times.push_back({name, ms});
+    }
+    bool readsUp = false;
 };
 
 namespace {
@@ -3152,6 +3187,618 @@ extern "C" int cmb_match_best(cmb_index* idx, const cmb_strategy* st, uint32_t x
     // (MAX_K, definitions.h:50)
     return matchBestWith(idx, st, 13u, true, run, x, min_identity, seqs, offs, n_reads, out);
 }
+// ---- BEST mode with the bookkeeping on the device (dev_best.hpp) ------------------------------------------------------------------
+// The stratum loop and every per-read decision are matchBestWith's (above; searchstrategy.cpp:623-712); what it keeps in vectors per
+// read, strand and distance is here a pool of records in HBM plus, per read, a few words on the host: which distances hold an
+// occurrence / an occurrence inside one sequence (from k_best_scan), which went through checkAlignments, best, k, prevK.  The host
+// touches those words once per read and stratum and no occurrence — except for the reads that keep an occurrence over a sequence end
+// under edit distance: trimming verifies again and moves the occurrence to another distance (checkAlignments, :536-571), so from that
+// stratum on such a read's lists live in host vectors as in matchBestWith, and its final records are spliced into the device lists.
+namespace {
+struct BestState {
+    uint8_t cutOff = 0, best = 0, k = 0, prevK = 0, maxED = 0, proc = 0; // proc: the distances below it have been processed (both strands)
+    bool bestFound = false, finished = false, host = false;
+    uint16_t any[2] = {0, 0}, asg[2] = {0, 0}, chk[2] = {0, 0};
+};
+struct BestHostRead {
+    std::vector<std::vector<BestOcc>> ov[2];
+    std::string fw, rc;
+};
+struct BestPoolBufs {
+    DevBuf<uint4> occ;
+    DevBuf<AlnRec> aln;
+    DevBuf<uint16_t> ops;
+    DevBuf<uint32_t> read;
+    uint64_t n = 0, cap = 0;
+    BestPool at(uint64_t i) { return BestPool{occ.p + i, aln.p + i, ops.p + i * BEST_OPS_STRIDE, read.p + i}; }
+    void reserve(uint64_t want) { // (the exact size is known before a record is written: the pool never overflows)
+        if (want <= cap) return;
+        const uint64_t c = want + want / 2 + 4096;
+        BestPoolBufs f;
+        f.occ.alloc(c), f.aln.alloc(c), f.ops.alloc(c * BEST_OPS_STRIDE), f.read.alloc(c);
+        if (n) {
+            HIPCHK(hipMemcpy(f.occ.p, occ.p, n * sizeof(uint4), hipMemcpyDeviceToDevice));
+            HIPCHK(hipMemcpy(f.aln.p, aln.p, n * sizeof(AlnRec), hipMemcpyDeviceToDevice));
+            HIPCHK(hipMemcpy(f.ops.p, ops.p, n * BEST_OPS_STRIDE * sizeof(uint16_t), hipMemcpyDeviceToDevice));
+            HIPCHK(hipMemcpy(f.read.p, read.p, n * sizeof(uint32_t), hipMemcpyDeviceToDevice));
+        }
+        std::swap(occ.p, f.occ.p), std::swap(occ.n, f.occ.n);
+        std::swap(aln.p, f.aln.p), std::swap(aln.n, f.aln.n);
+        std::swap(ops.p, f.ops.p), std::swap(ops.n, f.ops.n);
+        std::swap(read.p, f.read.p), std::swap(read.n, f.read.n);
+        cap = c;
+    }
+};
+template <typename T> void scanExclusive(DevBuf<uint8_t>& tmp, const T* in, uint64_t* out, size_t n) {
+    size_t bytes = 0;
+    HIPCHK(rocprim::exclusive_scan(nullptr, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), (hipStream_t)0));
+    if (tmp.n < bytes || !tmp.p) tmp.alloc(bytes + 256);
+    HIPCHK(rocprim::exclusive_scan(tmp.p, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), (hipStream_t)0));
+}
+inline BestOcc bestOccOf(const uint4& o, const AlnRec& a, const uint16_t* ops) { // (CIGAR runs are stored end to begin)
+    BestOcc b;
+    b.occ = cmb_occ{o.x, o.y, o.z, o.w};
+    const uint32_t nOps = std::min<uint32_t>(a.nOps, BEST_OPS_STRIDE);
+    b.aln = cmb_aln{a.seqId, a.seqBegin, 0, (uint16_t)nOps, (uint16_t)a.spans, 0};
+    for (uint32_t j = 0; j < nOps; j++) b.ops.push_back(ops[nOps - 1 - j]);
+    return b;
+}
+} // namespace
+
+extern "C" int cmb_match_best_device(cmb_index* idx, const cmb_strategy* st, uint32_t x, uint32_t min_identity, const char* seqs,
+                                     const uint64_t* offs, uint32_t n_reads, cmb_best** out) {
+    if (!idx || !st || !offs || !out || (!seqs && n_reads)) return fail(CMB_ERR_INVALID, "null argument");
+    if (min_identity < 50 || min_identity > 100) return fail(CMB_ERR_INVALID, "the minimal identity lies between 50 and 100");
+    if (idx->textOnly) return fail(CMB_ERR_INVALID, "this index holds only the text (cmb_index_create_text_only): nothing can be matched on it");
+    try {
+        useDevice(idx->device);
+        uint32_t maxSupported = 0;
+        while (st->schemes.count(maxSupported + 1) && !st->schemes.at(maxSupported + 1).empty()) maxSupported++;
+        maxSupported = std::min<uint32_t>(maxSupported, 13u); // (MAX_K, definitions.h:50)
+        const bool edit = st->metric != CMB_METRIC_HAMMING;
+        std::unique_ptr<cmb_best> R(new cmb_best());
+        memset(R->cnts, 0, sizeof(R->cnts));
+        R->onDevice = true, R->ix = idx, R->metric = st->metric, R->nReads = n_reads, R->x = x;
+        R->readOffs.assign(offs, offs + n_reads + 1);
+        std::vector<BestState> sv(n_reads);
+        std::map<uint32_t, BestHostRead> hr;
+        for (uint32_t i = 0; i < n_reads; i++) {
+            const uint32_t len = (uint32_t)(offs[i + 1] - offs[i]);
+            sv[i].cutOff = (uint8_t)std::min<uint32_t>(std::min<uint32_t>(13u, maxSupported), (len * (100 - min_identity)) / 100); // getMaxED (:1797)
+            sv[i].best = sv[i].cutOff + 1;
+        }
+        BestPoolBufs pool;
+        DevBuf<uint8_t> dMinD, dMode, tmp;
+        DevBuf<uint32_t> dIds, dList;
+        DevBuf<unsigned long long> dMasks;
+        DevBuf<uint64_t> dCnt, dPoff;
+        BestPoolBufs stage;
+        std::vector<uint8_t> hMinD, hMode(n_reads, 0);
+        std::vector<unsigned long long> hMasks;
+        auto nonEmpty = [&](uint32_t i, int s2, uint32_t d) -> bool {
+            return sv[i].host ? !hr[i].ov[s2][d].empty() : ((sv[i].any[s2] >> d) & 1u) != 0;
+        };
+        // checkAlignments (:536-571).  On the device's side an occurrence is assigned (it lies inside one sequence) or dropped
+        // (Hamming distance never trims); on the host's side it is matchBestWith's.
+        auto checkAlignments = [&](uint32_t i, int s2, uint32_t l, uint32_t cutOffTrim) {
+            BestState& r = sv[i];
+            if (l > r.cutOff) return;
+            if (!r.host) {
+                const uint16_t bit = (uint16_t)(1u << l);
+                r.any[s2] = (uint16_t)((r.any[s2] & ~bit) | (r.asg[s2] & bit));
+                r.chk[s2] |= bit;
+                if ((r.asg[s2] & bit) && l < r.best) r.best = (uint8_t)l;
+                return;
+            }
+            BestHostRead& h = hr[i];
+            std::vector<BestOcc> assigned, trimmed;
+            for (BestOcc& o : h.ov[s2][l]) {
+                if (o.aln.spans == 0 || o.aln.spans == 3) { // FOUND (3: checked before)
+                    o.aln.spans = 3;
+                    assigned.push_back(std::move(o));
+                    if (l < r.best) r.best = (uint8_t)l;
+                } else if (o.aln.spans == 1) {
+                    if (trimOccurrence(idx, s2 ? h.rc : h.fw, cutOffTrim, st->metric, o, R->cnts) && o.occ.distance > l &&
+                        o.occ.distance < h.ov[s2].size())
+                        trimmed.push_back(std::move(o));
+                }
+            }
+            h.ov[s2][l] = std::move(assigned);
+            for (BestOcc& o : trimmed) {
+                o.aln.spans = 3; // (removeTrimmingLabel)
+                const uint32_t d = o.occ.distance;
+                h.ov[s2][d].push_back(std::move(o));
+            }
+        };
+        // one stratum for a set of reads: ALL-mode search of both strands at distance k, every strand filtered by itself; the batch's
+        // lists stay where they are
+        auto runStratum = [&](const std::vector<uint32_t>& ids, uint32_t k) -> int {
+            const uint32_t n = (uint32_t)ids.size();
+            auto t0 = std::chrono::steady_clock::now();
+            auto lap = [&](const char* what) {
+                auto t1 = std::chrono::steady_clock::now();
+                R->addTime(what, std::chrono::duration<double, std::milli>(t1 - t0).count());
+                t0 = t1;
+            };
+            std::string cat;
+            std::vector<uint64_t> o(ids.size() + 1, 0);
+            for (size_t j = 0; j < ids.size(); j++) {
+                cat.append(seqs + offs[ids[j]], seqs + offs[ids[j] + 1]);
+                o[j + 1] = cat.size();
+            }
+            lap("host: gather of the stratum's reads");
+            cmb_batch* b = nullptr;
+            int rcode = cmb_batch_create(idx, st, k, cat.data(), o.data(), n, &b);
+            if (rcode) return rcode;
+            struct Guard {
+                cmb_batch* b;
+                ~Guard() { cmb_batch_destroy(b); }
+            } guard{b};
+            cmb_batch_filter_per_strand(b, 1);
+            cmb_batch_want_alignments(b, 1);
+            lap("host: cmb_batch_create");
+            if ((rcode = cmb_batch_run(b))) return rcode;
+            lap("host: cmb_batch_run");
+            for (int i = 0; i < CMB_CNT_MAX; i++) R->cnts[i] += b->cnts[i];
+            std::vector<cmb_batch*> parts;
+            if (b->subs.empty()) parts.push_back(b);
+            else parts = b->subs;
+            for (const cmb_batch* c : parts)
+                for (const KernelTime& t : c->times) R->addTime(std::string("strata: ") + t.name, t.ms);
+            // processSeq (:791-812): what lies below the first distance not processed yet is dropped
+            hMinD.resize(n);
+            for (uint32_t j = 0; j < n; j++) hMinD[j] = (uint8_t)std::min<uint32_t>(sv[ids[j]].proc, k);
+            growTo(dMinD, n), growTo(dIds, n), growTo(dMasks, n), growTo(dCnt, (size_t)n + 1), growTo(dPoff, (size_t)n + 1);
+            HIPCHK(hipMemcpy(dMinD.p, hMinD.data(), n, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(dIds.p, ids.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+            HIPCHK(hipMemset(dCnt.p + n, 0, sizeof(uint64_t)));
+            uint32_t base = 0;
+            for (cmb_batch* c : parts) {
+                if (c->nReads)
+                    hipLaunchKernelGGL(k_best_scan, dim3((c->nReads + 3u) / 4u), dim3(256), 0, 0, c->foffs.p, c->fout.p, c->alnRec.p, c->nReads,
+                                       dMinD.p + base, dMasks.p + base, dCnt.p + base);
+                base += c->nReads;
+            }
+            HIPCHK(hipGetLastError());
+            scanExclusive(tmp, dCnt.p, dPoff.p, (size_t)n + 1);
+            uint64_t kept = 0;
+            hMasks.resize(n);
+            HIPCHK(hipMemcpy(&kept, dPoff.p + n, sizeof(uint64_t), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(hMasks.data(), dMasks.p, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+            const uint64_t poolBase = pool.n;
+            if (poolBase + kept >= 0xFFFFFFFFull) return fail(CMB_ERR_UNSUPPORTED, "more than 2^32 occurrences in the strata of one chunk");
+            pool.reserve(poolBase + kept);
+            base = 0;
+            for (cmb_batch* c : parts) {
+                if (c->nReads && kept)
+                    hipLaunchKernelGGL(k_best_append, dim3((c->nReads + 3u) / 4u), dim3(256), 0, 0, c->foffs.p, c->fout.p, c->alnRec.p, c->alnOps.p,
+                                       c->alnStride, c->nReads, dMinD.p + base, dIds.p + base, dPoff.p + base, pool.at(poolBase));
+                base += c->nReads;
+            }
+            HIPCHK(hipGetLastError());
+            pool.n = poolBase + kept;
+            // the words of every read; the reads that go to, or are with, the host
+            bool anyHost = false, anyNew = false;
+            for (uint32_t j = 0; j < n; j++) {
+                BestState& r = sv[ids[j]];
+                const unsigned long long m = hMasks[j];
+                r.proc = (uint8_t)(k + 1);
+                if (r.host) {
+                    hMode[ids[j]] = 1, anyHost = true;
+                    continue;
+                }
+                r.any[0] |= (uint16_t)((m >> BEST_ANY0) & 0x3FFFu), r.any[1] |= (uint16_t)((m >> BEST_ANY1) & 0x3FFFu);
+                r.asg[0] |= (uint16_t)((m >> BEST_ASG0) & 0x3FFFu), r.asg[1] |= (uint16_t)((m >> BEST_ASG1) & 0x3FFFu);
+                if (edit && ((m >> BEST_SPAN) & 1ull)) hMode[ids[j]] = 2, anyHost = anyNew = true;
+            }
+            if (anyHost) {
+                const uint64_t from = anyNew ? 0 : poolBase, span = pool.n - from;
+                growTo(dMode, n_reads);
+                growTo(dList, (size_t)span + 1);
+                HIPCHK(hipMemcpy(dMode.p, hMode.data(), n_reads, hipMemcpyHostToDevice));
+                HIPCHK(hipMemset(dList.p, 0, sizeof(uint32_t)));
+                uint32_t nList = 0;
+                if (span) {
+                    hipLaunchKernelGGL(k_best_collect, dim3((uint32_t)((span + 255u) / 256u)), dim3(256), 0, 0, pool.read.p, from, pool.n, poolBase,
+                                       dMode.p, dList.p);
+                    HIPCHK(hipGetLastError());
+                    HIPCHK(hipMemcpy(&nList, dList.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+                }
+                std::vector<uint32_t> list(nList);
+                std::vector<uint4> go(nList);
+                std::vector<AlnRec> ga(nList);
+                std::vector<uint16_t> gp((size_t)nList * BEST_OPS_STRIDE);
+                std::vector<uint32_t> gr(nList);
+                if (nList) {
+                    HIPCHK(hipMemcpy(list.data(), dList.p + 1, (size_t)nList * sizeof(uint32_t), hipMemcpyDeviceToHost));
+                    std::sort(list.begin(), list.end()); // (the order in which the records were found)
+                    HIPCHK(hipMemcpy(dList.p + 1, list.data(), (size_t)nList * sizeof(uint32_t), hipMemcpyHostToDevice));
+                    growTo(stage.occ, nList), growTo(stage.aln, nList), growTo(stage.ops, (size_t)nList * BEST_OPS_STRIDE), growTo(stage.read, nList);
+                    hipLaunchKernelGGL(k_best_gather, dim3((nList + 255u) / 256u), dim3(256), 0, 0, dList.p + 1, nList, pool.at(0), stage.at(0));
+                    HIPCHK(hipGetLastError());
+                    HIPCHK(hipMemcpy(go.data(), stage.occ.p, (size_t)nList * sizeof(uint4), hipMemcpyDeviceToHost));
+                    HIPCHK(hipMemcpy(ga.data(), stage.aln.p, (size_t)nList * sizeof(AlnRec), hipMemcpyDeviceToHost));
+                    HIPCHK(hipMemcpy(gp.data(), stage.ops.p, gp.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
+                    HIPCHK(hipMemcpy(gr.data(), stage.read.p, (size_t)nList * sizeof(uint32_t), hipMemcpyDeviceToHost));
+                }
+                for (uint32_t j = 0; j < n; j++) {
+                    const uint32_t i = ids[j];
+                    if (hMode[i] == 2) {
+                        BestHostRead& h = hr[i];
+                        h.fw = cleanReadSeq(std::string(seqs + offs[i], seqs + offs[i + 1]));
+                        h.rc = revComplWithN(h.fw);
+                        for (int s2 = 0; s2 < 2; s2++) h.ov[s2].assign((size_t)sv[i].cutOff + 1, {});
+                        sv[i].host = true;
+                    }
+                    hMode[i] = 0;
+                }
+                for (uint32_t t = 0; t < nList; t++) {
+                    BestHostRead& h = hr[gr[t]];
+                    if (go[t].z < h.ov[0].size())
+                        h.ov[go[t].w ? 1 : 0][go[t].z].push_back(bestOccOf(go[t], ga[t], gp.data() + (size_t)t * BEST_OPS_STRIDE));
+                }
+            }
+            HIPCHK(hipDeviceSynchronize()); // (the batch and its lists go away)
+            lap("host: strata bookkeeping (k_best_scan, k_best_append, host reads)");
+            guard.b = nullptr;
+            cmb_batch_destroy(b);
+            lap("host: cmb_batch_destroy");
+            return CMB_OK;
+        };
+        // ---- exact matches first (x == 0), then the strata: matchBestWith's loop, word for word
+        std::vector<uint32_t> all(n_reads);
+        for (uint32_t i = 0; i < n_reads; i++) all[i] = i;
+        if (x == 0 && n_reads) {
+            int rcode = runStratum(all, 0);
+            if (rcode) return rcode;
+            for (uint32_t i = 0; i < n_reads; i++) {
+                BestState& r = sv[i];
+                if (nonEmpty(i, 0, 0) || nonEmpty(i, 1, 0)) {
+                    checkAlignments(i, 0, 0, r.cutOff);
+                    checkAlignments(i, 1, 0, r.cutOff);
+                    if (r.best == 0) r.bestFound = true;
+                }
+            }
+        }
+        for (uint32_t i = 0; i < n_reads; i++) {
+            BestState& r = sv[i];
+            r.maxED = (uint8_t)(r.best == 0 ? std::min<uint32_t>(x, 255u) : r.cutOff);
+            r.prevK = 0;
+            r.k = (uint8_t)std::min<uint32_t>(std::max(x, 1u), 255u);
+            r.finished = r.k > r.maxED;
+        }
+        std::vector<uint8_t> isFresh(n_reads, 0);
+        for (;;) {
+            std::map<uint32_t, std::vector<uint32_t>> byK;
+            for (uint32_t i = 0; i < n_reads; i++)
+                if (!sv[i].finished) byK[sv[i].k].push_back(i);
+            if (byK.empty()) break;
+            for (auto& kv : byK) {
+                const uint32_t k = kv.first;
+                std::vector<uint32_t> need; // (a stratum both strands have been through needs no new search)
+                for (uint32_t i : kv.second)
+                    if (sv[i].proc <= k) need.push_back(i);
+                for (uint32_t i : kv.second) isFresh[i] = 0;
+                for (uint32_t i : need) isFresh[i] = 1;
+                if (!need.empty()) {
+                    int rcode = runStratum(need, k);
+                    if (rcode) return rcode;
+                }
+                for (uint32_t i : kv.second) {
+                    BestState& r = sv[i];
+                    bool update = false; // hasUpdate (:674-681)
+                    for (int s2 = 0; s2 < 2; s2++) {
+                        if (!isFresh[i]) update |= nonEmpty(i, s2, k);
+                        else
+                            for (uint32_t d = 0; d <= k; d++) update |= nonEmpty(i, s2, d);
+                    }
+                    if (update)
+                        for (uint32_t l = r.prevK + 1u; l <= std::min<uint32_t>(k, r.best + x); l++) {
+                            checkAlignments(i, 0, l, r.maxED);
+                            checkAlignments(i, 1, l, r.maxED);
+                        }
+                    if (r.bestFound) {
+                        r.finished = true; // this was the last iteration
+                        continue;
+                    }
+                    if (update && r.best < r.cutOff + 1u) {
+                        r.bestFound = true;
+                        if (x == 0) {
+                            r.finished = true;
+                            continue;
+                        }
+                        r.prevK = (uint8_t)k;
+                        r.k = (uint8_t)std::min<uint32_t>(r.best + x, r.maxED); // check the final x strata
+                    } else {
+                        if (k == r.maxED) {
+                            r.finished = true;
+                            continue;
+                        }
+                        const uint32_t step = k < 5 ? 2 : 4;
+                        r.prevK = (uint8_t)k;
+                        r.k = (uint8_t)std::min<uint32_t>(k + x + step, r.maxED);
+                    }
+                }
+            }
+        }
+        const auto tFinal = std::chrono::steady_clock::now();
+        // ---- results: combineOccVectors (:573-620).  Pool reads on the device; host reads as matchBestWith does
+        std::vector<unsigned long long> hState(n_reads, 0);
+        R->best.assign(n_reads, 0xFFFFFFFFu);
+        R->hostRead.assign(n_reads, 0);
+        for (uint32_t i = 0; i < n_reads; i++) {
+            const BestState& r = sv[i];
+            if (r.host) R->hostRead[i] = 1, R->nHostReads++;
+            if (!r.bestFound) continue;
+            R->best[i] = r.best;
+            const unsigned long long hi = std::min<uint32_t>(r.best + x, r.cutOff);
+            if (!r.host)
+                hState[i] = (unsigned long long)r.best | (hi << 8) | (1ull << 16) | ((unsigned long long)(r.chk[0] & 0x3FFFu) << 32) |
+                            ((unsigned long long)(r.chk[1] & 0x3FFFu) << 46);
+        }
+        std::vector<uint4> sOcc; // the final records of the host reads, one read after the other
+        std::vector<AlnRec> sAln;
+        std::vector<uint16_t> sOps;
+        std::vector<uint32_t> hostHits;
+        std::vector<std::pair<uint32_t, uint64_t>> hostAt; // (read, its first record in sOcc)
+        for (auto& kv : hr) {
+            const uint32_t i = kv.first;
+            const BestState& r = sv[i];
+            BestHostRead& h = kv.second;
+            hostAt.push_back({i, sOcc.size()});
+            hostHits.push_back(0);
+            if (!r.bestFound) continue;
+            hostHits.back() = (uint32_t)(h.ov[0][r.best].size() + h.ov[1][r.best].size());
+            const uint32_t hi = std::min<uint32_t>(r.best + x, r.cutOff);
+            for (uint32_t d = r.best; d <= hi; d++)
+                for (int s2 = 0; s2 < 2; s2++) {
+                    std::vector<BestOcc>& v = h.ov[s2][d];
+                    std::stable_sort(v.begin(), v.end(), [](const BestOcc& a, const BestOcc& b2) {
+                        return a.aln.seq_id < b2.aln.seq_id || (a.aln.seq_id == b2.aln.seq_id && a.aln.seq_begin < b2.aln.seq_begin);
+                    });
+                    v.erase(std::unique(v.begin(), v.end(), [](const BestOcc& a, const BestOcc& b2) {
+                                return a.aln.seq_id == b2.aln.seq_id && a.aln.seq_begin == b2.aln.seq_begin;
+                            }), v.end());
+                    for (BestOcc& o : v) {
+                        const uint32_t nOps = (uint32_t)std::min<size_t>(o.ops.size(), BEST_OPS_STRIDE);
+                        sOcc.push_back(uint4{o.occ.begin, o.occ.end, o.occ.distance, o.occ.strand});
+                        sAln.push_back(AlnRec{o.aln.seq_id, o.aln.seq_begin, nOps, o.aln.spans == 2 ? 2u : 0u});
+                        const size_t at = sOps.size();
+                        sOps.resize(at + BEST_OPS_STRIDE, 0);
+                        for (uint32_t j = 0; j < nOps; j++) sOps[at + j] = o.ops[nOps - 1 - j];
+                    }
+                }
+        }
+        hostAt.push_back({n_reads, sOcc.size()});
+        DevBuf<unsigned long long> dState;
+        DevBuf<uint32_t> dFlag, dPerRead;
+        DevBuf<uint64_t> dPos, dUflag, dUpos, dDevBase;
+        DevBuf<BestKey> keysA, keysB;
+        const uint64_t nPool = pool.n;
+        growTo(dState, n_reads), growTo(R->dHits, n_reads), growTo(R->dBest, n_reads), growTo(dPerRead, n_reads);
+        growTo(dFlag, (size_t)nPool + 1), growTo(dPos, (size_t)nPool + 1);
+        if (n_reads) {
+            HIPCHK(hipMemcpy(dState.p, hState.data(), (size_t)n_reads * sizeof(unsigned long long), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(R->dBest.p, R->best.data(), (size_t)n_reads * sizeof(uint32_t), hipMemcpyHostToDevice));
+            HIPCHK(hipMemset(R->dHits.p, 0, (size_t)n_reads * sizeof(uint32_t)));
+            HIPCHK(hipMemset(dPerRead.p, 0, (size_t)n_reads * sizeof(uint32_t)));
+        }
+        HIPCHK(hipMemset(dFlag.p + nPool, 0, sizeof(uint32_t)));
+        uint64_t nSel = 0, nDev = 0;
+        if (nPool) {
+            hipLaunchKernelGGL(k_best_flag, dim3((uint32_t)((nPool + 255u) / 256u)), dim3(256), 0, 0, pool.at(0), nPool, dState.p, dFlag.p, R->dHits.p);
+            HIPCHK(hipGetLastError());
+            scanExclusive(tmp, dFlag.p, dPos.p, (size_t)nPool + 1);
+            HIPCHK(hipMemcpy(&nSel, dPos.p + nPool, sizeof(uint64_t), hipMemcpyDeviceToHost));
+        }
+        growTo(dUflag, (size_t)nSel + 1), growTo(dUpos, (size_t)nSel + 1);
+        if (nSel) {
+            keysA.alloc(nSel), keysB.alloc(nSel);
+            hipLaunchKernelGGL(k_best_keys, dim3((uint32_t)((nPool + 255u) / 256u)), dim3(256), 0, 0, pool.at(0), nPool, dFlag.p, dPos.p, keysA.p);
+            HIPCHK(hipGetLastError());
+            // order: distance, strand, (sequence, begin inside it), the order in which the records were found — the last key makes the
+            // order total, so the (stable) merge sort has no ties to keep
+            size_t bytes = 0;
+            HIPCHK(rocprim::merge_sort(nullptr, bytes, keysA.p, keysB.p, (size_t)nSel, BestKeyLess(), (hipStream_t)0));
+            if (tmp.n < bytes || !tmp.p) tmp.alloc(bytes + 256);
+            HIPCHK(rocprim::merge_sort(tmp.p, bytes, keysA.p, keysB.p, (size_t)nSel, BestKeyLess(), (hipStream_t)0));
+            HIPCHK(hipMemset(dUflag.p + nSel, 0, sizeof(uint64_t)));
+            hipLaunchKernelGGL(k_best_uniq, dim3((uint32_t)((nSel + 255u) / 256u)), dim3(256), 0, 0, keysB.p, nSel, dUflag.p, dPerRead.p);
+            HIPCHK(hipGetLastError());
+            scanExclusive(tmp, dUflag.p, dUpos.p, (size_t)nSel + 1);
+            HIPCHK(hipMemcpy(&nDev, dUpos.p + nSel, sizeof(uint64_t), hipMemcpyDeviceToHost));
+        }
+        // every read's place in the final lists: a running sum over one word per read
+        std::vector<uint32_t> perRead(n_reads, 0);
+        R->nHits.assign(n_reads, 0);
+        if (n_reads) {
+            HIPCHK(hipMemcpy(perRead.data(), dPerRead.p, (size_t)n_reads * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(R->nHits.data(), R->dHits.p, (size_t)n_reads * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        }
+        std::vector<uint64_t> devBase((size_t)n_reads + 1, 0);
+        R->offs.assign((size_t)n_reads + 1, 0);
+        {
+            size_t h = 0;
+            for (uint32_t i = 0; i < n_reads; i++) {
+                uint64_t mine = perRead[i];
+                if (h + 1 < hostAt.size() && hostAt[h].first == i) {
+                    mine = hostAt[h + 1].second - hostAt[h].second;
+                    R->nHits[i] = hostHits[h];
+                    HIPCHK(hipMemcpy(R->dHits.p + i, &hostHits[h], sizeof(uint32_t), hipMemcpyHostToDevice));
+                    h++;
+                }
+                devBase[i + 1] = devBase[i] + perRead[i];
+                R->offs[i + 1] = R->offs[i] + mine;
+            }
+        }
+        const uint64_t total = R->offs[n_reads];
+        R->nOcc = total;
+        growTo(R->dOffs, (size_t)n_reads + 1), growTo(dDevBase, (size_t)n_reads + 1);
+        HIPCHK(hipMemcpy(R->dOffs.p, R->offs.data(), ((size_t)n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dDevBase.p, devBase.data(), ((size_t)n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+        R->dOcc.alloc(total), R->dAln.alloc(total), R->dOps.alloc(total * BEST_OPS_STRIDE);
+        const BestPool fin{R->dOcc.p, R->dAln.p, R->dOps.p, nullptr};
+        if (nSel) {
+            hipLaunchKernelGGL(k_best_emit, dim3((uint32_t)((nSel + 255u) / 256u)), dim3(256), 0, 0, keysB.p, nSel, dUflag.p, dUpos.p, dDevBase.p,
+                               R->dOffs.p, pool.at(0), fin);
+            HIPCHK(hipGetLastError());
+        }
+        for (size_t h = 0; h + 1 < hostAt.size(); h++) { // the host reads' records at their place
+            const uint64_t s0 = hostAt[h].second, cnt = hostAt[h + 1].second - s0, at = R->offs[hostAt[h].first];
+            if (!cnt) continue;
+            HIPCHK(hipMemcpy(R->dOcc.p + at, sOcc.data() + s0, cnt * sizeof(uint4), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(R->dAln.p + at, sAln.data() + s0, cnt * sizeof(AlnRec), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(R->dOps.p + at * BEST_OPS_STRIDE, sOps.data() + s0 * BEST_OPS_STRIDE, cnt * BEST_OPS_STRIDE * sizeof(uint16_t),
+                             hipMemcpyHostToDevice));
+        }
+        HIPCHK(hipDeviceSynchronize());
+        R->addTime("host: final selection, sort, lists", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tFinal).count());
+        *out = R.release();
+        return CMB_OK;
+    } catch (const std::exception& e) {
+        return fail(CMB_ERR_DEVICE, e.what());
+    }
+}
+// SAM text of a chunk from a device-resident BEST result, written on the device: the text samOfBest (include/columba_amd_best.hpp) puts
+// together from cmb_best_results with the record builders, byte for byte.  The final lists have the layout k_sam_write reads, so only
+// the plan differs (k_sam_plan_best); the reads whose bookkeeping went through the host are formatted by the record builders and
+// spliced in as cmb_batch_sam_device does.
+extern "C" int cmb_best_sam_device(cmb_best* r, const cmb_sam_inputs* in, int unmapped_records, int xa_tag, const char** text,
+                                   uint64_t* length, uint64_t* host_reads) {
+    if (!r || !in || !text || !length) return fail(CMB_ERR_INVALID, "null argument");
+    if (!r->onDevice) return fail(CMB_ERR_INVALID, "the result does not live on the device (cmb_match_best_device)");
+    const uint32_t n = r->nReads;
+    if (!in->id_offs || (!in->seqs && n && r->readOffs[n]) || (!in->ids && in->id_offs[n]) || (in->quals && !in->qual_offs) ||
+        (in->n_seqs && (!in->seq_names || !in->seq_name_offs)))
+        return fail(CMB_ERR_INVALID, "null argument");
+    try {
+        cmb_index* idx = r->ix;
+        useDevice(idx->device);
+        *text = "";
+        *length = 0;
+        if (host_reads) *host_reads = r->nHostReads;
+        if (!n) return CMB_OK;
+        hipStream_t s = 0;
+        const uint64_t nameBytes = in->n_seqs ? in->seq_name_offs[in->n_seqs] : 0;
+        if (!r->readsUp) { // the chunk's raw reads: once per handle
+            const uint64_t chars = r->readOffs[n];
+            growTo(r->samReads, chars + 1);
+            growTo(r->samReadOffs, (size_t)n + 1);
+            if (chars) HIPCHK(hipMemcpy(r->samReads.p, in->seqs, chars, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(r->samReadOffs.p, r->readOffs.data(), ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+            growTo(r->samHostFlag, n);
+            HIPCHK(hipMemcpy(r->samHostFlag.p, r->hostRead.data(), n, hipMemcpyHostToDevice));
+            r->readsUp = true;
+        }
+        const uint64_t idLo = in->id_offs[0], idHi = in->id_offs[n];
+        if (idHi < idLo) return fail(CMB_ERR_INVALID, "identifier offsets must be non-decreasing");
+        growTo(r->samIds, idHi - idLo + 1);
+        growTo(r->samIdOffs, (size_t)n + 1);
+        if (idHi > idLo) HIPCHK(hipMemcpyAsync(r->samIds.p, in->ids + idLo, idHi - idLo, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(r->samIdOffs.p, in->id_offs, ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+        uint64_t qLo = 0;
+        if (in->quals) {
+            qLo = in->qual_offs[0];
+            const uint64_t qHi = in->qual_offs[n];
+            if (qHi < qLo) return fail(CMB_ERR_INVALID, "quality offsets must be non-decreasing");
+            growTo(r->samQuals, qHi - qLo);
+            growTo(r->samQualOffs, (size_t)n + 1);
+            if (qHi > qLo) HIPCHK(hipMemcpyAsync(r->samQuals.p, in->quals + qLo, qHi - qLo, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(r->samQualOffs.p, in->qual_offs, ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+        }
+        growTo(r->samNames, nameBytes);
+        growTo(r->samNameOffs, (size_t)in->n_seqs + 1);
+        if (nameBytes) HIPCHK(hipMemcpyAsync(r->samNames.p, in->seq_names, nameBytes, hipMemcpyHostToDevice, s));
+        if (in->n_seqs)
+            HIPCHK(hipMemcpyAsync(r->samNameOffs.p, in->seq_name_offs, ((size_t)in->n_seqs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+        growTo(r->samPlan, n);
+        growTo(r->samLen, (size_t)n + 1);
+        growTo(r->samOffs, (size_t)n + 1);
+        HIPCHK(hipMemsetAsync(r->samLen.p + n, 0, sizeof(uint64_t), s));
+        const SamCtx cx{r->samReads.p, r->samReadOffs.p, r->dOffs.p, 1u, r->dOcc.p, r->dAln.p, r->dOps.p, BEST_OPS_STRIDE,
+                        r->samIds.p, r->samIdOffs.p, idLo, in->quals ? r->samQuals.p : nullptr, r->samQualOffs.p, qLo,
+                        r->samNames.p, r->samNameOffs.p, in->n_seqs, n, unmapped_records ? 1u : 0u, xa_tag ? 1u : 0u};
+        hipLaunchKernelGGL(k_sam_plan_best, dim3((n + 3u) / 4u), dim3(256), 0, s, cx, r->dBest.p, r->dHits.p, r->samHostFlag.p, r->samPlan.p,
+                           r->samLen.p);
+        HIPCHK(hipGetLastError());
+        // ---- the host reads through the record builders (samOfBest's lines), their lengths over the plan's
+        if (r->nHostReads) {
+            std::vector<const char*> names(in->n_seqs);
+            std::vector<std::string> nameStr;
+            for (uint32_t q = 0; q < in->n_seqs; q++) nameStr.emplace_back(in->seq_names + in->seq_name_offs[q], in->seq_names + in->seq_name_offs[q + 1]);
+            std::vector<uint32_t> list;
+            for (uint32_t i = 0; i < n; i++)
+                if (r->hostRead[i]) list.push_back(i);
+            std::string side;
+            std::vector<uint64_t> sideOffs(list.size() + 1, 0);
+            for (size_t q = 0; q < list.size(); q++) {
+                const uint32_t i = list[q];
+                const std::string read = cleanReadSeq(std::string(in->seqs + r->readOffs[i], in->seqs + r->readOffs[i + 1])), revC = revComplWithN(read);
+                const std::string sid = cleanSeqID(std::string(in->ids + in->id_offs[i], in->ids + in->id_offs[i + 1]));
+                const std::string qual = in->quals ? std::string(in->quals + in->qual_offs[i], in->quals + in->qual_offs[i + 1]) : "*";
+                const uint64_t o0 = r->offs[i], cnt = r->offs[i + 1] - o0;
+                if (!cnt) {
+                    if (unmapped_records) side += samLineUnmappedSE(sid, read, qual);
+                } else {
+                    std::vector<uint4> oc(cnt);
+                    std::vector<AlnRec> al(cnt);
+                    std::vector<uint16_t> op(cnt * BEST_OPS_STRIDE);
+                    HIPCHK(hipMemcpy(oc.data(), r->dOcc.p + o0, cnt * sizeof(uint4), hipMemcpyDeviceToHost));
+                    HIPCHK(hipMemcpy(al.data(), r->dAln.p + o0, cnt * sizeof(AlnRec), hipMemcpyDeviceToHost));
+                    HIPCHK(hipMemcpy(op.data(), r->dOps.p + o0 * BEST_OPS_STRIDE, op.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
+                    std::vector<SamHit> hits;
+                    for (uint64_t t = 0; t < cnt; t++) {
+                        const BestOcc bo = bestOccOf(oc[t], al[t], op.data() + t * BEST_OPS_STRIDE);
+                        SamHit h;
+                        h.seqName = bo.aln.seq_id < nameStr.size() ? nameStr[bo.aln.seq_id] : std::string();
+                        h.cigar = cigarString(bo.ops.data(), (uint32_t)bo.ops.size());
+                        h.pos0 = bo.aln.seq_begin;
+                        h.distance = bo.occ.distance;
+                        h.revCompl = bo.occ.strand != 0;
+                        hits.push_back(h);
+                    }
+                    std::string revQ = qual;
+                    std::reverse(revQ.begin(), revQ.end());
+                    const bool rcFirst = hits[0].revCompl;
+                    if (xa_tag) {
+                        side += samLineSEWithXA(sid, hits, r->nHits[i], rcFirst ? revC : read, rcFirst ? revQ : qual);
+                    } else {
+                        side += samLineSE(sid, hits[0], true, r->nHits[i], r->best[i], rcFirst ? revC : read, rcFirst ? revQ : qual);
+                        for (size_t j = 1; j < hits.size(); j++) side += samLineSE(sid, hits[j], false, r->nHits[i], r->best[i], "*", "*");
+                    }
+                }
+                sideOffs[q + 1] = side.size();
+            }
+            growTo(r->samSide, side.size());
+            growTo(r->samSideOffs, sideOffs.size());
+            growTo(r->samSideReads, list.size());
+            if (!side.empty()) HIPCHK(hipMemcpy(r->samSide.p, side.data(), side.size(), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(r->samSideOffs.p, sideOffs.data(), sideOffs.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(r->samSideReads.p, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(k_sam_override, dim3(((uint32_t)list.size() + 255u) / 256u), dim3(256), 0, s, r->samSideReads.p, r->samSideOffs.p,
+                               (uint32_t)list.size(), r->samPlan.p, r->samLen.p);
+            HIPCHK(hipGetLastError());
+        }
+        scanExclusive(r->scanTmp, r->samLen.p, r->samOffs.p, (size_t)n + 1);
+        uint64_t total = 0;
+        HIPCHK(hipMemcpy(&total, r->samOffs.p + n, sizeof(uint64_t), hipMemcpyDeviceToHost));
+        r->samOut.resize((size_t)total + 1);
+        r->samOut.p[total] = '\0';
+        if (total) {
+            growTo(r->samText, (size_t)total + 16);
+            hipLaunchKernelGGL(k_sam_write, dim3((n + SAM_READS_PER_WAVE - 1u) / SAM_READS_PER_WAVE), dim3(64), 0, s, cx, r->samPlan.p, r->samOffs.p,
+                               r->samSide.p, r->samText.p);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(r->samOut.p, r->samText.p, (size_t)total, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+        }
+        *text = r->samOut.p;
+        *length = total;
+        return CMB_OK;
+    } catch (const std::exception& e) {
+        return fail(CMB_ERR_DEVICE, e.what());
+    }
+}
 // The same on the b-move index (the reference's RUN_LENGTH_COMPRESSION build runs the same matchApproxBestPlusX): the strata are
 // b-move batches, CIGARs and trimming read the matched string of an occurrence from the text beside the index (cmb_move_attach_text).
 extern "C" int cmb_move_match_best(cmb_move_index* idx, const cmb_strategy* st, uint32_t x, uint32_t min_identity, uint32_t kmer_size,
@@ -3189,8 +3836,40 @@ extern "C" int cmb_move_match_best(cmb_move_index* idx, const cmb_strategy* st, 
     // (strata up to 13 errors, the reference's MAX_K, as on the FM-index: the b-move search runs that far since round 3, its alignments since round 4)
     return matchBestWith(text, st, 13u, false, run, x, min_identity, seqs, offs, n_reads, out);
 }
+// the lists of a device-resident result on the host, packed as cmb_match_best packs them (CIGAR runs from the begin, one after the other)
+static void fetchBest(cmb_best* r) {
+    if (!r->onDevice || r->fetched) return;
+    useDevice(r->ix->device);
+    const uint64_t n = r->nOcc;
+    r->occ.resize(n);
+    r->aln.resize(n);
+    std::vector<AlnRec> ar(n);
+    std::vector<uint16_t> raw((size_t)n * BEST_OPS_STRIDE);
+    if (n) {
+        static_assert(sizeof(cmb_occ) == sizeof(uint4), "cmb_occ is the device's occurrence record");
+        HIPCHK(hipMemcpy(r->occ.data(), r->dOcc.p, n * sizeof(cmb_occ), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(ar.data(), r->dAln.p, n * sizeof(AlnRec), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(raw.data(), r->dOps.p, raw.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    }
+    uint64_t nOps = 0;
+    for (uint64_t i = 0; i < n; i++) nOps += ar[i].nOps;
+    r->ops.resize(nOps);
+    uint64_t po = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        r->aln[i] = cmb_aln{ar[i].seqId, ar[i].seqBegin, po, (uint16_t)ar[i].nOps, (uint16_t)ar[i].spans, 0};
+        const uint16_t* src = raw.data() + i * BEST_OPS_STRIDE;
+        for (uint32_t j = 0; j < ar[i].nOps; j++) r->ops[po + j] = src[ar[i].nOps - 1 - j]; // (stored end to begin)
+        po += ar[i].nOps;
+    }
+    r->fetched = true;
+}
 extern "C" int cmb_best_sizes(const cmb_best* r, uint64_t* n_occ, uint64_t* n_ops) {
     if (!r) return fail(CMB_ERR_INVALID, "null argument");
+    try {
+        fetchBest(const_cast<cmb_best*>(r));
+    } catch (const std::exception& e) {
+        return fail(CMB_ERR_DEVICE, e.what());
+    }
     if (n_occ) *n_occ = r->occ.size();
     if (n_ops) *n_ops = r->ops.size();
     return CMB_OK;
@@ -3198,7 +3877,13 @@ extern "C" int cmb_best_sizes(const cmb_best* r, uint64_t* n_occ, uint64_t* n_op
 extern "C" int cmb_best_results(const cmb_best* r, cmb_occ* occ, cmb_aln* aln, uint64_t cap, uint16_t* cigar_ops, uint64_t ops_cap,
                                 uint64_t* offs, uint32_t* best, uint32_t* n_hits, uint64_t* counters) {
     if (!r) return fail(CMB_ERR_INVALID, "null argument");
-    if (cap < r->occ.size() || ops_cap < r->ops.size()) return fail(CMB_ERR_OVERFLOW, "output buffer too small");
+    const bool lists = occ || aln || cigar_ops; // (a device-resident result downloads its lists only when they are asked for)
+    try {
+        if (lists) fetchBest(const_cast<cmb_best*>(r));
+    } catch (const std::exception& e) {
+        return fail(CMB_ERR_DEVICE, e.what());
+    }
+    if ((lists || !r->onDevice) && (cap < r->occ.size() || ops_cap < r->ops.size())) return fail(CMB_ERR_OVERFLOW, "output buffer too small");
     if (occ && !r->occ.empty()) memcpy(occ, r->occ.data(), r->occ.size() * sizeof(cmb_occ));
     if (aln && !r->aln.empty()) memcpy(aln, r->aln.data(), r->aln.size() * sizeof(cmb_aln));
     if (cigar_ops && !r->ops.empty()) memcpy(cigar_ops, r->ops.data(), r->ops.size() * sizeof(uint16_t));
@@ -3206,6 +3891,24 @@ extern "C" int cmb_best_results(const cmb_best* r, cmb_occ* occ, cmb_aln* aln, u
     if (best) memcpy(best, r->best.data(), r->best.size() * sizeof(uint32_t));
     if (n_hits) memcpy(n_hits, r->nHits.data(), r->nHits.size() * sizeof(uint32_t));
     if (counters) memcpy(counters, r->cnts, sizeof(r->cnts));
+    return CMB_OK;
+}
+extern "C" int cmb_best_timings(const cmb_best* r, const char** names, float* ms, uint32_t cap) {
+    if (!r) return 0;
+    uint32_t n = 0;
+    for (const auto& t : r->times) {
+        if (n >= cap) break;
+        if (names) names[n] = t.first.c_str();
+        if (ms) ms[n] = (float)t.second;
+        n++;
+    }
+    return (int)n;
+}
+extern "C" int cmb_best_host_reads(const cmb_best* r, uint8_t* status, uint32_t* n) {
+    if (!r) return fail(CMB_ERR_INVALID, "null argument");
+    if (status)
+        for (size_t i = 0; i < r->offs.size() - 1; i++) status[i] = i < r->hostRead.size() ? r->hostRead[i] : 0;
+    if (n) *n = r->nHostReads;
     return CMB_OK;
 }
 extern "C" void cmb_best_destroy(cmb_best* r) { delete r; }

@@ -191,6 +191,66 @@ k_sam_plan(SamCtx cx, SamPlan* __restrict__ plan, uint64_t* __restrict__ len, ui
     }
 }
 
+// The plan of a chunk matched in BEST mode (cmb_best_sam_device; generateSE_SAM / generateSE_SAM_XATag as matchApproxBestPlusX calls
+// them, searchstrategy.h:1612-1641): the lists are final and in the reference's order, so the primary is the first record and nothing
+// is swapped; minScore is the read's best distance and nHits the number of occurrences at it BEFORE the deduplication (both from the
+// strata bookkeeping, so X1 = n - nHits may wrap as it does on the host).  hostFlag: the reads the host formats (k_sam_override).
+__global__ void __launch_bounds__(256)
+k_sam_plan_best(SamCtx cx, const uint32_t* __restrict__ best, const uint32_t* __restrict__ hits, const uint8_t* __restrict__ hostFlag,
+                SamPlan* __restrict__ plan, uint64_t* __restrict__ len) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (r >= cx.nReads) return; // (a whole wavefront)
+    const uint8_t* id = cx.ids + (cx.idOffs[r] - cx.idBase);
+    const uint32_t idRaw = (uint32_t)(cx.idOffs[r + 1] - cx.idOffs[r]);
+    uint32_t sp = idRaw;
+    for (uint32_t base = 0; base < idRaw; base += 64u) {
+        const uint32_t i = base + lane;
+        const unsigned long long m = __ballot(i < idRaw && id[i] == ' ');
+        if (m) {
+            sp = base + (uint32_t)__builtin_ctzll(m);
+            break;
+        }
+    }
+    SamPlan pl{};
+    pl.idLen = sp ? sp - 1u : 0u;
+    const uint32_t readLen = (uint32_t)(cx.offs[r + 1] - cx.offs[r]);
+    const uint32_t qualLen = samQualLen(cx, r);
+    const uint64_t q0 = cx.foffs[(uint64_t)r * cx.groupStride], q1 = cx.foffs[(uint64_t)(r + 1) * cx.groupStride];
+    const uint32_t n = (uint32_t)(q1 - q0);
+    uint64_t total = 0;
+    if (hostFlag[r]) {
+        pl.kind = SAM_HOST; // (its length comes from the host: k_sam_override)
+    } else if (n == 0) {
+        pl.kind = cx.unmapped ? SAM_UNMAPPED : SAM_NOTHING;
+        if (cx.unmapped) total = (uint64_t)pl.idLen + 17u + readLen + 1u + qualLen + 14u; // indexhelpers.cpp:177-200
+    } else {
+        pl.kind = SAM_MAPPED;
+        pl.primary = 0;
+        pl.minScore = best[r];
+        pl.nHits = hits[r];
+        const uint32_t mapq = samMapQ(pl.nHits);
+        const bool star = !cx.quals || (cx.xa && qualLen == 0u); // (host_sam.hpp:96)
+        unsigned long long sum = 0;
+        for (uint32_t p = lane; p < n; p += 64u) {
+            const SamHitDev h = samLoadHit(cx, q0 + p);
+            if (p == 0u) {
+                sum += samLineLen(pl.idLen, h, h.strand ? 16u : 0u, mapq, readLen, star ? 1u : qualLen);
+                if (cx.xa) sum += 6u + decWidth(pl.nHits - 1u) + 6u + decWidth(n - pl.nHits) + 6u; // X0, X1, XA:Z:
+            } else if (cx.xa) {
+                sum += samXaEntryLen(h);
+            } else {
+                sum += samLineLen(pl.idLen, h, h.strand ? 272u : 256u, h.dist == pl.minScore ? mapq : 0u, 1u, 1u);
+            }
+        }
+        total = waveSum64(sum);
+    }
+    if (lane == 0) {
+        plan[r] = pl;
+        len[r] = total;
+    }
+}
+
 // the reads the host formatted (samOfRead): their lengths, and where their text lies in the side buffer
 __global__ void k_sam_override(const uint32_t* __restrict__ reads, const uint64_t* __restrict__ sideOffs, uint32_t n, SamPlan* __restrict__ plan,
                                uint64_t* __restrict__ len) {

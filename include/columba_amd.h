@@ -281,6 +281,30 @@ int cmb_best_sizes(const cmb_best* r, uint64_t* n_occ, uint64_t* n_ops);
 int cmb_best_results(const cmb_best* r, cmb_occ* occ, cmb_aln* aln, uint64_t cap, uint16_t* cigar_ops, uint64_t ops_cap,
                      uint64_t* offs /* [n_reads+1] */, uint32_t* best, uint32_t* n_hits, uint64_t* counters);
 void cmb_best_destroy(cmb_best* r);
+/* The same mode with the per-occurrence bookkeeping ON THE DEVICE.  cmb_match_best downloads every stratum and keeps its
+ * occurrences in host containers per read, strand and distance (checkAlignments, src/searchstrategy.cpp:536-571; processSeq,
+ * :791-812; combineOccVectors, :573-620); here a stratum's lists stay in HBM: a kernel keeps what lies at or above the first distance
+ * not processed yet, appends it to a pool and reports per read which distances hold an occurrence; the host advances best, k, prevK
+ * and bestFound from those few words per read (findBestAlignments, :623-712, unchanged: the same strata over the same reads, so the
+ * summed counters are equal); at the end the records at best ... min(best + x, cut-off) are selected, ordered (distance, strand,
+ * sequence, begin, order found) with a rocPRIM merge sort and deduplicated on the device.  The result's final lists live in HBM
+ * (occurrences as uint4, sequence assignment, CIGAR runs at a fixed stride, 64-bit offsets, best and n_hits per read);
+ * cmb_best_sizes / cmb_best_results work on the handle unchanged and download on first use — arrays and counters are bit-identical
+ * to cmb_match_best's.  The index must outlive the handle.  FM-index flavour only (cmb_move_match_best keeps the host path).
+ * HOST READS: an occurrence that runs over the end of its sequence is, under edit distance, trimmed and verified again
+ * (IndexInterface::findSeqName, src/indexinterface.cpp:833-899) and thereby changes its distance.  A read goes to matchBestWith's
+ * host bookkeeping at the first stratum in which it keeps such an occurrence, takes its pool records along, still runs exactly the
+ * strata it would have, and its final records (spans = 2 where trimmed) are spliced into the device lists at its place.  Hamming
+ * distance never trims: such occurrences are dropped and no read goes to the host.
+ * cmb_best_host_reads: status[i] = 1 for those reads (status may be NULL), *n their number (n may be NULL); on a result of
+ * cmb_match_best / cmb_move_match_best all zero.  CMB_ERR_INVALID: NULL arguments, min_identity outside 50 ... 100, a text-only index. */
+int cmb_match_best_device(cmb_index* idx, const cmb_strategy* st, uint32_t x, uint32_t min_identity, const char* seqs,
+                          const uint64_t* offs, uint32_t n_reads, cmb_best** out);
+int cmb_best_host_reads(const cmb_best* r, uint8_t* status /* [n_reads] or NULL */, uint32_t* n);
+/* where a cmb_match_best_device call spent its time (as cmb_batch_timings: names[i] / ms[i], returns how many): host time per
+ * phase — every phase ends in a synchronise — under "host: ...", and, summed over the strata, the device time of the batches'
+ * kernels under "strata: <name of cmb_batch_timings>".  Empty for results of the host paths. */
+int cmb_best_timings(const cmb_best* r, const char** names, float* ms, uint32_t cap);
 
 /* --- output records (host-only; no GPU needed) -----------------------------------------
  * SAM lines of single-end reads as the reference formats them (TextOcc::generateSAMSingleEnd / ...XA /
@@ -429,8 +453,9 @@ int64_t cmb_batch_sam(const cmb_batch* b, const char* seqs, const char* const* r
  * the text at their place.  Preconditions and error codes as cmb_batch_sam (run, alignments requested).  Composite batches format
  * every sub-batch on its own stream; the text is in read order.  MAPQ (TextOcc::getMapQ, src/indexhelpers.h:378-388) comes from
  * a table on the device: 60, 3, 2, then 1 up to nine and 0 from ten occurrences of minimal distance on.
- * ALL mode, single-end reads, FM-index batches only: BEST mode (cmb_match_best), read pairs (cmb_pair_sam) and the b-move
- * flavour (cmb_sam_chunk on caller-held records) keep the host formatter. */
+ * ALL mode, single-end reads, FM-index batches only: BEST mode has cmb_best_sam_device (below) on a result of
+ * cmb_match_best_device; results of cmb_match_best, read pairs (cmb_pair_sam) and the b-move flavour (cmb_sam_chunk on caller-held
+ * records) keep the host formatter. */
 typedef struct {
     const char* seqs;
     const char* ids;
@@ -443,6 +468,17 @@ typedef struct {
 } cmb_sam_inputs;
 int cmb_batch_sam_device(cmb_batch* b, const cmb_sam_inputs* in, int unmapped_records, int xa_tag, const char** text,
                          uint64_t* length, uint64_t* host_reads);
+/* The SAM text of a chunk matched with cmb_match_best_device, written on the device from the result's lists: byte for byte what
+ * generateOutputSingleEnd + generateSE_SAM / generateSE_SAM_XATag (src/searchstrategy.cpp:1824-1902, src/searchstrategy.h:1612-1641)
+ * give for BEST mode, i.e. what the host formatter (include/columba_amd_best.hpp: samOfBest) builds from cmb_best_results.  The
+ * lists are final, so nothing is trimmed or swapped: the first record of a read is the primary and sets the printed strand,
+ * MAPQ comes from n_hits[i] (0 for a secondary line whose distance is not best[i]), X0 = n_hits - 1, X1 = records - n_hits.
+ * `in` as for cmb_batch_sam_device; in->seqs = the read characters given to cmb_match_best_device (uploaded once per handle).
+ * The host reads (cmb_best_host_reads) are formatted by the record builders and spliced in; *host_reads (may be NULL) = their number.
+ * *text (page-locked, owned by the handle, *length bytes + a terminating 0) stays valid until the next cmb_best_sam_device on the
+ * handle or cmb_best_destroy.  CMB_ERR_INVALID: NULL arguments, or a result that does not live on the device. */
+int cmb_best_sam_device(cmb_best* r, const cmb_sam_inputs* in, int unmapped_records, int xa_tag, const char** text, uint64_t* length,
+                        uint64_t* host_reads);
 /* test hook: out[i] = the MAPQ the device path prints for i + 1 occurrences of minimal distance, evaluated on the device */
 int cmb_sam_device_mapq(uint32_t n, uint32_t* out);
 /* the same for occurrences and alignments the caller holds — cmb_batch_results + cmb_batch_alignments, or cmb_move_batch_results
