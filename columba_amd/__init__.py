@@ -783,6 +783,21 @@ def sam_device_mapq(n: int) -> np.ndarray:
     return out[:n]
 
 
+def _sam_device_bytes(entry, obj, ids, quals, seq_names, unmapped: bool, xa: bool):
+    """(SAM text as bytes, number of host-formatted reads) from ``entry`` (cmb_batch_sam_device or cmb_best_sam_device) on the handle
+    of ``obj``, whose reads the fields belong to"""
+    bi, oi = pack_fields(ids)
+    bn, on = pack_fields(seq_names)
+    bq, oq = pack_fields(quals) if quals is not None else (None, None)
+    if oi.shape[0] - 1 != obj.n_reads or (oq is not None and oq.shape[0] - 1 != obj.n_reads):
+        raise ValueError("one identifier and one quality per read")
+    inp = SamInputs(_p(obj._packed[0]), _p(bi), _p(oi), _p(bq) if bq is not None else None, _p(oq) if oq is not None else None,
+                    _p(bn), _p(on), on.shape[0] - 1)
+    text, n, host = C.c_void_p(), C.c_uint64(), C.c_uint64()
+    _chk(entry(obj.h, C.byref(inp), int(unmapped), int(xa), C.byref(text), C.byref(n), C.byref(host)))
+    return C.string_at(text.value, n.value) if n.value else b"", int(host.value)
+
+
 class Batch:
     """A batch of reads resident in HBM (handle of ``cmb_batch_*``)."""
 
@@ -876,16 +891,7 @@ class Batch:
         """the same text written on the device (cmb_batch_sam_device): (bytes, number of reads the host formatted — those with an
         occurrence over the end of its sequence).  ids / quals / seq_names: sequences of str or bytes, or (bytes, offsets) pairs
         packed with pack_fields; quals=None: no qualities."""
-        bi, oi = pack_fields(ids)
-        bn, on = pack_fields(seq_names)
-        bq, oq = pack_fields(quals) if quals is not None else (None, None)
-        if oi.shape[0] - 1 != self.n_reads or (oq is not None and oq.shape[0] - 1 != self.n_reads):
-            raise ValueError("one identifier and one quality per read")
-        inp = SamInputs(_p(self._packed[0]), _p(bi), _p(oi), _p(bq) if bq is not None else None, _p(oq) if oq is not None else None,
-                        _p(bn), _p(on), on.shape[0] - 1)
-        text, n, host = C.c_void_p(), C.c_uint64(), C.c_uint64()
-        _chk(lib().cmb_batch_sam_device(self.h, C.byref(inp), int(unmapped), int(xa), C.byref(text), C.byref(n), C.byref(host)))
-        return C.string_at(text.value, n.value) if n.value else b"", int(host.value)
+        return _sam_device_bytes(lib().cmb_batch_sam_device, self, ids, quals, seq_names, unmapped, xa)
 
     def sam_device(self, ids, quals, seq_names, unmapped: bool = True, xa: bool = False):
         """(SAM text, number of host-formatted reads): sam_device_bytes, decoded"""
@@ -981,16 +987,7 @@ class BestDevice:
 
     def sam_device_bytes(self, ids, quals, seq_names, unmapped: bool = True, xa: bool = False):
         """(the SAM text of the chunk as bytes, number of reads the host formatted); inputs as ``Batch.sam_device_bytes``"""
-        bi, oi = pack_fields(ids)
-        bn, on = pack_fields(seq_names)
-        bq, oq = pack_fields(quals) if quals is not None else (None, None)
-        if oi.shape[0] - 1 != self.n_reads or (oq is not None and oq.shape[0] - 1 != self.n_reads):
-            raise ValueError("one identifier and one quality per read")
-        inp = SamInputs(_p(self._packed[0]), _p(bi), _p(oi), _p(bq) if bq is not None else None, _p(oq) if oq is not None else None,
-                        _p(bn), _p(on), on.shape[0] - 1)
-        text, n, host = C.c_void_p(), C.c_uint64(), C.c_uint64()
-        _chk(lib().cmb_best_sam_device(self.h, C.byref(inp), int(unmapped), int(xa), C.byref(text), C.byref(n), C.byref(host)))
-        return C.string_at(text.value, n.value) if n.value else b"", int(host.value)
+        return _sam_device_bytes(lib().cmb_best_sam_device, self, ids, quals, seq_names, unmapped, xa)
 
     def sam_device(self, ids, quals, seq_names, unmapped: bool = True, xa: bool = False):
         t, host = self.sam_device_bytes(ids, quals, seq_names, unmapped, xa)

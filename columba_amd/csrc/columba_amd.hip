@@ -2,6 +2,7 @@
 #include "../../include/columba_amd.h"
 #include "host_sam.hpp"
 #include "host_schemes.hpp"
+#include "host_util.hpp"
 #include "kernels.hpp"
 #include "dev_sam.hpp"
 #include "dev_best.hpp"
@@ -25,69 +26,6 @@ static int fail(int code, const std::string& msg) {
 namespace cmb {
 int failWith(int code, const std::string& msg) { return fail(code, msg); } // for the library's other translation units
 }
-#define HIPCHK(expr)                                                                                  \
-    do {                                                                                              \
-        hipError_t _e = (expr);                                                                       \
-        if (_e != hipSuccess) throw std::runtime_error(std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
-template <typename T> struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    DevBuf() {}
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { release(); }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-    void alloc(size_t count) {
-        release();
-        if (count == 0) count = 1;
-        HIPCHK(hipMalloc((void**)&p, count * sizeof(T)));
-        n = count;
-    }
-    void upload(const T* h, size_t count) {
-        alloc(count);
-        if (count) HIPCHK(hipMemcpy(p, h, count * sizeof(T), hipMemcpyHostToDevice));
-    }
-    void uploadPadded(const T* h, size_t count, size_t pad) { // `pad` zeroed elements behind the data (k_prep reads 16-byte chunks)
-        alloc(count + pad);
-        if (count) HIPCHK(hipMemcpy(p, h, count * sizeof(T), hipMemcpyHostToDevice));
-        HIPCHK(hipMemset(p + count, 0, pad * sizeof(T)));
-    }
-    size_t bytes() const { return n * sizeof(T); }
-};
-
-// page-locked host memory (results are copied at PCIe speed, asynchronously)
-template <typename T> struct PinnedBuf {
-    T* p = nullptr;
-    size_t cap = 0, n = 0;
-    PinnedBuf() {}
-    PinnedBuf(const PinnedBuf&) = delete;
-    PinnedBuf& operator=(const PinnedBuf&) = delete;
-    ~PinnedBuf() {
-        if (p) (void)hipHostFree(p);
-    }
-    void resize(size_t count) { // contents are not kept
-        if (count > cap) {
-            if (p) (void)hipHostFree(p);
-            p = nullptr;
-            cap = 0;
-            const size_t want = count + count / 4 + 64;
-            HIPCHK(hipHostMalloc((void**)&p, want * sizeof(T), hipHostMallocDefault));
-            cap = want;
-        }
-        n = count;
-    }
-    size_t size() const { return n; }
-    bool empty() const { return n == 0; }
-    T* data() { return p; }
-    const T* data() const { return p; }
-};
-
 // ------------------------------------------------------------------------------------ index
 struct cmb_index {
     int device = 0;
@@ -244,7 +182,10 @@ extern "C" int cmb_index_create(const cmb_index_desc* desc, int device, cmb_inde
             HIPCHK(hipGetLastError());
             HIPCHK(hipDeviceSynchronize());
         }
-        ix->saSamples.upload(desc->sa_samples, desc->n_samples);
+        // (a description without samples has always left ONE element here: saSamples.n is the sample count of the probe and of
+        // cmb_index_layout_of, and counts into cmb_index_device_bytes)
+        ix->saSamples.alloc(std::max<size_t>(desc->n_samples, 1));
+        if (desc->n_samples) HIPCHK(hipMemcpy(ix->saSamples.p, desc->sa_samples, desc->n_samples * sizeof(uint32_t), hipMemcpyHostToDevice));
         // padded: the verification kernels read (unaligned) 16-byte chunks up to two chunks ahead, and lanes whose
         // candidate has ended keep prefetching while their wavefront runs (at most MAX_READ + 3 k rows + 48 bytes)
         constexpr uint64_t TEXT_PAD = 640;
@@ -594,9 +535,14 @@ extern "C" int cmb_strategy_export_partition(const cmb_strategy* s, uint32_t k, 
 }
 
 // ------------------------------------------------------------------------------------ batch
-struct KernelTime {
-    const char* name;
-    float ms;
+// What the device SAM driver (samUpload, samSplice, samScan, samWrite below) keeps in HBM for one (sub-)batch or one BEST result: the
+// chunk's packed identifiers, qualities and sequence names with their offsets, the plan, length and position of every read in the
+// text, the text of the reads the host formatted with its offsets and read numbers, the text itself (the scan's scratch is the owner's scanTmp)
+struct SamDeviceBufs {
+    DevBuf<uint8_t> ids, quals, names, side, text;
+    DevBuf<uint64_t> idOffs, qualOffs, nameOffs, len, offs, sideOffs;
+    DevBuf<SamPlan> plan;
+    DevBuf<uint32_t> sideReads;
 };
 
 struct cmb_batch {
@@ -670,13 +616,10 @@ struct cmb_batch {
     uint32_t alnStride = 0;
     PinnedBuf<uint16_t> hAlnOps;
     PinnedBuf<AlnRec> hAlnRec;
-    // cmb_batch_sam_device (dev_sam.hpp): the chunk's packed identifiers, qualities and sequence names, the plan and the
-    // position of every read in the text, the text of the reads the host formatted, the sub-batch's text; samOut: the
-    // finished text of the whole batch in page-locked memory (the composite's own, or the single batch's)
-    DevBuf<uint8_t> samIds, samQuals, samNames, samSide, samText;
-    DevBuf<uint64_t> samIdOffs, samQualOffs, samNameOffs, samLen, samOffs, samSideOffs;
-    DevBuf<SamPlan> samPlan;
-    DevBuf<uint32_t> samHostList, samSideReads;
+    // cmb_batch_sam_device: the sub-batch's buffers of the SAM driver; samHostList: the reads k_sam_plan leaves to the host ([0]: how
+    // many); samOut: the finished text of the whole batch in page-locked memory (the composite's own, or the single batch's)
+    SamDeviceBufs sam;
+    DevBuf<uint32_t> samHostList;
     PinnedBuf<char> samOut;
     // cmb_verify_batch_staged: candidates given by the caller take the place of the search's in-text items, and the
     // raw text occurrences (before the filter) are what is handed back
@@ -881,33 +824,6 @@ static int batchCreateOne(cmb_index* idx, const cmb_strategy* st, uint32_t max_d
 
 namespace {
 
-struct Timer {
-    hipStream_t s;
-    hipEvent_t a, b;
-    std::vector<KernelTime>& out;
-    Timer(hipStream_t st, std::vector<KernelTime>& o) : s(st), out(o) {
-        (void)hipEventCreate(&a);
-        (void)hipEventCreate(&b);
-    }
-    ~Timer() {
-        (void)hipEventDestroy(a);
-        (void)hipEventDestroy(b);
-    }
-    void begin() { (void)hipEventRecord(a, s); }
-    void end(const char* name) {
-        (void)hipEventRecord(b, s);
-        (void)hipEventSynchronize(b);
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, a, b);
-        for (auto& t : out)
-            if (!strcmp(t.name, name)) {
-                t.ms += ms;
-                return;
-            }
-        out.push_back({name, ms});
-    }
-};
-
 struct HostOcc {
     uint32_t begin, end, dist, strand;
 };
@@ -1110,7 +1026,7 @@ static int batchRunOne(cmb_batch* b) {
             memset(hcnt, 0, sizeof(hcnt));
             hcnt[0] = (uint32_t)b->presetItems.size();
             q.items = b->items.p;
-            q.itemCap = (uint32_t)std::min<size_t>(b->items.n, 0xFFFFFFF0u);
+            q.itemCap = cap32(b->items.n);
         }
         int bfsAttempts = 0;
         for (int attempt = 0; !preset; attempt++) {
@@ -1119,18 +1035,18 @@ static int batchRunOne(cmb_batch* b) {
                 HIPCHK(hipMemsetAsync(b->counters.p, 0, CMB_CNT_MAX * sizeof(unsigned long long), s));
             }
             q.items = b->items.p;
-            q.itemCap = (uint32_t)std::min<size_t>(b->items.n, 0xFFFFFFF0u);
+            q.itemCap = cap32(b->items.n);
             q.fm = b->fm.p;
-            q.fmCap = (uint32_t)std::min<size_t>(b->fm.n, 0xFFFFFFF0u);
+            q.fmCap = cap32(b->fm.n);
             q.text = b->text.p;
-            q.textCap = (uint32_t)std::min<size_t>(b->text.n, 0xFFFFFFF0u);
-            const uint32_t dfsCap = (uint32_t)std::min<size_t>(b->dfs.n, 0xFFFFFFF0u);
+            q.textCap = cap32(b->text.n);
+            const uint32_t dfsCap = cap32(b->dfs.n);
             tm.begin();
             const uint32_t pParts = b->k ? b->sNumParts : 1;
             const uint32_t stratBytes = (uint32_t)(((b->wide ? sizeof(DevStrategyKT<MAXP_WIDE>) : sizeof(DevStrategyK)) + 15) / 16 * 16);
             const uint32_t rdWords = 2 * ((b->maxLen + 31) / 32);
             const bool longReads = b->maxLen > 256;
-            const uint32_t exCap = (uint32_t)std::min<size_t>(b->exq.n, 0xFFFFFFF0u);
+            const uint32_t exCap = cap32(b->exq.n);
             if (b->k) {
                 if (b->psel.n < tasks) b->psel.alloc(tasks);
                 const size_t pLds = stratBytes + (5 * pParts + rdWords) * 256 * sizeof(uint32_t);
@@ -1181,7 +1097,7 @@ static int batchRunOne(cmb_batch* b) {
                 NaiveBufs N{};
                 N.Q[0] = b->nvQ[0].p;
                 N.Q[1] = b->nvQ[1].p;
-                N.qCap = (uint32_t)std::min<size_t>(b->nvQ[0].n / 3, 0xFFFFFFF0u);
+                N.qCap = cap32(b->nvQ[0].n / 3);
                 N.nq = b->nvCnt.p;
                 const bool edit = b->metric == CMB_METRIC_EDIT;
                 hipLaunchKernelGGL(k_naive_start, dim3((tasks + 255) / 256), dim3(256), 0, s, ix->d, b->psel.p, b->offs.p, tasks,
@@ -1263,13 +1179,13 @@ static int batchRunOne(cmb_batch* b) {
                     B.F = b->bfsF.p;
                     B.C = b->bfsC.p;
                     B.A = b->bfsA.p;
-                    B.qCap = (uint32_t)std::min<size_t>(b->bfsQ[0].n / qPlanes, 0xFFFFFFF0u);
-                    B.evCap = (uint32_t)std::min<size_t>(b->bfsEv[0].n / evU4, 0xFFFFFFF0u);
-                    B.fCap = (uint32_t)std::min<size_t>(b->bfsF.n / F_U4, 0xFFFFFFF0u);
-                    B.cCap = (uint32_t)std::min<size_t>(b->bfsC.n / ctxU4, 0xFFFFFFF0u);
+                    B.qCap = cap32(b->bfsQ[0].n / qPlanes);
+                    B.evCap = cap32(b->bfsEv[0].n / evU4);
+                    B.fCap = cap32(b->bfsF.n / F_U4);
+                    B.cCap = cap32(b->bfsC.n / ctxU4);
                     B.ctxU4 = ctxU4;
                     B.ctxMblk = b->geoX ? CTX_MBLK_X : ctxMblkFor(b->maxLen);
-                    B.aCap = (uint32_t)std::min<size_t>(b->bfsA.n, 0xFFFFFFF0u);
+                    B.aCap = cap32(b->bfsA.n);
                     B.chain = getenv("CMB_BFS_CHAIN") ? (uint32_t)std::max(1, atoi(getenv("CMB_BFS_CHAIN"))) : BFS_CHAIN;
                     B.gridX = getenv("CMB_BFS_GRID") ? (uint32_t)std::min<int>(BFS_GRID_CNT, std::max(1, atoi(getenv("CMB_BFS_GRID"))))
                                                      : BFS_GRID_X;
@@ -1373,7 +1289,7 @@ static int batchRunOne(cmb_batch* b) {
                     HbfsBufs H{};
                     H.Q[0] = b->bfsQ[0].p;
                     H.Q[1] = b->bfsQ[1].p;
-                    H.qCap = (uint32_t)std::min<size_t>(b->bfsQ[0].n / 2, 0xFFFFFFF0u);
+                    H.qCap = cap32(b->bfsQ[0].n / 2);
                     H.nq = b->bfsCnt.p;
                     H.blockCnt = b->bfsBlockCnt.p;
                     const uint32_t hLds = stratBytes;
@@ -1475,7 +1391,7 @@ static int batchRunOne(cmb_batch* b) {
         if (b->tbq.n < tbNeed) b->tbq.alloc(tbNeed + nItems / 8);
         for (int attempt = 0;; attempt++) {
             q.text = b->text.p;
-            q.textCap = (uint32_t)std::min<size_t>(b->text.n, 0xFFFFFFF0u);
+            q.textCap = cap32(b->text.n);
             uint32_t zero[2] = {0, 0};
             HIPCHK(hipMemcpyAsync(b->cnt.p + 2, zero, sizeof(zero), hipMemcpyHostToDevice, s));
             HIPCHK(hipMemcpyAsync(b->cnt.p + 7, zero, sizeof(uint32_t), hipMemcpyHostToDevice, s));
@@ -1494,7 +1410,7 @@ static int batchRunOne(cmb_batch* b) {
                 // hold at most 2^20 reads: the sorted bits below end at VKW_RS + rsBits <= 64)
                 const bool dedup = b->metric == CMB_METRIC_EDIT && b->k > 0 && 2ull * nReads < (b->wideEdit ? (1ull << (64u - VKW_RS)) : (1ull << 25));
                 if (b->wideEdit && !dedup) return fail(CMB_ERR_INTERNAL, "a sub-batch beyond 7 errors holds more reads than its verification keys number");
-                const uint32_t tbCap = (uint32_t)std::min<size_t>(b->tbq.n, 0xFFFFFFF0u);
+                const uint32_t tbCap = cap32(b->tbq.n);
                 const char* vGroup = "k_verify";
                 tm.begin();
                 if (dedup && b->vkeysA.n < nItems) {
@@ -1543,13 +1459,13 @@ static int batchRunOne(cmb_batch* b) {
                         auto kWide = k_verify_wide<true, WxTen>;
                         if (b->geoX) kFilter = k_wide_filter<WxThirteen>, kWide = k_verify_wide<true, WxThirteen>;
                         hipLaunchKernelGGL(kFilter, dim3(fGrid), dim3(256), 0, s, ix->d, b->offs.p, b->G.p, b->gw, b->vkeysA.p, b->vcounts.p, nRuns,
-                                           b->dpWork.p, b->dpList.p, (uint32_t)std::min<size_t>(b->dpList.n, 0xFFFFFFF0u), q);
+                                           b->dpWork.p, b->dpList.p, cap32(b->dpList.n), q);
                         const uint32_t slotBytes = (vwRows(b->maxLen) + 1u) * VW_ROW_BYTES;
                         // (six wavefronts per SIMD: 1024 SIMDs x 6 x 64 lanes — forward pass and traceback wait for memory; a slot is 3 - 8 KB)
                         const uint32_t dSlots = std::min<uint32_t>(((nRuns + 255) / 256) * 256, getenv("CMB_VW_SLOTS") ? (uint32_t)atoi(getenv("CMB_VW_SLOTS")) : 256u * 1536u);
                         if (b->dpSlab.n < (size_t)slotBytes * dSlots) b->dpSlab.alloc((size_t)slotBytes * dSlots);
                         hipLaunchKernelGGL(kWide, dim3(dSlots / 256), dim3(256), 0, s, ix->d, b->offs.p, b->maxLen, b->seq.p, b->G.p, b->gw,
-                                           (const uint4*)nullptr, (uint32_t)std::min<size_t>(b->dpList.n, 0xFFFFFFF0u), b->vkeysA.p, b->vcounts.p, b->dpList.p, b->dpWork.p + 1, b->dpSlab.p, slotBytes, q);
+                                           (const uint4*)nullptr, cap32(b->dpList.n), b->vkeysA.p, b->vcounts.p, b->dpList.p, b->dpWork.p + 1, b->dpSlab.p, slotBytes, q);
                         if (verbose) {
                             uint32_t hw[2];
                             HIPCHK(hipMemcpyAsync(hw, b->dpWork.p, sizeof(hw), hipMemcpyDeviceToHost, s));
@@ -1573,7 +1489,7 @@ static int batchRunOne(cmb_batch* b) {
                             }
                         if (b->vsN.n < nStages + 2) b->vsN.alloc(nStages + 2);
                         HIPCHK(hipMemsetAsync(b->vsN.p, 0, (nStages + 2) * sizeof(uint32_t), s));
-                        const uint32_t listCap = (uint32_t)std::min<size_t>(b->vsC[0].n, 0xFFFFFFF0u);
+                        const uint32_t listCap = cap32(b->vsC[0].n);
                         const uint32_t gridCap = getenv("CMB_STAGE_GRID") ? (uint32_t)std::max(256, atoi(getenv("CMB_STAGE_GRID"))) : 8192u;
                         const uint32_t grid = std::min<uint32_t>((nRuns + 255) / 256, gridCap);
                         VStageList L0{b->vsA[0].p, b->vsB[0].p, b->vsC[0].p}, L1{b->vsA[1].p, b->vsB[1].p, b->vsC[1].p};
@@ -1711,12 +1627,7 @@ static int batchRunOne(cmb_batch* b) {
             hipLaunchKernelGGL(k_filter_segments, dim3((nText + 255) / 256), dim3(256), 0, s, b->keysB.p, nText, b->fsegB.p, b->fsegE.p, groupShift);
             hipLaunchKernelGGL(k_filter_mark, dim3((nG + 255) / 256), dim3(256), 0, s, b->keysB.p, nG, b->k, mode, b->fcounts.p,
                                b->frank.p, b->fsegB.p, b->fsegE.p, keyLayout);
-            size_t scanBytes = 0;
-            HIPCHK(rocprim::exclusive_scan(nullptr, scanBytes, b->fcounts.p, b->foffs.p, (uint64_t)0, (size_t)nG + 1,
-                                           rocprim::plus<uint64_t>(), s));
-            if (b->scanTmp.n < scanBytes) b->scanTmp.alloc(scanBytes + 256);
-            HIPCHK(rocprim::exclusive_scan(b->scanTmp.p, scanBytes, b->fcounts.p, b->foffs.p, (uint64_t)0, (size_t)nG + 1,
-                                           rocprim::plus<uint64_t>(), s));
+            scanExclusive(b->scanTmp, b->fcounts.p, b->foffs.p, (size_t)nG + 1, s);
             HIPCHK(hipMemcpyAsync(&naiveSurvivors, b->foffs.p + nG, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
             HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
@@ -1781,12 +1692,7 @@ static int batchRunOne(cmb_batch* b) {
             if (nText) HIPCHK(hipMemsetAsync(b->frank.p, 0xFF, (size_t)nText * sizeof(uint32_t), s));
             hipLaunchKernelGGL(k_filter_mark, dim3((nGroups + 255) / 256), dim3(256), 0, s, b->keysB.p, nGroups, b->k, mode,
                                b->fcounts.p, b->frank.p, b->fsegB.p, b->fsegE.p, keyLayout);
-            size_t scanBytes = 0;
-            HIPCHK(rocprim::exclusive_scan(nullptr, scanBytes, b->fcounts.p, b->foffs.p, (uint64_t)0, (size_t)nGroups + 1,
-                                           rocprim::plus<uint64_t>(), s));
-            if (b->scanTmp.n < scanBytes) b->scanTmp.alloc(scanBytes + 256);
-            HIPCHK(rocprim::exclusive_scan(b->scanTmp.p, scanBytes, b->fcounts.p, b->foffs.p, (uint64_t)0, (size_t)nGroups + 1,
-                                           rocprim::plus<uint64_t>(), s));
+            scanExclusive(b->scanTmp, b->fcounts.p, b->foffs.p, (size_t)nGroups + 1, s);
             uint64_t total = 0;
             HIPCHK(hipMemcpyAsync(&total, b->foffs.p + nGroups, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
             HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
@@ -2684,9 +2590,80 @@ extern "C" int64_t cmb_batch_sam(const cmb_batch* b, const char* seqs, const cha
 // its own stream, the finished text in one page-locked buffer of the batch.  Reads with an occurrence that runs over the end of its
 // sequence (AlnRec::spans == 1) go through samOfRead on the host — findSeqName trims them and may drop them — and their bytes are
 // copied into place by the write kernel; nothing else is formatted on the host.
-template <typename T> static void growTo(DevBuf<T>& d, size_t count) {
-    if (d.n < count || !d.p) d.alloc(count + count / 8 + 256);
+// The driver's steps, shared with cmb_best_sam_device; every one works on the stream it is given.
+// 1. The slice [r0, r0 + n) of the packed inputs goes up, the plan's arrays are sized and the length behind the last read is cleared;
+//    cx gets the input fields of the context (the packed bytes stay where they are: idBase / qualBase are subtracted on the device).
+static int samUpload(SamDeviceBufs& d, const cmb_sam_inputs* in, uint64_t r0, uint32_t n, hipStream_t s, SamCtx& cx) {
+    const size_t offBytes = ((size_t)n + 1) * sizeof(uint64_t);
+    const uint64_t idLo = in->id_offs[r0], idHi = in->id_offs[r0 + n];
+    if (idHi < idLo) return fail(CMB_ERR_INVALID, "identifier offsets must be non-decreasing");
+    growTo(d.ids, idHi - idLo + 1); // (+ 1: the cleaned identifier starts at byte 1, also of an empty line)
+    growTo(d.idOffs, (size_t)n + 1);
+    if (idHi > idLo) HIPCHK(hipMemcpyAsync(d.ids.p, in->ids + idLo, idHi - idLo, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d.idOffs.p, in->id_offs + r0, offBytes, hipMemcpyHostToDevice, s));
+    uint64_t qLo = 0;
+    if (in->quals) {
+        qLo = in->qual_offs[r0];
+        const uint64_t qHi = in->qual_offs[r0 + n];
+        if (qHi < qLo) return fail(CMB_ERR_INVALID, "quality offsets must be non-decreasing");
+        growTo(d.quals, qHi - qLo);
+        growTo(d.qualOffs, (size_t)n + 1);
+        if (qHi > qLo) HIPCHK(hipMemcpyAsync(d.quals.p, in->quals + qLo, qHi - qLo, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d.qualOffs.p, in->qual_offs + r0, offBytes, hipMemcpyHostToDevice, s));
+    }
+    const uint64_t nameBytes = in->n_seqs ? in->seq_name_offs[in->n_seqs] : 0;
+    growTo(d.names, nameBytes);
+    growTo(d.nameOffs, (size_t)in->n_seqs + 1);
+    if (nameBytes) HIPCHK(hipMemcpyAsync(d.names.p, in->seq_names, nameBytes, hipMemcpyHostToDevice, s));
+    if (in->n_seqs) HIPCHK(hipMemcpyAsync(d.nameOffs.p, in->seq_name_offs, ((size_t)in->n_seqs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    growTo(d.plan, n);
+    growTo(d.len, (size_t)n + 1);
+    growTo(d.offs, (size_t)n + 1);
+    HIPCHK(hipMemsetAsync(d.len.p + n, 0, sizeof(uint64_t), s));
+    cx.ids = d.ids.p, cx.idOffs = d.idOffs.p, cx.idBase = idLo;
+    cx.quals = in->quals ? d.quals.p : nullptr, cx.qualOffs = d.qualOffs.p, cx.qualBase = qLo;
+    cx.names = d.names.p, cx.nameOffs = d.nameOffs.p, cx.nSeqs = in->n_seqs, cx.nReads = n;
+    return CMB_OK;
 }
+// 2. The reads of `list` (ascending) are formatted on the host — format(i, text) appends the records of read i — and spliced in: their
+//    text goes up and k_sam_override puts their lengths over the plan's.  The stream must have been waited for if `list` came from it.
+template <class F> static void samSplice(SamDeviceBufs& d, const std::vector<uint32_t>& list, hipStream_t s, F format) {
+    std::string side;
+    std::vector<uint64_t> sideOffs(list.size() + 1, 0);
+    for (size_t q = 0; q < list.size(); q++) {
+        format(list[q], side);
+        sideOffs[q + 1] = side.size();
+    }
+    growTo(d.side, side.size());
+    growTo(d.sideOffs, sideOffs.size());
+    growTo(d.sideReads, list.size());
+    if (!side.empty()) HIPCHK(hipMemcpy(d.side.p, side.data(), side.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d.sideOffs.p, sideOffs.data(), sideOffs.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d.sideReads.p, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_sam_override, dim3(((uint32_t)list.size() + 255u) / 256u), dim3(256), 0, s, d.sideReads.p, d.sideOffs.p, (uint32_t)list.size(),
+                       d.plan.p, d.len.p);
+    HIPCHK(hipGetLastError());
+}
+// 3. The position of every read in the text; *total (the text's length) is valid once the stream has been waited for ...
+static void samScan(SamDeviceBufs& d, DevBuf<uint8_t>& scanTmp, uint32_t n, uint64_t* total, hipStream_t s) {
+    scanExclusive(scanTmp, d.len.p, d.offs.p, (size_t)n + 1, s);
+    HIPCHK(hipMemcpyAsync(total, d.offs.p + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+}
+//    ... and then the text is written and copied to dst (page-locked); the caller waits for the stream once more.
+static void samWrite(SamDeviceBufs& d, const SamCtx& cx, uint64_t total, char* dst, hipStream_t s) {
+    growTo(d.text, (size_t)total + 16);
+    hipLaunchKernelGGL(k_sam_write, dim3((cx.nReads + SAM_READS_PER_WAVE - 1u) / SAM_READS_PER_WAVE), dim3(64), 0, s, cx, d.plan.p, d.offs.p, d.side.p,
+                       d.text.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(dst, d.text.p, (size_t)total, hipMemcpyDeviceToHost, s));
+}
+// the sequence names of packed inputs as the host formatters take them
+static std::vector<std::string> samNamesOf(const cmb_sam_inputs* in) {
+    std::vector<std::string> names;
+    for (uint32_t q = 0; q < in->n_seqs; q++) names.emplace_back(in->seq_names + in->seq_name_offs[q], in->seq_names + in->seq_name_offs[q + 1]);
+    return names;
+}
+
 extern "C" int cmb_batch_sam_device(cmb_batch* b, const cmb_sam_inputs* in, int unmapped_records, int xa_tag, const char** text,
                                     uint64_t* length, uint64_t* host_reads) {
     if (!b || !in || !text || !length || !in->seqs || !in->ids || !in->id_offs || (in->quals && !in->qual_offs) ||
@@ -2701,7 +2678,6 @@ extern "C" int cmb_batch_sam_device(cmb_batch* b, const cmb_sam_inputs* in, int 
         cmb_index* idx = b->ix;
         useDevice(idx->device);
         const size_t P = parts.size();
-        const uint64_t nameBytes = in->n_seqs ? in->seq_name_offs[in->n_seqs] : 0;
         const bool verbose = getenv("CMB_VERBOSE") != nullptr;
         auto t0 = std::chrono::steady_clock::now();
         auto lap = [&](const char* what) {
@@ -2723,44 +2699,18 @@ extern "C" int cmb_batch_sam_device(cmb_batch* b, const cmb_sam_inputs* in, int 
             const uint32_t n = c->nReads;
             if (!n) continue;
             hipStream_t s = c->stream;
-            const uint64_t r0 = readBase[j];
-            const uint64_t idLo = in->id_offs[r0], idHi = in->id_offs[r0 + n];
-            if (idHi < idLo) return fail(CMB_ERR_INVALID, "identifier offsets must be non-decreasing");
-            growTo(c->samIds, idHi - idLo + 1); // (+ 1: the cleaned identifier starts at byte 1, also of an empty line)
-            growTo(c->samIdOffs, (size_t)n + 1);
-            if (idHi > idLo) HIPCHK(hipMemcpyAsync(c->samIds.p, in->ids + idLo, idHi - idLo, hipMemcpyHostToDevice, s));
-            HIPCHK(hipMemcpyAsync(c->samIdOffs.p, in->id_offs + r0, ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-            uint64_t qLo = 0;
-            if (in->quals) {
-                qLo = in->qual_offs[r0];
-                const uint64_t qHi = in->qual_offs[r0 + n];
-                if (qHi < qLo) return fail(CMB_ERR_INVALID, "quality offsets must be non-decreasing");
-                growTo(c->samQuals, qHi - qLo);
-                growTo(c->samQualOffs, (size_t)n + 1);
-                if (qHi > qLo) HIPCHK(hipMemcpyAsync(c->samQuals.p, in->quals + qLo, qHi - qLo, hipMemcpyHostToDevice, s));
-                HIPCHK(hipMemcpyAsync(c->samQualOffs.p, in->qual_offs + r0, ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-            }
-            growTo(c->samNames, nameBytes);
-            growTo(c->samNameOffs, (size_t)in->n_seqs + 1);
-            if (nameBytes) HIPCHK(hipMemcpyAsync(c->samNames.p, in->seq_names, nameBytes, hipMemcpyHostToDevice, s));
-            if (in->n_seqs)
-                HIPCHK(hipMemcpyAsync(c->samNameOffs.p, in->seq_name_offs, ((size_t)in->n_seqs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-            growTo(c->samPlan, n);
-            growTo(c->samLen, (size_t)n + 1);
-            growTo(c->samOffs, (size_t)n + 1);
-            growTo(c->samHostList, (size_t)n + 1);
-            HIPCHK(hipMemsetAsync(c->samLen.p + n, 0, sizeof(uint64_t), s));
-            HIPCHK(hipMemsetAsync(c->samHostList.p, 0, sizeof(uint32_t), s));
             SamCtx& cx = ctx[j];
-            cx = SamCtx{c->reads.p, c->offs.p, c->foffs.p, c->perStrand ? 2u : 1u, c->fout.p, c->alnRec.p, c->alnOps.p, c->alnStride,
-                        c->samIds.p, c->samIdOffs.p, idLo, in->quals ? c->samQuals.p : nullptr, c->samQualOffs.p, qLo,
-                        c->samNames.p, c->samNameOffs.p, in->n_seqs, n, unmapped_records ? 1u : 0u, xa_tag ? 1u : 0u};
-            hipLaunchKernelGGL(k_sam_plan, dim3((n + 3u) / 4u), dim3(256), 0, s, cx, c->samPlan.p, c->samLen.p, c->samHostList.p);
+            cx = SamCtx{c->reads.p, c->offs.p, c->foffs.p, c->perStrand ? 2u : 1u, c->fout.p, c->alnRec.p, c->alnOps.p, c->alnStride};
+            cx.unmapped = unmapped_records ? 1u : 0u, cx.xa = xa_tag ? 1u : 0u;
+            if (int rc = samUpload(c->sam, in, readBase[j], n, s, cx)) return rc;
+            growTo(c->samHostList, (size_t)n + 1);
+            HIPCHK(hipMemsetAsync(c->samHostList.p, 0, sizeof(uint32_t), s));
+            hipLaunchKernelGGL(k_sam_plan, dim3((n + 3u) / 4u), dim3(256), 0, s, cx, c->sam.plan.p, c->sam.len.p, c->samHostList.p);
             HIPCHK(hipGetLastError());
             HIPCHK(hipMemcpyAsync(&nHost[j], c->samHostList.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         }
         lap("inputs up, plan started");
-        // ---- the reads the host formats, then the position of every read in its sub-batch's text
+        // ---- the reads the host formats (k_sam_plan listed them), then the position of every read in its sub-batch's text
         std::vector<std::string> names;
         std::vector<const char*> namePtrs;
         uint64_t nHostAll = 0;
@@ -2771,18 +2721,13 @@ extern "C" int cmb_batch_sam_device(cmb_batch* b, const cmb_sam_inputs* in, int 
             hipStream_t s = c->stream;
             HIPCHK(hipStreamSynchronize(s));
             if (nHost[j]) {
-                if (names.empty())
-                    for (uint32_t q = 0; q < in->n_seqs; q++)
-                        names.emplace_back(in->seq_names + in->seq_name_offs[q], in->seq_names + in->seq_name_offs[q + 1]);
+                if (names.empty()) names = samNamesOf(in);
                 if (namePtrs.empty())
                     for (const std::string& nm : names) namePtrs.push_back(nm.c_str());
                 std::vector<uint32_t> list(nHost[j]);
                 HIPCHK(hipMemcpy(list.data(), c->samHostList.p + 1, (size_t)nHost[j] * sizeof(uint32_t), hipMemcpyDeviceToHost));
                 std::sort(list.begin(), list.end());
-                std::string side;
-                std::vector<uint64_t> sideOffs(list.size() + 1, 0);
-                for (size_t q = 0; q < list.size(); q++) {
-                    const uint32_t i = list[q];
+                samSplice(c->sam, list, s, [&](uint32_t i, std::string& side) {
                     const uint64_t gi = readBase[j] + i;
                     const uint64_t o0 = charBase[j] + c->hostOffs[i], o1 = charBase[j] + c->hostOffs[i + 1];
                     const std::string read = cleanReadSeq(std::string(in->seqs + o0, in->seqs + o1)), revC = revComplWithN(read);
@@ -2790,24 +2735,10 @@ extern "C" int cmb_batch_sam_device(cmb_batch* b, const cmb_sam_inputs* in, int 
                     const std::string qual = in->quals ? std::string(in->quals + in->qual_offs[gi], in->quals + in->qual_offs[gi + 1]) : "*";
                     std::vector<BestOcc> occs = occsOfBatchRead(c, i);
                     samOfRead(side, idx, c->k, c->metric, read, revC, sid, qual, occs, namePtrs.data(), unmapped_records, xa_tag);
-                    sideOffs[q + 1] = side.size();
-                }
-                growTo(c->samSide, side.size());
-                growTo(c->samSideOffs, sideOffs.size());
-                growTo(c->samSideReads, list.size());
-                if (!side.empty()) HIPCHK(hipMemcpy(c->samSide.p, side.data(), side.size(), hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(c->samSideOffs.p, sideOffs.data(), sideOffs.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(c->samSideReads.p, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-                hipLaunchKernelGGL(k_sam_override, dim3((nHost[j] + 255u) / 256u), dim3(256), 0, s, c->samSideReads.p, c->samSideOffs.p, nHost[j],
-                                   c->samPlan.p, c->samLen.p);
-                HIPCHK(hipGetLastError());
+                });
                 nHostAll += nHost[j];
             }
-            size_t scanBytes = 0;
-            HIPCHK(rocprim::exclusive_scan(nullptr, scanBytes, c->samLen.p, c->samOffs.p, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), s));
-            if (c->scanTmp.n < scanBytes) c->scanTmp.alloc(scanBytes + 256);
-            HIPCHK(rocprim::exclusive_scan(c->scanTmp.p, scanBytes, c->samLen.p, c->samOffs.p, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), s));
-            HIPCHK(hipMemcpyAsync(&partBytes[j], c->samOffs.p + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+            samScan(c->sam, c->scanTmp, n, &partBytes[j], s);
         }
         uint64_t total = 0;
         for (size_t j = 0; j < P; j++) {
@@ -2820,14 +2751,8 @@ extern "C" int cmb_batch_sam_device(cmb_batch* b, const cmb_sam_inputs* in, int 
         b->samOut.p[total] = '\0';
         uint64_t at = 0;
         for (size_t j = 0; j < P; j++) {
-            cmb_batch* c = parts[j];
-            const uint32_t n = c->nReads;
-            if (!n || !partBytes[j]) continue;
-            growTo(c->samText, (size_t)partBytes[j] + 16);
-            hipLaunchKernelGGL(k_sam_write, dim3((n + SAM_READS_PER_WAVE - 1u) / SAM_READS_PER_WAVE), dim3(64), 0, c->stream, ctx[j], c->samPlan.p,
-                               c->samOffs.p, c->samSide.p, c->samText.p);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(b->samOut.p + at, c->samText.p, (size_t)partBytes[j], hipMemcpyDeviceToHost, c->stream));
+            if (!parts[j]->nReads || !partBytes[j]) continue;
+            samWrite(parts[j]->sam, ctx[j], partBytes[j], b->samOut.p + at, parts[j]->stream);
             at += partBytes[j];
         }
         for (size_t j = 0; j < P; j++)
@@ -2918,12 +2843,11 @@ struct cmb_best {
     DevBuf<uint32_t> dBest, dHits;
     std::vector<uint8_t> hostRead; // reads whose bookkeeping went through the host (an occurrence over a sequence end, edit distance)
     uint32_t nHostReads = 0;
-    // cmb_best_sam_device: the chunk's raw reads and packed inputs, the plan, the text
-    DevBuf<uint8_t> samReads, samIds, samQuals, samNames, samSide, samText, scanTmp;
-    DevBuf<uint64_t> samReadOffs, samIdOffs, samQualOffs, samNameOffs, samLen, samOffs, samSideOffs;
-    DevBuf<SamPlan> samPlan;
-    DevBuf<uint32_t> samSideReads;
-    DevBuf<uint8_t> samHostFlag;
+    // cmb_best_sam_device: the SAM driver's buffers, the chunk's raw reads (the batches of the strata are gone), the reads the host
+    // formats as a flag per read (k_sam_plan_best), the finished text
+    SamDeviceBufs sam;
+    DevBuf<uint8_t> samReads, samHostFlag, scanTmp;
+    DevBuf<uint64_t> samReadOffs;
     PinnedBuf<char> samOut;
     std::vector<uint64_t> readOffs; // the chunk's read offsets, as given to cmb_match_best_device
     // cmb_best_timings: host time per phase of the call (every phase ends in a synchronise) and, summed over the strata, the
@@ -3229,12 +3153,6 @@ struct BestPoolBufs {
         cap = c;
     }
 };
-template <typename T> void scanExclusive(DevBuf<uint8_t>& tmp, const T* in, uint64_t* out, size_t n) {
-    size_t bytes = 0;
-    HIPCHK(rocprim::exclusive_scan(nullptr, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), (hipStream_t)0));
-    if (tmp.n < bytes || !tmp.p) tmp.alloc(bytes + 256);
-    HIPCHK(rocprim::exclusive_scan(tmp.p, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), (hipStream_t)0));
-}
 inline BestOcc bestOccOf(const uint4& o, const AlnRec& a, const uint16_t* ops) { // (CIGAR runs are stored end to begin)
     BestOcc b;
     b.occ = cmb_occ{o.x, o.y, o.z, o.w};
@@ -3360,7 +3278,7 @@ extern "C" int cmb_match_best_device(cmb_index* idx, const cmb_strategy* st, uin
                 base += c->nReads;
             }
             HIPCHK(hipGetLastError());
-            scanExclusive(tmp, dCnt.p, dPoff.p, (size_t)n + 1);
+            scanExclusive(tmp, dCnt.p, dPoff.p, (size_t)n + 1, (hipStream_t)0);
             uint64_t kept = 0;
             hMasks.resize(n);
             HIPCHK(hipMemcpy(&kept, dPoff.p + n, sizeof(uint64_t), hipMemcpyDeviceToHost));
@@ -3588,7 +3506,7 @@ extern "C" int cmb_match_best_device(cmb_index* idx, const cmb_strategy* st, uin
         if (nPool) {
             hipLaunchKernelGGL(k_best_flag, dim3((uint32_t)((nPool + 255u) / 256u)), dim3(256), 0, 0, pool.at(0), nPool, dState.p, dFlag.p, R->dHits.p);
             HIPCHK(hipGetLastError());
-            scanExclusive(tmp, dFlag.p, dPos.p, (size_t)nPool + 1);
+            scanExclusive(tmp, dFlag.p, dPos.p, (size_t)nPool + 1, (hipStream_t)0);
             HIPCHK(hipMemcpy(&nSel, dPos.p + nPool, sizeof(uint64_t), hipMemcpyDeviceToHost));
         }
         growTo(dUflag, (size_t)nSel + 1), growTo(dUpos, (size_t)nSel + 1);
@@ -3605,7 +3523,7 @@ extern "C" int cmb_match_best_device(cmb_index* idx, const cmb_strategy* st, uin
             HIPCHK(hipMemset(dUflag.p + nSel, 0, sizeof(uint64_t)));
             hipLaunchKernelGGL(k_best_uniq, dim3((uint32_t)((nSel + 255u) / 256u)), dim3(256), 0, 0, keysB.p, nSel, dUflag.p, dPerRead.p);
             HIPCHK(hipGetLastError());
-            scanExclusive(tmp, dUflag.p, dUpos.p, (size_t)nSel + 1);
+            scanExclusive(tmp, dUflag.p, dUpos.p, (size_t)nSel + 1, (hipStream_t)0);
             HIPCHK(hipMemcpy(&nDev, dUpos.p + nSel, sizeof(uint64_t), hipMemcpyDeviceToHost));
         }
         // every read's place in the final lists: a running sum over one word per read
@@ -3679,7 +3597,6 @@ extern "C" int cmb_best_sam_device(cmb_best* r, const cmb_sam_inputs* in, int un
         if (host_reads) *host_reads = r->nHostReads;
         if (!n) return CMB_OK;
         hipStream_t s = 0;
-        const uint64_t nameBytes = in->n_seqs ? in->seq_name_offs[in->n_seqs] : 0;
         if (!r->readsUp) { // the chunk's raw reads: once per handle
             const uint64_t chars = r->readOffs[n];
             growTo(r->samReads, chars + 1);
@@ -3690,106 +3607,62 @@ extern "C" int cmb_best_sam_device(cmb_best* r, const cmb_sam_inputs* in, int un
             HIPCHK(hipMemcpy(r->samHostFlag.p, r->hostRead.data(), n, hipMemcpyHostToDevice));
             r->readsUp = true;
         }
-        const uint64_t idLo = in->id_offs[0], idHi = in->id_offs[n];
-        if (idHi < idLo) return fail(CMB_ERR_INVALID, "identifier offsets must be non-decreasing");
-        growTo(r->samIds, idHi - idLo + 1);
-        growTo(r->samIdOffs, (size_t)n + 1);
-        if (idHi > idLo) HIPCHK(hipMemcpyAsync(r->samIds.p, in->ids + idLo, idHi - idLo, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(r->samIdOffs.p, in->id_offs, ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-        uint64_t qLo = 0;
-        if (in->quals) {
-            qLo = in->qual_offs[0];
-            const uint64_t qHi = in->qual_offs[n];
-            if (qHi < qLo) return fail(CMB_ERR_INVALID, "quality offsets must be non-decreasing");
-            growTo(r->samQuals, qHi - qLo);
-            growTo(r->samQualOffs, (size_t)n + 1);
-            if (qHi > qLo) HIPCHK(hipMemcpyAsync(r->samQuals.p, in->quals + qLo, qHi - qLo, hipMemcpyHostToDevice, s));
-            HIPCHK(hipMemcpyAsync(r->samQualOffs.p, in->qual_offs, ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-        }
-        growTo(r->samNames, nameBytes);
-        growTo(r->samNameOffs, (size_t)in->n_seqs + 1);
-        if (nameBytes) HIPCHK(hipMemcpyAsync(r->samNames.p, in->seq_names, nameBytes, hipMemcpyHostToDevice, s));
-        if (in->n_seqs)
-            HIPCHK(hipMemcpyAsync(r->samNameOffs.p, in->seq_name_offs, ((size_t)in->n_seqs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-        growTo(r->samPlan, n);
-        growTo(r->samLen, (size_t)n + 1);
-        growTo(r->samOffs, (size_t)n + 1);
-        HIPCHK(hipMemsetAsync(r->samLen.p + n, 0, sizeof(uint64_t), s));
-        const SamCtx cx{r->samReads.p, r->samReadOffs.p, r->dOffs.p, 1u, r->dOcc.p, r->dAln.p, r->dOps.p, BEST_OPS_STRIDE,
-                        r->samIds.p, r->samIdOffs.p, idLo, in->quals ? r->samQuals.p : nullptr, r->samQualOffs.p, qLo,
-                        r->samNames.p, r->samNameOffs.p, in->n_seqs, n, unmapped_records ? 1u : 0u, xa_tag ? 1u : 0u};
-        hipLaunchKernelGGL(k_sam_plan_best, dim3((n + 3u) / 4u), dim3(256), 0, s, cx, r->dBest.p, r->dHits.p, r->samHostFlag.p, r->samPlan.p,
-                           r->samLen.p);
+        SamCtx cx{r->samReads.p, r->samReadOffs.p, r->dOffs.p, 1u, r->dOcc.p, r->dAln.p, r->dOps.p, BEST_OPS_STRIDE};
+        cx.unmapped = unmapped_records ? 1u : 0u, cx.xa = xa_tag ? 1u : 0u;
+        if (int rc = samUpload(r->sam, in, 0, n, s, cx)) return rc;
+        hipLaunchKernelGGL(k_sam_plan_best, dim3((n + 3u) / 4u), dim3(256), 0, s, cx, r->dBest.p, r->dHits.p, r->samHostFlag.p, r->sam.plan.p,
+                           r->sam.len.p);
         HIPCHK(hipGetLastError());
-        // ---- the host reads through the record builders (samOfBest's lines), their lengths over the plan's
+        // ---- the host reads (known from the strata bookkeeping) through the record builders: samOfBest's lines
         if (r->nHostReads) {
-            std::vector<const char*> names(in->n_seqs);
-            std::vector<std::string> nameStr;
-            for (uint32_t q = 0; q < in->n_seqs; q++) nameStr.emplace_back(in->seq_names + in->seq_name_offs[q], in->seq_names + in->seq_name_offs[q + 1]);
+            const std::vector<std::string> nameStr = samNamesOf(in);
             std::vector<uint32_t> list;
             for (uint32_t i = 0; i < n; i++)
                 if (r->hostRead[i]) list.push_back(i);
-            std::string side;
-            std::vector<uint64_t> sideOffs(list.size() + 1, 0);
-            for (size_t q = 0; q < list.size(); q++) {
-                const uint32_t i = list[q];
+            samSplice(r->sam, list, s, [&](uint32_t i, std::string& side) {
                 const std::string read = cleanReadSeq(std::string(in->seqs + r->readOffs[i], in->seqs + r->readOffs[i + 1])), revC = revComplWithN(read);
                 const std::string sid = cleanSeqID(std::string(in->ids + in->id_offs[i], in->ids + in->id_offs[i + 1]));
                 const std::string qual = in->quals ? std::string(in->quals + in->qual_offs[i], in->quals + in->qual_offs[i + 1]) : "*";
                 const uint64_t o0 = r->offs[i], cnt = r->offs[i + 1] - o0;
                 if (!cnt) {
                     if (unmapped_records) side += samLineUnmappedSE(sid, read, qual);
-                } else {
-                    std::vector<uint4> oc(cnt);
-                    std::vector<AlnRec> al(cnt);
-                    std::vector<uint16_t> op(cnt * BEST_OPS_STRIDE);
-                    HIPCHK(hipMemcpy(oc.data(), r->dOcc.p + o0, cnt * sizeof(uint4), hipMemcpyDeviceToHost));
-                    HIPCHK(hipMemcpy(al.data(), r->dAln.p + o0, cnt * sizeof(AlnRec), hipMemcpyDeviceToHost));
-                    HIPCHK(hipMemcpy(op.data(), r->dOps.p + o0 * BEST_OPS_STRIDE, op.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
-                    std::vector<SamHit> hits;
-                    for (uint64_t t = 0; t < cnt; t++) {
-                        const BestOcc bo = bestOccOf(oc[t], al[t], op.data() + t * BEST_OPS_STRIDE);
-                        SamHit h;
-                        h.seqName = bo.aln.seq_id < nameStr.size() ? nameStr[bo.aln.seq_id] : std::string();
-                        h.cigar = cigarString(bo.ops.data(), (uint32_t)bo.ops.size());
-                        h.pos0 = bo.aln.seq_begin;
-                        h.distance = bo.occ.distance;
-                        h.revCompl = bo.occ.strand != 0;
-                        hits.push_back(h);
-                    }
-                    std::string revQ = qual;
-                    std::reverse(revQ.begin(), revQ.end());
-                    const bool rcFirst = hits[0].revCompl;
-                    if (xa_tag) {
-                        side += samLineSEWithXA(sid, hits, r->nHits[i], rcFirst ? revC : read, rcFirst ? revQ : qual);
-                    } else {
-                        side += samLineSE(sid, hits[0], true, r->nHits[i], r->best[i], rcFirst ? revC : read, rcFirst ? revQ : qual);
-                        for (size_t j = 1; j < hits.size(); j++) side += samLineSE(sid, hits[j], false, r->nHits[i], r->best[i], "*", "*");
-                    }
+                    return;
                 }
-                sideOffs[q + 1] = side.size();
-            }
-            growTo(r->samSide, side.size());
-            growTo(r->samSideOffs, sideOffs.size());
-            growTo(r->samSideReads, list.size());
-            if (!side.empty()) HIPCHK(hipMemcpy(r->samSide.p, side.data(), side.size(), hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(r->samSideOffs.p, sideOffs.data(), sideOffs.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(r->samSideReads.p, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(k_sam_override, dim3(((uint32_t)list.size() + 255u) / 256u), dim3(256), 0, s, r->samSideReads.p, r->samSideOffs.p,
-                               (uint32_t)list.size(), r->samPlan.p, r->samLen.p);
-            HIPCHK(hipGetLastError());
+                std::vector<uint4> oc(cnt);
+                std::vector<AlnRec> al(cnt);
+                std::vector<uint16_t> op(cnt * BEST_OPS_STRIDE);
+                HIPCHK(hipMemcpy(oc.data(), r->dOcc.p + o0, cnt * sizeof(uint4), hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(al.data(), r->dAln.p + o0, cnt * sizeof(AlnRec), hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(op.data(), r->dOps.p + o0 * BEST_OPS_STRIDE, op.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
+                std::vector<SamHit> hits;
+                for (uint64_t t = 0; t < cnt; t++) {
+                    const BestOcc bo = bestOccOf(oc[t], al[t], op.data() + t * BEST_OPS_STRIDE);
+                    SamHit h;
+                    h.seqName = bo.aln.seq_id < nameStr.size() ? nameStr[bo.aln.seq_id] : std::string();
+                    h.cigar = cigarString(bo.ops.data(), (uint32_t)bo.ops.size());
+                    h.pos0 = bo.aln.seq_begin;
+                    h.distance = bo.occ.distance;
+                    h.revCompl = bo.occ.strand != 0;
+                    hits.push_back(h);
+                }
+                std::string revQ = qual;
+                std::reverse(revQ.begin(), revQ.end());
+                const bool rcFirst = hits[0].revCompl;
+                if (xa_tag) {
+                    side += samLineSEWithXA(sid, hits, r->nHits[i], rcFirst ? revC : read, rcFirst ? revQ : qual);
+                } else {
+                    side += samLineSE(sid, hits[0], true, r->nHits[i], r->best[i], rcFirst ? revC : read, rcFirst ? revQ : qual);
+                    for (size_t j = 1; j < hits.size(); j++) side += samLineSE(sid, hits[j], false, r->nHits[i], r->best[i], "*", "*");
+                }
+            });
         }
-        scanExclusive(r->scanTmp, r->samLen.p, r->samOffs.p, (size_t)n + 1);
         uint64_t total = 0;
-        HIPCHK(hipMemcpy(&total, r->samOffs.p + n, sizeof(uint64_t), hipMemcpyDeviceToHost));
+        samScan(r->sam, r->scanTmp, n, &total, s);
+        HIPCHK(hipStreamSynchronize(s));
         r->samOut.resize((size_t)total + 1);
         r->samOut.p[total] = '\0';
         if (total) {
-            growTo(r->samText, (size_t)total + 16);
-            hipLaunchKernelGGL(k_sam_write, dim3((n + SAM_READS_PER_WAVE - 1u) / SAM_READS_PER_WAVE), dim3(64), 0, s, cx, r->samPlan.p, r->samOffs.p,
-                               r->samSide.p, r->samText.p);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(r->samOut.p, r->samText.p, (size_t)total, hipMemcpyDeviceToHost, s));
+            samWrite(r->sam, cx, total, r->samOut.p, s);
             HIPCHK(hipStreamSynchronize(s));
         }
         *text = r->samOut.p;

@@ -10,10 +10,14 @@
 //   TextOcc::createUnmappedSAMOccurrenceSE       indexhelpers.cpp:177-200
 //   SearchStrategy::generateOutputSingleEnd      searchstrategy.cpp:1824-1902
 //
+//   shared by the two plan kernels: samIdLen (the cleaned identifier's length), samMappedLen (the bytes of a mapped read's records),
+//   samUnmappedLen / samUnmappedSeqAt (the record of a read without an occurrence; the latter also places SEQ in k_sam_write)
 //   k_sam_plan      a wavefront per read, lane-strided over its occurrences: the primary (first occurrence of minimal distance),
 //                   minScore, nHits, whether an occurrence runs over the end of its sequence (that read is formatted on the host:
 //                   findSeqName trims and verifies again, and may drop the occurrence), the exact byte length of the read's records
 //   (rocPRIM)       exclusive 64-bit scan of the lengths: the position of every read in the text
+//   k_sam_plan_best the same plan for the final lists of BEST mode: primary, minScore and nHits come from the strata bookkeeping,
+//                   the host-formatted reads from a flag per read
 //   k_sam_override  the lengths of the host-formatted reads, before the scan
 //   k_sam_write     a wavefront per SAM_READS_PER_WAVE consecutive reads, i.e. per contiguous piece of the text.  The piece is
 //                   cut into windows of SAM_WIN bytes aligned in the TEXT; a window is assembled in LDS and stored with 16-byte
@@ -122,12 +126,14 @@ __device__ __forceinline__ uint32_t samQualLen(const SamCtx& cx, uint32_t r) {
     return cx.quals ? (uint32_t)(cx.qualOffs[r + 1] - cx.qualOffs[r]) : 1u;
 }
 
-__global__ void __launch_bounds__(256)
-k_sam_plan(SamCtx cx, SamPlan* __restrict__ plan, uint64_t* __restrict__ len, uint32_t* __restrict__ hostList /* [0]: how many */) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (r >= cx.nReads) return; // (a whole wavefront)
-    // cleaned identifier (reads.h:43-52): cut at the first space, without the first character
+// the record of a read without an occurrence (indexhelpers.cpp:177-200): "id \t4\t*\t0\t0\t*\t*\t0\t0\t SEQ \t QUAL \tPG:Z:Columba\n"
+// (samUnmappedSeqAt: where SEQ begins in a record that begins at `start`)
+__device__ __forceinline__ uint64_t samUnmappedSeqAt(uint64_t start, uint32_t idLen) { return start + idLen + 17u; }
+__device__ __forceinline__ uint64_t samUnmappedLen(uint32_t idLen, uint32_t readLen, uint32_t qualLen) {
+    return samUnmappedSeqAt(0, idLen) + readLen + 1u + qualLen + 14u;
+}
+// length of read r's cleaned identifier (reads.h:43-52): cut at the first space, without the first character.  A whole wavefront.
+__device__ __forceinline__ uint32_t samIdLen(const SamCtx& cx, uint32_t r, uint32_t lane) {
     const uint8_t* id = cx.ids + (cx.idOffs[r] - cx.idBase);
     const uint32_t idRaw = (uint32_t)(cx.idOffs[r + 1] - cx.idOffs[r]);
     uint32_t sp = idRaw;
@@ -139,8 +145,36 @@ k_sam_plan(SamCtx cx, SamPlan* __restrict__ plan, uint64_t* __restrict__ len, ui
             break;
         }
     }
+    return sp ? sp - 1u : 0u;
+}
+// bytes of the records of a mapped read whose plan (primary, minScore, nHits, idLen) is pl and whose n occurrences begin at q0: the
+// primary's line with SEQ and QUAL, then a secondary line or an XA entry each.  A whole wavefront, lane-strided over the occurrences.
+__device__ __forceinline__ uint64_t samMappedLen(const SamCtx& cx, const SamPlan& pl, uint64_t q0, uint32_t n, uint32_t readLen, uint32_t qualLen,
+                                                 uint32_t lane) {
+    const uint32_t mapq = samMapQ(pl.nHits);
+    const bool star = !cx.quals || (cx.xa && qualLen == 0u); // (host_sam.hpp:96: an empty quality prints as "*" beside an XA tag)
+    unsigned long long sum = 0;
+    for (uint32_t p = lane; p < n; p += 64u) {
+        const SamHitDev h = samLoadHit(cx, q0 + samOccAt(p, pl.primary));
+        if (p == 0u) {
+            sum += samLineLen(pl.idLen, h, h.strand ? 16u : 0u, mapq, readLen, star ? 1u : qualLen);
+            if (cx.xa) sum += 6u + decWidth(pl.nHits - 1u) + 6u + decWidth(n - pl.nHits) + 6u; // X0, X1, XA:Z: (the newline moves to the end)
+        } else if (cx.xa) {
+            sum += samXaEntryLen(h);
+        } else {
+            sum += samLineLen(pl.idLen, h, h.strand ? 272u : 256u, h.dist == pl.minScore ? mapq : 0u, 1u, 1u);
+        }
+    }
+    return waveSum64(sum);
+}
+
+__global__ void __launch_bounds__(256)
+k_sam_plan(SamCtx cx, SamPlan* __restrict__ plan, uint64_t* __restrict__ len, uint32_t* __restrict__ hostList /* [0]: how many */) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (r >= cx.nReads) return; // (a whole wavefront)
     SamPlan pl{};
-    pl.idLen = sp ? sp - 1u : 0u;
+    pl.idLen = samIdLen(cx, r, lane);
     const uint32_t readLen = (uint32_t)(cx.offs[r + 1] - cx.offs[r]);
     const uint32_t qualLen = samQualLen(cx, r);
     const uint64_t q0 = cx.foffs[(uint64_t)r * cx.groupStride], q1 = cx.foffs[(uint64_t)(r + 1) * cx.groupStride];
@@ -148,7 +182,7 @@ k_sam_plan(SamCtx cx, SamPlan* __restrict__ plan, uint64_t* __restrict__ len, ui
     uint64_t total = 0;
     if (n == 0) {
         pl.kind = cx.unmapped ? SAM_UNMAPPED : SAM_NOTHING;
-        if (cx.unmapped) total = (uint64_t)pl.idLen + 17u + readLen + 1u + qualLen + 14u; // indexhelpers.cpp:177-200
+        if (cx.unmapped) total = samUnmappedLen(pl.idLen, readLen, qualLen);
     } else {
         unsigned long long best = ~0ull;
         uint32_t over = 0;
@@ -168,21 +202,7 @@ k_sam_plan(SamCtx cx, SamPlan* __restrict__ plan, uint64_t* __restrict__ len, ui
             uint32_t cnt = 0;
             for (uint32_t j = lane; j < n; j += 64u) cnt += cx.occ[q0 + j].z == pl.minScore ? 1u : 0u;
             pl.nHits = (uint32_t)waveSum64(cnt);
-            const uint32_t mapq = samMapQ(pl.nHits);
-            const bool star = !cx.quals || (cx.xa && qualLen == 0u); // (host_sam.hpp:96: an empty quality prints as "*" beside an XA tag)
-            unsigned long long sum = 0;
-            for (uint32_t p = lane; p < n; p += 64u) {
-                const SamHitDev h = samLoadHit(cx, q0 + samOccAt(p, pl.primary));
-                if (p == 0u) {
-                    sum += samLineLen(pl.idLen, h, h.strand ? 16u : 0u, mapq, readLen, star ? 1u : qualLen);
-                    if (cx.xa) sum += 6u + decWidth(pl.nHits - 1u) + 6u + decWidth(n - pl.nHits) + 6u; // X0, X1, XA:Z: (the newline moves to the end)
-                } else if (cx.xa) {
-                    sum += samXaEntryLen(h);
-                } else {
-                    sum += samLineLen(pl.idLen, h, h.strand ? 272u : 256u, h.dist == pl.minScore ? mapq : 0u, 1u, 1u);
-                }
-            }
-            total = waveSum64(sum);
+            total = samMappedLen(cx, pl, q0, n, readLen, qualLen, lane);
         }
     }
     if (lane == 0) {
@@ -201,19 +221,8 @@ k_sam_plan_best(SamCtx cx, const uint32_t* __restrict__ best, const uint32_t* __
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (r >= cx.nReads) return; // (a whole wavefront)
-    const uint8_t* id = cx.ids + (cx.idOffs[r] - cx.idBase);
-    const uint32_t idRaw = (uint32_t)(cx.idOffs[r + 1] - cx.idOffs[r]);
-    uint32_t sp = idRaw;
-    for (uint32_t base = 0; base < idRaw; base += 64u) {
-        const uint32_t i = base + lane;
-        const unsigned long long m = __ballot(i < idRaw && id[i] == ' ');
-        if (m) {
-            sp = base + (uint32_t)__builtin_ctzll(m);
-            break;
-        }
-    }
     SamPlan pl{};
-    pl.idLen = sp ? sp - 1u : 0u;
+    pl.idLen = samIdLen(cx, r, lane);
     const uint32_t readLen = (uint32_t)(cx.offs[r + 1] - cx.offs[r]);
     const uint32_t qualLen = samQualLen(cx, r);
     const uint64_t q0 = cx.foffs[(uint64_t)r * cx.groupStride], q1 = cx.foffs[(uint64_t)(r + 1) * cx.groupStride];
@@ -223,27 +232,13 @@ k_sam_plan_best(SamCtx cx, const uint32_t* __restrict__ best, const uint32_t* __
         pl.kind = SAM_HOST; // (its length comes from the host: k_sam_override)
     } else if (n == 0) {
         pl.kind = cx.unmapped ? SAM_UNMAPPED : SAM_NOTHING;
-        if (cx.unmapped) total = (uint64_t)pl.idLen + 17u + readLen + 1u + qualLen + 14u; // indexhelpers.cpp:177-200
+        if (cx.unmapped) total = samUnmappedLen(pl.idLen, readLen, qualLen);
     } else {
         pl.kind = SAM_MAPPED;
-        pl.primary = 0;
+        pl.primary = 0; // (samOccAt(p, 0) == p)
         pl.minScore = best[r];
         pl.nHits = hits[r];
-        const uint32_t mapq = samMapQ(pl.nHits);
-        const bool star = !cx.quals || (cx.xa && qualLen == 0u); // (host_sam.hpp:96)
-        unsigned long long sum = 0;
-        for (uint32_t p = lane; p < n; p += 64u) {
-            const SamHitDev h = samLoadHit(cx, q0 + p);
-            if (p == 0u) {
-                sum += samLineLen(pl.idLen, h, h.strand ? 16u : 0u, mapq, readLen, star ? 1u : qualLen);
-                if (cx.xa) sum += 6u + decWidth(pl.nHits - 1u) + 6u + decWidth(n - pl.nHits) + 6u; // X0, X1, XA:Z:
-            } else if (cx.xa) {
-                sum += samXaEntryLen(h);
-            } else {
-                sum += samLineLen(pl.idLen, h, h.strand ? 272u : 256u, h.dist == pl.minScore ? mapq : 0u, 1u, 1u);
-            }
-        }
-        total = waveSum64(sum);
+        total = samMappedLen(cx, pl, q0, n, readLen, qualLen, lane);
     }
     if (lane == 0) {
         plan[r] = pl;
@@ -403,8 +398,8 @@ k_sam_write(SamCtx cx, const SamPlan* __restrict__ plan, const uint64_t* __restr
         const uint8_t* rd = cx.reads + samUniform(rc.rdOff);
         const uint8_t* ql = cx.quals ? cx.quals + samUniform(rc.qlOff) : nullptr;
         uint32_t qualLen = samUniform(rc.qualLen);
-        if (kind == SAM_UNMAPPED) { // indexhelpers.cpp:177-200
-            const uint64_t seqAt = start + idLen + 17u;
+        if (kind == SAM_UNMAPPED) {
+            const uint64_t seqAt = samUnmappedSeqAt(start, idLen);
             w.stream(start + bytes, [&]() {
                 w.coop(start, idLen, [&](uint64_t i) { return id[i]; });
                 w.coop(seqAt, readLen, [&](uint64_t i) { return samCleanBase(rd[i]); });

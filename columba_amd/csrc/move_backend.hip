@@ -2,6 +2,7 @@
 // gfx950 only.  A translation unit of its own, linked into libcolumba_amd.so.
 #include "../../include/columba_amd.h"
 #include "host_schemes.hpp"
+#include "host_util.hpp"
 #include "move_search.hpp"
 
 #include <hipcub/hipcub.hpp>
@@ -21,12 +22,6 @@ namespace cmb {
 int failWith(int code, const std::string& msg); // columba_amd.hip: sets the calling thread's cmb_last_error
 }
 using namespace cmb;
-
-#define MV_HIPCHK(expr)                                                                               \
-    do {                                                                                              \
-        hipError_t _e = (expr);                                                                       \
-        if (_e != hipSuccess) throw std::runtime_error(std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
 
 // hipcub takes its element counts as int: a count of 2^31 or more is refused here instead of being truncated by the cast
 #define MV_CUB_COUNT(n, what)                                                                                                  \
@@ -54,7 +49,7 @@ template <typename T> struct MvHostVec {
         if (count > cap) {
             const size_t want = count + count / 2 + 1024;
             T* q = nullptr;
-            MV_HIPCHK(hipHostMalloc((void**)&q, want * sizeof(T), hipHostMallocDefault));
+            HIPCHK(hipHostMalloc((void**)&q, want * sizeof(T), hipHostMallocDefault));
             if (n) memcpy(q, p, n * sizeof(T));
             if (p) (void)hipHostFree(p);
             p = q;
@@ -75,34 +70,10 @@ template <typename T> struct MvHostVec {
     const T& operator[](size_t i) const { return p[i]; }
 };
 
-template <typename T> struct MvBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    MvBuf() {}
-    MvBuf(const MvBuf&) = delete;
-    MvBuf& operator=(const MvBuf&) = delete;
-    ~MvBuf() { release(); }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-    void alloc(size_t count) {
-        release();
-        MV_HIPCHK(hipMalloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T)));
-        n = count;
-    }
-    void upload(const T* h, size_t count) {
-        alloc(count);
-        if (count) MV_HIPCHK(hipMemcpy(p, h, count * sizeof(T), hipMemcpyHostToDevice));
-    }
-    size_t bytes() const { return n * sizeof(T); }
-};
-
 unsigned gridFor(uint64_t n) { return (unsigned)std::min<uint64_t>((n + 255) / 256 + 1, 256 * 32); }
 
 struct PosSetHost {
-    MvBuf<uint64_t> pos, dir;
+    DevBuf<uint64_t> pos, dir;
     uint32_t shift = 0;
     uint64_t count = 0;
     PosSet dev() const { return PosSet{pos.p, count, dir.p, shift}; }
@@ -116,14 +87,14 @@ struct PosSetHost {
         const uint64_t buckets = (limit >> shift) + 1;
         dir.alloc(buckets + 1);
         hipLaunchKernelGGL(k_posset_dir, dim3(gridFor(buckets + 1)), dim3(256), 0, 0, pos.p, cnt, shift, buckets, dir.p);
-        MV_HIPCHK(hipGetLastError());
+        HIPCHK(hipGetLastError());
     }
     size_t bytes() const { return pos.bytes() + dir.bytes(); }
 };
 
 struct TableHost {
-    MvBuf<uint4> rows;
-    MvBuf<uint64_t> smpF, smpL;
+    DevBuf<uint4> rows;
+    DevBuf<uint64_t> smpF, smpL;
     uint64_t runs = 0, zeroCharPos = 0;
     MoveTable dev() const { return MoveTable{rows.p, runs, zeroCharPos, smpF.p, smpL.p}; }
     size_t bytes() const { return rows.bytes() + smpF.bytes() + smpL.bytes(); }
@@ -146,10 +117,10 @@ struct cmb_move_index {
     TableHost tab[2];
     bool hasLocate = false;
     PosSetHost predFirst, predLast, plcpPos;
-    MvBuf<uint64_t> firstToRun, lastToRun, plcpSum;
+    DevBuf<uint64_t> firstToRun, lastToRun, plcpSum;
     MoveDev d{};
     // the k-mer table of the search (populateTable), built on first use for the word size asked for
-    MvBuf<MoveRangeRec> kmer;
+    DevBuf<MoveRangeRec> kmer;
     uint32_t kmerSize = 0;
     std::mutex kmerMutex;
     // optional: the text itself (cmb_move_attach_text), for the CIGARs of the occurrences — codes and a 2-bit copy
@@ -189,15 +160,15 @@ static void loadTable(TableHost& t, const uint8_t* file, uint64_t fileBytes, uin
     const uint64_t body = (uint64_t)rowBytes * (runs + 1);
     if (fileBytes < 3 * W + body) throw std::invalid_argument(std::string(what) + ": truncated (" + std::to_string(fileBytes) + " bytes, " + std::to_string(3 * W + body) + " expected)");
     if (hdr[2] >= n) throw std::invalid_argument(std::string(what) + ": position of the sentinel outside the text");
-    MvBuf<uint8_t> packed;
+    DevBuf<uint8_t> packed;
     packed.upload(file + 3 * W, body);
     t.rows.alloc(runs + 2);
-    MV_HIPCHK(hipMemset(t.rows.p + runs + 1, 0xFF, sizeof(uint4)));
+    HIPCHK(hipMemset(t.rows.p + runs + 1, 0xFF, sizeof(uint4)));
     hipLaunchKernelGGL(k_move_unpack, dim3(gridFor(runs + 1)), dim3(256), 0, 0, packed.p, runs + 1, rowBytes, bitsN, bitsR, t.rows.p);
     hipLaunchKernelGGL(k_move_gaps, dim3(gridFor(runs)), dim3(256), 0, 0, t.rows.p, runs);
     hipLaunchKernelGGL(k_move_check, dim3(gridFor(runs + 1)), dim3(256), 0, 0, t.rows.p, runs, n, dFlags);
-    MV_HIPCHK(hipGetLastError());
-    MV_HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
     t.runs = runs;
     t.zeroCharPos = hdr[2];
     t.smpF.upload(smpF, runs);
@@ -218,12 +189,12 @@ extern "C" int cmb_move_create(const cmb_move_desc* desc, int device, cmb_move_i
         int count = 0;
         if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count)
             return failWith(CMB_ERR_DEVICE, "no such GPU (the move tables live in HBM; there is no CPU path)");
-        MV_HIPCHK(hipSetDevice(device));
+        HIPCHK(hipSetDevice(device));
         std::unique_ptr<cmb_move_index> ix(new cmb_move_index());
         ix->device = device;
-        MvBuf<uint32_t> flags;
+        DevBuf<uint32_t> flags;
         flags.alloc(4);
-        MV_HIPCHK(hipMemset(flags.p, 0, 4 * sizeof(uint32_t)));
+        HIPCHK(hipMemset(flags.p, 0, 4 * sizeof(uint32_t)));
         uint64_t nF = 0, nR = 0;
         loadTable(ix->tab[0], desc->lfbp, desc->lfbp_bytes, desc->length_bits, desc->samples_first, desc->samples_last, nF, flags.p, ".LFBP");
         loadTable(ix->tab[1], desc->rev_lfbp, desc->rev_lfbp_bytes, desc->length_bits, desc->rev_samples_first, desc->rev_samples_last, nR,
@@ -243,9 +214,9 @@ extern "C" int cmb_move_create(const cmb_move_desc* desc, int device, cmb_move_i
             if (desc->plcp_pos[0] != 0) return failWith(CMB_ERR_INVALID, "the PLCP samples must start at position 0");
             ix->hasLocate = true;
         }
-        MV_HIPCHK(hipGetLastError());
+        HIPCHK(hipGetLastError());
         uint32_t h[4];
-        MV_HIPCHK(hipMemcpy(h, flags.p, sizeof(h), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(h, flags.p, sizeof(h), hipMemcpyDeviceToHost));
         if (h[0] || h[1])
             return failWith(CMB_ERR_INVALID, "inconsistent move table (" + std::to_string(h[0]) + " rows of .LFBP, " + std::to_string(h[1]) +
                                                  " rows of .rev.LFBP break the order of the runs, the LF targets or the terminating row)");
@@ -301,9 +272,9 @@ extern "C" int cmb_move_info(const cmb_move_index* idx, uint64_t* text_length, u
 extern "C" int cmb_move_complete_range(const cmb_move_index* idx, cmb_move_range* out) {
     if (!idx || !out) return failWith(CMB_ERR_INVALID, "bad argument");
     try {
-        MV_HIPCHK(hipSetDevice(idx->device));
+        HIPCHK(hipSetDevice(idx->device));
         uint64_t last = 0;
-        MV_HIPCHK(hipMemcpy(&last, idx->tab[0].smpL.p + idx->tab[0].runs - 1, sizeof(last), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(&last, idx->tab[0].smpL.p + idx->tab[0].runs - 1, sizeof(last), hipMemcpyDeviceToHost));
         std::memset(out, 0, sizeof(*out));
         out->begin = 0, out->end = idx->n, out->begin_run = 0, out->end_run = idx->tab[0].runs - 1;
         out->rev_begin = 0, out->rev_end = idx->n, out->rev_begin_run = 0, out->rev_end_run = idx->tab[1].runs - 1;
@@ -318,9 +289,9 @@ extern "C" int cmb_move_complete_range(const cmb_move_index* idx, cmb_move_range
 extern "C" int cmb_move_rows(const cmb_move_index* idx, int rev, uint64_t first, uint64_t count, uint64_t* out) {
     if (!idx || !out || rev < 0 || rev > 1 || first + count > idx->tab[rev].runs + 1) return failWith(CMB_ERR_INVALID, "bad argument");
     try {
-        MV_HIPCHK(hipSetDevice(idx->device));
+        HIPCHK(hipSetDevice(idx->device));
         std::vector<uint4> h(count);
-        if (count) MV_HIPCHK(hipMemcpy(h.data(), idx->tab[rev].rows.p + first, count * sizeof(uint4), hipMemcpyDeviceToHost));
+        if (count) HIPCHK(hipMemcpy(h.data(), idx->tab[rev].rows.p + first, count * sizeof(uint4), hipMemcpyDeviceToHost));
         for (uint64_t i = 0; i < count; i++) {
             const MoveRow r = unpackMoveRow(h[i]);
             out[4 * i] = r.head, out[4 * i + 1] = r.in, out[4 * i + 2] = r.out, out[4 * i + 3] = r.outRun;
@@ -337,25 +308,25 @@ extern "C" int cmb_move_extend_batch(const cmb_move_index* idx, int mode, const 
                                      uint8_t* ok) {
     if (!idx || mode < 0 || mode > 2 || (n && (!parents || !children || !ok))) return failWith(CMB_ERR_INVALID, "bad argument");
     try {
-        MV_HIPCHK(hipSetDevice(idx->device));
-        MvBuf<MoveRangeRec> din, dout;
-        MvBuf<uint8_t> dok;
-        MvBuf<uint32_t> bad;
+        HIPCHK(hipSetDevice(idx->device));
+        DevBuf<MoveRangeRec> din, dout;
+        DevBuf<uint8_t> dok;
+        DevBuf<uint32_t> bad;
         din.upload((const MoveRangeRec*)parents, n);
         dout.alloc(4 * n);
         dok.alloc(4 * n);
         bad.alloc(1);
-        MV_HIPCHK(hipMemset(bad.p, 0, sizeof(uint32_t)));
+        HIPCHK(hipMemset(bad.p, 0, sizeof(uint32_t)));
         if (n) hipLaunchKernelGGL(k_move_extend, dim3(gridFor(n)), dim3(256), 0, 0, idx->d, mode, din.p, n, dout.p, dok.p, bad.p);
-        MV_HIPCHK(hipGetLastError());
+        HIPCHK(hipGetLastError());
         uint32_t hb = 0;
-        MV_HIPCHK(hipMemcpy(&hb, bad.p, sizeof(hb), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(&hb, bad.p, sizeof(hb), hipMemcpyDeviceToHost));
         if (hb)
             return failWith(CMB_ERR_INVALID, std::to_string(hb) + " of the parents are not ranges of this index (empty, outside the text, or "
                                                                   "with run indices that do not enclose them)");
         if (n) {
-            MV_HIPCHK(hipMemcpy(children, dout.p, 4 * n * sizeof(MoveRangeRec), hipMemcpyDeviceToHost));
-            MV_HIPCHK(hipMemcpy(ok, dok.p, 4 * n, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(children, dout.p, 4 * n * sizeof(MoveRangeRec), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(ok, dok.p, 4 * n, hipMemcpyDeviceToHost));
         }
         return CMB_OK;
     } catch (const std::exception& e) {
@@ -367,32 +338,32 @@ extern "C" int cmb_move_extend_bench(const cmb_move_index* idx, int mode, const 
                                      uint32_t iters, float* avg_ms) {
     if (!idx || mode < 0 || mode > 2 || !d_parents || !d_children || !d_ok || !avg_ms || !iters || !n) return failWith(CMB_ERR_INVALID, "bad argument");
     try {
-        MV_HIPCHK(hipSetDevice(idx->device));
+        HIPCHK(hipSetDevice(idx->device));
         hipStream_t s;
-        MV_HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
         hipEvent_t a, b;
-        MV_HIPCHK(hipEventCreate(&a));
-        MV_HIPCHK(hipEventCreate(&b));
-        MvBuf<uint32_t> bad;
+        HIPCHK(hipEventCreate(&a));
+        HIPCHK(hipEventCreate(&b));
+        DevBuf<uint32_t> bad;
         bad.alloc(1);
-        MV_HIPCHK(hipMemset(bad.p, 0, sizeof(uint32_t)));
+        HIPCHK(hipMemset(bad.p, 0, sizeof(uint32_t)));
         auto launch = [&]() {
             hipLaunchKernelGGL(k_move_extend, dim3(gridFor(n)), dim3(256), 0, s, idx->d, mode, (const MoveRangeRec*)d_parents, n,
                                (MoveRangeRec*)d_children, (uint8_t*)d_ok, bad.p);
         };
         launch(); // warm-up
-        MV_HIPCHK(hipEventRecord(a, s));
+        HIPCHK(hipEventRecord(a, s));
         for (uint32_t i = 0; i < iters; i++) launch();
-        MV_HIPCHK(hipEventRecord(b, s));
-        MV_HIPCHK(hipEventSynchronize(b));
+        HIPCHK(hipEventRecord(b, s));
+        HIPCHK(hipEventSynchronize(b));
         float ms = 0;
-        MV_HIPCHK(hipEventElapsedTime(&ms, a, b));
+        HIPCHK(hipEventElapsedTime(&ms, a, b));
         *avg_ms = ms / iters;
-        MV_HIPCHK(hipEventDestroy(a));
-        MV_HIPCHK(hipEventDestroy(b));
-        MV_HIPCHK(hipStreamDestroy(s));
+        HIPCHK(hipEventDestroy(a));
+        HIPCHK(hipEventDestroy(b));
+        HIPCHK(hipStreamDestroy(s));
         uint32_t hb = 0;
-        MV_HIPCHK(hipMemcpy(&hb, bad.p, sizeof(hb), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(&hb, bad.p, sizeof(hb), hipMemcpyDeviceToHost));
         if (hb) return failWith(CMB_ERR_INVALID, "parents that are not ranges of this index");
         return CMB_OK;
     } catch (const std::exception& e) {
@@ -408,24 +379,24 @@ extern "C" int cmb_move_locate_batch(const cmb_move_index* idx, const cmb_move_r
         if (ranges[i].end <= ranges[i].begin || offsets[i + 1] - offsets[i] != ranges[i].end - ranges[i].begin || offsets[i + 1] < offsets[i])
             return failWith(CMB_ERR_INVALID, "offsets[i + 1] - offsets[i] must be the width of range i");
     try {
-        MV_HIPCHK(hipSetDevice(idx->device));
-        MvBuf<MoveRangeRec> din;
-        MvBuf<uint64_t> doff, dpos;
-        MvBuf<uint32_t> bad;
+        HIPCHK(hipSetDevice(idx->device));
+        DevBuf<MoveRangeRec> din;
+        DevBuf<uint64_t> doff, dpos;
+        DevBuf<uint32_t> bad;
         din.upload((const MoveRangeRec*)ranges, n);
         doff.upload(offsets, n + 1);
         const uint64_t total = n ? offsets[n] - offsets[0] : 0;
         dpos.alloc(total);
         bad.alloc(1);
-        MV_HIPCHK(hipMemset(bad.p, 0, sizeof(uint32_t)));
+        HIPCHK(hipMemset(bad.p, 0, sizeof(uint32_t)));
         if (n) hipLaunchKernelGGL(k_move_locate, dim3(gridFor(n)), dim3(256), 0, 0, idx->d, din.p, n, doff.p, offsets[0], dpos.p, bad.p, false);
-        MV_HIPCHK(hipGetLastError());
+        HIPCHK(hipGetLastError());
         uint32_t hb = 0;
-        MV_HIPCHK(hipMemcpy(&hb, bad.p, sizeof(hb), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(&hb, bad.p, sizeof(hb), hipMemcpyDeviceToHost));
         if (hb)
             return failWith(CMB_ERR_INVALID, std::to_string(hb) + " of the ranges do not belong to this index (toehold, depth and width "
                                                                   "do not describe one suffix array interval)");
-        if (total) MV_HIPCHK(hipMemcpy(positions + offsets[0], dpos.p, total * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        if (total) HIPCHK(hipMemcpy(positions + offsets[0], dpos.p, total * sizeof(uint64_t), hipMemcpyDeviceToHost));
         return CMB_OK;
     } catch (const std::exception& e) {
         return failWith(CMB_ERR_DEVICE, e.what());
@@ -451,13 +422,13 @@ extern "C" int cmb_move_match_exact(const cmb_move_index* idx, const char* reads
     for (uint64_t i = 0; i < n_reads; i++)
         if (read_offsets[i + 1] < read_offsets[i]) return failWith(CMB_ERR_INVALID, "read offsets must not decrease");
     try {
-        MV_HIPCHK(hipSetDevice(idx->device));
+        HIPCHK(hipSetDevice(idx->device));
         const uint64_t nTasks = 2 * n_reads, nChars = read_offsets[n_reads] - read_offsets[0];
-        MvBuf<uint8_t> dReads;
-        MvBuf<uint64_t> dOff, dWidth, dTaskOff, dPos, dReadOcc;
-        MvBuf<MoveRangeRec> dRanges;
-        MvBuf<unsigned long long> dNodes;
-        MvBuf<uint32_t> bad;
+        DevBuf<uint8_t> dReads;
+        DevBuf<uint64_t> dOff, dWidth, dTaskOff, dPos, dReadOcc;
+        DevBuf<MoveRangeRec> dRanges;
+        DevBuf<unsigned long long> dNodes;
+        DevBuf<uint32_t> bad;
         dReads.upload((const uint8_t*)reads + read_offsets[0], nChars);
         std::vector<uint64_t> off(read_offsets, read_offsets + n_reads + 1);
         for (auto& o : off) o -= read_offsets[0];
@@ -467,11 +438,11 @@ extern "C" int cmb_move_match_exact(const cmb_move_index* idx, const char* reads
         dRanges.alloc(nTasks);
         dNodes.alloc(2);
         bad.alloc(1);
-        MV_HIPCHK(hipMemset(dNodes.p, 0, 2 * sizeof(unsigned long long)));
-        MV_HIPCHK(hipMemset(bad.p, 0, sizeof(uint32_t)));
-        MV_HIPCHK(hipMemset(dWidth.p, 0, (nTasks + 1) * sizeof(uint64_t)));
+        HIPCHK(hipMemset(dNodes.p, 0, 2 * sizeof(unsigned long long)));
+        HIPCHK(hipMemset(bad.p, 0, sizeof(uint32_t)));
+        HIPCHK(hipMemset(dWidth.p, 0, (nTasks + 1) * sizeof(uint64_t)));
         hipEvent_t ev[4];
-        for (auto& e : ev) MV_HIPCHK(hipEventCreate(&e));
+        for (auto& e : ev) HIPCHK(hipEventCreate(&e));
         struct EvGuard {
             hipEvent_t* e;
             ~EvGuard() {
@@ -479,24 +450,24 @@ extern "C" int cmb_move_match_exact(const cmb_move_index* idx, const char* reads
             }
         } evGuard{ev};
         g_exactMs[0] = g_exactMs[1] = g_exactMs[2] = 0;
-        MV_HIPCHK(hipEventRecord(ev[0], 0));
+        HIPCHK(hipEventRecord(ev[0], 0));
         if (nTasks) hipLaunchKernelGGL(k_move_exact, dim3(gridFor(nTasks)), dim3(256), 0, 0, idx->d, dReads.p, dOff.p, nTasks, dRanges.p, dWidth.p, dNodes.p);
-        MV_HIPCHK(hipGetLastError());
-        MV_HIPCHK(hipEventRecord(ev[1], 0));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ev[1], 0));
         // offsets of the tasks' occurrences: exclusive prefix sum over nTasks + 1 widths (the last one is zero)
         size_t tmpBytes = 0;
         MV_CUB_COUNT(nTasks + 1, "exact-match tasks"); // (below 2^31: 2^30 reads per call at most)
-        MV_HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmpBytes, dWidth.p, dTaskOff.p, (int)(nTasks + 1)));
-        MvBuf<uint8_t> tmp;
+        HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmpBytes, dWidth.p, dTaskOff.p, (int)(nTasks + 1)));
+        DevBuf<uint8_t> tmp;
         tmp.alloc(tmpBytes);
-        MV_HIPCHK(hipcub::DeviceScan::ExclusiveSum(tmp.p, tmpBytes, dWidth.p, dTaskOff.p, (int)(nTasks + 1)));
-        MV_HIPCHK(hipEventRecord(ev[2], 0));
+        HIPCHK(hipcub::DeviceScan::ExclusiveSum(tmp.p, tmpBytes, dWidth.p, dTaskOff.p, (int)(nTasks + 1)));
+        HIPCHK(hipEventRecord(ev[2], 0));
         uint64_t total = 0;
-        MV_HIPCHK(hipMemcpy(&total, dTaskOff.p + nTasks, sizeof(total), hipMemcpyDeviceToHost));
-        MV_HIPCHK(hipEventElapsedTime(&g_exactMs[0], ev[0], ev[1]));
-        MV_HIPCHK(hipEventElapsedTime(&g_exactMs[1], ev[1], ev[2]));
+        HIPCHK(hipMemcpy(&total, dTaskOff.p + nTasks, sizeof(total), hipMemcpyDeviceToHost));
+        HIPCHK(hipEventElapsedTime(&g_exactMs[0], ev[0], ev[1]));
+        HIPCHK(hipEventElapsedTime(&g_exactMs[1], ev[1], ev[2]));
         unsigned long long nodes = 0, nodes2[2] = {0, 0};
-        MV_HIPCHK(hipMemcpy(nodes2, dNodes.p, sizeof(nodes2), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(nodes2, dNodes.p, sizeof(nodes2), hipMemcpyDeviceToHost));
         nodes = nodes2[0];
         g_exactExpansions = nodes2[1];
         *n_occ = total;
@@ -504,25 +475,25 @@ extern "C" int cmb_move_match_exact(const cmb_move_index* idx, const char* reads
         if (occ_offsets) {
             dReadOcc.alloc(n_reads + 1);
             hipLaunchKernelGGL(k_move_read_offsets, dim3(gridFor(n_reads + 1)), dim3(256), 0, 0, dTaskOff.p, n_reads, dReadOcc.p);
-            MV_HIPCHK(hipMemcpy(occ_offsets, dReadOcc.p, (n_reads + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(occ_offsets, dReadOcc.p, (n_reads + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
         }
         if (total > occ_cap)
             return failWith(CMB_ERR_OVERFLOW, std::to_string(total) + " occurrences, room for " + std::to_string(occ_cap) + " (n_occ holds the number needed)");
         if (total) {
             dPos.alloc(total);
-            MvBuf<MoveOccRec> dOcc;
+            DevBuf<MoveOccRec> dOcc;
             dOcc.alloc(total);
-            MV_HIPCHK(hipEventRecord(ev[2], 0));
+            HIPCHK(hipEventRecord(ev[2], 0));
             hipLaunchKernelGGL(k_move_locate, dim3(gridFor(nTasks)), dim3(256), 0, 0, idx->d, dRanges.p, nTasks, dTaskOff.p, (uint64_t)0, dPos.p, bad.p, true);
             hipLaunchKernelGGL(k_move_occ, dim3(gridFor(total)), dim3(256), 0, 0, dPos.p, dTaskOff.p, nTasks, total, dOff.p, dOcc.p);
-            MV_HIPCHK(hipGetLastError());
-            MV_HIPCHK(hipEventRecord(ev[3], 0));
-            MV_HIPCHK(hipEventSynchronize(ev[3]));
-            MV_HIPCHK(hipEventElapsedTime(&g_exactMs[2], ev[2], ev[3]));
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(ev[3], 0));
+            HIPCHK(hipEventSynchronize(ev[3]));
+            HIPCHK(hipEventElapsedTime(&g_exactMs[2], ev[2], ev[3]));
             uint32_t hb = 0;
-            MV_HIPCHK(hipMemcpy(&hb, bad.p, sizeof(hb), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(&hb, bad.p, sizeof(hb), hipMemcpyDeviceToHost));
             if (hb) return failWith(CMB_ERR_INTERNAL, std::to_string(hb) + " ranges whose phi chains do not have the width of the range (inconsistent locate arrays)");
-            MV_HIPCHK(hipMemcpy(occ_out, dOcc.p, total * sizeof(MoveOccRec), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(occ_out, dOcc.p, total * sizeof(MoveOccRec), hipMemcpyDeviceToHost));
         }
         return CMB_OK;
     } catch (const std::exception& e) {
@@ -534,13 +505,13 @@ extern "C" int cmb_move_match_exact(const cmb_move_index* idx, const char* reads
 extern "C" int cmb_move_kmer_table(const cmb_move_index* idx, uint32_t word_size, cmb_move_range* out) {
     if (!idx || !out || word_size > 12) return failWith(CMB_ERR_INVALID, "bad argument (k-mer size up to 12)");
     try {
-        MV_HIPCHK(hipSetDevice(idx->device));
+        HIPCHK(hipSetDevice(idx->device));
         const uint64_t total = 1ull << (2 * word_size);
-        MvBuf<MoveRangeRec> d;
+        DevBuf<MoveRangeRec> d;
         d.alloc(total);
         hipLaunchKernelGGL(k_move_kmer_table, dim3(gridFor(total)), dim3(256), 0, 0, idx->d, word_size, d.p);
-        MV_HIPCHK(hipGetLastError());
-        MV_HIPCHK(hipMemcpy(out, d.p, total * sizeof(MoveRangeRec), hipMemcpyDeviceToHost));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpy(out, d.p, total * sizeof(MoveRangeRec), hipMemcpyDeviceToHost));
         return CMB_OK;
     } catch (const std::exception& e) {
         return failWith(CMB_ERR_DEVICE, e.what());
@@ -594,7 +565,7 @@ extern "C" int cmb_move_create_empty(const cmb_move_layout* L, int device, cmb_m
         int count = 0;
         if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count)
             return failWith(CMB_ERR_DEVICE, "no such GPU (the move tables live in HBM; there is no CPU path)");
-        MV_HIPCHK(hipSetDevice(device));
+        HIPCHK(hipSetDevice(device));
         std::unique_ptr<cmb_move_index> ix(new cmb_move_index());
         ix->device = device;
         ix->n = L->text_length;
@@ -607,7 +578,7 @@ extern "C" int cmb_move_create_empty(const cmb_move_layout* L, int device, cmb_m
         for (int i = 0; i < CMB_MOVE_DEV_ARRAYS; i++) {
             if (L->bytes[i] % a[i].elem) return failWith(CMB_ERR_INVALID, "move index layout: array size is not a whole number of elements");
             if (L->bytes[i] == 0) continue; // absent (an index without the locate arrays)
-            MV_HIPCHK(hipMalloc(a[i].p, L->bytes[i]));
+            HIPCHK(hipMalloc(a[i].p, L->bytes[i]));
             *a[i].n = L->bytes[i] / a[i].elem;
         }
         // sizes must fit what the kernels index
@@ -644,10 +615,10 @@ extern "C" int cmb_move_device_arrays(cmb_move_index* idx, void** ptrs, uint64_t
 extern "C" int cmb_move_validate(cmb_move_index* idx) {
     if (!idx) return failWith(CMB_ERR_INVALID, "bad argument");
     try {
-        MV_HIPCHK(hipSetDevice(idx->device));
-        MvBuf<uint32_t> flags;
+        HIPCHK(hipSetDevice(idx->device));
+        DevBuf<uint32_t> flags;
         flags.alloc(4);
-        MV_HIPCHK(hipMemset(flags.p, 0, 4 * sizeof(uint32_t)));
+        HIPCHK(hipMemset(flags.p, 0, 4 * sizeof(uint32_t)));
         for (int t = 0; t < 2; t++)
             hipLaunchKernelGGL(k_move_check, dim3(gridFor(idx->tab[t].runs + 1)), dim3(256), 0, 0, idx->tab[t].rows.p, idx->tab[t].runs, idx->n, flags.p + t);
         if (idx->hasLocate) {
@@ -658,12 +629,12 @@ extern "C" int cmb_move_validate(cmb_move_index* idx) {
             hipLaunchKernelGGL(k_run_map_check, dim3(gridFor(r)), dim3(256), 0, 0, idx->lastToRun.p, r, r, flags.p + 2);
             for (auto* ps : sets) hipLaunchKernelGGL(k_posset_dir_check, dim3(gridFor((idx->n >> ps->shift) + 2)), dim3(256), 0, 0, ps->pos.p, ps->count, ps->shift, (idx->n >> ps->shift) + 1, ps->dir.p, flags.p + 3);
         }
-        MV_HIPCHK(hipGetLastError());
+        HIPCHK(hipGetLastError());
         uint32_t h[4];
-        MV_HIPCHK(hipMemcpy(h, flags.p, sizeof(h), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(h, flags.p, sizeof(h), hipMemcpyDeviceToHost));
         if (idx->hasLocate) { // plcpAt reads plcpSum[rank - 1]: position 0 must be a PLCP run start (cmb_move_create checks the same)
             uint64_t first = ~0ull;
-            if (idx->plcpPos.count) MV_HIPCHK(hipMemcpy(&first, idx->plcpPos.pos.p, sizeof(first), hipMemcpyDeviceToHost));
+            if (idx->plcpPos.count) HIPCHK(hipMemcpy(&first, idx->plcpPos.pos.p, sizeof(first), hipMemcpyDeviceToHost));
             if (first != 0) return failWith(CMB_ERR_INVALID, "inconsistent move index arrays (the PLCP run starts do not begin at position 0)");
         }
         if (h[0] || h[1] || h[2] || h[3])
@@ -689,47 +660,47 @@ struct cmb_move_batch {
     bool wide = false;
     bool noSmallMatrix = false; // a phase of an earlier run did not fit the 32-bit in-index matrix (GeoN32): this batch stays on GeoN
     DevStrategyKT<MAXP_WIDE> hostStratW{};
-    MvBuf<DevStrategyKT<MAXP_WIDE>> stratW;
-    MvBuf<PartOutT<MAXP_WIDE>> partsW;
+    DevBuf<DevStrategyKT<MAXP_WIDE>> stratW;
+    DevBuf<PartOutT<MAXP_WIDE>> partsW;
     uint32_t sNumParts = 0, sPartition = 0, sNSchemes = 0, sMaxSearches = 0;
     hipStream_t stream = nullptr;
     std::vector<uint8_t> hostReads; // (k = 0 goes through cmb_move_match_exact, which takes host buffers)
     std::vector<uint64_t> hostOffs;
-    MvBuf<uint8_t> reads, seq, psel, sortTmp;
-    MvBuf<uint64_t> offs;
-    MvBuf<uint32_t> G, cnt, bfsCnt, fmIdxA, fmIdxB, keep, slot, vals, valsB, bad;
-    MvBuf<DevStrategyK> strat;
-    MvBuf<PartOut> parts;
-    MvBuf<MoveRangeRec> exr, locRanges;
-    MvBuf<MvTask> tasks;
-    MvBuf<uint4> Q[2], Ev[2], F, C, A, locMeta;
-    MvBuf<unsigned long long> counters, blockCnt, keysA, keysB;
-    MvBuf<MvFmRec> fm;
-    MvBuf<uint64_t> widths, locWidths, locOff, positions, readCnt, readOff;
-    MvBuf<MoveOccOut> out;
+    DevBuf<uint8_t> reads, seq, psel, sortTmp;
+    DevBuf<uint64_t> offs;
+    DevBuf<uint32_t> G, cnt, bfsCnt, fmIdxA, fmIdxB, keep, slot, vals, valsB, bad;
+    DevBuf<DevStrategyK> strat;
+    DevBuf<PartOut> parts;
+    DevBuf<MoveRangeRec> exr, locRanges;
+    DevBuf<MvTask> tasks;
+    DevBuf<uint4> Q[2], Ev[2], F, C, A, locMeta;
+    DevBuf<unsigned long long> counters, blockCnt, keysA, keysB;
+    DevBuf<MvFmRec> fm;
+    DevBuf<uint64_t> widths, locWidths, locOff, positions, readCnt, readOff;
+    DevBuf<MoveOccOut> out;
     size_t qCap = 0, evCap = 0, fCap = 0, cCap = 0, aCap = 0;
     // naive backtracking (k_mvs_naive): node double buffer, nodes per pass, the survivors of its own filter pass per read x strand
-    MvBuf<uint4> nvQ[2];
-    MvBuf<uint32_t> nvCnt;
+    DevBuf<uint4> nvQ[2];
+    DevBuf<uint32_t> nvCnt;
     size_t nvQCap = 0;
-    MvBuf<MoveOccOut> naiveOut;
-    MvBuf<uint64_t> naiveOff;
+    DevBuf<MoveOccOut> naiveOut;
+    DevBuf<uint64_t> naiveOff;
     // BEST mode's strata (cmb_move_match_best): every strand of a read filtered by itself, as mapRead does (searchstrategy.h:490-523)
     bool perStrand = false;
-    MvBuf<uint64_t> rsOff;
+    DevBuf<uint64_t> rsOff;
     // alignments of the final occurrences (cmb_move_batch_want_alignments; needs cmb_move_attach_text)
     bool wantAln = false;
     uint32_t alnStride = 0;
-    MvBuf<uint4> occ32, alnRec;
-    MvBuf<uint32_t> occRead;
-    MvBuf<uint16_t> alnOps;
+    DevBuf<uint4> occ32, alnRec;
+    DevBuf<uint32_t> occRead;
+    DevBuf<uint16_t> alnOps;
     std::vector<uint4> hAlnRec; // {seqId, seqBegin, nOps, spans} per occurrence
     std::vector<uint16_t> hAlnOps;
     // results
     MvHostVec<cmb_move_occ> occs;
     std::vector<uint64_t> occOffs;
     uint64_t cnts[CMB_CNT_MAX];
-    std::vector<std::pair<const char*, float>> times;
+    std::vector<KernelTime> times;
     bool done = false;
     // the occurrence records of a slice travel to the host on a stream of their own while the next slice is matched
     hipStream_t copyStream = nullptr;
@@ -761,8 +732,8 @@ static int ensureKmerTable(cmb_move_index* ix, uint32_t ws) {
     const uint64_t entries = 1ull << (2 * ws);
     ix->kmer.alloc(entries);
     hipLaunchKernelGGL(k_move_kmer_table, dim3(gridFor(entries)), dim3(256), 0, 0, ix->d, ws, ix->kmer.p);
-    MV_HIPCHK(hipGetLastError());
-    MV_HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
     ix->kmerSize = ws;
     return CMB_OK;
 }
@@ -806,7 +777,7 @@ static int moveBatchCreateOne(cmb_move_index* idx, const cmb_strategy* st, uint3
     if (n_reads >= (1u << 23)) return failWith(CMB_ERR_UNSUPPORTED, "2^23 reads and more per b-move batch (24-bit read numbers in the filter keys)");
     if (idx->n >> 40) return failWith(CMB_ERR_UNSUPPORTED, "texts of 2^40 characters and more");
     try {
-        MV_HIPCHK(hipSetDevice(idx->device));
+        HIPCHK(hipSetDevice(idx->device));
         std::unique_ptr<cmb_move_batch> b(new cmb_move_batch());
         b->ix = idx;
         b->k = max_distance;
@@ -845,10 +816,10 @@ static int moveBatchCreateOne(cmb_move_index* idx, const cmb_strategy* st, uint3
         b->hostOffs.assign(offs, offs + n_reads + 1);
         for (auto& o : b->hostOffs) o -= offs[0];
         b->hostReads.assign((const uint8_t*)seqs + offs[0], (const uint8_t*)seqs + offs[n_reads]);
-        MV_HIPCHK(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
-        MV_HIPCHK(hipStreamCreateWithFlags(&b->copyStream, hipStreamNonBlocking));
-        MV_HIPCHK(hipEventCreateWithFlags(&b->outReady, hipEventDisableTiming));
-        MV_HIPCHK(hipEventCreateWithFlags(&b->copyDone, hipEventDisableTiming));
+        HIPCHK(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+        HIPCHK(hipStreamCreateWithFlags(&b->copyStream, hipStreamNonBlocking));
+        HIPCHK(hipEventCreateWithFlags(&b->outReady, hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&b->copyDone, hipEventDisableTiming));
         b->reads.upload(b->hostReads.data(), b->hostReads.size());
         b->offs.upload(b->hostOffs.data(), n_reads + 1);
         if (max_distance > 0) { // (per-read scratch is sized per slice, at the first run)
@@ -866,35 +837,6 @@ static int moveBatchCreateOne(cmb_move_index* idx, const cmb_strategy* st, uint3
 }
 
 extern "C" void cmb_move_batch_destroy(cmb_move_batch* b) { delete b; }
-
-namespace {
-struct MvTimer {
-    hipStream_t s;
-    hipEvent_t a, b;
-    std::vector<std::pair<const char*, float>>& out;
-    MvTimer(hipStream_t st, std::vector<std::pair<const char*, float>>& o) : s(st), out(o) {
-        (void)hipEventCreate(&a);
-        (void)hipEventCreate(&b);
-    }
-    ~MvTimer() {
-        (void)hipEventDestroy(a);
-        (void)hipEventDestroy(b);
-    }
-    void begin() { (void)hipEventRecord(a, s); }
-    void end(const char* name) {
-        (void)hipEventRecord(b, s);
-        (void)hipEventSynchronize(b);
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, a, b);
-        for (auto& t : out)
-            if (!strcmp(t.first, name)) {
-                t.second += ms;
-                return;
-            }
-        out.push_back({name, ms});
-    }
-};
-} // namespace
 
 static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi);
 
@@ -938,7 +880,7 @@ extern "C" int cmb_move_batch_run(cmb_move_batch* b) {
         for (const auto& t : c->times) { // busy time per kernel group, summed over the halves (they overlap on the device)
             bool found = false;
             for (auto& u : b->times)
-                if (!strcmp(u.first, t.first)) u.second += t.second, found = true;
+                if (!strcmp(u.name, t.name)) u.ms += t.ms, found = true;
             if (!found) b->times.push_back(t);
         }
     }
@@ -978,7 +920,7 @@ static int moveBatchRunOne(cmb_move_batch* b) {
 static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
     try {
         cmb_move_index* ix = b->ix;
-        MV_HIPCHK(hipSetDevice(ix->device));
+        HIPCHK(hipSetDevice(ix->device));
         hipStream_t s = b->stream;
         const uint32_t nReads = hi - lo, tasksRS = 2 * nReads;
         const uint64_t* dOffs = b->offs.p + lo; // (the kernels number the slice's reads from 0; offsets stay absolute)
@@ -1019,7 +961,7 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
             b->times.push_back({"locate", ms[1] + ms[2]});
             return CMB_OK;
         }
-        MvTimer tm(s, b->times);
+        Timer tm(s, b->times);
         Queues q{};
         q.cnt = b->cnt.p;
         q.counters = b->counters.p;
@@ -1042,7 +984,7 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
         }
         // ---- read preparation
         tm.begin();
-        MV_HIPCHK(hipMemsetAsync(b->G.p, 0, (size_t)nReads * 8 * b->gw * sizeof(uint32_t), s));
+        HIPCHK(hipMemsetAsync(b->G.p, 0, (size_t)nReads * 8 * b->gw * sizeof(uint32_t), s));
         hipLaunchKernelGGL(k_mvs_prep, dim3(gridFor((uint64_t)nReads * b->gw)), dim3(256), 0, s, b->reads.p, dOffs, nReads, b->maxLen, b->gw, b->seq.p, b->G.p);
         tm.end("k_prep");
         const uint32_t P = b->sNumParts, maxSearches = b->sMaxSearches;
@@ -1050,10 +992,10 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
         bool hasNaive = false; // reads of the slice are matched by naive backtracking (k_mvs_parts marked them in psel)
         for (int attempt = 0;; attempt++) {
             if (attempt >= 60) return failWith(CMB_ERR_INTERNAL, "work queues keep overflowing");
-            MV_HIPCHK(hipMemsetAsync(b->cnt.p, 0, 8 * sizeof(uint32_t), s));
-            MV_HIPCHK(hipMemsetAsync(b->counters.p, 0, CMB_CNT_MAX * sizeof(unsigned long long), s));
+            HIPCHK(hipMemsetAsync(b->cnt.p, 0, 8 * sizeof(uint32_t), s));
+            HIPCHK(hipMemsetAsync(b->counters.p, 0, CMB_CNT_MAX * sizeof(unsigned long long), s));
             if (!b->fm.n) b->fm.alloc((size_t)nReads * 16 + 4096);
-            q.fmCap = (uint32_t)std::min<size_t>(b->fm.n, 0xFFFFFFF0u);
+            q.fmCap = cap32(b->fm.n);
             // ---- prologue
             tm.begin();
             {
@@ -1066,19 +1008,19 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                     hipLaunchKernelGGL(kp, dim3(grid), dim3(64), exLdsBytes, s, sx, b->stratW.p, nReads, b->maxLen, b->seq.p, dOffs, b->partsW.p, b->exr.p,
                                        b->psel.p, q);
                     hipLaunchKernelGGL(k_mvs_exact<MAXP_WIDE>, dim3(gridE), dim3(64), 0, s, sx, b->stratW.p, nReads, b->maxLen, maxSearches, b->seq.p, b->partsW.p,
-                                       b->exr.p, b->psel.p, b->tasks.p, (uint32_t)std::min<size_t>(b->tasks.n, 0xFFFFFFF0u), q);
+                                       b->exr.p, b->psel.p, b->tasks.p, cap32(b->tasks.n), q);
                 } else {
                     auto kp = b->sPartition == 0 ? k_mvs_parts<0, MAXP> : b->sPartition == 1 ? k_mvs_parts<1, MAXP> : k_mvs_parts<2, MAXP>;
                     hipLaunchKernelGGL(kp, dim3(grid), dim3(64), exLdsBytes, s, sx, b->strat.p, nReads, b->maxLen, b->seq.p, dOffs, b->parts.p, b->exr.p,
                                        b->psel.p, q);
                     hipLaunchKernelGGL(k_mvs_exact<MAXP>, dim3(gridE), dim3(64), 0, s, sx, b->strat.p, nReads, b->maxLen, maxSearches, b->seq.p, b->parts.p,
-                                       b->exr.p, b->psel.p, b->tasks.p, (uint32_t)std::min<size_t>(b->tasks.n, 0xFFFFFFF0u), q);
+                                       b->exr.p, b->psel.p, b->tasks.p, cap32(b->tasks.n), q);
                 }
             }
             tm.end("k_partition");
-            MV_HIPCHK(hipGetLastError());
-            MV_HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
-            MV_HIPCHK(hipStreamSynchronize(s));
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
             hasNaive = (hcnt[3] & FLAG_UNSUPPORTED_READ) != 0;
             if (hcnt[3] & FLAG_SEED_OVERLAP)
                 return failWith(CMB_ERR_INVALID, "dynamic partitioning: the seeds of a read overlap — the k-mer size is too large for the seeding "
@@ -1095,11 +1037,11 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                     if (b->nvQ[j].n < (PU + 2) * b->nvQCap) b->nvQ[j].alloc((PU + 2) * b->nvQCap);
                 const size_t cntWords = (size_t)maxPassN + 2;
                 if (b->nvCnt.n < cntWords) b->nvCnt.alloc(cntWords);
-                MV_HIPCHK(hipMemsetAsync(b->nvCnt.p, 0, cntWords * sizeof(uint32_t), s));
+                HIPCHK(hipMemsetAsync(b->nvCnt.p, 0, cntWords * sizeof(uint32_t), s));
                 MvHbfsBufs N{};
                 N.Q[0] = b->nvQ[0].p;
                 N.Q[1] = b->nvQ[1].p;
-                N.qCap = (uint32_t)std::min<size_t>(b->nvQ[0].n / (PU + 2), 0xFFFFFFF0u);
+                N.qCap = cap32(b->nvQ[0].n / (PU + 2));
                 N.nq = b->nvCnt.p;
                 N.blockCnt = nullptr;
                 N.fmX = b->fm.p;
@@ -1116,15 +1058,15 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                     for (; pass < upTo; pass++)
                         hipLaunchKernelGGL(kNaivePass, dim3(BFS_GRID), dim3(256), 0, s, ix->d, N, pass,
                                            (const uint8_t*)b->psel.p, tasksRS, dOffs, b->gw, b->G.p, b->seq.p, b->maxLen, b->k, q);
-                    MV_HIPCHK(hipMemcpyAsync(hc.data(), b->nvCnt.p, cntWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                    MV_HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
-                    MV_HIPCHK(hipStreamSynchronize(s));
+                    HIPCHK(hipMemcpyAsync(hc.data(), b->nvCnt.p, cntWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+                    HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
+                    HIPCHK(hipStreamSynchronize(s));
                     if (hcnt[3] & MVS_NAIVE_STOP) break;
                     drained = hc[pass] == 0;
                 }
                 for (uint32_t p2 = 0; p2 <= pass && p2 < cntWords; p2++) peakQ = std::max(peakQ, hc[p2]);
                 tm.end("k_naive");
-                MV_HIPCHK(hipGetLastError());
+                HIPCHK(hipGetLastError());
                 if (hcnt[3] & MVS_NAIVE_STOP) {
                     // (the search stopped at the overflow: it has only counted what it needed up to there)
                     if (hcnt[3] & FLAG_NAIVE_Q) b->nvQCap = std::max<size_t>(4 * b->nvQCap, (size_t)peakQ + peakQ / 4);
@@ -1146,12 +1088,12 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                 const size_t cntWords = (size_t)maxPass + 2;
                 if (b->bfsCnt.n < cntWords) b->bfsCnt.alloc(cntWords);
                 if (b->blockCnt.n < (size_t)BFS_GRID * 4) b->blockCnt.alloc((size_t)BFS_GRID * 4);
-                MV_HIPCHK(hipMemsetAsync(b->bfsCnt.p, 0, cntWords * sizeof(uint32_t), s));
-                MV_HIPCHK(hipMemsetAsync(b->blockCnt.p, 0, (size_t)BFS_GRID * 4 * sizeof(unsigned long long), s));
+                HIPCHK(hipMemsetAsync(b->bfsCnt.p, 0, cntWords * sizeof(uint32_t), s));
+                HIPCHK(hipMemsetAsync(b->blockCnt.p, 0, (size_t)BFS_GRID * 4 * sizeof(unsigned long long), s));
                 MvHbfsBufs H{};
                 H.Q[0] = b->Q[0].p;
                 H.Q[1] = b->Q[1].p;
-                H.qCap = (uint32_t)std::min<size_t>(b->Q[0].n / (PU + 1), 0xFFFFFFF0u);
+                H.qCap = cap32(b->Q[0].n / (PU + 1));
                 H.nq = b->bfsCnt.p;
                 H.blockCnt = b->blockCnt.p;
                 H.fmX = b->fm.p;
@@ -1173,9 +1115,9 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                         else
                             hipLaunchKernelGGL((k_mvs_hbfs<false, MAXP>), dim3(BFS_GRID), dim3(256), 0, s, ix->d, b->strat.p, H, pass, (const MvTask*)nullptr, 0u,
                                                b->maxLen, b->seq.p, b->parts.p, q);
-                    MV_HIPCHK(hipMemcpyAsync(hc.data(), b->bfsCnt.p, cntWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                    MV_HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
-                    MV_HIPCHK(hipStreamSynchronize(s));
+                    HIPCHK(hipMemcpyAsync(hc.data(), b->bfsCnt.p, cntWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+                    HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
+                    HIPCHK(hipStreamSynchronize(s));
                     if (hcnt[3] & BFS_STOP) break;
                     drained = hc[pass] == 0;
                 }
@@ -1184,7 +1126,7 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                 Bf.blockCnt = b->blockCnt.p;
                 hipLaunchKernelGGL(k_mvs_finish, dim3(1), dim3(256), 0, s, Bf, q);
                 tm.end("k_dfs");
-                MV_HIPCHK(hipGetLastError());
+                HIPCHK(hipGetLastError());
                 if (hcnt[3] & (FLAG_BFS_Q | FLAG_FMOCC_OVERFLOW)) {
                     if (hcnt[3] & FLAG_BFS_Q) b->qCap = std::max<size_t>(2 * b->qCap, (size_t)peakQ + peakQ / 4);
                     if (hcnt[3] & FLAG_FMOCC_OVERFLOW) b->fm.alloc(std::max<size_t>(2 * b->fm.n, (size_t)hcnt[1] + hcnt[1] / 4 + 1024));
@@ -1218,8 +1160,8 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                 const size_t cntWords = 2 * ((size_t)maxPass + 2) + 4;
                 if (b->bfsCnt.n < cntWords) b->bfsCnt.alloc(cntWords);
                 if (b->blockCnt.n < (size_t)BFS_GRID * 4) b->blockCnt.alloc((size_t)BFS_GRID * 4);
-                MV_HIPCHK(hipMemsetAsync(b->bfsCnt.p, 0, cntWords * sizeof(uint32_t), s));
-                MV_HIPCHK(hipMemsetAsync(b->blockCnt.p, 0, (size_t)BFS_GRID * 4 * sizeof(unsigned long long), s));
+                HIPCHK(hipMemsetAsync(b->bfsCnt.p, 0, cntWords * sizeof(uint32_t), s));
+                HIPCHK(hipMemsetAsync(b->blockCnt.p, 0, (size_t)BFS_GRID * 4 * sizeof(unsigned long long), s));
                 MvBufs B{};
                 for (int j = 0; j < 2; j++) {
                     B.Q[j] = b->Q[j].p;
@@ -1228,13 +1170,13 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                 B.F = b->F.p;
                 B.C = b->C.p;
                 B.A = b->A.p;
-                B.qCap = (uint32_t)std::min<size_t>(b->Q[0].n / (PU + 2 + pkU4), 0xFFFFFFF0u);
-                B.evCap = (uint32_t)std::min<size_t>(b->Ev[0].n / (1 + pkU4), 0xFFFFFFF0u);
-                B.fCap = (uint32_t)std::min<size_t>(b->F.n / (PU + 1), 0xFFFFFFF0u);
-                B.cCap = (uint32_t)std::min<size_t>(b->C.n / ctxU4, 0xFFFFFFF0u);
+                B.qCap = cap32(b->Q[0].n / (PU + 2 + pkU4));
+                B.evCap = cap32(b->Ev[0].n / (1 + pkU4));
+                B.fCap = cap32(b->F.n / (PU + 1));
+                B.cCap = cap32(b->C.n / ctxU4);
                 B.ctxU4 = ctxU4;
                 B.ctxMblk = geoX ? CTX_MBLK_X : ctxMblkFor(b->maxLen);
-                B.aCap = (uint32_t)std::min<size_t>(b->A.n, 0xFFFFFFF0u);
+                B.aCap = cap32(b->A.n);
                 // text and run counts below 2^32 (the reference's default build of length_t): the expanding blocks work on 32-bit positions with
                 // the children in slots (mvExpandSlots; CMB_MOVE_POS64=1: the general 40-bit path)
                 const bool smallPos = !b->wide && ix->d.n < 0xFFFFFFF0ull && ix->d.fwd.runs < 0xFFFFFFF0ull && ix->d.rev.runs < 0xFFFFFFF0ull && !getenv("CMB_MOVE_POS64");
@@ -1278,9 +1220,9 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                         else
                             hipLaunchKernelGGL((smallPos ? k_mvs_pass<GeoN, true> : k_mvs_pass<GeoN, false>), dim3(B.gridX + B.gridEv), dim3(256), 0, s, ix->d,
                                                b->strat.p, B, pass, dOffs, b->gw, b->G.p, b->parts.p, q);
-                    MV_HIPCHK(hipMemcpyAsync(hc.data(), b->bfsCnt.p, cntWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                    MV_HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
-                    MV_HIPCHK(hipStreamSynchronize(s));
+                    HIPCHK(hipMemcpyAsync(hc.data(), b->bfsCnt.p, cntWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+                    HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
+                    HIPCHK(hipStreamSynchronize(s));
                     if (hcnt[3] & BFS_STOP) break;
                     drained = hc[pass] == 0 && hc[maxPass + 2 + pass] == 0;
                 }
@@ -1294,7 +1236,7 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                             pool[0], pool[1], pool[2]);
                 hipLaunchKernelGGL(k_mvs_finish, dim3(1), dim3(256), 0, s, B, q);
                 tm.end("k_dfs");
-                MV_HIPCHK(hipGetLastError());
+                HIPCHK(hipGetLastError());
                 if (hcnt[3] & FLAG_NARROW_MATRIX) { // (a first column wider than the small matrix holds: once more on the reference's words)
                     b->noSmallMatrix = true;
                     continue;
@@ -1326,17 +1268,17 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
             hipLaunchKernelGGL(k_mvs_fm_keys, dim3(gridFor(nFm)), dim3(256), 0, s, b->fm.p, nFm, b->keysA.p, b->fmIdxA.p);
             size_t tb = 0;
             MV_CUB_COUNT((uint64_t)nFm + 1, "in-index occurrences of one slice"); // (2^31 records of 96 bytes would not fit the HBM)
-            MV_HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, b->keysA.p, b->keysB.p, b->fmIdxA.p, b->fmIdxB.p, (int)nFm, 0, 64, s));
+            HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, b->keysA.p, b->keysB.p, b->fmIdxA.p, b->fmIdxB.p, (int)nFm, 0, 64, s));
             if (b->sortTmp.n < tb) b->sortTmp.alloc(tb + tb / 4);
-            MV_HIPCHK(hipcub::DeviceRadixSort::SortPairs(b->sortTmp.p, tb, b->keysA.p, b->keysB.p, b->fmIdxA.p, b->fmIdxB.p, (int)nFm, 0, 64, s));
+            HIPCHK(hipcub::DeviceRadixSort::SortPairs(b->sortTmp.p, tb, b->keysA.p, b->keysB.p, b->fmIdxA.p, b->fmIdxB.p, (int)nFm, 0, 64, s));
             hipLaunchKernelGGL(k_mvs_fm_unique, dim3(gridFor(nFm)), dim3(256), 0, s, b->fm.p, b->fmIdxB.p, nFm, b->keep.p, b->widths.p);
-            MV_HIPCHK(hipMemsetAsync(b->keep.p + nFm, 0, sizeof(uint32_t), s));
+            HIPCHK(hipMemsetAsync(b->keep.p + nFm, 0, sizeof(uint32_t), s));
             tb = 0;
-            MV_HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, b->keep.p, b->slot.p, (int)(nFm + 1), s));
+            HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, b->keep.p, b->slot.p, (int)(nFm + 1), s));
             if (b->sortTmp.n < tb) b->sortTmp.alloc(tb + tb / 4);
-            MV_HIPCHK(hipcub::DeviceScan::ExclusiveSum(b->sortTmp.p, tb, b->keep.p, b->slot.p, (int)(nFm + 1), s));
-            MV_HIPCHK(hipMemcpyAsync(&nUniq, b->slot.p + nFm, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            MV_HIPCHK(hipStreamSynchronize(s));
+            HIPCHK(hipcub::DeviceScan::ExclusiveSum(b->sortTmp.p, tb, b->keep.p, b->slot.p, (int)(nFm + 1), s));
+            HIPCHK(hipMemcpyAsync(&nUniq, b->slot.p + nFm, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
             if (nUniq) {
                 if (b->locRanges.n < nUniq) {
                     const size_t c = (size_t)nUniq + nUniq / 4 + 256;
@@ -1344,14 +1286,14 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                 }
                 hipLaunchKernelGGL(k_mvs_fm_compact, dim3(gridFor(nFm)), dim3(256), 0, s, b->fm.p, b->fmIdxB.p, b->keep.p, b->slot.p, nFm, b->locRanges.p,
                                    b->locMeta.p, b->locWidths.p);
-                MV_HIPCHK(hipMemsetAsync(b->locWidths.p + nUniq, 0, sizeof(uint64_t), s));
+                HIPCHK(hipMemsetAsync(b->locWidths.p + nUniq, 0, sizeof(uint64_t), s));
                 tb = 0;
                 MV_CUB_COUNT((uint64_t)nUniq + 1, "distinct in-index occurrences of one slice"); // (nUniq <= nFm)
-                MV_HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, b->locWidths.p, b->locOff.p, (int)(nUniq + 1), s));
+                HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, b->locWidths.p, b->locOff.p, (int)(nUniq + 1), s));
                 if (b->sortTmp.n < tb) b->sortTmp.alloc(tb + tb / 4);
-                MV_HIPCHK(hipcub::DeviceScan::ExclusiveSum(b->sortTmp.p, tb, b->locWidths.p, b->locOff.p, (int)(nUniq + 1), s));
-                MV_HIPCHK(hipMemcpyAsync(&totalPos, b->locOff.p + nUniq, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-                MV_HIPCHK(hipStreamSynchronize(s));
+                HIPCHK(hipcub::DeviceScan::ExclusiveSum(b->sortTmp.p, tb, b->locWidths.p, b->locOff.p, (int)(nUniq + 1), s));
+                HIPCHK(hipMemcpyAsync(&totalPos, b->locOff.p + nUniq, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+                HIPCHK(hipStreamSynchronize(s));
             }
         }
         tm.end("fm_unique");
@@ -1363,7 +1305,7 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                 b->positions.alloc(c), b->keysA.alloc(std::max(c, b->keysA.n)), b->keysB.alloc(std::max(c, b->keysB.n)), b->vals.alloc(c), b->valsB.alloc(c);
             }
             if (b->keysA.n < totalPos) b->keysA.alloc(totalPos + 256), b->keysB.alloc(totalPos + 256);
-            MV_HIPCHK(hipMemsetAsync(b->bad.p, 0, sizeof(uint32_t), s));
+            HIPCHK(hipMemsetAsync(b->bad.p, 0, sizeof(uint32_t), s));
             hipLaunchKernelGGL(k_move_locate, dim3(gridFor(nUniq)), dim3(256), 0, s, ix->d, b->locRanges.p, (uint64_t)nUniq, b->locOff.p, (uint64_t)0,
                                b->positions.p, b->bad.p, true);
         }
@@ -1373,23 +1315,23 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
         uint64_t nOut = 0, nNaiveKept = 0;
         const uint32_t window = b->metric == CMB_METRIC_EDIT ? b->k : 0u;
         const uint32_t uniqueOnly = b->metric == CMB_METRIC_EDIT ? 0u : 1u; // (getTextOccHamming, indexinterface.cpp:1331-1371: no redundancy filter)
-        auto sortAndFilter = [&](uint64_t nKeys, uint32_t nGroups, MvBuf<MoveOccOut>& dst, uint64_t& kept) -> int {
+        auto sortAndFilter = [&](uint64_t nKeys, uint32_t nGroups, DevBuf<MoveOccOut>& dst, uint64_t& kept) -> int {
             // (nKeys < 2^31: the refusals of 2^31 text positions per slice; nGroups <= 2^24: 2^23 reads per batch)
             MV_CUB_COUNT(nKeys, "text occurrences of one slice");
             MV_CUB_COUNT((uint64_t)nGroups + 1, "filter groups of one slice");
             size_t tb = 0;
-            MV_HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, b->keysA.p, b->keysB.p, b->vals.p, b->valsB.p, (int)nKeys, 0, 64, s));
+            HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, b->keysA.p, b->keysB.p, b->vals.p, b->valsB.p, (int)nKeys, 0, 64, s));
             if (b->sortTmp.n < tb) b->sortTmp.alloc(tb + tb / 4);
-            MV_HIPCHK(hipcub::DeviceRadixSort::SortPairs(b->sortTmp.p, tb, b->keysA.p, b->keysB.p, b->vals.p, b->valsB.p, (int)nKeys, 0, 64, s));
-            MV_HIPCHK(hipMemsetAsync(b->readCnt.p, 0, ((size_t)nGroups + 1) * sizeof(uint64_t), s));
+            HIPCHK(hipcub::DeviceRadixSort::SortPairs(b->sortTmp.p, tb, b->keysA.p, b->keysB.p, b->vals.p, b->valsB.p, (int)nKeys, 0, 64, s));
+            HIPCHK(hipMemsetAsync(b->readCnt.p, 0, ((size_t)nGroups + 1) * sizeof(uint64_t), s));
             hipLaunchKernelGGL(k_mvs_filter<false>, dim3(gridFor(nGroups)), dim3(256), 0, s, b->keysB.p, b->valsB.p, nKeys, nGroups, window, b->readCnt.p,
                                (const uint64_t*)nullptr, (MoveOccOut*)nullptr, uniqueOnly);
             tb = 0;
-            MV_HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, b->readCnt.p, b->readOff.p, (int)(nGroups + 1), s));
+            HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, b->readCnt.p, b->readOff.p, (int)(nGroups + 1), s));
             if (b->sortTmp.n < tb) b->sortTmp.alloc(tb + tb / 4);
-            MV_HIPCHK(hipcub::DeviceScan::ExclusiveSum(b->sortTmp.p, tb, b->readCnt.p, b->readOff.p, (int)(nGroups + 1), s));
-            MV_HIPCHK(hipMemcpyAsync(&kept, b->readOff.p + nGroups, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-            MV_HIPCHK(hipStreamSynchronize(s));
+            HIPCHK(hipcub::DeviceScan::ExclusiveSum(b->sortTmp.p, tb, b->readCnt.p, b->readOff.p, (int)(nGroups + 1), s));
+            HIPCHK(hipMemcpyAsync(&kept, b->readOff.p + nGroups, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
             if (dst.n < kept) dst.alloc(kept + kept / 4 + 256);
             if (kept)
                 hipLaunchKernelGGL(k_mvs_filter<true>, dim3(gridFor(nGroups)), dim3(256), 0, s, b->keysB.p, b->valsB.p, nKeys, nGroups, window, b->readCnt.p,
@@ -1402,11 +1344,11 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                                    b->keysA.p, b->vals.p, b->bad.p, (const uint8_t*)b->psel.p, 1);
                 if (const int rc = sortAndFilter(totalPos, 2 * nReads, b->naiveOut, nNaiveKept); rc != CMB_OK) return rc;
                 if (b->naiveOff.n < (size_t)2 * nReads + 1) b->naiveOff.alloc((size_t)2 * nReads + 1);
-                MV_HIPCHK(hipMemcpyAsync(b->naiveOff.p, b->readOff.p, ((size_t)2 * nReads + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+                HIPCHK(hipMemcpyAsync(b->naiveOff.p, b->readOff.p, ((size_t)2 * nReads + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
                 const uint64_t need = totalPos + nNaiveKept;
                 if (need >= (1ull << 31)) return failWith(CMB_ERR_UNSUPPORTED, "2^31 and more text positions in one b-move batch");
                 if (b->keysA.n < need || b->vals.n < need) {
-                    MV_HIPCHK(hipStreamSynchronize(s));
+                    HIPCHK(hipStreamSynchronize(s));
                     b->keysA.alloc(need + 256), b->keysB.alloc(need + 256), b->vals.alloc(need + 256), b->valsB.alloc(need + 256);
                 }
             }
@@ -1418,16 +1360,16 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                                    b->vals.p + totalPos, perStrand);
             // (the previous slice's records may still be on their way out of b->out: this stream waits for them before the buffer is
             // written or enlarged — sortAndFilter synchronises the stream before it allocates)
-            if (b->copyPending) MV_HIPCHK(hipStreamWaitEvent(s, b->copyDone, 0));
+            if (b->copyPending) HIPCHK(hipStreamWaitEvent(s, b->copyDone, 0));
             if (const int rc = sortAndFilter(totalPos + nNaiveKept, perStrand ? 2 * nReads : nReads, b->out, nOut); rc != CMB_OK) return rc;
             if (perStrand) { // per read again: the two strands of a read are neighbouring groups
                 if (b->rsOff.n < (size_t)2 * nReads + 1) b->rsOff.alloc((size_t)2 * nReads + 1);
-                MV_HIPCHK(hipMemcpyAsync(b->rsOff.p, b->readOff.p, ((size_t)2 * nReads + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+                HIPCHK(hipMemcpyAsync(b->rsOff.p, b->readOff.p, ((size_t)2 * nReads + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
                 hipLaunchKernelGGL(k_mvs_read_offsets, dim3(gridFor(nReads + 1)), dim3(256), 0, s, b->rsOff.p, nReads, b->readOff.p);
             }
         }
         tm.end("filter");
-        MV_HIPCHK(hipGetLastError());
+        HIPCHK(hipGetLastError());
         if (b->wantAln && nOut) { // CIGAR and sequence of every final occurrence: findCIGAR on text[begin, end) (k_cigar)
             tm.begin();
             if (b->occ32.n < nOut) {
@@ -1436,40 +1378,40 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
             }
             hipLaunchKernelGGL(k_mvs_occ32, dim3(gridFor(nReads)), dim3(256), 0, s, b->out.p, b->readOff.p, nReads, b->occ32.p, b->occRead.p);
             uint32_t flagBefore = 0;
-            MV_HIPCHK(hipMemcpyAsync(&flagBefore, b->cnt.p + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(&flagBefore, b->cnt.p + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
             const int rc = cmb::moveCigarsOnText(ix->textIndex, s, dOffs, b->G.p, b->gw, nReads, b->maxLen, b->k, b->metric == CMB_METRIC_EDIT ? 0 : 1,
                                                  b->occ32.p, b->occRead.p, nOut, b->alnRec.p, b->alnOps.p, b->alnStride, b->cnt.p + 3);
             if (rc != CMB_OK) return rc;
             const size_t base = b->hAlnRec.size();
             b->hAlnRec.resize(base + nOut);
             b->hAlnOps.resize((base + nOut) * b->alnStride);
-            MV_HIPCHK(hipMemcpyAsync(b->hAlnRec.data() + base, b->alnRec.p, nOut * sizeof(uint4), hipMemcpyDeviceToHost, s));
-            MV_HIPCHK(hipMemcpyAsync(b->hAlnOps.data() + base * b->alnStride, b->alnOps.p, nOut * b->alnStride * sizeof(uint16_t), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(b->hAlnRec.data() + base, b->alnRec.p, nOut * sizeof(uint4), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(b->hAlnOps.data() + base * b->alnStride, b->alnOps.p, nOut * b->alnStride * sizeof(uint16_t), hipMemcpyDeviceToHost, s));
             uint32_t flagAfter = 0;
-            MV_HIPCHK(hipMemcpyAsync(&flagAfter, b->cnt.p + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            MV_HIPCHK(hipStreamSynchronize(s));
+            HIPCHK(hipMemcpyAsync(&flagAfter, b->cnt.p + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
             tm.end("k_cigar");
             if ((flagAfter & ~flagBefore) & FLAG_CAPACITY)
                 return failWith(CMB_ERR_INTERNAL, "a CIGAR traceback left the band or an occurrence is not an alignment within its distance");
         }
         uint32_t hb = 0;
-        MV_HIPCHK(hipMemcpyAsync(&hb, b->bad.p, sizeof(hb), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&hb, b->bad.p, sizeof(hb), hipMemcpyDeviceToHost, s));
         unsigned long long hc64[CMB_CNT_MAX];
-        MV_HIPCHK(hipMemcpyAsync(hc64, b->counters.p, sizeof(hc64), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(hc64, b->counters.p, sizeof(hc64), hipMemcpyDeviceToHost, s));
         static_assert(sizeof(cmb_move_occ) == sizeof(MoveOccOut), "cmb_move_occ layout");
         const size_t occBase = b->occs.size();
         if (occBase + nOut > b->occs.cap) b->waitForCopies(); // (the page-locked vector moves when it grows)
         b->occs.resize(occBase + nOut);
         std::vector<uint64_t> sliceOffs((size_t)nReads + 1, 0);
         if (nOut) { // on the copy stream, behind everything this slice has queued: the next slice starts while the records travel
-            MV_HIPCHK(hipEventRecord(b->outReady, s));
-            MV_HIPCHK(hipStreamWaitEvent(b->copyStream, b->outReady, 0));
-            MV_HIPCHK(hipMemcpyAsync(b->occs.data() + occBase, b->out.p, nOut * sizeof(MoveOccOut), hipMemcpyDeviceToHost, b->copyStream));
-            MV_HIPCHK(hipEventRecord(b->copyDone, b->copyStream));
+            HIPCHK(hipEventRecord(b->outReady, s));
+            HIPCHK(hipStreamWaitEvent(b->copyStream, b->outReady, 0));
+            HIPCHK(hipMemcpyAsync(b->occs.data() + occBase, b->out.p, nOut * sizeof(MoveOccOut), hipMemcpyDeviceToHost, b->copyStream));
+            HIPCHK(hipEventRecord(b->copyDone, b->copyStream));
             b->copyPending = true;
         }
-        if (totalPos) MV_HIPCHK(hipMemcpyAsync(sliceOffs.data(), b->readOff.p, ((size_t)nReads + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        MV_HIPCHK(hipStreamSynchronize(s));
+        if (totalPos) HIPCHK(hipMemcpyAsync(sliceOffs.data(), b->readOff.p, ((size_t)nReads + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
         for (uint32_t i = 0; i <= nReads; i++) b->occOffs[(size_t)lo + i] = occBase + sliceOffs[i];
         if (totalPos && hb)
             return failWith(CMB_ERR_INTERNAL, std::to_string(hb) + " occurrences whose phi chains do not have the width of their range, or whose "
@@ -1557,8 +1499,8 @@ extern "C" int cmb_move_batch_timings(const cmb_move_batch* b, const char** name
     uint32_t n = 0;
     for (const auto& t : b->times) {
         if (n >= cap) break;
-        names[n] = t.first;
-        ms[n] = t.second;
+        names[n] = t.name;
+        ms[n] = t.ms;
         n++;
     }
     return (int)n;

@@ -264,6 +264,32 @@ class SearchStrategy {
             for (uint64_t j = oo[i]; j < oo[i + 1]; j++)
                 result[i].emplace_back(Range(occ[j].begin, occ[j].end), occ[j].distance, (Strand)occ[j].strand);
     }
+    // the identifiers, qualities and sequence names of a chunk's records, packed as cmb_batch_sam_device / cmb_best_sam_device take them
+    struct SamPacked {
+        std::string idBuf, qualBuf, nameBuf;
+        std::vector<uint64_t> idOffs, qualOffs, nameOffs;
+        bool noQuals;
+        template <class Names, class Id, class Qual> // id(i), qual(i): the fields of read i (qual is not called if noQuals)
+        SamPacked(size_t nReads, const Names& seqNames, Id id, bool withoutQuals, Qual qual)
+            : idOffs(nReads + 1, 0), qualOffs(nReads + 1, 0), nameOffs(seqNames.size() + 1, 0), noQuals(withoutQuals) {
+            for (size_t i = 0; i < nReads; i++) {
+                idBuf += id(i);
+                idOffs[i + 1] = idBuf.size();
+                if (!noQuals) {
+                    qualBuf += qual(i);
+                    qualOffs[i + 1] = qualBuf.size();
+                }
+            }
+            for (size_t i = 0; i < seqNames.size(); i++) {
+                nameBuf += seqNames[i];
+                nameOffs[i + 1] = nameBuf.size();
+            }
+        }
+        cmb_sam_inputs inputs(const std::string& seqs) const {
+            return cmb_sam_inputs{seqs.data(),     idBuf.data(),   idOffs.data(),   noQuals ? nullptr : qualBuf.data(),
+                                  qualOffs.data(), nameBuf.data(), nameOffs.data(), (uint32_t)(nameOffs.size() - 1)};
+        }
+    };
     // the SAM text of a chunk in ALL mode (matchApproxAllMap + generateOutputSingleEnd, searchstrategy.cpp:495-535, :1824-1902)
     std::string samOfChunkAll(const std::string& seqs, const std::vector<uint64_t>& offs, const std::vector<const char*>& ids,
                               const std::vector<const char*>& quals, const std::vector<const char*>& seqNames, length_t maxED,
@@ -277,24 +303,10 @@ class SearchStrategy {
         check(cmb_batch_want_alignments(b, 1));
         check(cmb_batch_run(b));
         if (const char* e = getenv("CMB_SAM_HOST"); !e || atoi(e) == 0) { // the text is written on the device (cmb_batch_sam_device)
-            const size_t nReads = offs.size() - 1;
             const bool noQuals = quals.empty() || !quals.data();
-            std::string idBuf, qualBuf, nameBuf;
-            std::vector<uint64_t> idOffs(nReads + 1, 0), qualOffs(nReads + 1, 0), nameOffs(seqNames.size() + 1, 0);
-            for (size_t i = 0; i < nReads; i++) {
-                idBuf += ids[i];
-                idOffs[i + 1] = idBuf.size();
-                if (!noQuals) {
-                    qualBuf += quals[i] ? quals[i] : "*";
-                    qualOffs[i + 1] = qualBuf.size();
-                }
-            }
-            for (size_t i = 0; i < seqNames.size(); i++) {
-                nameBuf += seqNames[i];
-                nameOffs[i + 1] = nameBuf.size();
-            }
-            const cmb_sam_inputs in{seqs.data(),    idBuf.data(),    idOffs.data(),           noQuals ? nullptr : qualBuf.data(),
-                                    qualOffs.data(), nameBuf.data(), nameOffs.data(), (uint32_t)seqNames.size()};
+            const SamPacked packed(offs.size() - 1, seqNames, [&](size_t i) { return ids[i]; }, noQuals,
+                                   [&](size_t i) { return quals[i] ? quals[i] : "*"; });
+            const cmb_sam_inputs in = packed.inputs(seqs);
             const char* text = nullptr;
             uint64_t length = 0;
             check(cmb_batch_sam_device(b, &in, unmappedRecords, xaTag, &text, &length, nullptr));
@@ -670,20 +682,9 @@ class SearchStrategy {
                 cmb_best* r;
                 ~Guard() { cmb_best_destroy(r); }
             } guard{r};
-            std::string idBuf, qualBuf, nameBuf;
-            std::vector<uint64_t> idOffs(nReads + 1, 0), qualOffs(nReads + 1, 0), nameOffs(seqNames.size() + 1, 0);
-            for (uint32_t i = 0; i < nReads; i++) {
-                idBuf += recs[i].seqID;
-                idOffs[i + 1] = idBuf.size();
-                qualBuf += recs[i].qual;
-                qualOffs[i + 1] = qualBuf.size();
-            }
-            for (size_t i = 0; i < seqNames.size(); i++) {
-                nameBuf += seqNames[i];
-                nameOffs[i + 1] = nameBuf.size();
-            }
-            const cmb_sam_inputs in{seqs.data(),     idBuf.data(),   idOffs.data(),   qualBuf.data(),
-                                    qualOffs.data(), nameBuf.data(), nameOffs.data(), (uint32_t)seqNames.size()};
+            const SamPacked packed(nReads, seqNames, [&](size_t i) -> const std::string& { return recs[i].seqID; }, false,
+                                   [&](size_t i) -> const std::string& { return recs[i].qual; });
+            const cmb_sam_inputs in = packed.inputs(seqs);
             const char* text = nullptr;
             uint64_t length = 0;
             check(cmb_best_sam_device(r, &in, unmappedRecords, xaTag, &text, &length, nullptr));

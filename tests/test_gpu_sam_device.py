@@ -246,6 +246,48 @@ def test_composite_batch(chunk_world):
     single.close()
 
 
+def _text_of(entry, obj, ids, quals, names, xa):
+    """the text `entry` (cmb_batch_sam_device / cmb_best_sam_device) writes for the handle of `obj` from (bytes, offsets) pairs.
+    SamInputs is filled here, not by the package's wrapper: offsets that do not start at 0 must reach the C ABI untouched"""
+    import ctypes as C
+    (bi, oi), (bq, oq), (bn, on) = ids, quals, names
+    inp = ca.SamInputs(ca._p(obj._packed[0]), ca._p(bi), ca._p(oi), ca._p(bq), ca._p(oq), ca._p(bn), ca._p(on), on.shape[0] - 1)
+    text, n, host = C.c_void_p(), C.c_uint64(), C.c_uint64()
+    ca._chk(entry(obj.h, C.byref(inp), 1, int(xa), C.byref(text), C.byref(n), C.byref(host)))
+    return (C.string_at(text.value, n.value) if n.value else b"").decode(), int(host.value)
+
+
+def test_packed_inputs_that_do_not_start_at_zero(chunk_world):
+    """8: identifiers and qualities whose offsets begin at 7 and 5 (the driver subtracts id_offs[r0] / qual_offs[r0] as a base, which
+    only a sub-batch exercises otherwise) give the text of the zero-based packing, in ALL and in BEST mode, with a host-formatted
+    read among the 65 (one more than a wavefront has lanes, five pieces of SAM_READS_PER_WAVE)"""
+    w = chunk_world
+    g = w["genome"]
+    reads = synth.sample_reads(g, 63, 150, seed=71, n_frac=0.01, edit_choices=(0, 1, 2))
+    s = int(np.asarray(w["ix"].seq_starts, dtype=np.int64)[1])
+    reads += [g[s - 75:s + 75].tobytes(), g[s - 2:s + 148].tobytes()]  # (the sequence-boundary reads of _chunk)
+    assert len(reads) == 65 and all(len(r) == 150 for r in reads)
+    rng = np.random.default_rng(72)
+    ids = ca.pack_fields([("@" if i % 2 else ">") + f"read{i}/1 some description" for i in range(65)])
+    quals = ca.pack_fields(["".join(chr(33 + int(q)) for q in rng.integers(0, 41, 150)) for _ in reads])
+    names = ca.pack_fields([f"chr{j + 1}" for j in range(len(w["ix"].seq_starts) - 1)])
+    shifted_ids = (np.concatenate([np.frombuffer(b"\tjunk \n", np.uint8), ids[0]]), ids[1] + np.uint64(7))
+    shifted_quals = (np.concatenate([np.frombuffer(b"~~~~\n", np.uint8), quals[0]]), quals[1] + np.uint64(5))
+    assert shifted_ids[0].shape[0] == ids[0].shape[0] + 7 and shifted_quals[0].shape[0] == quals[0].shape[0] + 5
+    st = ca.SearchStrategy("columba", "edit", "dynamic")
+    b = _batch(w["dev"], "columba", "edit", 2, reads)
+    best = ca.BestDevice(w["dev"], st, reads, x=0, min_identity=95)
+    for entry, obj in ((ca.lib().cmb_batch_sam_device, b), (ca.lib().cmb_best_sam_device, best)):
+        for xa in (False, True):
+            want, host_reads = _text_of(entry, obj, ids, quals, names, xa)
+            got, host_shifted = _text_of(entry, obj, shifted_ids, shifted_quals, names, xa)
+            _same(got, want)
+            assert host_shifted == host_reads >= 1 and want.count("\n") >= 65
+    _same(_text_of(ca.lib().cmb_batch_sam_device, b, ids, quals, names, False)[0], b.sam_device(ids, quals, names)[0])
+    b.close()
+    best.close()
+
+
 def test_run_format_stage_run_format(chunk_world):
     """6b: a batch that is run, formatted, fed a staged chunk and formatted again (a staged chunk travels during the next run
     and is matched by the one after it)"""
