@@ -57,6 +57,7 @@ EXPORTS = [
     "cmb_move_match_batch", "cmb_move_batch_create", "cmb_move_batch_run", "cmb_move_batch_result_size", "cmb_move_batch_results",
     "cmb_move_batch_timings", "cmb_move_batch_destroy", "cmb_move_attach_text", "cmb_move_text_index", "cmb_index_create_text_only", "cmb_sam_chunk", "cmb_move_batch_want_alignments",
     "cmb_move_batch_alignments", "cmb_move_batch_filter_per_strand", "cmb_move_match_best",
+    "cmb_move_batch_keep_device_lists", "cmb_move_batch_sam_device", "cmb_move_match_best_device",
     "cmb_last_error", "cmb_version",
 ]
 
@@ -324,6 +325,9 @@ def lib():
         L.cmb_move_batch_want_alignments.argtypes = [vp, i32]
         L.cmb_move_batch_filter_per_strand.argtypes = [vp, i32]
         L.cmb_move_match_best.argtypes = [vp, vp, u32, u32, u32, vp, vp, u32, C.POINTER(vp)]
+        L.cmb_move_match_best_device.argtypes = [vp, vp, u32, u32, u32, vp, vp, u32, C.POINTER(vp)]
+        L.cmb_move_batch_keep_device_lists.argtypes = [vp, i32]
+        L.cmb_move_batch_sam_device.argtypes = [vp, C.POINTER(SamInputs), i32, i32, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
         L.cmb_move_batch_alignments.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
         L.cmb_move_kmer_table.argtypes = [vp, u32, vp]
         L.cmb_move_layout_of.argtypes = [vp, C.POINTER(MoveLayout)]
@@ -784,8 +788,8 @@ def sam_device_mapq(n: int) -> np.ndarray:
 
 
 def _sam_device_bytes(entry, obj, ids, quals, seq_names, unmapped: bool, xa: bool):
-    """(SAM text as bytes, number of host-formatted reads) from ``entry`` (cmb_batch_sam_device or cmb_best_sam_device) on the handle
-    of ``obj``, whose reads the fields belong to"""
+    """(SAM text as bytes, number of host-formatted reads) from ``entry`` (cmb_batch_sam_device, cmb_move_batch_sam_device or
+    cmb_best_sam_device) on the handle of ``obj``, whose reads the fields belong to"""
     bi, oi = pack_fields(ids)
     bn, on = pack_fields(seq_names)
     bq, oq = pack_fields(quals) if quals is not None else (None, None)
@@ -956,15 +960,19 @@ def match_best(index, strategy: SearchStrategy, reads: Sequence[bytes], x: int =
 
 class BestDevice:
     """A BEST-mode result whose lists stay on the device (cmb_match_best_device): ``results()`` downloads them, ``sam_device()``
-    writes the chunk's SAM text from them on the device (cmb_best_sam_device).  FM-index flavour, single-end reads."""
+    writes the chunk's SAM text from them on the device (cmb_best_sam_device).  Single-end reads; ``index``: an ``Index``, or a
+    ``MoveIndex`` with its text attached (cmb_move_match_best_device; ``kmer_size``: the k-mer table of that flavour's search)."""
 
-    def __init__(self, index: "Index", strategy: SearchStrategy, reads: Sequence[bytes], x: int = 0, min_identity: int = 95):
+    def __init__(self, index, strategy: SearchStrategy, reads: Sequence[bytes], x: int = 0, min_identity: int = 95, kmer_size: int = 10):
         self._packed = pack_reads(reads)
         self.n_reads = len(reads)
         self.index = index
         self.h = C.c_void_p()
-        _chk(lib().cmb_match_best_device(index.h, strategy.h, x, min_identity, _p(self._packed[0]), _p(self._packed[1]), self.n_reads,
-                                         C.byref(self.h)))
+        args = (_p(self._packed[0]), _p(self._packed[1]), self.n_reads, C.byref(self.h))
+        if isinstance(index, MoveIndex):
+            _chk(lib().cmb_move_match_best_device(index.h, strategy.h, x, min_identity, kmer_size, *args))
+        else:
+            _chk(lib().cmb_match_best_device(index.h, strategy.h, x, min_identity, *args))
 
     def results(self):
         """the tuple of ``match_best``"""
@@ -1001,10 +1009,10 @@ class BestDevice:
     __del__ = close
 
 
-def match_best_device(index: "Index", strategy: SearchStrategy, reads: Sequence[bytes], x: int = 0, min_identity: int = 95):
-    """``match_best`` with the strata bookkeeping on the device (cmb_match_best_device): the tuple of ``match_best`` plus the per-read
-    host-read status (``BestDevice.host_reads``)"""
-    b = BestDevice(index, strategy, reads, x, min_identity)
+def match_best_device(index, strategy: SearchStrategy, reads: Sequence[bytes], x: int = 0, min_identity: int = 95, kmer_size: int = 10):
+    """``match_best`` with the strata bookkeeping on the device (cmb_match_best_device, or cmb_move_match_best_device for a
+    ``MoveIndex``): the tuple of ``match_best`` plus the per-read host-read status (``BestDevice.host_reads``)"""
+    b = BestDevice(index, strategy, reads, x, min_identity, kmer_size)
     try:
         return b.results() + (b.host_reads(),)
     finally:
@@ -1200,6 +1208,7 @@ class MoveBatch:
         self.n_reads = offs.shape[0] - 1
         self.max_distance = max_distance
         self._keep = (index, strategy, buf, offs)
+        self._packed = (buf, offs)
         h = C.c_void_p()
         _chk(lib().cmb_move_batch_create(index.h, strategy.h, max_distance, kmer_size, _p(buf), _p(offs), self.n_reads, C.byref(h)))
         self.h = h
@@ -1223,6 +1232,10 @@ class MoveBatch:
     def want_alignments(self, on: bool = True):
         """CIGAR and sequence of every occurrence (needs MoveIndex.attach_text)"""
         _chk(lib().cmb_move_batch_want_alignments(self.h, int(on)))
+
+    def keep_device_lists(self, on: bool = True):
+        """the final lists of the whole chunk stay on the device as well (what sam_device reads); after want_alignments(), before run()"""
+        _chk(lib().cmb_move_batch_keep_device_lists(self.h, int(on)))
 
     def alignments(self):
         """(cmb_aln records parallel to the occurrences, pool of CIGAR run-length operations), as Batch.alignments"""
@@ -1256,6 +1269,16 @@ class MoveBatch:
         out = C.create_string_buffer(int(n) + 1)
         lib().cmb_sam_chunk(*args, out, int(n) + 1)
         return out.value.decode()
+
+    def sam_device_bytes(self, ids, quals, seq_names, unmapped: bool = True, xa: bool = False):
+        """the text of sam() written on the device from the kept lists (cmb_move_batch_sam_device; needs keep_device_lists() before
+        run()): (bytes, number of reads the host formatted); inputs as ``Batch.sam_device_bytes``"""
+        return _sam_device_bytes(lib().cmb_move_batch_sam_device, self, ids, quals, seq_names, unmapped, xa)
+
+    def sam_device(self, ids, quals, seq_names, unmapped: bool = True, xa: bool = False):
+        """(SAM text, number of host-formatted reads): sam_device_bytes, decoded"""
+        t, host = self.sam_device_bytes(ids, quals, seq_names, unmapped, xa)
+        return t.decode(), host
 
     def timings(self) -> Dict[str, float]:
         names = (C.c_char_p * 16)()

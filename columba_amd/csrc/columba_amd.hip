@@ -535,16 +535,6 @@ extern "C" int cmb_strategy_export_partition(const cmb_strategy* s, uint32_t k, 
 }
 
 // ------------------------------------------------------------------------------------ batch
-// What the device SAM driver (samUpload, samSplice, samScan, samWrite below) keeps in HBM for one (sub-)batch or one BEST result: the
-// chunk's packed identifiers, qualities and sequence names with their offsets, the plan, length and position of every read in the
-// text, the text of the reads the host formatted with its offsets and read numbers, the text itself (the scan's scratch is the owner's scanTmp)
-struct SamDeviceBufs {
-    DevBuf<uint8_t> ids, quals, names, side, text;
-    DevBuf<uint64_t> idOffs, qualOffs, nameOffs, len, offs, sideOffs;
-    DevBuf<SamPlan> plan;
-    DevBuf<uint32_t> sideReads;
-};
-
 struct cmb_batch {
     cmb_index* ix = nullptr;
     uint32_t k = 0, nReads = 0, maxLen = 0, gw = 0;
@@ -2664,104 +2654,175 @@ static std::vector<std::string> samNamesOf(const cmb_sam_inputs* in) {
     return names;
 }
 
+// One part of a chunk as the driver sees it: a (sub-)batch of either flavour with its lists in HBM (cx: the list fields of the context),
+// the buffers it keeps for the driver, and its occurrences on the host for the reads the host formats
+struct SamPart {
+    uint32_t n = 0, k = 0;
+    int metric = 1;
+    hipStream_t s = nullptr;
+    SamCtx cx{};
+    SamDeviceBufs* sam = nullptr;
+    DevBuf<uint32_t>* hostList = nullptr;
+    DevBuf<uint8_t>* scanTmp = nullptr;
+    const uint64_t* hostOffs = nullptr; // read offsets of the part, from 0
+    std::function<std::vector<BestOcc>(uint32_t)> occsOf;
+};
+// idx: the index whose text and sequence starts serve the trimming of the host-formatted reads
+static int samDeviceOver(cmb_index* idx, std::vector<SamPart>& parts, const cmb_sam_inputs* in, int unmapped_records, int xa_tag,
+                         PinnedBuf<char>& samOut, const char** text, uint64_t* length, uint64_t* host_reads) {
+    useDevice(idx->device);
+    const size_t P = parts.size();
+    const bool verbose = getenv("CMB_VERBOSE") != nullptr;
+    auto t0 = std::chrono::steady_clock::now();
+    auto lap = [&](const char* what) {
+        if (!verbose) return;
+        auto t1 = std::chrono::steady_clock::now();
+        fprintf(stderr, "[host] sam: %-28s %7.3f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count());
+        t0 = t1;
+    };
+    std::vector<uint64_t> readBase(P + 1, 0), charBase(P + 1, 0), partBytes(P, 0);
+    std::vector<uint32_t> nHost(P, 0);
+    for (size_t j = 0; j < P; j++) {
+        readBase[j + 1] = readBase[j] + parts[j].n;
+        charBase[j + 1] = charBase[j] + (parts[j].n ? parts[j].hostOffs[parts[j].n] : 0);
+    }
+    // ---- plan: inputs up, one wavefront per read
+    for (size_t j = 0; j < P; j++) {
+        SamPart& c = parts[j];
+        const uint32_t n = c.n;
+        if (!n) continue;
+        hipStream_t s = c.s;
+        SamCtx& cx = c.cx;
+        cx.unmapped = unmapped_records ? 1u : 0u, cx.xa = xa_tag ? 1u : 0u;
+        if (int rc = samUpload(*c.sam, in, readBase[j], n, s, cx)) return rc;
+        growTo(*c.hostList, (size_t)n + 1);
+        HIPCHK(hipMemsetAsync(c.hostList->p, 0, sizeof(uint32_t), s));
+        hipLaunchKernelGGL(k_sam_plan, dim3((n + 3u) / 4u), dim3(256), 0, s, cx, c.sam->plan.p, c.sam->len.p, c.hostList->p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&nHost[j], c.hostList->p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    }
+    lap("inputs up, plan started");
+    // ---- the reads the host formats (k_sam_plan listed them), then the position of every read in its sub-batch's text
+    std::vector<std::string> names;
+    std::vector<const char*> namePtrs;
+    uint64_t nHostAll = 0;
+    for (size_t j = 0; j < P; j++) {
+        SamPart& c = parts[j];
+        const uint32_t n = c.n;
+        if (!n) continue;
+        hipStream_t s = c.s;
+        HIPCHK(hipStreamSynchronize(s));
+        if (nHost[j]) {
+            if (names.empty()) names = samNamesOf(in);
+            if (namePtrs.empty())
+                for (const std::string& nm : names) namePtrs.push_back(nm.c_str());
+            std::vector<uint32_t> list(nHost[j]);
+            HIPCHK(hipMemcpy(list.data(), c.hostList->p + 1, (size_t)nHost[j] * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            std::sort(list.begin(), list.end());
+            samSplice(*c.sam, list, s, [&](uint32_t i, std::string& side) {
+                const uint64_t gi = readBase[j] + i;
+                const uint64_t o0 = charBase[j] + c.hostOffs[i], o1 = charBase[j] + c.hostOffs[i + 1];
+                const std::string read = cleanReadSeq(std::string(in->seqs + o0, in->seqs + o1)), revC = revComplWithN(read);
+                const std::string sid = cleanSeqID(std::string(in->ids + in->id_offs[gi], in->ids + in->id_offs[gi + 1]));
+                const std::string qual = in->quals ? std::string(in->quals + in->qual_offs[gi], in->quals + in->qual_offs[gi + 1]) : "*";
+                std::vector<BestOcc> occs = c.occsOf(i);
+                samOfRead(side, idx, c.k, c.metric, read, revC, sid, qual, occs, namePtrs.data(), unmapped_records, xa_tag);
+            });
+            nHostAll += nHost[j];
+        }
+        samScan(*c.sam, *c.scanTmp, n, &partBytes[j], s);
+    }
+    uint64_t total = 0;
+    for (size_t j = 0; j < P; j++) {
+        if (parts[j].n) HIPCHK(hipStreamSynchronize(parts[j].s));
+        total += partBytes[j];
+    }
+    lap("plan, host reads, scan");
+    // ---- write: every sub-batch its piece, copied to its place in the batch's text
+    samOut.resize((size_t)total + 1);
+    samOut.p[total] = '\0';
+    uint64_t at = 0;
+    for (size_t j = 0; j < P; j++) {
+        if (!parts[j].n || !partBytes[j]) continue;
+        samWrite(*parts[j].sam, parts[j].cx, partBytes[j], samOut.p + at, parts[j].s);
+        at += partBytes[j];
+    }
+    for (size_t j = 0; j < P; j++)
+        if (parts[j].n && partBytes[j]) HIPCHK(hipStreamSynchronize(parts[j].s));
+    lap("write, text down");
+    *text = samOut.p;
+    *length = total;
+    if (host_reads) *host_reads = nHostAll;
+    return CMB_OK;
+}
+static bool samInputsOk(const cmb_sam_inputs* in) {
+    return in && in->seqs && in->ids && in->id_offs && (!in->quals || in->qual_offs) && (!in->n_seqs || (in->seq_names && in->seq_name_offs));
+}
+
 extern "C" int cmb_batch_sam_device(cmb_batch* b, const cmb_sam_inputs* in, int unmapped_records, int xa_tag, const char** text,
                                     uint64_t* length, uint64_t* host_reads) {
-    if (!b || !in || !text || !length || !in->seqs || !in->ids || !in->id_offs || (in->quals && !in->qual_offs) ||
-        (in->n_seqs && (!in->seq_names || !in->seq_name_offs)))
-        return fail(CMB_ERR_INVALID, "null argument");
+    if (!b || !text || !length || !samInputsOk(in)) return fail(CMB_ERR_INVALID, "null argument");
     if (!b->done) return fail(CMB_ERR_INVALID, "batch has not been run");
     if (!b->wantAln) return fail(CMB_ERR_INVALID, "alignments were not requested (cmb_batch_want_alignments)");
     try {
-        std::vector<cmb_batch*> parts;
-        if (b->subs.empty()) parts.push_back(b);
-        else parts = b->subs;
-        cmb_index* idx = b->ix;
+        std::vector<cmb_batch*> subs;
+        if (b->subs.empty()) subs.push_back(b);
+        else subs = b->subs;
+        std::vector<SamPart> parts;
+        for (cmb_batch* c : subs) {
+            SamPart p;
+            p.n = c->nReads, p.k = c->k, p.metric = c->metric, p.s = c->stream;
+            p.cx = SamCtx{c->reads.p, c->offs.p, c->foffs.p, c->perStrand ? 2u : 1u, c->fout.p, c->alnRec.p, c->alnOps.p, c->alnStride};
+            p.sam = &c->sam, p.hostList = &c->samHostList, p.scanTmp = &c->scanTmp;
+            p.hostOffs = c->hostOffs.data();
+            p.occsOf = [c](uint32_t i) { return occsOfBatchRead(c, i); };
+            parts.push_back(std::move(p));
+        }
+        return samDeviceOver(b->ix, parts, in, unmapped_records, xa_tag, b->samOut, text, length, host_reads);
+    } catch (const std::exception& e) {
+        return fail(CMB_ERR_DEVICE, e.what());
+    }
+}
+
+// ---- the same on a b-move batch whose final lists stayed in HBM (cmb_move_batch_keep_device_lists; move_backend.hip) -----------------
+namespace cmb {
+int moveBatchListViews(cmb_move_batch* b, std::vector<MoveListView>& out);
+cmb_index* moveTextIndexOfBatch(const cmb_move_batch* b);
+} // namespace cmb
+extern "C" int cmb_move_batch_sam_device(cmb_move_batch* b, const cmb_sam_inputs* in, int unmapped_records, int xa_tag, const char** text,
+                                         uint64_t* length, uint64_t* host_reads) {
+    if (!b || !text || !length || !samInputsOk(in)) return fail(CMB_ERR_INVALID, "null argument");
+    try {
+        std::vector<MoveListView> views;
+        if (int rc = moveBatchListViews(b, views)) return rc;
+        cmb_index* idx = moveTextIndexOfBatch(b);
+        if (!idx) return fail(CMB_ERR_INVALID, "the batch's index has no text beside it (cmb_move_attach_text)");
         useDevice(idx->device);
-        const size_t P = parts.size();
-        const bool verbose = getenv("CMB_VERBOSE") != nullptr;
-        auto t0 = std::chrono::steady_clock::now();
-        auto lap = [&](const char* what) {
-            if (!verbose) return;
-            auto t1 = std::chrono::steady_clock::now();
-            fprintf(stderr, "[host] sam: %-28s %7.3f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count());
-            t0 = t1;
-        };
-        std::vector<uint64_t> readBase(P + 1, 0), charBase(P + 1, 0), partBytes(P, 0);
-        std::vector<uint32_t> nHost(P, 0);
-        std::vector<SamCtx> ctx(P);
-        for (size_t j = 0; j < P; j++) {
-            readBase[j + 1] = readBase[j] + parts[j]->nReads;
-            charBase[j + 1] = charBase[j] + (parts[j]->nReads ? parts[j]->hostOffs[parts[j]->nReads] : 0);
+        std::vector<SamPart> parts;
+        for (const MoveListView& v : views) {
+            MoveSamBufs* st = v.samBufs;
+            SamPart p;
+            p.n = v.nReads, p.k = v.k, p.metric = v.metric, p.s = v.stream;
+            p.cx = SamCtx{v.reads, v.offs, v.goffs, v.groupStride, v.occ, (const AlnRec*)v.aln, v.ops, v.stride};
+            p.sam = &st->sam, p.hostList = &st->hostList, p.scanTmp = &st->scanTmp;
+            p.hostOffs = v.hostOffs;
+            p.occsOf = [v](uint32_t i) { // (texts below 2^32: cmb_move_attach_text)
+                std::vector<BestOcc> occs;
+                const cmb_move_occ* ho = (const cmb_move_occ*)v.hOcc;
+                for (uint64_t q = v.hOccOffs[i]; q < v.hOccOffs[i + 1]; q++) {
+                    BestOcc o;
+                    o.occ = cmb_occ{(uint32_t)ho[q].begin, (uint32_t)ho[q].end, ho[q].distance, ho[q].strand};
+                    const uint4& ar = v.hAln[q];
+                    o.aln = cmb_aln{ar.x, ar.y, 0, (uint16_t)ar.z, (uint16_t)ar.w, 0};
+                    const uint16_t* src = v.hOps + q * v.stride;
+                    for (uint32_t j = 0; j < ar.z; j++) o.ops.push_back(src[ar.z - 1 - j]);
+                    occs.push_back(std::move(o));
+                }
+                return occs;
+            };
+            parts.push_back(std::move(p));
         }
-        // ---- plan: inputs up, one wavefront per read
-        for (size_t j = 0; j < P; j++) {
-            cmb_batch* c = parts[j];
-            const uint32_t n = c->nReads;
-            if (!n) continue;
-            hipStream_t s = c->stream;
-            SamCtx& cx = ctx[j];
-            cx = SamCtx{c->reads.p, c->offs.p, c->foffs.p, c->perStrand ? 2u : 1u, c->fout.p, c->alnRec.p, c->alnOps.p, c->alnStride};
-            cx.unmapped = unmapped_records ? 1u : 0u, cx.xa = xa_tag ? 1u : 0u;
-            if (int rc = samUpload(c->sam, in, readBase[j], n, s, cx)) return rc;
-            growTo(c->samHostList, (size_t)n + 1);
-            HIPCHK(hipMemsetAsync(c->samHostList.p, 0, sizeof(uint32_t), s));
-            hipLaunchKernelGGL(k_sam_plan, dim3((n + 3u) / 4u), dim3(256), 0, s, cx, c->sam.plan.p, c->sam.len.p, c->samHostList.p);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(&nHost[j], c->samHostList.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        }
-        lap("inputs up, plan started");
-        // ---- the reads the host formats (k_sam_plan listed them), then the position of every read in its sub-batch's text
-        std::vector<std::string> names;
-        std::vector<const char*> namePtrs;
-        uint64_t nHostAll = 0;
-        for (size_t j = 0; j < P; j++) {
-            cmb_batch* c = parts[j];
-            const uint32_t n = c->nReads;
-            if (!n) continue;
-            hipStream_t s = c->stream;
-            HIPCHK(hipStreamSynchronize(s));
-            if (nHost[j]) {
-                if (names.empty()) names = samNamesOf(in);
-                if (namePtrs.empty())
-                    for (const std::string& nm : names) namePtrs.push_back(nm.c_str());
-                std::vector<uint32_t> list(nHost[j]);
-                HIPCHK(hipMemcpy(list.data(), c->samHostList.p + 1, (size_t)nHost[j] * sizeof(uint32_t), hipMemcpyDeviceToHost));
-                std::sort(list.begin(), list.end());
-                samSplice(c->sam, list, s, [&](uint32_t i, std::string& side) {
-                    const uint64_t gi = readBase[j] + i;
-                    const uint64_t o0 = charBase[j] + c->hostOffs[i], o1 = charBase[j] + c->hostOffs[i + 1];
-                    const std::string read = cleanReadSeq(std::string(in->seqs + o0, in->seqs + o1)), revC = revComplWithN(read);
-                    const std::string sid = cleanSeqID(std::string(in->ids + in->id_offs[gi], in->ids + in->id_offs[gi + 1]));
-                    const std::string qual = in->quals ? std::string(in->quals + in->qual_offs[gi], in->quals + in->qual_offs[gi + 1]) : "*";
-                    std::vector<BestOcc> occs = occsOfBatchRead(c, i);
-                    samOfRead(side, idx, c->k, c->metric, read, revC, sid, qual, occs, namePtrs.data(), unmapped_records, xa_tag);
-                });
-                nHostAll += nHost[j];
-            }
-            samScan(c->sam, c->scanTmp, n, &partBytes[j], s);
-        }
-        uint64_t total = 0;
-        for (size_t j = 0; j < P; j++) {
-            if (parts[j]->nReads) HIPCHK(hipStreamSynchronize(parts[j]->stream));
-            total += partBytes[j];
-        }
-        lap("plan, host reads, scan");
-        // ---- write: every sub-batch its piece, copied to its place in the batch's text
-        b->samOut.resize((size_t)total + 1);
-        b->samOut.p[total] = '\0';
-        uint64_t at = 0;
-        for (size_t j = 0; j < P; j++) {
-            if (!parts[j]->nReads || !partBytes[j]) continue;
-            samWrite(parts[j]->sam, ctx[j], partBytes[j], b->samOut.p + at, parts[j]->stream);
-            at += partBytes[j];
-        }
-        for (size_t j = 0; j < P; j++)
-            if (parts[j]->nReads && partBytes[j]) HIPCHK(hipStreamSynchronize(parts[j]->stream));
-        lap("write, text down");
-        *text = b->samOut.p;
-        *length = total;
-        if (host_reads) *host_reads = nHostAll;
-        return CMB_OK;
+        return samDeviceOver(idx, parts, in, unmapped_records, xa_tag, views[0].samBufs->samOut, text, length, host_reads);
     } catch (const std::exception& e) {
         return fail(CMB_ERR_DEVICE, e.what());
     }
@@ -3163,11 +3224,36 @@ inline BestOcc bestOccOf(const uint4& o, const AlnRec& a, const uint16_t* ops) {
 }
 } // namespace
 
-extern "C" int cmb_match_best_device(cmb_index* idx, const cmb_strategy* st, uint32_t x, uint32_t min_identity, const char* seqs,
-                                     const uint64_t* offs, uint32_t n_reads, cmb_best** out) {
+namespace {
+// What one stratum leaves in HBM, whichever flavour matched it: per part the lists k_best_scan / k_best_append read (two filter groups
+// per read), the counters and kernel times of its run, and how to let go of the batch that owns the lists.
+struct StratumLists {
+    uint32_t nReads;
+    const uint64_t* foffs;
+    const uint4* fout;
+    const AlnRec* aln;
+    const uint16_t* ops;
+    uint32_t stride;
+};
+struct DevStratum {
+    std::vector<StratumLists> parts;
+    uint64_t cnts[CMB_CNT_MAX] = {};
+    std::vector<KernelTime> times;
+    std::function<void()> destroy;
+    ~DevStratum() {
+        if (destroy) destroy();
+    }
+};
+// create, per-strand filter, alignments, run: an ALL-mode search of both strands of `n` reads at distance k whose lists stay on the device
+typedef std::function<int(const char* cat, const uint64_t* o, uint32_t n, uint32_t k, DevStratum& r, const std::function<void(const char*)>& lap)>
+    DevStratumRunner;
+
+// idx: the index whose text and sequence starts serve the trimming (the FM-index itself, or the text beside a b-move index);
+// trimCounters: as for matchBestWith
+int matchBestDeviceWith(cmb_index* idx, const cmb_strategy* st, bool trimCounters, const DevStratumRunner& runOn, uint32_t x, uint32_t min_identity,
+                        const char* seqs, const uint64_t* offs, uint32_t n_reads, cmb_best** out) {
     if (!idx || !st || !offs || !out || (!seqs && n_reads)) return fail(CMB_ERR_INVALID, "null argument");
     if (min_identity < 50 || min_identity > 100) return fail(CMB_ERR_INVALID, "the minimal identity lies between 50 and 100");
-    if (idx->textOnly) return fail(CMB_ERR_INVALID, "this index holds only the text (cmb_index_create_text_only): nothing can be matched on it");
     try {
         useDevice(idx->device);
         uint32_t maxSupported = 0;
@@ -3216,7 +3302,7 @@ extern "C" int cmb_match_best_device(cmb_index* idx, const cmb_strategy* st, uin
                     assigned.push_back(std::move(o));
                     if (l < r.best) r.best = (uint8_t)l;
                 } else if (o.aln.spans == 1) {
-                    if (trimOccurrence(idx, s2 ? h.rc : h.fw, cutOffTrim, st->metric, o, R->cnts) && o.occ.distance > l &&
+                    if (trimOccurrence(idx, s2 ? h.rc : h.fw, cutOffTrim, st->metric, o, trimCounters ? R->cnts : nullptr) && o.occ.distance > l &&
                         o.occ.distance < h.ov[s2].size())
                         trimmed.push_back(std::move(o));
                 }
@@ -3245,24 +3331,11 @@ extern "C" int cmb_match_best_device(cmb_index* idx, const cmb_strategy* st, uin
                 o[j + 1] = cat.size();
             }
             lap("host: gather of the stratum's reads");
-            cmb_batch* b = nullptr;
-            int rcode = cmb_batch_create(idx, st, k, cat.data(), o.data(), n, &b);
-            if (rcode) return rcode;
-            struct Guard {
-                cmb_batch* b;
-                ~Guard() { cmb_batch_destroy(b); }
-            } guard{b};
-            cmb_batch_filter_per_strand(b, 1);
-            cmb_batch_want_alignments(b, 1);
-            lap("host: cmb_batch_create");
-            if ((rcode = cmb_batch_run(b))) return rcode;
-            lap("host: cmb_batch_run");
-            for (int i = 0; i < CMB_CNT_MAX; i++) R->cnts[i] += b->cnts[i];
-            std::vector<cmb_batch*> parts;
-            if (b->subs.empty()) parts.push_back(b);
-            else parts = b->subs;
-            for (const cmb_batch* c : parts)
-                for (const KernelTime& t : c->times) R->addTime(std::string("strata: ") + t.name, t.ms);
+            DevStratum ds;
+            if (const int rcode = runOn(cat.data(), o.data(), n, k, ds, lap)) return rcode;
+            for (int i = 0; i < CMB_CNT_MAX; i++) R->cnts[i] += ds.cnts[i];
+            const std::vector<StratumLists>& parts = ds.parts;
+            for (const KernelTime& t : ds.times) R->addTime(std::string("strata: ") + t.name, t.ms);
             // processSeq (:791-812): what lies below the first distance not processed yet is dropped
             hMinD.resize(n);
             for (uint32_t j = 0; j < n; j++) hMinD[j] = (uint8_t)std::min<uint32_t>(sv[ids[j]].proc, k);
@@ -3271,11 +3344,11 @@ extern "C" int cmb_match_best_device(cmb_index* idx, const cmb_strategy* st, uin
             HIPCHK(hipMemcpy(dIds.p, ids.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
             HIPCHK(hipMemset(dCnt.p + n, 0, sizeof(uint64_t)));
             uint32_t base = 0;
-            for (cmb_batch* c : parts) {
-                if (c->nReads)
-                    hipLaunchKernelGGL(k_best_scan, dim3((c->nReads + 3u) / 4u), dim3(256), 0, 0, c->foffs.p, c->fout.p, c->alnRec.p, c->nReads,
-                                       dMinD.p + base, dMasks.p + base, dCnt.p + base);
-                base += c->nReads;
+            for (const StratumLists& c : parts) {
+                if (c.nReads)
+                    hipLaunchKernelGGL(k_best_scan, dim3((c.nReads + 3u) / 4u), dim3(256), 0, 0, c.foffs, c.fout, c.aln, c.nReads, dMinD.p + base,
+                                       dMasks.p + base, dCnt.p + base);
+                base += c.nReads;
             }
             HIPCHK(hipGetLastError());
             scanExclusive(tmp, dCnt.p, dPoff.p, (size_t)n + 1, (hipStream_t)0);
@@ -3287,11 +3360,11 @@ extern "C" int cmb_match_best_device(cmb_index* idx, const cmb_strategy* st, uin
             if (poolBase + kept >= 0xFFFFFFFFull) return fail(CMB_ERR_UNSUPPORTED, "more than 2^32 occurrences in the strata of one chunk");
             pool.reserve(poolBase + kept);
             base = 0;
-            for (cmb_batch* c : parts) {
-                if (c->nReads && kept)
-                    hipLaunchKernelGGL(k_best_append, dim3((c->nReads + 3u) / 4u), dim3(256), 0, 0, c->foffs.p, c->fout.p, c->alnRec.p, c->alnOps.p,
-                                       c->alnStride, c->nReads, dMinD.p + base, dIds.p + base, dPoff.p + base, pool.at(poolBase));
-                base += c->nReads;
+            for (const StratumLists& c : parts) {
+                if (c.nReads && kept)
+                    hipLaunchKernelGGL(k_best_append, dim3((c.nReads + 3u) / 4u), dim3(256), 0, 0, c.foffs, c.fout, c.aln, c.ops, c.stride, c.nReads,
+                                       dMinD.p + base, dIds.p + base, dPoff.p + base, pool.at(poolBase));
+                base += c.nReads;
             }
             HIPCHK(hipGetLastError());
             pool.n = poolBase + kept;
@@ -3358,8 +3431,8 @@ extern "C" int cmb_match_best_device(cmb_index* idx, const cmb_strategy* st, uin
             }
             HIPCHK(hipDeviceSynchronize()); // (the batch and its lists go away)
             lap("host: strata bookkeeping (k_best_scan, k_best_append, host reads)");
-            guard.b = nullptr;
-            cmb_batch_destroy(b);
+            ds.destroy();
+            ds.destroy = nullptr;
             lap("host: cmb_batch_destroy");
             return CMB_OK;
         };
@@ -3576,6 +3649,67 @@ extern "C" int cmb_match_best_device(cmb_index* idx, const cmb_strategy* st, uin
     } catch (const std::exception& e) {
         return fail(CMB_ERR_DEVICE, e.what());
     }
+}
+} // namespace
+
+extern "C" int cmb_match_best_device(cmb_index* idx, const cmb_strategy* st, uint32_t x, uint32_t min_identity, const char* seqs,
+                                     const uint64_t* offs, uint32_t n_reads, cmb_best** out) {
+    if (!idx || !st || !offs || !out || (!seqs && n_reads)) return fail(CMB_ERR_INVALID, "null argument");
+    if (min_identity < 50 || min_identity > 100) return fail(CMB_ERR_INVALID, "the minimal identity lies between 50 and 100");
+    if (idx->textOnly) return fail(CMB_ERR_INVALID, "this index holds only the text (cmb_index_create_text_only): nothing can be matched on it");
+    const DevStratumRunner run = [&](const char* cat, const uint64_t* o, uint32_t n, uint32_t k, DevStratum& r,
+                                     const std::function<void(const char*)>& lap) -> int {
+        cmb_batch* b = nullptr;
+        int rcode = cmb_batch_create(idx, st, k, cat, o, n, &b);
+        if (rcode) return rcode;
+        r.destroy = [b] { cmb_batch_destroy(b); };
+        cmb_batch_filter_per_strand(b, 1);
+        cmb_batch_want_alignments(b, 1);
+        lap("host: cmb_batch_create");
+        if ((rcode = cmb_batch_run(b))) return rcode;
+        lap("host: cmb_batch_run");
+        for (int i = 0; i < CMB_CNT_MAX; i++) r.cnts[i] = b->cnts[i];
+        std::vector<cmb_batch*> parts;
+        if (b->subs.empty()) parts.push_back(b);
+        else parts = b->subs;
+        for (const cmb_batch* c : parts) {
+            r.parts.push_back(StratumLists{c->nReads, c->foffs.p, c->fout.p, c->alnRec.p, c->alnOps.p, c->alnStride});
+            r.times.insert(r.times.end(), c->times.begin(), c->times.end());
+        }
+        return CMB_OK;
+    };
+    return matchBestDeviceWith(idx, st, true, run, x, min_identity, seqs, offs, n_reads, out);
+}
+// The same on the b-move index: the strata are b-move batches whose final lists stay in HBM (cmb_move_batch_keep_device_lists), the
+// trimming of the host reads uses the text beside the index and counts nothing, as cmb_move_match_best; the result carries the text-only
+// index, so cmb_best_results, cmb_best_host_reads, cmb_best_timings and cmb_best_sam_device work on it as on an FM-index result.
+extern "C" int cmb_move_match_best_device(cmb_move_index* idx, const cmb_strategy* st, uint32_t x, uint32_t min_identity, uint32_t kmer_size,
+                                          const char* seqs, const uint64_t* offs, uint32_t n_reads, cmb_best** out) {
+    if (!idx || !st || !offs || !out || (!seqs && n_reads)) return fail(CMB_ERR_INVALID, "null argument");
+    cmb_index* text = cmb_move_text_index(idx);
+    if (!text) return fail(CMB_ERR_INVALID, "BEST mode on the b-move index needs the text beside it (cmb_move_attach_text)");
+    const DevStratumRunner run = [&](const char* cat, const uint64_t* o, uint32_t n, uint32_t k, DevStratum& r,
+                                     const std::function<void(const char*)>& lap) -> int {
+        cmb_move_batch* b = nullptr;
+        int rcode = cmb_move_batch_create(idx, st, k, kmer_size, cat, o, n, &b);
+        if (rcode) return rcode;
+        r.destroy = [b] { cmb_move_batch_destroy(b); };
+        cmb_move_batch_filter_per_strand(b, 1);
+        if ((rcode = cmb_move_batch_want_alignments(b, 1))) return rcode;
+        if ((rcode = cmb_move_batch_keep_device_lists(b, 1))) return rcode;
+        lap("host: cmb_batch_create");
+        if ((rcode = cmb_move_batch_run(b))) return rcode;
+        lap("host: cmb_batch_run");
+        std::vector<MoveListView> views;
+        if ((rcode = moveBatchListViews(b, views))) return rcode;
+        for (const MoveListView& v : views) {
+            for (int i = 0; i < CMB_CNT_MAX; i++) r.cnts[i] += v.cnts[i];
+            r.parts.push_back(StratumLists{v.nReads, v.goffs, v.occ, (const AlnRec*)v.aln, v.ops, v.stride});
+            r.times.insert(r.times.end(), v.times->begin(), v.times->end());
+        }
+        return CMB_OK;
+    };
+    return matchBestDeviceWith(text, st, false, run, x, min_identity, seqs, offs, n_reads, out);
 }
 // SAM text of a chunk from a device-resident BEST result, written on the device: the text samOfBest (include/columba_amd_best.hpp) puts
 // together from cmb_best_results with the record builders, byte for byte.  The final lists have the layout k_sam_write reads, so only

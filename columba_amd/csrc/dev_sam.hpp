@@ -27,6 +27,7 @@
 //                   does not fit the window is emitted again, clipped, after the window went out — so a line (an XA line of a
 //                   repeat: tens of kilobytes) may be any number of windows long.
 #pragma once
+#include "host_util.hpp" // (SamPlan, SamDeviceBufs)
 #include "kernels.hpp"
 
 namespace cmb {
@@ -34,15 +35,6 @@ namespace cmb {
 constexpr uint32_t SAM_WIN = 8192;           // bytes of text a wavefront assembles in LDS before it stores them
 constexpr uint32_t SAM_READS_PER_WAVE = 16;  // consecutive reads per wavefront of k_sam_write
 constexpr uint32_t SAM_NOTHING = 0, SAM_UNMAPPED = 1, SAM_MAPPED = 2, SAM_HOST = 3;
-
-struct SamPlan { // per read (32 bytes)
-    uint32_t kind;    // SAM_*
-    uint32_t primary; // index of the primary among the read's occurrences
-    uint32_t minScore, nHits;
-    uint32_t idLen; // cleaned identifier: raw[1, idLen + 1)
-    uint32_t pad;
-    uint64_t sideOff; // SAM_HOST: where the read's text lies in the side buffer
-};
 
 struct SamCtx {
     const uint8_t* reads; // raw read characters of the sub-batch

@@ -125,4 +125,57 @@ struct Timer {
     }
 };
 
+struct SamPlan { // per read (32 bytes; dev_sam.hpp)
+    uint32_t kind;    // SAM_*
+    uint32_t primary; // index of the primary among the read's occurrences
+    uint32_t minScore, nHits;
+    uint32_t idLen; // cleaned identifier: raw[1, idLen + 1)
+    uint32_t pad;
+    uint64_t sideOff; // SAM_HOST: where the read's text lies in the side buffer
+};
+// What the device SAM driver (columba_amd.hip: samUpload, samSplice, samScan, samWrite) keeps in HBM for one (sub-)batch or one BEST result:
+// the chunk's packed identifiers, qualities and sequence names with their offsets, the plan, length and position of every read in the
+// text, the text of the reads the host formatted with its offsets and read numbers, the text itself (the scan's scratch is the owner's)
+struct SamDeviceBufs {
+    DevBuf<uint8_t> ids, quals, names, side, text;
+    DevBuf<uint64_t> idOffs, qualOffs, nameOffs, len, offs, sideOffs;
+    DevBuf<SamPlan> plan;
+    DevBuf<uint32_t> sideReads;
+};
+// ... and what a b-move (sub-)batch owns for that driver (cmb_move_batch_sam_device): its buffers, the list of host-formatted reads, the
+// scan's scratch, and — in the first part — the finished text of the whole batch in page-locked memory
+struct MoveSamBufs {
+    SamDeviceBufs sam;
+    DevBuf<uint32_t> hostList;
+    DevBuf<uint8_t> scanTmp;
+    PinnedBuf<char> samOut;
+};
+// The final lists a b-move (sub-)batch keeps in HBM for its whole chunk (cmb_move_batch_keep_device_lists), as columba_amd.hip's SAM
+// driver and strata bookkeeping read them (dev_sam.hpp: SamCtx; dev_best.hpp: k_best_scan / k_best_append), beside the host copies the
+// host-formatted reads are taken from.  One view per part, in read order (move_backend.hip: moveBatchListViews).
+struct MoveListView {
+    uint32_t nReads = 0, k = 0;
+    int metric = 1;
+    const uint8_t* reads = nullptr; // device: raw read characters of the part, and their offsets
+    const uint64_t* offs = nullptr;
+    const uint64_t* goffs = nullptr; // device: first record of every filter group, groupStride groups per read
+    uint32_t groupStride = 1;
+    const uint4* occ = nullptr; // device: {begin, end, distance, strand}
+    const uint4* aln = nullptr; //         AlnRec {seqId, seqBegin, nOps, spans}
+    const uint16_t* ops = nullptr; //      CIGAR runs at `stride`, stored end to begin
+    uint32_t stride = 0;
+    uint64_t nOcc = 0;
+    hipStream_t stream = nullptr;
+    // host: read offsets of the part (from 0), occurrences as {begin, end (64 bits), distance, strand} of 24 bytes with their offsets per
+    // read, AlnRec and CIGAR runs as on the device
+    const uint64_t* hostOffs = nullptr;
+    const void* hOcc = nullptr;
+    const uint64_t* hOccOffs = nullptr;
+    const uint4* hAln = nullptr;
+    const uint16_t* hOps = nullptr;
+    const uint64_t* cnts = nullptr; // counters and kernel times of the part's run
+    const std::vector<KernelTime>* times = nullptr;
+    MoveSamBufs* samBufs = nullptr;
+};
+
 } // namespace cmb

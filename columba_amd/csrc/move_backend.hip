@@ -696,6 +696,34 @@ struct cmb_move_batch {
     DevBuf<uint16_t> alnOps;
     std::vector<uint4> hAlnRec; // {seqId, seqBegin, nOps, spans} per occurrence
     std::vector<uint16_t> hAlnOps;
+    // the same lists of the WHOLE chunk in HBM (cmb_move_batch_keep_device_lists): occ32 / alnRec / alnOps above are a slice's and are
+    // reused by the next one; with the lists kept, k_mvs_occ32 and k_cigar write a slice's records straight behind those of the slices
+    // before it (keepN records so far; the arrays grow with a copy of what they hold), and keepOff holds the group offsets of every
+    // read — one group per read, or two with every strand filtered by itself — rebased to the chunk (k_mvs_keep_offsets)
+    bool keepLists = false;
+    DevBuf<uint4> keepOcc, keepAln;
+    DevBuf<uint16_t> keepOps;
+    DevBuf<uint64_t> keepOff;
+    uint64_t keepN = 0, keepCap = 0;
+    uint32_t keepStride = 1; // groups per read of the last run
+    MoveSamBufs samBufs; // (what the SAM driver keeps with this part: cmb_move_batch_sam_device, columba_amd.hip)
+    void keepReserve(uint64_t want, hipStream_t s) {
+        if (want <= keepCap) return;
+        const uint64_t c = want + want / 2 + 4096;
+        DevBuf<uint4> o, a;
+        DevBuf<uint16_t> p;
+        o.alloc(c), a.alloc(c), p.alloc(c * alnStride);
+        if (keepN) {
+            HIPCHK(hipMemcpyAsync(o.p, keepOcc.p, keepN * sizeof(uint4), hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(a.p, keepAln.p, keepN * sizeof(uint4), hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(p.p, keepOps.p, keepN * alnStride * sizeof(uint16_t), hipMemcpyDeviceToDevice, s));
+        }
+        HIPCHK(hipStreamSynchronize(s)); // (the old arrays are freed below)
+        std::swap(keepOcc.p, o.p), std::swap(keepOcc.n, o.n);
+        std::swap(keepAln.p, a.p), std::swap(keepAln.n, a.n);
+        std::swap(keepOps.p, p.p), std::swap(keepOps.n, p.n);
+        keepCap = c;
+    }
     // results
     MvHostVec<cmb_move_occ> occs;
     std::vector<uint64_t> occOffs;
@@ -898,6 +926,19 @@ static int moveBatchRunOne(cmb_move_batch* b) {
     b->hAlnRec.clear();
     b->hAlnOps.clear();
     b->alnStride = 2u * b->k + 3u;
+    b->keepN = 0; // (a new run starts the kept lists empty; their capacity stays)
+    if (b->keepLists) {
+        try {
+            HIPCHK(hipSetDevice(b->ix->device));
+            b->keepStride = b->perStrand ? 2u : 1u;
+            const size_t nOff = (size_t)b->keepStride * b->nReads + 1;
+            if (b->keepOff.n < nOff || !b->keepOff.p) b->keepOff.alloc(nOff);
+            HIPCHK(hipMemsetAsync(b->keepOff.p, 0, nOff * sizeof(uint64_t), b->stream));
+            HIPCHK(hipStreamSynchronize(b->stream));
+        } catch (const std::exception& e) {
+            return failWith(CMB_ERR_DEVICE, e.what());
+        }
+    }
     uint32_t slice = b->k >= 5 ? (1u << 18) : b->k >= 3 ? (1u << 19) : (1u << 20);
     if (getenv("CMB_MOVE_SLICE")) slice = (uint32_t)std::max(1, atoi(getenv("CMB_MOVE_SLICE")));
     if (b->k == 0) slice = b->nReads ? b->nReads : 1;
@@ -949,6 +990,24 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                         b->hAlnRec[i] = make_uint4(id, (uint32_t)o.begin - sp[id], 1u, o.end > sp[id + 1] ? 1u : 0u);
                     }
                     b->hAlnOps[i * b->alnStride] = (uint16_t)(((o.end - o.begin) << 2) | 0u);
+                }
+                if (b->keepLists) { // the same records into the kept lists (the consumers read a read's first and last group offset only)
+                    b->keepReserve(nOcc, s);
+                    std::vector<uint4> o32(nOcc);
+                    for (uint64_t i = 0; i < nOcc; i++) o32[i] = make_uint4((uint32_t)b->occs[i].begin, (uint32_t)b->occs[i].end, b->occs[i].distance, b->occs[i].strand);
+                    const uint32_t gs = b->keepStride;
+                    std::vector<uint64_t> go((size_t)gs * nReads + 1);
+                    for (uint32_t r = 0; r < nReads; r++)
+                        for (uint32_t g = 0; g < gs; g++) go[(size_t)gs * r + g] = b->occOffs[r];
+                    go[(size_t)gs * nReads] = b->occOffs[nReads];
+                    if (nOcc) {
+                        HIPCHK(hipMemcpyAsync(b->keepOcc.p, o32.data(), nOcc * sizeof(uint4), hipMemcpyHostToDevice, s));
+                        HIPCHK(hipMemcpyAsync(b->keepAln.p, b->hAlnRec.data(), nOcc * sizeof(uint4), hipMemcpyHostToDevice, s));
+                        HIPCHK(hipMemcpyAsync(b->keepOps.p, b->hAlnOps.data(), nOcc * b->alnStride * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+                    }
+                    HIPCHK(hipMemcpyAsync(b->keepOff.p, go.data(), go.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+                    HIPCHK(hipStreamSynchronize(s)); // (the host vectors go out of scope)
+                    b->keepN = nOcc;
                 }
             }
             b->cnts[CMB_CNT_NODE] = c2[0];
@@ -1372,27 +1431,44 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
         HIPCHK(hipGetLastError());
         if (b->wantAln && nOut) { // CIGAR and sequence of every final occurrence: findCIGAR on text[begin, end) (k_cigar)
             tm.begin();
-            if (b->occ32.n < nOut) {
-                const size_t c = nOut + nOut / 4 + 256;
-                b->occ32.alloc(c), b->alnRec.alloc(c), b->occRead.alloc(c), b->alnOps.alloc(c * b->alnStride);
+            uint4 *dOcc = nullptr, *dAln = nullptr;
+            uint16_t* dOps = nullptr;
+            if (b->keepLists) { // in place, behind the records of the slices before this one
+                b->keepReserve(b->keepN + nOut, s);
+                if (b->occRead.n < nOut) b->occRead.alloc(nOut + nOut / 4 + 256);
+                dOcc = b->keepOcc.p + b->keepN, dAln = b->keepAln.p + b->keepN, dOps = b->keepOps.p + b->keepN * b->alnStride;
+            } else {
+                if (b->occ32.n < nOut) {
+                    const size_t c = nOut + nOut / 4 + 256;
+                    b->occ32.alloc(c), b->alnRec.alloc(c), b->occRead.alloc(c), b->alnOps.alloc(c * b->alnStride);
+                }
+                dOcc = b->occ32.p, dAln = b->alnRec.p, dOps = b->alnOps.p;
             }
-            hipLaunchKernelGGL(k_mvs_occ32, dim3(gridFor(nReads)), dim3(256), 0, s, b->out.p, b->readOff.p, nReads, b->occ32.p, b->occRead.p);
+            hipLaunchKernelGGL(k_mvs_occ32, dim3(gridFor(nReads)), dim3(256), 0, s, b->out.p, b->readOff.p, nReads, dOcc, b->occRead.p);
             uint32_t flagBefore = 0;
             HIPCHK(hipMemcpyAsync(&flagBefore, b->cnt.p + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
             const int rc = cmb::moveCigarsOnText(ix->textIndex, s, dOffs, b->G.p, b->gw, nReads, b->maxLen, b->k, b->metric == CMB_METRIC_EDIT ? 0 : 1,
-                                                 b->occ32.p, b->occRead.p, nOut, b->alnRec.p, b->alnOps.p, b->alnStride, b->cnt.p + 3);
+                                                 dOcc, b->occRead.p, nOut, dAln, dOps, b->alnStride, b->cnt.p + 3);
             if (rc != CMB_OK) return rc;
             const size_t base = b->hAlnRec.size();
             b->hAlnRec.resize(base + nOut);
             b->hAlnOps.resize((base + nOut) * b->alnStride);
-            HIPCHK(hipMemcpyAsync(b->hAlnRec.data() + base, b->alnRec.p, nOut * sizeof(uint4), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(b->hAlnOps.data() + base * b->alnStride, b->alnOps.p, nOut * b->alnStride * sizeof(uint16_t), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(b->hAlnRec.data() + base, dAln, nOut * sizeof(uint4), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(b->hAlnOps.data() + base * b->alnStride, dOps, nOut * b->alnStride * sizeof(uint16_t), hipMemcpyDeviceToHost, s));
             uint32_t flagAfter = 0;
             HIPCHK(hipMemcpyAsync(&flagAfter, b->cnt.p + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
             tm.end("k_cigar");
             if ((flagAfter & ~flagBefore) & FLAG_CAPACITY)
                 return failWith(CMB_ERR_INTERNAL, "a CIGAR traceback left the band or an occurrence is not an alignment within its distance");
+        }
+        if (b->keepLists) { // the slice's group offsets behind those of the slices before it
+            const uint32_t gs = b->keepStride;
+            const uint64_t* src = !totalPos ? nullptr : gs == 2 ? b->rsOff.p : b->readOff.p;
+            hipLaunchKernelGGL(k_mvs_keep_offsets, dim3(gridFor((uint64_t)gs * nReads + 1)), dim3(256), 0, s, src, (uint64_t)gs * nReads, b->keepN,
+                               b->keepOff.p + (size_t)gs * lo);
+            HIPCHK(hipGetLastError());
+            b->keepN += nOut;
         }
         uint32_t hb = 0;
         HIPCHK(hipMemcpyAsync(&hb, b->bad.p, sizeof(hb), hipMemcpyDeviceToHost, s));
@@ -1466,9 +1542,45 @@ extern "C" int cmb_move_batch_want_alignments(cmb_move_batch* b, int on) {
     if (!b) return failWith(CMB_ERR_INVALID, "null argument");
     if (on && !b->ix->textIndex) return failWith(CMB_ERR_INVALID, "alignments need the text beside the index (cmb_move_attach_text)");
     b->wantAln = on != 0;
-    for (cmb_move_batch* c : b->subs) c->wantAln = on != 0;
+    if (!on) b->keepLists = false; // (the kept lists hold alignments)
+    for (cmb_move_batch* c : b->subs) c->wantAln = on != 0, c->keepLists = c->keepLists && on;
     return CMB_OK;
 }
+// The final lists of the whole chunk stay in HBM as well (what cmb_move_batch_sam_device and cmb_move_match_best_device read); before
+// cmb_move_batch_run, after cmb_move_batch_want_alignments
+extern "C" int cmb_move_batch_keep_device_lists(cmb_move_batch* b, int on) {
+    if (!b) return failWith(CMB_ERR_INVALID, "null argument");
+    if (on && !b->wantAln) return failWith(CMB_ERR_INVALID, "the kept lists hold alignments: ask for them first (cmb_move_batch_want_alignments)");
+    b->keepLists = on != 0;
+    for (cmb_move_batch* c : b->subs) c->keepLists = on != 0;
+    return CMB_OK;
+}
+namespace cmb {
+// one view per part of a batch that has run with its lists kept (columba_amd.hip: the SAM driver, the strata of BEST mode)
+int moveBatchListViews(cmb_move_batch* b, std::vector<MoveListView>& out) {
+    if (!b) return failWith(CMB_ERR_INVALID, "null argument");
+    if (!b->done) return failWith(CMB_ERR_INVALID, "batch has not been run");
+    if (!b->keepLists || !b->wantAln) return failWith(CMB_ERR_INVALID, "the lists were not kept on the device (cmb_move_batch_keep_device_lists)");
+    std::vector<cmb_move_batch*> parts = b->subs;
+    if (parts.empty()) parts.push_back(b);
+    out.clear();
+    for (cmb_move_batch* c : parts) {
+        MoveListView v;
+        v.nReads = c->nReads, v.k = c->k, v.metric = c->metric;
+        v.reads = c->reads.p, v.offs = c->offs.p;
+        v.goffs = c->keepOff.p, v.groupStride = c->keepStride;
+        v.occ = c->keepOcc.p, v.aln = c->keepAln.p, v.ops = c->keepOps.p, v.stride = c->alnStride, v.nOcc = c->keepN;
+        v.stream = c->stream;
+        v.hostOffs = c->hostOffs.data();
+        v.hOcc = c->occs.data(), v.hOccOffs = c->occOffs.data(), v.hAln = c->hAlnRec.data(), v.hOps = c->hAlnOps.data();
+        v.cnts = c->cnts, v.times = &c->times;
+        v.samBufs = &c->samBufs;
+        out.push_back(v);
+    }
+    return CMB_OK;
+}
+cmb_index* moveTextIndexOfBatch(const cmb_move_batch* b) { return b ? b->ix->textIndex : nullptr; }
+} // namespace cmb
 // as cmb_batch_alignments: one record per occurrence of cmb_move_batch_results, CIGAR runs (length << 2 | op, op 0 M / 1 I / 2 D) in a pool
 extern "C" int cmb_move_batch_alignments(const cmb_move_batch* b, cmb_aln* out, uint64_t cap, uint16_t* cigar_ops, uint64_t ops_cap, uint64_t* n_ops) {
     if (!b) return failWith(CMB_ERR_INVALID, "null argument");

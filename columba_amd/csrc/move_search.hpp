@@ -1822,4 +1822,12 @@ __global__ void k_mvs_occ32(const MoveOccOut* __restrict__ occ, const uint64_t* 
         }
 }
 
+// The group offsets of a slice behind those of the slices before it (cmb_move_batch_keep_device_lists): dst[i] = base + src[i] for the
+// nGroups + 1 offsets of the slice — its first equals the last of the slice before, its last is where the next slice goes on.
+// src == nullptr: a slice without any text position (every group is empty).
+__global__ void k_mvs_keep_offsets(const uint64_t* __restrict__ src, uint64_t nGroups, uint64_t base, uint64_t* __restrict__ dst) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= nGroups; i += (uint64_t)gridDim.x * blockDim.x)
+        dst[i] = base + (src ? src[i] : 0ull);
+}
+
 } // namespace cmb

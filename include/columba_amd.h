@@ -290,7 +290,7 @@ void cmb_best_destroy(cmb_best* r);
  * sequence, begin, order found) with a rocPRIM merge sort and deduplicated on the device.  The result's final lists live in HBM
  * (occurrences as uint4, sequence assignment, CIGAR runs at a fixed stride, 64-bit offsets, best and n_hits per read);
  * cmb_best_sizes / cmb_best_results work on the handle unchanged and download on first use — arrays and counters are bit-identical
- * to cmb_match_best's.  The index must outlive the handle.  FM-index flavour only (cmb_move_match_best keeps the host path).
+ * to cmb_match_best's.  The index must outlive the handle.  (The b-move flavour: cmb_move_match_best_device.)
  * HOST READS: an occurrence that runs over the end of its sequence is, under edit distance, trimmed and verified again
  * (IndexInterface::findSeqName, src/indexinterface.cpp:833-899) and thereby changes its distance.  A read goes to matchBestWith's
  * host bookkeeping at the first stratum in which it keeps such an occurrence, takes its pool records along, still runs exactly the
@@ -453,9 +453,8 @@ int64_t cmb_batch_sam(const cmb_batch* b, const char* seqs, const char* const* r
  * the text at their place.  Preconditions and error codes as cmb_batch_sam (run, alignments requested).  Composite batches format
  * every sub-batch on its own stream; the text is in read order.  MAPQ (TextOcc::getMapQ, src/indexhelpers.h:378-388) comes from
  * a table on the device: 60, 3, 2, then 1 up to nine and 0 from ten occurrences of minimal distance on.
- * ALL mode, single-end reads, FM-index batches only: BEST mode has cmb_best_sam_device (below) on a result of
- * cmb_match_best_device; results of cmb_match_best, read pairs (cmb_pair_sam) and the b-move flavour (cmb_sam_chunk on caller-held
- * records) keep the host formatter. */
+ * ALL mode, single-end reads, FM-index batches: BEST mode has cmb_best_sam_device (below) on a result of cmb_match_best_device, the
+ * b-move flavour cmb_move_batch_sam_device; results of cmb_match_best and read pairs (cmb_pair_sam) keep the host formatter. */
 typedef struct {
     const char* seqs;
     const char* ids;
@@ -692,6 +691,31 @@ int cmb_move_batch_filter_per_strand(cmb_move_batch* b, int on);
  * read text[begin, end).  Cut-off: min(13, what the strategy has schemes for, len * (100 - min_identity) / 100), as on the FM-index.  Results through cmb_best_sizes / cmb_best_results / cmb_best_free. */
 int cmb_move_match_best(cmb_move_index* idx, const cmb_strategy* st, uint32_t x, uint32_t min_identity, uint32_t kmer_size,
                         const char* seqs, const uint64_t* offs, uint32_t n_reads, cmb_best** out);
+/* The FINAL LISTS of a b-move batch kept in HBM for the whole chunk.  A large chunk is matched in slices that reuse one set of buffers,
+ * so without this call only the host copies (cmb_move_batch_results / cmb_move_batch_alignments) outlive a slice.  With it every
+ * (sub-)batch also keeps, for the chunk, the occurrences as {begin, end, distance, strand} in 32 bits, the sequence assignment, the
+ * CIGAR runs at a fixed stride and 64-bit group offsets per read (two groups per read with cmb_move_batch_filter_per_strand): each
+ * slice writes its records behind those of the slices before it, the arrays grow with a copy of what they hold, a new run starts them
+ * empty.  The host copies and every other result are unchanged.  Call before cmb_move_batch_run and after
+ * cmb_move_batch_want_alignments; CMB_ERR_INVALID without requested alignments (and therefore without cmb_move_attach_text). */
+int cmb_move_batch_keep_device_lists(cmb_move_batch* b, int on);
+/* cmb_batch_sam_device for a b-move batch: the SAM text of a single-end chunk in ALL mode (matchApproxAllMap ->
+ * SearchStrategy::generateOutputSingleEnd, src/searchstrategy.cpp:530-533, :1824-1902; generateSE_SAM / generateSE_SAM_XATag,
+ * src/searchstrategy.h:1612-1641) written on the device from the kept lists, byte for byte what cmb_sam_chunk returns for the batch's
+ * host records.  `in`, *text, *length, *host_reads as for cmb_batch_sam_device; the reads with an occurrence over the end of its
+ * sequence are formatted on the host with the text beside the index (IndexInterface::findSeqName, src/indexinterface.cpp:833-899) and
+ * spliced in.  Every part of a composite batch is formatted on its own stream; the text is in read order and stays valid until the
+ * next call on the batch.  CMB_ERR_INVALID: NULL arguments, a batch that has not run, lists that were not kept. */
+int cmb_move_batch_sam_device(cmb_move_batch* b, const cmb_sam_inputs* in, int unmapped_records, int xa_tag, const char** text,
+                              uint64_t* length, uint64_t* host_reads);
+/* cmb_match_best_device on the b-move index (SearchStrategy::matchApproxBestPlusX, src/searchstrategy.cpp:623-746; checkAlignments,
+ * :536-571; processSeq, :791-812; combineOccVectors, :573-620): the strata are b-move batches with kept lists, the bookkeeping is
+ * cmb_match_best_device's, the trimming of the host reads is cmb_move_match_best's (checkTrimmedMatch, src/indexinterface.cpp:722-796:
+ * no counters).  Arrays and counters equal cmb_move_match_best's bit for bit.  The result lives on the device and refers to the
+ * text-only index of idx, which must outlive it: cmb_best_sizes / cmb_best_results / cmb_best_host_reads / cmb_best_timings /
+ * cmb_best_sam_device work on it as on a result of cmb_match_best_device.  Needs cmb_move_attach_text. */
+int cmb_move_match_best_device(cmb_move_index* idx, const cmb_strategy* st, uint32_t x, uint32_t min_identity, uint32_t kmer_size,
+                               const char* seqs, const uint64_t* offs, uint32_t n_reads, cmb_best** out);
 /* device time (ms, HIP events) of the calling thread's last cmb_move_match_exact: [0] the backward extension of all reads,
  * [1] the prefix sum of the widths, [2] locate + occurrence records */
 int cmb_move_last_timings(float* ms, uint32_t n);

@@ -27,6 +27,7 @@
 #include "columba_amd_best.hpp"
 
 #include <cstdint>
+#include <cstdlib>
 #include <fstream>
 #include <map>
 #include <stdexcept>
@@ -236,9 +237,39 @@ class SearchStrategy {
     }
     SearchStrategy(const SearchStrategy&) = delete;
     ~SearchStrategy() { cmb_strategy_destroy(h); }
+    // identifiers, qualities and sequence names packed as cmb_move_batch_sam_device / cmb_best_sam_device take them
+    struct SamPacked {
+        std::string idBuf, qualBuf, nameBuf;
+        std::vector<uint64_t> idOffs, qualOffs, nameOffs;
+        SamPacked(const std::vector<std::string>& ids, const std::vector<std::string>& quals, const std::vector<std::string>& seqNames)
+            : idOffs(ids.size() + 1, 0), qualOffs(quals.size() + 1, 0), nameOffs(seqNames.size() + 1, 0) {
+            for (size_t i = 0; i < ids.size(); i++) idBuf += ids[i], idOffs[i + 1] = idBuf.size();
+            for (size_t i = 0; i < quals.size(); i++) qualBuf += quals[i], qualOffs[i + 1] = qualBuf.size();
+            for (size_t i = 0; i < seqNames.size(); i++) nameBuf += seqNames[i], nameOffs[i + 1] = nameBuf.size();
+        }
+        cmb_sam_inputs inputs(const std::string& seqs) const {
+            return cmb_sam_inputs{seqs.data(),     idBuf.data(),   idOffs.data(),   qualBuf.data(),
+                                  qualOffs.data(), nameBuf.data(), nameOffs.data(), (uint32_t)(nameOffs.size() - 1)};
+        }
+    };
+    static bool envSet(const char* name) {
+        const char* e = getenv(name);
+        return e && atoi(e) != 0;
+    }
+    // Which path writes the text: CMB_SAM_HOST=1 / CMB_BEST_HOST=1 ask for the host paths, CMB_SAM_DEVICE=1 / CMB_BEST_DEVICE=1 for the
+    // device paths (as columba_align's switches for the FM-index flavour); without either, DEVICE_DEFAULT.  The device paths of this
+    // flavour have not been measured against the host paths yet, so the default stays on the host paths.
+    static constexpr bool DEVICE_DEFAULT = false;
+    static bool onDevice(const char* hostVar, const char* deviceVar) {
+        if (envSet(hostVar)) return false;
+        if (envSet(deviceVar)) return true;
+        return DEVICE_DEFAULT;
+    }
     // The SAM records of a chunk in ALL mode (generateOutputSingleEnd, searchstrategy.cpp:1824-1902): occurrences, their CIGARs
     // (findCIGAR on text[begin, end) — the matched string of this flavour, indexinterface.h:294-303) and sequence names.  Needs
     // BMove::attachText.  ids / quals as read from the FASTQ file; seqNames: the sequences of the index in text order.
+    // CMB_SAM_DEVICE=1: the text is written on the device from the batch's kept lists (cmb_move_batch_keep_device_lists +
+    // cmb_move_batch_sam_device) instead of by the host formatter (cmb_sam_chunk on the downloaded records).  The text is the same either way.
     std::string samOfChunk(const std::vector<std::string>& ids, const std::vector<std::string>& reads, const std::vector<std::string>& quals,
                            const std::vector<std::string>& seqNames, length_t maxED, int metric = CMB_METRIC_EDIT, bool unmappedRecords = true,
                            bool xaTag = false) {
@@ -252,7 +283,17 @@ class SearchStrategy {
             ~Guard() { cmb_move_batch_destroy(b); }
         } guard{b};
         check(cmb_move_batch_want_alignments(b, 1));
+        const bool onDevice = SearchStrategy::onDevice("CMB_SAM_HOST", "CMB_SAM_DEVICE") && ids.size() == reads.size() && quals.size() == reads.size();
+        if (onDevice) check(cmb_move_batch_keep_device_lists(b, 1));
         check(cmb_move_batch_run(b));
+        if (onDevice) {
+            const SamPacked packed(ids, quals, seqNames);
+            const cmb_sam_inputs in = packed.inputs(buf);
+            const char* text = nullptr;
+            uint64_t length = 0;
+            check(cmb_move_batch_sam_device(b, &in, unmappedRecords, xaTag, &text, &length, nullptr));
+            return std::string(text, (size_t)length);
+        }
         uint64_t n = 0, nOps = 0;
         check(cmb_move_batch_result_size(b, &n));
         std::vector<cmb_move_occ> occ(n ? n : 1);
@@ -278,7 +319,8 @@ class SearchStrategy {
         return out;
     }
     // The SAM records of a chunk in BEST (+x strata) mode — the reference's default, `-a best` (matchApproxBestPlusX,
-    // searchstrategy.cpp:714-746, + generateSE_SAM): cmb_move_match_best.  Needs BMove::attachText.
+    // searchstrategy.cpp:714-746, + generateSE_SAM): cmb_move_match_best + samOfBest, or with CMB_BEST_DEVICE=1 strata bookkeeping and SAM
+    // text on the device (cmb_move_match_best_device + cmb_best_sam_device).  Needs BMove::attachText.
     struct BestRecord {
         std::string seqID, qual;
     };
@@ -290,6 +332,23 @@ class SearchStrategy {
         std::vector<BestRecord> recs(reads.size());
         for (size_t i = 0; i < reads.size(); i++) buf += reads[i], off[i + 1] = buf.size(), recs[i] = BestRecord{ids[i], quals[i]};
         cmb_best* r = nullptr;
+        if (onDevice("CMB_BEST_HOST", "CMB_BEST_DEVICE")) {
+            const uint32_t nReads = (uint32_t)reads.size();
+            check(cmb_move_match_best_device(index.handle(), h, x, minIdentity, kmerSize, buf.data(), off.data(), nReads, &r));
+            struct Guard {
+                cmb_best* r;
+                ~Guard() { cmb_best_destroy(r); }
+            } guard{r};
+            const SamPacked packed(ids, quals, seqNames);
+            const cmb_sam_inputs in = packed.inputs(buf);
+            const char* text = nullptr;
+            uint64_t length = 0;
+            check(cmb_best_sam_device(r, &in, unmappedRecords, xaTag, &text, &length, nullptr));
+            std::vector<uint64_t> oo((size_t)nReads + 1, 0);
+            check(cmb_best_results(r, nullptr, nullptr, 0, nullptr, 0, oo.data(), nullptr, nullptr, nullptr)); // (the offsets: nothing is downloaded)
+            for (uint32_t i = 0; i < nReads; i++) nMapped += oo[i + 1] != oo[i];
+            return std::string(text, (size_t)length);
+        }
         check(cmb_move_match_best(index.handle(), h, x, minIdentity, kmerSize, buf.data(), off.data(), (uint32_t)reads.size(), &r));
         return samOfBest(r, buf, off, recs, seqNames, unmappedRecords, xaTag, nMapped);
     }

@@ -16,6 +16,9 @@ partitioning, x = 0, identity 95.
     python tools/best_rate.py --align 200000 --out ...      also columba_align end to end on a FASTQ of that many reads,
                                                             CMB_BEST_HOST=1 against CMB_BEST_DEVICE=1, alternating
     rocprofv3 --kernel-trace --stats -d DIR -o best -- python tools/best_rate.py --reps 1 --device-only   (a run of its own)
+    python tools/best_rate.py --rlc --out profiles/move_best_device_rate.json
+                                                            the same arms on the b-move backend (cmb_move_match_best against
+                                                            cmb_move_match_best_device) on a `bench.py --config rlc` style text
 """
 import argparse
 import ctypes as C
@@ -91,6 +94,11 @@ def main():
     ap.add_argument("--device-only", action="store_true", help="leave the host path out (profiling runs)")
     ap.add_argument("--align", type=int, default=0, help="also run columba_align end to end on a FASTQ of this many reads")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--rlc", action="store_true", help="the b-move backend on a pan-genome-like text (below 2^32 characters)")
+    ap.add_argument("--haplotypes", type=int, default=64)
+    ap.add_argument("--base-mbp", type=float, default=4)
+    ap.add_argument("--snp", type=float, default=0.005)
+    ap.add_argument("--kmer-size", type=int, default=10)
     args = ap.parse_args()
 
     import torch
@@ -98,11 +106,27 @@ def main():
     dev = "cuda:0"
     n = int(args.genome_mbp * 1e6)
     t0 = time.time()
-    g, starts = synth.genome_human_like(n, seed=2025, device=dev)
-    ix = ib.build_index(g, seq_starts=starts, device=dev, with_bwt=False)
-    index = ca.Index(ix, device=0)
-    print(f"[best_rate] index for {n / 1e6:.0f} Mbp, {len(starts) - 1} sequences, built in {time.time() - t0:.1f} s", flush=True)
     R, L = args.reads, args.read_len
+    if args.rlc:
+        from columba_amd import movebuild
+        base = int(args.base_mbp * 1e6)
+        text = movebuild.pangenome(base, args.haplotypes, args.snp, seed=1)
+        mv = movebuild.build_move(text, device=dev, with_locate=False)
+        mv.plcp = movebuild.plcp_gpu(mv)
+        torch.cuda.empty_cache()
+        index = ca.MoveIndex(mv, device=0)
+        n = int(text.shape[0])
+        starts = np.array([min(j * base, n) for j in range(args.haplotypes)] + [n], dtype=np.uint32)
+        index.attach_text(text, starts)
+        print(f"[best_rate] b-move index of {n / 1e6:.1f} Mbp ({args.haplotypes} haplotypes), n/r = {mv.n / mv.runs_fwd:.1f}, built in "
+              f"{time.time() - t0:.1f} s", flush=True)
+        g = torch.from_numpy(text).to(dev)
+        ix = None
+    else:
+        g, starts = synth.genome_human_like(n, seed=2025, device=dev)
+        ix = ib.build_index(g, seq_starts=starts, device=dev, with_bwt=False)
+        index = ca.Index(ix, device=0)
+        print(f"[best_rate] index for {n / 1e6:.0f} Mbp, {len(starts) - 1} sequences, built in {time.time() - t0:.1f} s", flush=True)
     buf, offs = synth.sample_reads_fast(g, R, L, seed=3, device=dev)
     del g
     torch.cuda.empty_cache()
@@ -115,9 +139,12 @@ def main():
     st = ca.SearchStrategy("columba", "edit", "dynamic")
     lib = ca.lib()
 
+    host_fn, dev_fn = (lib.cmb_move_match_best, lib.cmb_move_match_best_device) if args.rlc else (lib.cmb_match_best, lib.cmb_match_best_device)
+
     def match(fn):
         h = C.c_void_p()
-        rc = fn(index.h, st.h, args.x, args.identity, ca._p(buf), ca._p(offs), R, C.byref(h))
+        extra = (args.kmer_size,) if args.rlc else ()
+        rc = fn(index.h, st.h, args.x, args.identity, *extra, ca._p(buf), ca._p(offs), R, C.byref(h))
         assert rc == 0, lib.cmb_last_error()
         return h
 
@@ -131,7 +158,7 @@ def main():
 
     def arm_sam():
         t = time.perf_counter()
-        h = match(lib.cmb_match_best_device)
+        h = match(dev_fn)
         t1 = time.perf_counter()
         inp = ca.SamInputs(ca._p(buf), ca._p(pi[0]), ca._p(pi[1]), ca._p(quals), ca._p(qoffs), ca._p(pn[0]), ca._p(pn[1]), len(names))
         text, length, host_reads = C.c_void_p(), C.c_uint64(), C.c_uint64()
@@ -152,11 +179,11 @@ def main():
         keep = rep >= args.warmup
         ra = None
         if not args.device_only:
-            h, ra, dt, _ = arm_results(lib.cmb_match_best)
+            h, ra, dt, _ = arm_results(host_fn)
             lib.cmb_best_destroy(h)
             if keep:
                 a.append(dt)
-        h, rb, dt, dm = arm_results(lib.cmb_match_best_device)
+        h, rb, dt, dm = arm_results(dev_fn)
         if keep:
             b.append(dt), b_match.append(dm)
             parts = timings(h)
@@ -172,7 +199,7 @@ def main():
             c.append(dt), c_sam.append(ds)
         print(f"[best_rate] repetition {rep}: a {a[-1] if a and keep else float('nan'):.1f} ms, b {b[-1] if keep else float('nan'):.1f} ms, "
               f"c {c[-1] if keep else float('nan'):.1f} ms", flush=True)
-    res = {"tool": "best_rate", "genome_mbp": n / 1e6, "reads": R, "read_len": L, "x": args.x, "identity": args.identity, "reps": args.reps,
+    res = {"tool": "best_rate --rlc" if args.rlc else "best_rate", "genome_mbp": n / 1e6, "reads": R, "read_len": L, "x": args.x, "identity": args.identity, "reps": args.reps,
            "occurrences": n_occ, "sam_text_bytes": text_bytes, "host_reads": host_reads, "a_equals_b": equal,
            "result_bytes": int(n_occ * (16 + 24) + 16 * (R + 1)),
            "b_match_best_device_plus_results": _stats(b), "b_match_call_alone": _stats(b_match),
@@ -182,7 +209,7 @@ def main():
         res["a_match_best_plus_results"] = _stats(a)
         res["b_below_a_by_more_than_either_spread"] = _faster(res["a_match_best_plus_results"], res["b_match_best_device_plus_results"])
         res["c_below_a_by_more_than_either_spread"] = _faster(res["a_match_best_plus_results"], res["c_match_best_device_plus_sam_device"])
-    if args.align:
+    if args.align and not args.rlc:
         with tempfile.TemporaryDirectory() as tmp:
             res["columba_align"] = _align(ix, buf, offs, min(args.align, R), L, 3, tmp)
     else:
