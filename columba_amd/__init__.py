@@ -77,7 +77,7 @@ def build_library(force: bool = False) -> str:
              # (the b-move backend shares the event handler, the matrix and the wave helpers with the matcher)
              "move_backend.hip": [f for f in os.listdir(csrc) if not f.startswith("pair_") and f != "columba_amd.hip"],
              "pair_sam.hip": ["pair_sam.hip", "host_sam.hpp"],
-             "pair_best.hip": ["pair_best.hip", "host_sam.hpp"]}
+             "pair_best.hip": ["pair_best.hip", "host_best.hpp", "host_sam.hpp"]}
     every = [os.path.join(csrc, f) for f in os.listdir(csrc)] + [header]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in every):
         return LIB_PATH  # (the objects are build scratch: only the library travels to the GPU box)

@@ -1,5 +1,6 @@
 // C-ABI implementation (include/columba_amd.h) on top of the HIP kernels.  gfx950 only.
 #include "../../include/columba_amd.h"
+#include "host_best.hpp"
 #include "host_sam.hpp"
 #include "host_schemes.hpp"
 #include "host_util.hpp"
@@ -2396,18 +2397,6 @@ extern "C" int cmb_cigar_windows(cmb_index* idx, const char* pattern, uint32_t p
 
 namespace {
 
-struct BestOcc {
-    cmb_occ occ;
-    cmb_aln aln;
-    std::vector<uint16_t> ops;
-};
-struct BestRead {
-    uint32_t len = 0, cutOff = 0, best = 0, k = 0, prevK = 0, maxED = 0;
-    bool bestFound = false, finished = false;
-    std::vector<std::vector<BestOcc>> ov[2];  // [strand][distance]
-    std::vector<uint8_t> processed[2];        // [strand][distance]
-};
-
 // IndexInterface::findSeqName for an occurrence that runs over the end of its sequence (indexinterface.cpp:833-899):
 // trim to the sequence it mostly lies in and verify again inside that window (edit distance only)
 static bool trimOccurrence(cmb_index* idx, const std::string& seq, uint32_t largestStratum, int metric, BestOcc& o,
@@ -2935,205 +2924,84 @@ struct StratumOut {
 };
 typedef std::function<int(const char* cat, const uint64_t* o, uint32_t n, uint32_t k, StratumOut& r)> StratumRunner;
 
+// The strata loop's store (host_best.hpp) with every read's occurrences in host vectors.
 // idx: the index whose text and sequence starts serve the trimming (the FM-index itself, or the text beside a b-move index);
-// deviceCap: the largest distance the flavour's device path runs; trimCounters: the in-text counters of a trimming count
-// (FM-index flavour: inTextVerificationOneString; the b-move flavour's checkTrimmedMatch counts nothing, indexinterface.cpp:722-796)
+// trimCounters: the in-text counters of a trimming count (FM-index flavour: inTextVerificationOneString; the b-move flavour's
+// checkTrimmedMatch counts nothing, indexinterface.cpp:722-796)
+struct BestHostStore {
+    cmb_index* idx;
+    const cmb_strategy* st;
+    bool trimCounters;
+    const StratumRunner& runOn;
+    const char* seqs;
+    const uint64_t* offs;
+    cmb_best* R;
+    std::vector<BestCursor> cur;
+    std::vector<BestHostRead> rd;
+
+    BestCursor& cursor(uint32_t i) { return cur[i]; }
+    bool nonEmpty(uint32_t i, int s2, uint32_t d) const { return rd[i].nonEmpty(s2, d); }
+    void check(uint32_t i, int s2, uint32_t l, uint32_t cutOffTrim) {
+        bestCheckHost(rd[i], cur[i].best, s2, l, cutOffTrim, [&](const std::string& seq, BestOcc& o, uint32_t cutOff) {
+            return trimOccurrence(idx, seq, cutOff, st->metric, o, trimCounters ? R->cnts : nullptr);
+        });
+    }
+    // one stratum for a set of reads: ALL-mode search of both strands at distance k, every strand filtered by itself
+    int run(const std::vector<uint32_t>& ids, uint32_t k) {
+        std::string cat;
+        std::vector<uint64_t> o;
+        bestGatherReads(seqs, offs, ids, cat, o);
+        StratumOut so;
+        if (const int rcode = runOn(cat.data(), o.data(), (uint32_t)ids.size(), k, so)) return rcode;
+        for (int i = 0; i < CMB_CNT_MAX; i++) R->cnts[i] += so.cnt[i];
+        for (size_t j = 0; j < ids.size(); j++) {
+            const uint32_t minD = std::min<uint32_t>(cur[ids[j]].proc, k); // processSeq (:791-812): the first distance not processed yet
+            for (uint64_t q2 = so.oo[j]; q2 < so.oo[j + 1]; q2++) {
+                const cmb_aln& a = so.al[q2];
+                if (so.oc[q2].distance >= minD)
+                    rd[ids[j]].add(BestOcc{so.oc[q2], a, std::vector<uint16_t>(so.ops.begin() + a.cigar_off, so.ops.begin() + a.cigar_off + a.cigar_len)});
+            }
+        }
+        return CMB_OK;
+    }
+};
+
+// deviceCap: the largest distance the flavour's device path runs
 int matchBestWith(cmb_index* idx, const cmb_strategy* st, uint32_t deviceCap, bool trimCounters, const StratumRunner& runOn, uint32_t x,
                   uint32_t min_identity, const char* seqs, const uint64_t* offs, uint32_t n_reads, cmb_best** out) {
     if (!idx || !st || !offs || !out || (!seqs && n_reads)) return fail(CMB_ERR_INVALID, "null argument");
     if (min_identity < 50 || min_identity > 100) return fail(CMB_ERR_INVALID, "the minimal identity lies between 50 and 100");
     try {
-        // getMaxSupportedDistanceForBestMapping (searchstrategy.h:1864, :2744): the largest k such that 1..k all have a
-        // scheme — and that this device runs (deviceCap)
-        uint32_t maxSupported = 0;
-        while (st->schemes.count(maxSupported + 1) && !st->schemes.at(maxSupported + 1).empty()) maxSupported++;
-        maxSupported = std::min<uint32_t>(maxSupported, deviceCap);
+        const uint32_t maxSupported = bestMaxSupported(st->schemes, deviceCap);
         std::unique_ptr<cmb_best> R(new cmb_best());
         memset(R->cnts, 0, sizeof(R->cnts));
-        std::vector<BestRead> rd(n_reads);
-        std::vector<std::string> fw(n_reads), rc(n_reads);
+        BestHostStore S{idx, st, trimCounters, runOn, seqs, offs, R.get(), std::vector<BestCursor>(n_reads), std::vector<BestHostRead>(n_reads)};
         for (uint32_t i = 0; i < n_reads; i++) {
-            BestRead& r = rd[i];
-            r.len = (uint32_t)(offs[i + 1] - offs[i]);
-            fw[i] = cleanReadSeq(std::string(seqs + offs[i], seqs + offs[i + 1]));
-            rc[i] = revComplWithN(fw[i]);
-            r.cutOff = std::min<uint32_t>(std::min<uint32_t>(13u, maxSupported), (r.len * (100 - min_identity)) / 100); // getMaxED (:1797)
-            r.best = r.cutOff + 1;
-            for (int s2 = 0; s2 < 2; s2++) {
-                r.ov[s2].assign(r.cutOff + 1, {});
-                r.processed[s2].assign(r.cutOff + 1, 0);
-            }
+            S.cur[i] = bestCursor(bestMaxED(maxSupported, (uint32_t)(offs[i + 1] - offs[i]), min_identity));
+            S.rd[i].fw = cleanReadSeq(std::string(seqs + offs[i], seqs + offs[i + 1]));
+            S.rd[i].rc = revComplWithN(S.rd[i].fw);
+            S.rd[i].start(S.cur[i].cutOff);
         }
-        // one stratum for a set of reads: ALL-mode search of both strands at distance k, every strand filtered by itself
-        auto runStratum = [&](const std::vector<uint32_t>& ids, uint32_t k) -> int {
-            std::string cat;
-            std::vector<uint64_t> o(ids.size() + 1, 0);
-            for (size_t j = 0; j < ids.size(); j++) {
-                cat.append(seqs + offs[ids[j]], seqs + offs[ids[j] + 1]);
-                o[j + 1] = cat.size();
-            }
-            StratumOut so;
-            const int rcode = runOn(cat.data(), o.data(), (uint32_t)ids.size(), k, so);
-            if (rcode) return rcode;
-            const std::vector<cmb_occ>& oc = so.oc;
-            const std::vector<cmb_aln>& al = so.al;
-            const std::vector<uint16_t>& ops = so.ops;
-            const std::vector<uint64_t>&oo = so.oo, &cnt = so.cnt;
-            for (int i = 0; i < CMB_CNT_MAX; i++) R->cnts[i] += cnt[i];
-            for (size_t j = 0; j < ids.size(); j++) {
-                BestRead& r = rd[ids[j]];
-                for (int s2 = 0; s2 < 2; s2++) {
-                    if (r.processed[s2][k]) continue; // (hasUpdate: this distance was looked at before)
-                    // processSeq (:791-812): minD = the first distance not processed yet
-                    uint32_t minD = 0;
-                    while (minD < k && r.processed[s2][minD]) minD++;
-                    for (uint64_t q2 = oo[j]; q2 < oo[j + 1]; q2++) {
-                        if ((int)oc[q2].strand != s2 || oc[q2].distance < minD) continue;
-                        BestOcc bo;
-                        bo.occ = oc[q2];
-                        bo.aln = al[q2];
-                        bo.ops.assign(ops.begin() + al[q2].cigar_off, ops.begin() + al[q2].cigar_off + al[q2].cigar_len);
-                        r.ov[s2][oc[q2].distance].push_back(std::move(bo));
-                    }
-                    for (uint32_t d = minD; d <= k; d++) r.processed[s2][d] = 1;
-                }
-            }
-            return CMB_OK;
-        };
-        // checkAlignments (:536-571): keep what lies inside one sequence; trimmed occurrences move to their new distance
-        auto checkAlignments = [&](uint32_t i, int s2, uint32_t l, uint32_t cutOffTrim) {
-            BestRead& r = rd[i];
-            if (l >= r.ov[s2].size()) return;
-            std::vector<BestOcc> assigned, trimmed;
-            for (BestOcc& o : r.ov[s2][l]) {
-                if (o.aln.spans == 0 || o.aln.spans == 3) { // FOUND (3: checked before)
-                    o.aln.spans = 3;
-                    assigned.push_back(std::move(o));
-                    if (l < r.best) r.best = l;
-                } else if (o.aln.spans == 1) {
-                    if (trimOccurrence(idx, s2 ? rc[i] : fw[i], cutOffTrim, st->metric, o, trimCounters ? R->cnts : nullptr) && o.occ.distance > l &&
-                        o.occ.distance < r.ov[s2].size())
-                        trimmed.push_back(std::move(o));
-                }
-            }
-            r.ov[s2][l] = std::move(assigned);
-            for (BestOcc& o : trimmed) {
-                o.aln.spans = 3; // (removeTrimmingLabel: it is an ordinary assigned occurrence of its new stratum)
-                const uint32_t d = o.occ.distance;
-                r.ov[s2][d].push_back(std::move(o));
-            }
-        };
-        // ---- exact matches first (x == 0), then the strata
-        std::vector<uint32_t> all(n_reads);
-        for (uint32_t i = 0; i < n_reads; i++) all[i] = i;
-        if (x == 0 && n_reads) {
-            int rcode = runStratum(all, 0);
-            if (rcode) return rcode;
-            for (uint32_t i = 0; i < n_reads; i++) {
-                BestRead& r = rd[i];
-                if (!r.ov[0][0].empty() || !r.ov[1][0].empty()) {
-                    checkAlignments(i, 0, 0, r.cutOff);
-                    checkAlignments(i, 1, 0, r.cutOff);
-                    if (r.best == 0) r.bestFound = true;
-                }
-            }
-        }
-        for (uint32_t i = 0; i < n_reads; i++) {
-            BestRead& r = rd[i];
-            r.maxED = r.best == 0 ? x : r.cutOff;
-            r.prevK = 0;
-            r.k = std::max(x, 1u);
-            r.finished = r.k > r.maxED;
-        }
-        std::vector<uint8_t> isFresh(n_reads, 0);
-        for (;;) {
-            // the reads that look at a stratum now, grouped by its distance
-            std::map<uint32_t, std::vector<uint32_t>> byK;
-            for (uint32_t i = 0; i < n_reads; i++)
-                if (!rd[i].finished) byK[rd[i].k].push_back(i);
-            if (byK.empty()) break;
-            for (auto& kv : byK) {
-                const uint32_t k = kv.first;
-                std::vector<uint32_t> need; // (a stratum both strands have been through needs no new search)
-                for (uint32_t i : kv.second)
-                    if (!rd[i].processed[0][k] || !rd[i].processed[1][k]) need.push_back(i);
-                std::fill(isFresh.begin(), isFresh.end(), 0);
-                for (uint32_t i : need) isFresh[i] = 1;
-                if (!need.empty()) {
-                    int rcode = runStratum(need, k);
-                    if (rcode) return rcode;
-                }
-                for (uint32_t i : kv.second) {
-                    BestRead& r = rd[i];
-                    // hasUpdate (:674-681): a stratum looked at before answers with ITS occurrences only; a new one
-                    // (processSeq) with any occurrence at distance 0..k
-                    bool update = false;
-                    for (int s2 = 0; s2 < 2; s2++) {
-                        const bool fresh = isFresh[i] != 0;
-                        if (!fresh) update |= !r.ov[s2][k].empty();
-                        else
-                            for (uint32_t d = 0; d <= k; d++) update |= !r.ov[s2][d].empty();
-                    }
-                    if (update)
-                        for (uint32_t l = r.prevK + 1; l <= std::min(k, r.best + x); l++) {
-                            checkAlignments(i, 0, l, r.maxED);
-                            checkAlignments(i, 1, l, r.maxED);
-                        }
-                    if (r.bestFound) {
-                        r.finished = true; // this was the last iteration
-                        continue;
-                    }
-                    if (update && r.best < r.cutOff + 1) {
-                        r.bestFound = true;
-                        if (x == 0) {
-                            r.finished = true;
-                            continue;
-                        }
-                        r.prevK = k;
-                        r.k = std::min(r.best + x, r.maxED); // check the final x strata
-                    } else {
-                        if (k == r.maxED) {
-                            r.finished = true;
-                            continue;
-                        }
-                        const uint32_t step = k < 5 ? 2 : 4;
-                        r.prevK = k;
-                        r.k = std::min(k + x + step, r.maxED);
-                    }
-                }
-            }
-        }
+        if (const int rcode = bestStrataLoop(S, n_reads, x)) return rcode;
         // ---- results: combineOccVectors (:573-620) per read
         R->offs.assign(n_reads + 1, 0);
         R->best.assign(n_reads, 0xFFFFFFFFu);
         R->nHits.assign(n_reads, 0);
-        // occurrences found with trimming still need their CIGAR: one more (small) pass through the device
         for (uint32_t i = 0; i < n_reads; i++) {
-            BestRead& r = rd[i];
+            const BestCursor& r = S.cur[i];
             R->offs[i] = R->occ.size();
             if (!r.bestFound) continue;
             R->best[i] = r.best;
-            R->nHits[i] = (uint32_t)(r.ov[0][r.best].size() + r.ov[1][r.best].size());
-            const uint32_t hi = std::min(r.best + x, r.cutOff);
-            for (uint32_t d = r.best; d <= hi; d++)
-                for (int s2 = 0; s2 < 2; s2++) {
-                    std::vector<BestOcc>& v = r.ov[s2][d];
-                    std::stable_sort(v.begin(), v.end(), [](const BestOcc& a, const BestOcc& b2) {
-                        return a.aln.seq_id < b2.aln.seq_id || (a.aln.seq_id == b2.aln.seq_id && a.aln.seq_begin < b2.aln.seq_begin);
-                    });
-                    v.erase(std::unique(v.begin(), v.end(), [](const BestOcc& a, const BestOcc& b2) {
-                                return a.aln.seq_id == b2.aln.seq_id && a.aln.seq_begin == b2.aln.seq_begin;
-                            }), v.end());
-                    for (BestOcc& o : v) {
-                        cmb_aln a = o.aln;
-                        a.cigar_off = R->ops.size();
-                        a.cigar_len = (uint16_t)o.ops.size();
-                        a.spans = o.aln.spans == 2 ? 2 : 0;
-                        R->ops.insert(R->ops.end(), o.ops.begin(), o.ops.end());
-                        R->occ.push_back(o.occ);
-                        R->aln.push_back(a);
-                    }
-                }
+            R->nHits[i] = S.rd[i].hitsAt(r.best);
+            bestCombineHost(S.rd[i], r.best, std::min<uint32_t>(r.best + x, r.cutOff), [&](const BestOcc& o) {
+                cmb_aln a = o.aln;
+                a.cigar_off = R->ops.size();
+                a.cigar_len = (uint16_t)o.ops.size();
+                a.spans = o.aln.spans == 2 ? 2 : 0;
+                R->ops.insert(R->ops.end(), o.ops.begin(), o.ops.end());
+                R->occ.push_back(o.occ);
+                R->aln.push_back(a);
+            });
         }
         R->offs[n_reads] = R->occ.size();
         *out = R.release();
@@ -3173,21 +3041,17 @@ extern "C" int cmb_match_best(cmb_index* idx, const cmb_strategy* st, uint32_t x
     return matchBestWith(idx, st, 13u, true, run, x, min_identity, seqs, offs, n_reads, out);
 }
 // ---- BEST mode with the bookkeeping on the device (dev_best.hpp) ------------------------------------------------------------------
-// The stratum loop and every per-read decision are matchBestWith's (above; searchstrategy.cpp:623-712); what it keeps in vectors per
-// read, strand and distance is here a pool of records in HBM plus, per read, a few words on the host: which distances hold an
-// occurrence / an occurrence inside one sequence (from k_best_scan), which went through checkAlignments, best, k, prevK.  The host
-// touches those words once per read and stratum and no occurrence — except for the reads that keep an occurrence over a sequence end
+// The strata loop and every per-read decision are the ones matchBestWith runs (host_best.hpp; searchstrategy.cpp:623-712); what that
+// keeps in vectors per read, strand and distance is here a pool of records in HBM plus, per read, a few words on the host: which
+// distances hold an occurrence / an occurrence inside one sequence (from k_best_scan), which went through checkAlignments, and the
+// cursor.  The host touches those words once per read and stratum and no occurrence — except for the reads that keep an occurrence over a sequence end
 // under edit distance: trimming verifies again and moves the occurrence to another distance (checkAlignments, :536-571), so from that
 // stratum on such a read's lists live in host vectors as in matchBestWith, and its final records are spliced into the device lists.
 namespace {
-struct BestState {
-    uint8_t cutOff = 0, best = 0, k = 0, prevK = 0, maxED = 0, proc = 0; // proc: the distances below it have been processed (both strands)
-    bool bestFound = false, finished = false, host = false;
+struct BestDevRead {
+    BestCursor c;
+    bool host = false; // its lists live in a BestHostRead
     uint16_t any[2] = {0, 0}, asg[2] = {0, 0}, chk[2] = {0, 0};
-};
-struct BestHostRead {
-    std::vector<std::vector<BestOcc>> ov[2];
-    std::string fw, rc;
 };
 struct BestPoolBufs {
     DevBuf<uint4> occ;
@@ -3248,283 +3112,194 @@ struct DevStratum {
 typedef std::function<int(const char* cat, const uint64_t* o, uint32_t n, uint32_t k, DevStratum& r, const std::function<void(const char*)>& lap)>
     DevStratumRunner;
 
+// The strata loop's store (host_best.hpp) with the occurrences in a pool in HBM and, per read, masks of the distances that hold one;
+// the reads that trimming takes to the host keep theirs in a BestHostRead.
 // idx: the index whose text and sequence starts serve the trimming (the FM-index itself, or the text beside a b-move index);
-// trimCounters: as for matchBestWith
+// trimCounters: as for BestHostStore
+struct BestDevStore {
+    cmb_index* idx;
+    const cmb_strategy* st;
+    bool trimCounters;
+    const DevStratumRunner& runOn;
+    const char* seqs;
+    const uint64_t* offs;
+    uint32_t nReads;
+    cmb_best* R;
+    bool edit;
+    std::vector<BestDevRead> rd;
+    std::map<uint32_t, BestHostRead> hr;
+    BestPoolBufs pool, stage;
+    DevBuf<uint8_t> dMinD, dMode, tmp;
+    DevBuf<uint32_t> dIds, dList;
+    DevBuf<unsigned long long> dMasks;
+    DevBuf<uint64_t> dCnt, dPoff;
+    std::vector<uint8_t> hMinD, hMode;
+    std::vector<unsigned long long> hMasks;
+
+    BestCursor& cursor(uint32_t i) { return rd[i].c; }
+    bool nonEmpty(uint32_t i, int s2, uint32_t d) { return rd[i].host ? hr[i].nonEmpty(s2, d) : ((rd[i].any[s2] >> d) & 1u) != 0; }
+    // checkAlignments (:536-571).  On the device's side an occurrence is assigned (it lies inside one sequence) or dropped
+    // (Hamming distance never trims); on the host's side it is BestHostStore's.
+    void check(uint32_t i, int s2, uint32_t l, uint32_t cutOffTrim) {
+        BestDevRead& r = rd[i];
+        if (l > r.c.cutOff) return;
+        if (r.host) {
+            bestCheckHost(hr[i], r.c.best, s2, l, cutOffTrim, [&](const std::string& seq, BestOcc& o, uint32_t cutOff) {
+                return trimOccurrence(idx, seq, cutOff, st->metric, o, trimCounters ? R->cnts : nullptr);
+            });
+            return;
+        }
+        const uint16_t bit = (uint16_t)(1u << l);
+        r.any[s2] = (uint16_t)((r.any[s2] & ~bit) | (r.asg[s2] & bit));
+        r.chk[s2] |= bit;
+        if ((r.asg[s2] & bit) && l < r.c.best) r.c.best = (uint8_t)l;
+    }
+    // one stratum for a set of reads: ALL-mode search of both strands at distance k, every strand filtered by itself; the batch's
+    // lists stay where they are
+    int run(const std::vector<uint32_t>& ids, uint32_t k) {
+        const uint32_t n = (uint32_t)ids.size();
+        auto t0 = std::chrono::steady_clock::now();
+        auto lap = [&](const char* what) {
+            auto t1 = std::chrono::steady_clock::now();
+            R->addTime(what, std::chrono::duration<double, std::milli>(t1 - t0).count());
+            t0 = t1;
+        };
+        std::string cat;
+        std::vector<uint64_t> o;
+        bestGatherReads(seqs, offs, ids, cat, o);
+        lap("host: gather of the stratum's reads");
+        DevStratum ds;
+        if (const int rcode = runOn(cat.data(), o.data(), n, k, ds, lap)) return rcode;
+        for (int i = 0; i < CMB_CNT_MAX; i++) R->cnts[i] += ds.cnts[i];
+        const std::vector<StratumLists>& parts = ds.parts;
+        for (const KernelTime& t : ds.times) R->addTime(std::string("strata: ") + t.name, t.ms);
+        // processSeq (:791-812): what lies below the first distance not processed yet is dropped
+        hMinD.resize(n);
+        for (uint32_t j = 0; j < n; j++) hMinD[j] = (uint8_t)std::min<uint32_t>(rd[ids[j]].c.proc, k);
+        growTo(dMinD, n), growTo(dIds, n), growTo(dMasks, n), growTo(dCnt, (size_t)n + 1), growTo(dPoff, (size_t)n + 1);
+        HIPCHK(hipMemcpy(dMinD.p, hMinD.data(), n, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dIds.p, ids.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(dCnt.p + n, 0, sizeof(uint64_t)));
+        uint32_t base = 0;
+        for (const StratumLists& c : parts) {
+            if (c.nReads)
+                hipLaunchKernelGGL(k_best_scan, dim3((c.nReads + 3u) / 4u), dim3(256), 0, 0, c.foffs, c.fout, c.aln, c.nReads, dMinD.p + base,
+                                   dMasks.p + base, dCnt.p + base);
+            base += c.nReads;
+        }
+        HIPCHK(hipGetLastError());
+        scanExclusive(tmp, dCnt.p, dPoff.p, (size_t)n + 1, (hipStream_t)0);
+        uint64_t kept = 0;
+        hMasks.resize(n);
+        HIPCHK(hipMemcpy(&kept, dPoff.p + n, sizeof(uint64_t), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(hMasks.data(), dMasks.p, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        const uint64_t poolBase = pool.n;
+        if (poolBase + kept >= 0xFFFFFFFFull) return fail(CMB_ERR_UNSUPPORTED, "more than 2^32 occurrences in the strata of one chunk");
+        pool.reserve(poolBase + kept);
+        base = 0;
+        for (const StratumLists& c : parts) {
+            if (c.nReads && kept)
+                hipLaunchKernelGGL(k_best_append, dim3((c.nReads + 3u) / 4u), dim3(256), 0, 0, c.foffs, c.fout, c.aln, c.ops, c.stride, c.nReads,
+                                   dMinD.p + base, dIds.p + base, dPoff.p + base, pool.at(poolBase));
+            base += c.nReads;
+        }
+        HIPCHK(hipGetLastError());
+        pool.n = poolBase + kept;
+        // the words of every read; the reads that go to, or are with, the host
+        bool anyHost = false, anyNew = false;
+        for (uint32_t j = 0; j < n; j++) {
+            BestDevRead& r = rd[ids[j]];
+            const unsigned long long m = hMasks[j];
+            if (r.host) {
+                hMode[ids[j]] = 1, anyHost = true;
+                continue;
+            }
+            r.any[0] |= (uint16_t)((m >> BEST_ANY0) & 0x3FFFu), r.any[1] |= (uint16_t)((m >> BEST_ANY1) & 0x3FFFu);
+            r.asg[0] |= (uint16_t)((m >> BEST_ASG0) & 0x3FFFu), r.asg[1] |= (uint16_t)((m >> BEST_ASG1) & 0x3FFFu);
+            if (edit && ((m >> BEST_SPAN) & 1ull)) hMode[ids[j]] = 2, anyHost = anyNew = true;
+        }
+        if (anyHost) {
+            const uint64_t from = anyNew ? 0 : poolBase, span = pool.n - from;
+            growTo(dMode, nReads);
+            growTo(dList, (size_t)span + 1);
+            HIPCHK(hipMemcpy(dMode.p, hMode.data(), nReads, hipMemcpyHostToDevice));
+            HIPCHK(hipMemset(dList.p, 0, sizeof(uint32_t)));
+            uint32_t nList = 0;
+            if (span) {
+                hipLaunchKernelGGL(k_best_collect, dim3((uint32_t)((span + 255u) / 256u)), dim3(256), 0, 0, pool.read.p, from, pool.n, poolBase,
+                                   dMode.p, dList.p);
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipMemcpy(&nList, dList.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+            }
+            std::vector<uint32_t> list(nList);
+            std::vector<uint4> go(nList);
+            std::vector<AlnRec> ga(nList);
+            std::vector<uint16_t> gp((size_t)nList * BEST_OPS_STRIDE);
+            std::vector<uint32_t> gr(nList);
+            if (nList) {
+                HIPCHK(hipMemcpy(list.data(), dList.p + 1, (size_t)nList * sizeof(uint32_t), hipMemcpyDeviceToHost));
+                std::sort(list.begin(), list.end()); // (the order in which the records were found)
+                HIPCHK(hipMemcpy(dList.p + 1, list.data(), (size_t)nList * sizeof(uint32_t), hipMemcpyHostToDevice));
+                growTo(stage.occ, nList), growTo(stage.aln, nList), growTo(stage.ops, (size_t)nList * BEST_OPS_STRIDE), growTo(stage.read, nList);
+                hipLaunchKernelGGL(k_best_gather, dim3((nList + 255u) / 256u), dim3(256), 0, 0, dList.p + 1, nList, pool.at(0), stage.at(0));
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipMemcpy(go.data(), stage.occ.p, (size_t)nList * sizeof(uint4), hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(ga.data(), stage.aln.p, (size_t)nList * sizeof(AlnRec), hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(gp.data(), stage.ops.p, gp.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(gr.data(), stage.read.p, (size_t)nList * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            }
+            for (uint32_t j = 0; j < n; j++) {
+                const uint32_t i = ids[j];
+                if (hMode[i] == 2) {
+                    BestHostRead& h = hr[i];
+                    h.fw = cleanReadSeq(std::string(seqs + offs[i], seqs + offs[i + 1]));
+                    h.rc = revComplWithN(h.fw);
+                    h.start(rd[i].c.cutOff);
+                    rd[i].host = true;
+                }
+                hMode[i] = 0;
+            }
+            for (uint32_t t = 0; t < nList; t++) hr[gr[t]].add(bestOccOf(go[t], ga[t], gp.data() + (size_t)t * BEST_OPS_STRIDE));
+        }
+        HIPCHK(hipDeviceSynchronize()); // (the batch and its lists go away)
+        lap("host: strata bookkeeping (k_best_scan, k_best_append, host reads)");
+        ds.destroy();
+        ds.destroy = nullptr;
+        lap("host: cmb_batch_destroy");
+        return CMB_OK;
+    }
+};
+
 int matchBestDeviceWith(cmb_index* idx, const cmb_strategy* st, bool trimCounters, const DevStratumRunner& runOn, uint32_t x, uint32_t min_identity,
                         const char* seqs, const uint64_t* offs, uint32_t n_reads, cmb_best** out) {
     if (!idx || !st || !offs || !out || (!seqs && n_reads)) return fail(CMB_ERR_INVALID, "null argument");
     if (min_identity < 50 || min_identity > 100) return fail(CMB_ERR_INVALID, "the minimal identity lies between 50 and 100");
     try {
         useDevice(idx->device);
-        uint32_t maxSupported = 0;
-        while (st->schemes.count(maxSupported + 1) && !st->schemes.at(maxSupported + 1).empty()) maxSupported++;
-        maxSupported = std::min<uint32_t>(maxSupported, 13u); // (MAX_K, definitions.h:50)
-        const bool edit = st->metric != CMB_METRIC_HAMMING;
+        const uint32_t maxSupported = bestMaxSupported(st->schemes, 13u); // (MAX_K, definitions.h:50)
         std::unique_ptr<cmb_best> R(new cmb_best());
         memset(R->cnts, 0, sizeof(R->cnts));
         R->onDevice = true, R->ix = idx, R->metric = st->metric, R->nReads = n_reads, R->x = x;
         R->readOffs.assign(offs, offs + n_reads + 1);
-        std::vector<BestState> sv(n_reads);
-        std::map<uint32_t, BestHostRead> hr;
-        for (uint32_t i = 0; i < n_reads; i++) {
-            const uint32_t len = (uint32_t)(offs[i + 1] - offs[i]);
-            sv[i].cutOff = (uint8_t)std::min<uint32_t>(std::min<uint32_t>(13u, maxSupported), (len * (100 - min_identity)) / 100); // getMaxED (:1797)
-            sv[i].best = sv[i].cutOff + 1;
-        }
-        BestPoolBufs pool;
-        DevBuf<uint8_t> dMinD, dMode, tmp;
-        DevBuf<uint32_t> dIds, dList;
-        DevBuf<unsigned long long> dMasks;
-        DevBuf<uint64_t> dCnt, dPoff;
-        BestPoolBufs stage;
-        std::vector<uint8_t> hMinD, hMode(n_reads, 0);
-        std::vector<unsigned long long> hMasks;
-        auto nonEmpty = [&](uint32_t i, int s2, uint32_t d) -> bool {
-            return sv[i].host ? !hr[i].ov[s2][d].empty() : ((sv[i].any[s2] >> d) & 1u) != 0;
-        };
-        // checkAlignments (:536-571).  On the device's side an occurrence is assigned (it lies inside one sequence) or dropped
-        // (Hamming distance never trims); on the host's side it is matchBestWith's.
-        auto checkAlignments = [&](uint32_t i, int s2, uint32_t l, uint32_t cutOffTrim) {
-            BestState& r = sv[i];
-            if (l > r.cutOff) return;
-            if (!r.host) {
-                const uint16_t bit = (uint16_t)(1u << l);
-                r.any[s2] = (uint16_t)((r.any[s2] & ~bit) | (r.asg[s2] & bit));
-                r.chk[s2] |= bit;
-                if ((r.asg[s2] & bit) && l < r.best) r.best = (uint8_t)l;
-                return;
-            }
-            BestHostRead& h = hr[i];
-            std::vector<BestOcc> assigned, trimmed;
-            for (BestOcc& o : h.ov[s2][l]) {
-                if (o.aln.spans == 0 || o.aln.spans == 3) { // FOUND (3: checked before)
-                    o.aln.spans = 3;
-                    assigned.push_back(std::move(o));
-                    if (l < r.best) r.best = (uint8_t)l;
-                } else if (o.aln.spans == 1) {
-                    if (trimOccurrence(idx, s2 ? h.rc : h.fw, cutOffTrim, st->metric, o, trimCounters ? R->cnts : nullptr) && o.occ.distance > l &&
-                        o.occ.distance < h.ov[s2].size())
-                        trimmed.push_back(std::move(o));
-                }
-            }
-            h.ov[s2][l] = std::move(assigned);
-            for (BestOcc& o : trimmed) {
-                o.aln.spans = 3; // (removeTrimmingLabel)
-                const uint32_t d = o.occ.distance;
-                h.ov[s2][d].push_back(std::move(o));
-            }
-        };
-        // one stratum for a set of reads: ALL-mode search of both strands at distance k, every strand filtered by itself; the batch's
-        // lists stay where they are
-        auto runStratum = [&](const std::vector<uint32_t>& ids, uint32_t k) -> int {
-            const uint32_t n = (uint32_t)ids.size();
-            auto t0 = std::chrono::steady_clock::now();
-            auto lap = [&](const char* what) {
-                auto t1 = std::chrono::steady_clock::now();
-                R->addTime(what, std::chrono::duration<double, std::milli>(t1 - t0).count());
-                t0 = t1;
-            };
-            std::string cat;
-            std::vector<uint64_t> o(ids.size() + 1, 0);
-            for (size_t j = 0; j < ids.size(); j++) {
-                cat.append(seqs + offs[ids[j]], seqs + offs[ids[j] + 1]);
-                o[j + 1] = cat.size();
-            }
-            lap("host: gather of the stratum's reads");
-            DevStratum ds;
-            if (const int rcode = runOn(cat.data(), o.data(), n, k, ds, lap)) return rcode;
-            for (int i = 0; i < CMB_CNT_MAX; i++) R->cnts[i] += ds.cnts[i];
-            const std::vector<StratumLists>& parts = ds.parts;
-            for (const KernelTime& t : ds.times) R->addTime(std::string("strata: ") + t.name, t.ms);
-            // processSeq (:791-812): what lies below the first distance not processed yet is dropped
-            hMinD.resize(n);
-            for (uint32_t j = 0; j < n; j++) hMinD[j] = (uint8_t)std::min<uint32_t>(sv[ids[j]].proc, k);
-            growTo(dMinD, n), growTo(dIds, n), growTo(dMasks, n), growTo(dCnt, (size_t)n + 1), growTo(dPoff, (size_t)n + 1);
-            HIPCHK(hipMemcpy(dMinD.p, hMinD.data(), n, hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(dIds.p, ids.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
-            HIPCHK(hipMemset(dCnt.p + n, 0, sizeof(uint64_t)));
-            uint32_t base = 0;
-            for (const StratumLists& c : parts) {
-                if (c.nReads)
-                    hipLaunchKernelGGL(k_best_scan, dim3((c.nReads + 3u) / 4u), dim3(256), 0, 0, c.foffs, c.fout, c.aln, c.nReads, dMinD.p + base,
-                                       dMasks.p + base, dCnt.p + base);
-                base += c.nReads;
-            }
-            HIPCHK(hipGetLastError());
-            scanExclusive(tmp, dCnt.p, dPoff.p, (size_t)n + 1, (hipStream_t)0);
-            uint64_t kept = 0;
-            hMasks.resize(n);
-            HIPCHK(hipMemcpy(&kept, dPoff.p + n, sizeof(uint64_t), hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(hMasks.data(), dMasks.p, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-            const uint64_t poolBase = pool.n;
-            if (poolBase + kept >= 0xFFFFFFFFull) return fail(CMB_ERR_UNSUPPORTED, "more than 2^32 occurrences in the strata of one chunk");
-            pool.reserve(poolBase + kept);
-            base = 0;
-            for (const StratumLists& c : parts) {
-                if (c.nReads && kept)
-                    hipLaunchKernelGGL(k_best_append, dim3((c.nReads + 3u) / 4u), dim3(256), 0, 0, c.foffs, c.fout, c.aln, c.ops, c.stride, c.nReads,
-                                       dMinD.p + base, dIds.p + base, dPoff.p + base, pool.at(poolBase));
-                base += c.nReads;
-            }
-            HIPCHK(hipGetLastError());
-            pool.n = poolBase + kept;
-            // the words of every read; the reads that go to, or are with, the host
-            bool anyHost = false, anyNew = false;
-            for (uint32_t j = 0; j < n; j++) {
-                BestState& r = sv[ids[j]];
-                const unsigned long long m = hMasks[j];
-                r.proc = (uint8_t)(k + 1);
-                if (r.host) {
-                    hMode[ids[j]] = 1, anyHost = true;
-                    continue;
-                }
-                r.any[0] |= (uint16_t)((m >> BEST_ANY0) & 0x3FFFu), r.any[1] |= (uint16_t)((m >> BEST_ANY1) & 0x3FFFu);
-                r.asg[0] |= (uint16_t)((m >> BEST_ASG0) & 0x3FFFu), r.asg[1] |= (uint16_t)((m >> BEST_ASG1) & 0x3FFFu);
-                if (edit && ((m >> BEST_SPAN) & 1ull)) hMode[ids[j]] = 2, anyHost = anyNew = true;
-            }
-            if (anyHost) {
-                const uint64_t from = anyNew ? 0 : poolBase, span = pool.n - from;
-                growTo(dMode, n_reads);
-                growTo(dList, (size_t)span + 1);
-                HIPCHK(hipMemcpy(dMode.p, hMode.data(), n_reads, hipMemcpyHostToDevice));
-                HIPCHK(hipMemset(dList.p, 0, sizeof(uint32_t)));
-                uint32_t nList = 0;
-                if (span) {
-                    hipLaunchKernelGGL(k_best_collect, dim3((uint32_t)((span + 255u) / 256u)), dim3(256), 0, 0, pool.read.p, from, pool.n, poolBase,
-                                       dMode.p, dList.p);
-                    HIPCHK(hipGetLastError());
-                    HIPCHK(hipMemcpy(&nList, dList.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
-                }
-                std::vector<uint32_t> list(nList);
-                std::vector<uint4> go(nList);
-                std::vector<AlnRec> ga(nList);
-                std::vector<uint16_t> gp((size_t)nList * BEST_OPS_STRIDE);
-                std::vector<uint32_t> gr(nList);
-                if (nList) {
-                    HIPCHK(hipMemcpy(list.data(), dList.p + 1, (size_t)nList * sizeof(uint32_t), hipMemcpyDeviceToHost));
-                    std::sort(list.begin(), list.end()); // (the order in which the records were found)
-                    HIPCHK(hipMemcpy(dList.p + 1, list.data(), (size_t)nList * sizeof(uint32_t), hipMemcpyHostToDevice));
-                    growTo(stage.occ, nList), growTo(stage.aln, nList), growTo(stage.ops, (size_t)nList * BEST_OPS_STRIDE), growTo(stage.read, nList);
-                    hipLaunchKernelGGL(k_best_gather, dim3((nList + 255u) / 256u), dim3(256), 0, 0, dList.p + 1, nList, pool.at(0), stage.at(0));
-                    HIPCHK(hipGetLastError());
-                    HIPCHK(hipMemcpy(go.data(), stage.occ.p, (size_t)nList * sizeof(uint4), hipMemcpyDeviceToHost));
-                    HIPCHK(hipMemcpy(ga.data(), stage.aln.p, (size_t)nList * sizeof(AlnRec), hipMemcpyDeviceToHost));
-                    HIPCHK(hipMemcpy(gp.data(), stage.ops.p, gp.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
-                    HIPCHK(hipMemcpy(gr.data(), stage.read.p, (size_t)nList * sizeof(uint32_t), hipMemcpyDeviceToHost));
-                }
-                for (uint32_t j = 0; j < n; j++) {
-                    const uint32_t i = ids[j];
-                    if (hMode[i] == 2) {
-                        BestHostRead& h = hr[i];
-                        h.fw = cleanReadSeq(std::string(seqs + offs[i], seqs + offs[i + 1]));
-                        h.rc = revComplWithN(h.fw);
-                        for (int s2 = 0; s2 < 2; s2++) h.ov[s2].assign((size_t)sv[i].cutOff + 1, {});
-                        sv[i].host = true;
-                    }
-                    hMode[i] = 0;
-                }
-                for (uint32_t t = 0; t < nList; t++) {
-                    BestHostRead& h = hr[gr[t]];
-                    if (go[t].z < h.ov[0].size())
-                        h.ov[go[t].w ? 1 : 0][go[t].z].push_back(bestOccOf(go[t], ga[t], gp.data() + (size_t)t * BEST_OPS_STRIDE));
-                }
-            }
-            HIPCHK(hipDeviceSynchronize()); // (the batch and its lists go away)
-            lap("host: strata bookkeeping (k_best_scan, k_best_append, host reads)");
-            ds.destroy();
-            ds.destroy = nullptr;
-            lap("host: cmb_batch_destroy");
-            return CMB_OK;
-        };
-        // ---- exact matches first (x == 0), then the strata: matchBestWith's loop, word for word
-        std::vector<uint32_t> all(n_reads);
-        for (uint32_t i = 0; i < n_reads; i++) all[i] = i;
-        if (x == 0 && n_reads) {
-            int rcode = runStratum(all, 0);
-            if (rcode) return rcode;
-            for (uint32_t i = 0; i < n_reads; i++) {
-                BestState& r = sv[i];
-                if (nonEmpty(i, 0, 0) || nonEmpty(i, 1, 0)) {
-                    checkAlignments(i, 0, 0, r.cutOff);
-                    checkAlignments(i, 1, 0, r.cutOff);
-                    if (r.best == 0) r.bestFound = true;
-                }
-            }
-        }
-        for (uint32_t i = 0; i < n_reads; i++) {
-            BestState& r = sv[i];
-            r.maxED = (uint8_t)(r.best == 0 ? std::min<uint32_t>(x, 255u) : r.cutOff);
-            r.prevK = 0;
-            r.k = (uint8_t)std::min<uint32_t>(std::max(x, 1u), 255u);
-            r.finished = r.k > r.maxED;
-        }
-        std::vector<uint8_t> isFresh(n_reads, 0);
-        for (;;) {
-            std::map<uint32_t, std::vector<uint32_t>> byK;
-            for (uint32_t i = 0; i < n_reads; i++)
-                if (!sv[i].finished) byK[sv[i].k].push_back(i);
-            if (byK.empty()) break;
-            for (auto& kv : byK) {
-                const uint32_t k = kv.first;
-                std::vector<uint32_t> need; // (a stratum both strands have been through needs no new search)
-                for (uint32_t i : kv.second)
-                    if (sv[i].proc <= k) need.push_back(i);
-                for (uint32_t i : kv.second) isFresh[i] = 0;
-                for (uint32_t i : need) isFresh[i] = 1;
-                if (!need.empty()) {
-                    int rcode = runStratum(need, k);
-                    if (rcode) return rcode;
-                }
-                for (uint32_t i : kv.second) {
-                    BestState& r = sv[i];
-                    bool update = false; // hasUpdate (:674-681)
-                    for (int s2 = 0; s2 < 2; s2++) {
-                        if (!isFresh[i]) update |= nonEmpty(i, s2, k);
-                        else
-                            for (uint32_t d = 0; d <= k; d++) update |= nonEmpty(i, s2, d);
-                    }
-                    if (update)
-                        for (uint32_t l = r.prevK + 1u; l <= std::min<uint32_t>(k, r.best + x); l++) {
-                            checkAlignments(i, 0, l, r.maxED);
-                            checkAlignments(i, 1, l, r.maxED);
-                        }
-                    if (r.bestFound) {
-                        r.finished = true; // this was the last iteration
-                        continue;
-                    }
-                    if (update && r.best < r.cutOff + 1u) {
-                        r.bestFound = true;
-                        if (x == 0) {
-                            r.finished = true;
-                            continue;
-                        }
-                        r.prevK = (uint8_t)k;
-                        r.k = (uint8_t)std::min<uint32_t>(r.best + x, r.maxED); // check the final x strata
-                    } else {
-                        if (k == r.maxED) {
-                            r.finished = true;
-                            continue;
-                        }
-                        const uint32_t step = k < 5 ? 2 : 4;
-                        r.prevK = (uint8_t)k;
-                        r.k = (uint8_t)std::min<uint32_t>(k + x + step, r.maxED);
-                    }
-                }
-            }
-        }
+        BestDevStore S{idx, st, trimCounters, runOn, seqs, offs, n_reads, R.get(), st->metric != CMB_METRIC_HAMMING};
+        S.rd.resize(n_reads), S.hMode.assign(n_reads, 0);
+        for (uint32_t i = 0; i < n_reads; i++) S.rd[i].c = bestCursor(bestMaxED(maxSupported, (uint32_t)(offs[i + 1] - offs[i]), min_identity));
+        if (const int rcode = bestStrataLoop(S, n_reads, x)) return rcode;
+        BestPoolBufs& pool = S.pool;
+        DevBuf<uint8_t>& tmp = S.tmp;
         const auto tFinal = std::chrono::steady_clock::now();
         // ---- results: combineOccVectors (:573-620).  Pool reads on the device; host reads as matchBestWith does
         std::vector<unsigned long long> hState(n_reads, 0);
         R->best.assign(n_reads, 0xFFFFFFFFu);
         R->hostRead.assign(n_reads, 0);
         for (uint32_t i = 0; i < n_reads; i++) {
-            const BestState& r = sv[i];
+            const BestDevRead& r = S.rd[i];
             if (r.host) R->hostRead[i] = 1, R->nHostReads++;
-            if (!r.bestFound) continue;
-            R->best[i] = r.best;
-            const unsigned long long hi = std::min<uint32_t>(r.best + x, r.cutOff);
+            if (!r.c.bestFound) continue;
+            R->best[i] = r.c.best;
+            const unsigned long long hi = std::min<uint32_t>(r.c.best + x, r.c.cutOff);
             if (!r.host)
-                hState[i] = (unsigned long long)r.best | (hi << 8) | (1ull << 16) | ((unsigned long long)(r.chk[0] & 0x3FFFu) << 32) |
+                hState[i] = (unsigned long long)r.c.best | (hi << 8) | (1ull << 16) | ((unsigned long long)(r.chk[0] & 0x3FFFu) << 32) |
                             ((unsigned long long)(r.chk[1] & 0x3FFFu) << 46);
         }
         std::vector<uint4> sOcc; // the final records of the host reads, one read after the other
@@ -3532,33 +3307,22 @@ int matchBestDeviceWith(cmb_index* idx, const cmb_strategy* st, bool trimCounter
         std::vector<uint16_t> sOps;
         std::vector<uint32_t> hostHits;
         std::vector<std::pair<uint32_t, uint64_t>> hostAt; // (read, its first record in sOcc)
-        for (auto& kv : hr) {
+        for (auto& kv : S.hr) {
             const uint32_t i = kv.first;
-            const BestState& r = sv[i];
+            const BestCursor& r = S.rd[i].c;
             BestHostRead& h = kv.second;
             hostAt.push_back({i, sOcc.size()});
             hostHits.push_back(0);
             if (!r.bestFound) continue;
-            hostHits.back() = (uint32_t)(h.ov[0][r.best].size() + h.ov[1][r.best].size());
-            const uint32_t hi = std::min<uint32_t>(r.best + x, r.cutOff);
-            for (uint32_t d = r.best; d <= hi; d++)
-                for (int s2 = 0; s2 < 2; s2++) {
-                    std::vector<BestOcc>& v = h.ov[s2][d];
-                    std::stable_sort(v.begin(), v.end(), [](const BestOcc& a, const BestOcc& b2) {
-                        return a.aln.seq_id < b2.aln.seq_id || (a.aln.seq_id == b2.aln.seq_id && a.aln.seq_begin < b2.aln.seq_begin);
-                    });
-                    v.erase(std::unique(v.begin(), v.end(), [](const BestOcc& a, const BestOcc& b2) {
-                                return a.aln.seq_id == b2.aln.seq_id && a.aln.seq_begin == b2.aln.seq_begin;
-                            }), v.end());
-                    for (BestOcc& o : v) {
-                        const uint32_t nOps = (uint32_t)std::min<size_t>(o.ops.size(), BEST_OPS_STRIDE);
-                        sOcc.push_back(uint4{o.occ.begin, o.occ.end, o.occ.distance, o.occ.strand});
-                        sAln.push_back(AlnRec{o.aln.seq_id, o.aln.seq_begin, nOps, o.aln.spans == 2 ? 2u : 0u});
-                        const size_t at = sOps.size();
-                        sOps.resize(at + BEST_OPS_STRIDE, 0);
-                        for (uint32_t j = 0; j < nOps; j++) sOps[at + j] = o.ops[nOps - 1 - j];
-                    }
-                }
+            hostHits.back() = h.hitsAt(r.best);
+            bestCombineHost(h, r.best, std::min<uint32_t>(r.best + x, r.cutOff), [&](const BestOcc& o) {
+                const uint32_t nOps = (uint32_t)std::min<size_t>(o.ops.size(), BEST_OPS_STRIDE);
+                sOcc.push_back(uint4{o.occ.begin, o.occ.end, o.occ.distance, o.occ.strand});
+                sAln.push_back(AlnRec{o.aln.seq_id, o.aln.seq_begin, nOps, o.aln.spans == 2 ? 2u : 0u});
+                const size_t at = sOps.size();
+                sOps.resize(at + BEST_OPS_STRIDE, 0);
+                for (uint32_t j = 0; j < nOps; j++) sOps[at + j] = o.ops[nOps - 1 - j]; // (CIGAR runs are stored end to begin)
+            });
         }
         hostAt.push_back({n_reads, sOcc.size()});
         DevBuf<unsigned long long> dState;

@@ -16,6 +16,7 @@
 // batches (one per distance).  A list is the device's ALL-mode result of that read at that distance with each strand filtered by
 // itself (cmb_batch_filter_per_strand) and the alignments of cmb_batch_alignments.
 #include "../../include/columba_amd.h"
+#include "host_best.hpp"
 #include "host_sam.hpp"
 
 #include <algorithm>
@@ -351,7 +352,7 @@ struct Walk {
         }
     }
     // checkAlignments (:536-567)
-    void checkAlignments(uint32_t m, uint32_t s, uint32_t& best, uint32_t l, uint32_t cutOff) {
+    void checkAlignments(uint32_t m, uint32_t s, uint8_t& best, uint32_t l, uint32_t cutOff) {
         OccVector& v = ov[m][s];
         std::vector<BOcc> trimmed, assignedOccs;
         for (BOcc& o : v[l].v) {
@@ -360,7 +361,7 @@ struct Walk {
                 if (f == FOUND_WITH_TRIMMING && o.distance > l) trimmed.push_back(std::move(o));
             } else {
                 assignedOccs.push_back(std::move(o));
-                if (l < best) best = l;
+                if (l < best) best = (uint8_t)l;
             }
         }
         v[l].v = std::move(assignedOccs);
@@ -369,12 +370,10 @@ struct Walk {
             if (o.distance < v.size()) v[o.distance].v.push_back(std::move(o));
         }
     }
-    // findBestAlignments (:623-712) on the strata the pairing has filled so far
+    // findBestAlignments (:623-712) on the strata the pairing has filled so far; the rule itself is host_best.hpp's
     bool findBestAlignments(uint32_t m, uint32_t x, uint32_t& best) {
         OccVector &fw = ov[m][0], &rc = ov[m][1];
-        const uint32_t cutOff = (uint32_t)fw.size() - 1;
-        best = cutOff + 1;
-        bool bestFound = false;
+        BestCursor c = bestCursor((uint32_t)fw.size() - 1);
         if (x == 0) {
             for (uint32_t s = 0; s < 2; s++)
                 if (!ov[m][s][0].done) {
@@ -382,39 +381,28 @@ struct Walk {
                     ov[m][s][0].done = true;
                 }
             if (!fw[0].v.empty() || !rc[0].v.empty()) {
-                checkAlignments(m, 0, best, 0, cutOff);
-                checkAlignments(m, 1, best, 0, cutOff);
-                if (best == 0) bestFound = true;
+                checkAlignments(m, 0, c.best, 0, c.cutOff);
+                checkAlignments(m, 1, c.best, 0, c.cutOff);
             }
         }
-        const uint32_t maxED = best == 0 ? x : cutOff;
-        uint32_t prevK = 0;
         auto hasUpdate = [&](uint32_t s, uint32_t k) {
             if (ov[m][s][k].done) return !ov[m][s][k].v.empty();
             return processSeq(m, s, k);
         };
-        for (uint32_t k = std::max(x, 1u); k <= maxED;) {
+        for (bestAfterExact(c, x); !c.finished;) {
+            const uint32_t k = c.k;
             bool update = false;
             update |= hasUpdate(0, k);
             update |= hasUpdate(1, k);
             if (update)
-                for (uint32_t l = prevK + 1; l <= std::min(k, best + x); l++) {
-                    checkAlignments(m, 0, best, l, maxED);
-                    checkAlignments(m, 1, best, l, maxED);
-                }
-            if (bestFound) break;
-            if (update && best < cutOff + 1) {
-                bestFound = true;
-                if (x == 0) break;
-                prevK = k, k = std::min(best + x, maxED);
-            } else {
-                if (k == maxED) break;
-                const uint32_t step = k < 5 ? 2 : 4;
-                prevK = k;
-                k = std::min(k + x + step, maxED);
-            }
+                bestSweep(c, k, x, [&](uint32_t l) {
+                    checkAlignments(m, 0, c.best, l, c.maxED);
+                    checkAlignments(m, 1, c.best, l, c.maxED);
+                });
+            bestAdvance(c, k, update, x);
         }
-        return bestFound;
+        best = c.best;
+        return c.bestFound;
     }
     // combineOccVectors (:569-621)
     std::vector<BOcc> combineOccVectors(uint32_t m, uint32_t best, uint32_t max) {
@@ -560,7 +548,7 @@ extern "C" int cmb_pair_best_create(const cmb_pair_params* prm, uint32_t x, uint
             P.id[m] = R[m]->id, P.seq[m] = R[m]->seq, P.rc[m] = R[m]->revcomp;
             P.qual[m] = R[m]->qual ? R[m]->qual : "", P.rqual[m] = R[m]->revqual ? R[m]->revqual : "";
             // getMaxED (searchstrategy.h:1797): the identity cut-off, held to what the strategy and the device support
-            P.cutOff[m] = std::min<uint32_t>(max_supported, (uint32_t)((P.seq[m].size() * (100 - min_identity)) / 100));
+            P.cutOff[m] = bestMaxED(max_supported, (uint32_t)P.seq[m].size(), min_identity);
         }
     }
     *out = b.release();
