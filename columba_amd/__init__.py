@@ -699,7 +699,7 @@ class PairBest:
         return int(v.value)
 
     def seed(self, pair: int, se1, se2, read2_done: bool):
-        """start pair `pair` from the mates' single-end BEST results (cmb_pair_best_seed): se = (occ, aln, ops)"""
+        """start pair `pair` from the mates' single-end results, every stratum up to the cut-off (cmb_pair_best_seed): se = (occ, aln, ops)"""
         a = [np.ascontiguousarray(se1[0], dtype=OCC_DTYPE), np.ascontiguousarray(se1[1], dtype=ALN_DTYPE), np.ascontiguousarray(se1[2], dtype=np.uint16),
              np.ascontiguousarray(se2[0], dtype=OCC_DTYPE), np.ascontiguousarray(se2[1], dtype=ALN_DTYPE), np.ascontiguousarray(se2[2], dtype=np.uint16)]
         ptr = [(_p(x) if x.shape[0] else None) for x in a]
@@ -1360,7 +1360,8 @@ def pair_chunk_sam_best(index: "Index", strategy: "SearchStrategy", reads1, read
     (ALL mode, every strand filtered by itself, with alignments), and both strands of a result are handed in.  `index`: an Index, or a
     MoveIndex with its text attached (the b-move backend: MoveBatch per (mate, distance); kmer_size is its seed table's).  Returns (SAM
     text, number of properly or discordantly mapped pairs, number of device batches).  start_from: the single-end results of
-    infer_paired_end_best for this chunk — the pairs start from them (pairSingleEndedMatchesBest; x = 0)."""
+    infer_paired_end_best for this chunk, every stratum up to each read's cut-off — the pairs start from them (pairSingleEndedMatchesBest;
+    x = 0)."""
     if start_from is not None:
         x = 0
     is_move = isinstance(index, MoveIndex)
@@ -1373,15 +1374,8 @@ def pair_chunk_sam_best(index: "Index", strategy: "SearchStrategy", reads1, read
     else:
         trim_index = index
     n = len(reads1)
-    if max_supported is None:  # getMaxSupportedDistanceForBestMapping: the largest k such that 1 .. k all have a scheme (13 at most)
-        max_supported = 0
-        while max_supported < 13:
-            try:
-                if strategy.describe(max_supported + 1)[0] == 0:
-                    break
-            except CmbError:
-                break
-            max_supported += 1
+    if max_supported is None:
+        max_supported = _max_supported_for_best(strategy)
     mates = []
     for reads, ids, quals in ((reads1, ids1, quals1), (reads2, ids2, quals2)):
         prep = []
@@ -1435,45 +1429,109 @@ def pair_chunk_sam_best(index: "Index", strategy: "SearchStrategy", reads1, read
     return "".join(text), mapped, batches
 
 
+def _max_supported_for_best(strategy: "SearchStrategy") -> int:
+    """getMaxSupportedDistanceForBestMapping: the largest k such that 1 .. k all have a scheme (13 at most)"""
+    k = 0
+    while k < 13:
+        try:
+            if strategy.describe(k + 1)[0] == 0:
+                break
+        except CmbError:
+            break
+        k += 1
+    return k
+
+
+def _single_end_all(index, strategy: "SearchStrategy", max_distance: int, reads, kmer_size: int = 10):
+    """A chunk of reads matched single-end in ALL mode at one distance, with alignments, the two strands of a read filtered TOGETHER
+    (SearchStrategy::matchApprox -> matchApproxAllMap): per read (occ, aln, ops) with every occurrence's sequence assigned — one that runs
+    past the end of its sequence is trimmed and verified again (cmb_trim_occurrence) or dropped, as in pair_chunk_sam.  `index`: an Index,
+    or a MoveIndex with its text attached."""
+    is_move = isinstance(index, MoveIndex)
+    if is_move:
+        trim_h = C.c_void_p(lib().cmb_move_text_index(index.h))
+        if not trim_h:
+            raise CmbError(-1, "alignments on the b-move index need the text beside it (MoveIndex.attach_text)")
+        b = MoveBatch(index, strategy, max_distance, reads=reads, kmer_size=kmer_size)
+    else:
+        trim_h = index.h
+        b = Batch(index, strategy, max_distance, reads=reads)
+    b.want_alignments()
+    b.run()
+    occ, offs, _ = b.results()
+    aln, ops = b.alignments()
+    b.close() if hasattr(b, "close") else None
+    if is_move:  # (64-bit positions there; alignments exist for texts below 2^32 only)
+        occ32 = np.zeros(len(occ), OCC_DTYPE)
+        for f in ("begin", "end", "distance", "strand"):
+            occ32[f] = occ[f]
+        occ = occ32
+    out = []
+    for j, read in enumerate(reads):
+        lo, hi = int(offs[j]), int(offs[j + 1])
+        o, a, pool = occ[lo:hi].copy(), aln[lo:hi].copy(), ops
+        spanning = np.flatnonzero(a["spans"] == 1)
+        if spanning.size:
+            _sid, seq, rc, _rq = read_prepare("read", read.decode() if isinstance(read, bytes) else read, "")
+            keep, extra = np.ones(hi - lo, bool), []
+            for q in spanning:
+                oc1, al1 = o[q:q + 1].copy(), a[q:q + 1].copy()
+                ops1 = np.zeros(2 * max_distance + 8, np.uint16)
+                nops, found = C.c_uint32(), C.c_int32()
+                pat = (rc if int(oc1["strand"][0]) else seq).encode()
+                _chk(lib().cmb_trim_occurrence(trim_h, pat, len(pat), max_distance, METRIC["edit"], _p(oc1), _p(al1), _p(ops1), ops1.shape[0],
+                                               C.byref(nops), C.byref(found)))
+                if not found.value:
+                    keep[q] = False  # NOT_FOUND: the occurrence takes no part
+                    continue
+                o[q], a[q] = oc1[0], al1[0]
+                a["cigar_off"][q], a["cigar_len"][q] = len(ops) + sum(len(e) for e in extra), nops.value
+                extra.append(ops1[:nops.value])
+            o, a, pool = o[keep], a[keep], np.concatenate([ops] + extra)
+        a["spans"] = 0  # (assigned; a trimmed occurrence carries its trimmed coordinates)
+        out.append((o, a, pool))
+    return out
+
 
 def infer_paired_end_best(index: "Index", strategy: "SearchStrategy", reads1, reads2, min_identity: int = 95, seqs_in_first_file: Optional[int] = None,
                           kmer_size: int = 10):
-    """The single-end phase that infers the paired-end parameters (parallel.cpp:236-312, :700-727): read 1 of every pair in BEST mode
-    (match_best, x = 0); read 2 where read 1 has exactly one match in the first reference file (it moves to the front:
-    hasUnambiguousMatchInFirstFile); the pairs whose mates both do are the sample of cmb_pair_infer.  Returns a dict: "inferred"
-    (PairInferred), "unambiguous_pairs", "read2done", and "single" — per mate and pair (occ, aln, ops) for
-    pair_chunk_sam_best(..., start_from=...)."""
+    """The single-end phase that infers the paired-end parameters (parallel.cpp:236-312, :700-727).  As there it runs in ALL mode
+    (parallel.cpp:887-890): read 1 of every pair matched as a single read at ITS OWN cut-off (getMaxED of its length and min_identity) —
+    one device batch per distinct cut-off, the two strands of a read filtered together — so its list holds every stratum up to the cut-off;
+    read 2 where read 1 has exactly one match in the first reference file among ALL those matches (it moves to the front:
+    hasUnambiguousMatchInFirstFile); the pairs whose mates both do are the sample of cmb_pair_infer.  `index`: an Index, or a MoveIndex
+    with its text attached.  Returns a dict: "inferred" (PairInferred), "unambiguous_pairs", "sample" (their indices), "read2done", and
+    "single" — per mate and pair the COMPLETE list (occ, aln, ops) for pair_chunk_sam_best(..., start_from=...)."""
     n = len(reads1)
     lim = 0xFFFFFFFF if seqs_in_first_file is None else seqs_in_first_file
     empty = (np.zeros(0, OCC_DTYPE), np.zeros(0, ALN_DTYPE), np.zeros(0, np.uint16))
+    most = _max_supported_for_best(strategy)
 
     def single(reads, ids):
-        out = {}
-        if not ids:
-            return out
-        occ, aln, ops, offs, _best, _hits, _cnt = match_best(index, strategy, [reads[i] for i in ids], x=0, min_identity=min_identity, kmer_size=kmer_size)
-        for j, i in enumerate(ids):
-            lo, hi = int(offs[j]), int(offs[j + 1])
-            o, a = occ[lo:hi].copy(), aln[lo:hi].copy()
-            a["spans"] = 0
-            first = [q for q in range(hi - lo) if int(a["seq_id"][q]) < lim]
-            unambiguous = len(first) == 1
-            if unambiguous and first[0] != 0:
-                o[[0, first[0]]] = o[[first[0], 0]]
-                a[[0, first[0]]] = a[[first[0], 0]]
-            out[i] = ((o, a, ops), unambiguous)
+        out, by_cutoff = {}, {}
+        for i in ids:
+            by_cutoff.setdefault(min(most, len(reads[i]) * (100 - min_identity) // 100), []).append(i)
+        for k, group in sorted(by_cutoff.items()):
+            lists = _single_end_all(index, strategy, k, [reads[i] if isinstance(reads[i], bytes) else reads[i].encode() for i in group], kmer_size)
+            for i, (o, a, ops) in zip(group, lists):
+                first = [q for q in range(o.shape[0]) if int(a["seq_id"][q]) < lim]
+                unambiguous = len(first) == 1
+                if unambiguous and first[0] != 0:
+                    o[[0, first[0]]] = o[[first[0], 0]]
+                    a[[0, first[0]]] = a[[first[0], 0]]
+                out[i] = ((o, a, ops), unambiguous)
         return out
 
     r1 = single(reads1, list(range(n)))
     second = [i for i in range(n) if r1[i][1]]
     r2 = single(reads2, second)
-    samples = []
+    samples, sample = [], []
     for i in second:
         if r2[i][1]:
             (o1, a1, _), (o2, a2, _) = r1[i][0], r2[i][0]
             samples.append((int(a1["seq_begin"][0]), int(a1["seq_begin"][0]) + int(o1["end"][0]) - int(o1["begin"][0]), int(o1["strand"][0]),
                             int(a2["seq_begin"][0]), int(a2["seq_begin"][0]) + int(o2["end"][0]) - int(o2["begin"][0]), int(o2["strand"][0])))
-    return {"inferred": pair_infer(samples if samples else np.zeros((0, 6), np.uint32)), "unambiguous_pairs": len(samples),
+            sample.append(i)
+    return {"inferred": pair_infer(samples if samples else np.zeros((0, 6), np.uint32)), "unambiguous_pairs": len(samples), "sample": sample,
             "read2done": [i in r2 for i in range(n)],
             "single": ([r1[i][0] for i in range(n)], [r2[i][0] if i in r2 else empty for i in range(n)])}
-

@@ -401,9 +401,11 @@ int cmb_pair_best_create(const cmb_pair_params* params, uint32_t x, uint32_t min
 int cmb_pair_best_set_trim(cmb_pair_best* b, cmb_pair_trim_fn fn, void* user);
 int cmb_pair_best_cutoff(const cmb_pair_best* b, uint32_t pair, uint32_t mate, uint32_t* cut_off);
 /* pairSingleEndedMatchesBest (src/searchstrategy.h:1454-1462) over addSingleEndedForBest (src/searchstrategy.cpp:1064-1089), x = 0: the pair
- * starts from the mates' single-end BEST results (what the parameter-inference phase has computed, src/parallel.cpp:790-810) — occurrences
- * with their sequence assigned (aln[j].spans != 1) and their CIGAR; every stratum of read 1 then counts as looked at, those of read 2 if
- * read2_done.  Before the first cmb_pair_best_advance of that pair. */
+ * starts from the mates' single-end results of the parameter-inference phase (src/parallel.cpp:790-810), which runs in ALL mode at each
+ * read's cut-off (src/parallel.cpp:887-890, :288-298): the lists must be COMPLETE, every occurrence of every stratum up to the cut-off,
+ * with their sequence assigned (aln[j].spans != 1) and their CIGAR, each filed under its own distance.  Every stratum of read 1 then
+ * counts as looked at, those of read 2 if read2_done — an occurrence that is missing from a list is never searched for.  Before the
+ * first cmb_pair_best_advance of that pair. */
 int cmb_pair_best_seed(cmb_pair_best* b, uint32_t pair, const cmb_occ* occ1, const cmb_aln* aln1, uint64_t n1, const uint16_t* cigar_ops1,
                        const cmb_occ* occ2, const cmb_aln* aln2, uint64_t n2, const uint16_t* cigar_ops2, int read2_done);
 /* at most one request per unfinished pair; CMB_ERR_OVERFLOW (with *n = the number wanted) if cap is too small — nothing is lost, call again */

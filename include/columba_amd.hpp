@@ -490,10 +490,23 @@ class SearchStrategy {
         return pairListsAll(mates1, mates2, startFrom->first, startFrom->second, seqNames, orientation, maxFragSize, minFragSize, discordantAllowed,
                             unmappedRecords, mappedPairs);
     }
+    // getMaxSupportedDistanceForBestMapping: the largest k such that 1 .. k all have a scheme (13 at most)
+    uint32_t maxSupportedForBest() const {
+        uint32_t maxSupported = 0;
+        for (; maxSupported < 13; maxSupported++) {
+            uint32_t ns = 0, np = 0, crit[16];
+            if (cmb_strategy_describe(h, maxSupported + 1, &ns, &np, crit, 16) != CMB_OK || ns == 0) break;
+        }
+        return maxSupported;
+    }
     // The single-end phase that infers the paired-end parameters (parallel.cpp:236-262 hasUnambiguousMatchInFirstFile, :276-312
-    // processChunkSingleEndForPairInferring, :700-727 and cmb_pair_infer for :329-466): read 1 of every pair in BEST mode; read 2 where read 1 has
-    // exactly one match in the first reference file; the pairs whose mates both do are the sample.  The single-end results stay here: the
-    // same chunk is then paired from them (samOfChunkPairedBest(..., &inference): pairSingleEndedMatchesBest, searchstrategy.h:1454-1462).
+    // processChunkSingleEndForPairInferring, :700-727 and cmb_pair_infer for :329-466).  As there it runs in ALL mode (parallel.cpp:887-890):
+    // read 1 of every pair matched as a single read at ITS OWN cut-off (getMaxED of its length and the minimal identity) — one device batch
+    // per distinct cut-off, the two strands of a read filtered together (listsOfMate, as inferPairedEndParametersAll) — so its list holds every
+    // stratum up to the cut-off; read 2 where read 1 has exactly one match in the first reference file among ALL those matches; the pairs
+    // whose mates both do are the sample.  The complete lists stay here: the same chunk is then paired from them
+    // (samOfChunkPairedBest(..., &inference): pairSingleEndedMatchesBest, searchstrategy.h:1454-1462, whose addSingleEndedForBest marks every
+    // stratum of a matched read as explored because its list is complete).
     struct PairedEndInference {
         cmb_pair_inferred inferred{};
         size_t readsGiven = 0, unambiguousPairs = 0;
@@ -512,38 +525,29 @@ class SearchStrategy {
         const size_t n = mates1.size();
         PairedEndInference inf;
         inf.single[0].resize(n), inf.single[1].resize(n), inf.read2done.assign(n, 0);
+        const uint32_t maxSupported = maxSupportedForBest();
         auto matchSingle = [&](const std::vector<Record>& recs, const std::vector<size_t>& ids, std::vector<typename PairedEndInference::Single>& out) {
-            std::string seqs;
-            std::vector<uint64_t> offs(ids.size() + 1, 0);
-            for (size_t j = 0; j < ids.size(); j++) seqs += recs[ids[j]].read, offs[j + 1] = seqs.size();
-            cmb_best* r = nullptr;
-            check(cmb_match_best(index.handle(), h, 0, minIdentity, seqs.data(), offs.data(), (uint32_t)ids.size(), &r));
-            struct Guard {
-                cmb_best* r;
-                ~Guard() { cmb_best_destroy(r); }
-            } guard{r};
-            uint64_t nOcc = 0, nOps = 0;
-            check(cmb_best_sizes(r, &nOcc, &nOps));
-            std::vector<cmb_occ> occ(nOcc ? nOcc : 1);
-            std::vector<cmb_aln> aln(nOcc ? nOcc : 1);
-            std::vector<uint16_t> ops(nOps ? nOps : 1);
-            std::vector<uint64_t> oo(ids.size() + 1);
-            std::vector<uint32_t> best(ids.size() ? ids.size() : 1), hits(ids.size() ? ids.size() : 1);
-            check(cmb_best_results(r, occ.data(), aln.data(), occ.size(), ops.data(), ops.size(), oo.data(), best.data(), hits.data(), nullptr));
-            for (size_t j = 0; j < ids.size(); j++) {
-                typename PairedEndInference::Single& s = out[ids[j]];
-                for (uint64_t q = oo[j]; q < oo[j + 1]; q++) {
-                    cmb_aln a = aln[q];
-                    const uint64_t from = a.cigar_off;
-                    a.cigar_off = s.ops.size();
-                    a.spans = 0; // (assigned; a trimmed occurrence carries its trimmed coordinates)
-                    s.ops.insert(s.ops.end(), ops.begin() + from, ops.begin() + from + a.cigar_len);
-                    s.occ.push_back(occ[q]);
-                    s.aln.push_back(a);
+            std::map<uint32_t, std::vector<size_t>> byCutOff; // getMaxED (searchstrategy.h:1797) -> reads
+            for (size_t i : ids)
+                byCutOff[std::min<uint32_t>(std::min<uint32_t>(13u, maxSupported), (uint32_t)(recs[i].read.size() * (100 - minIdentity) / 100))].push_back(i);
+            for (const auto& g : byCutOff) {
+                MateLists lists = listsOfMate(recs, g.second, (length_t)g.first, false);
+                for (size_t j = 0; j < g.second.size(); j++) {
+                    typename PairedEndInference::Single& s = out[g.second[j]];
+                    for (const PairOccStore& st : lists[j]) {
+                        cmb_occ o{};
+                        o.begin = st.p.index_begin, o.end = st.p.index_begin + (st.p.end - st.p.begin), o.distance = st.p.distance, o.strand = st.p.strand;
+                        cmb_aln a{};
+                        a.seq_id = st.p.seq_id, a.seq_begin = st.p.begin, a.cigar_off = s.ops.size(), a.cigar_len = (uint16_t)st.ops.size();
+                        a.spans = 0; // (assigned; a trimmed occurrence carries its trimmed coordinates)
+                        s.ops.insert(s.ops.end(), st.ops.begin(), st.ops.end());
+                        s.occ.push_back(o);
+                        s.aln.push_back(a);
+                    }
                 }
             }
         };
-        // hasUnambiguousMatchInFirstFile: exactly one of the matches lies in the first file; it moves to the front
+        // hasUnambiguousMatchInFirstFile: exactly one of ALL the matches lies in the first file; it moves to the front
         auto unambiguous = [&](typename PairedEndInference::Single& s) {
             size_t count = 0, at = 0;
             for (size_t j = 0; j < s.occ.size(); j++)
@@ -580,11 +584,7 @@ class SearchStrategy {
         if (mates1.size() != mates2.size()) throw std::runtime_error("the two read files do not hold the same number of reads");
         const uint32_t n = (uint32_t)mates1.size();
         if (startFrom) x = 0; // (pairSingleEndedMatchesBest: no strata beyond the best one)
-        uint32_t maxSupported = 0;
-        for (; maxSupported < 13; maxSupported++) {
-            uint32_t ns = 0, np = 0, crit[16];
-            if (cmb_strategy_describe(h, maxSupported + 1, &ns, &np, crit, 16) != CMB_OK || ns == 0) break;
-        }
+        const uint32_t maxSupported = maxSupportedForBest();
         const std::vector<Record>* in[2] = {&mates1, &mates2};
         std::vector<std::vector<char>> store; // identifiers, reads, reverse complements and reversed qualities as cmb_read_prepare leaves them
         store.reserve((size_t)n * 8);

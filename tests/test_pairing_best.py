@@ -573,10 +573,12 @@ def test_best_pairing_equals_the_restatement(x, orientation):
         assert n_lines > 150 and (n_mapped > 10 or not disc)
 
 
-@pytest.mark.parametrize("orientation", [ca.ORIENTATION_FR, ca.ORIENTATION_RF, ca.ORIENTATION_FF])
-def test_pairs_that_start_from_single_end_results(orientation):
-    """pairSingleEndedMatchesBest (searchstrategy.h:1454-1462): the walk starts from the mates' single-end BEST results — the best stratum of
-    each mate, both strands — with every stratum of read 1 (and of read 2 if it was processed) counting as looked at"""
+@pytest.mark.parametrize("orientation,every_stratum", [(o, e) for e in (False, True) for o in (ca.ORIENTATION_FR, ca.ORIENTATION_RF, ca.ORIENTATION_FF)],
+                         ids=[f"{o}{e}" for e in ("", "-every-stratum") for o in (ca.ORIENTATION_FR, ca.ORIENTATION_RF, ca.ORIENTATION_FF)])
+def test_pairs_that_start_from_single_end_results(orientation, every_stratum):
+    """pairSingleEndedMatchesBest (searchstrategy.h:1454-1462): the walk starts from the mates' single-end results, both strands — the best
+    stratum of each mate only, or every stratum up to the cut-off (what the inference phase hands over: it runs in ALL mode) — with every
+    stratum of read 1 (and of read 2 if it was processed) counting as looked at"""
     rng = np.random.default_rng(300 + orientation)
     pairs, seeds = [], []
     for i in range(240):
@@ -586,7 +588,7 @@ def test_pairs_that_start_from_single_end_results(orientation):
         for m in (0, 1):
             every = [o for s in (0, 1) for o in table[(m, s, cut[m])] if not o.spans]
             best = min((o.d for o in every), default=None)
-            se.append([o for o in every if o.d == best])
+            se.append([o for o in every if every_stratum or o.d == best])
         read2done = bool(i % 4)
         seeds.append((se[0], se[1] if read2done else [], read2done))
     got, asked, _ = _run_library(pairs, 0, 95, 5, orientation, 600, 0, True, True, seeds=seeds)
