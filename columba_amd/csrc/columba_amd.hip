@@ -1005,7 +1005,7 @@ static int batchRunOne(cmb_batch* b) {
         tm.end("k_prep");
 
         // ---- prologue + DFS (re-run with larger queues if they overflow: nothing is truncated)
-        const uint32_t pCap = getenv("CMB_P_SLOTS") ? (uint32_t)std::max(256, atoi(getenv("CMB_P_SLOTS"))) / 256u * 256u : 256u * 32768u; // (one lane per read x strand
+        const uint32_t pCap = capSlots(envSlots("CMB_P_SLOTS", 256u * 32768u)); // (one lane per read x strand
         // up to 8 M: k_parts 65.7 ms with 512 k lanes looping over the tasks, 65.0 / 62.1 / 62.5 ms with 1 M / 4 M / 8 M)
         const uint32_t pSlots = std::min<uint32_t>(((tasks + 255) / 256) * 256, pCap);
         const bool preset = !b->presetItems.empty();
@@ -1041,6 +1041,7 @@ static int batchRunOne(cmb_batch* b) {
             if (b->k) {
                 if (b->psel.n < tasks) b->psel.alloc(tasks);
                 const size_t pLds = stratBytes + (5 * pParts + rdWords) * 256 * sizeof(uint32_t);
+                gridLine(verbose, "k_parts", tasks, pSlots);
                 if (b->wide) {
                     constexpr int W = MAXP_WIDE;
                     auto kp = longReads ? (b->sPartition == 0 ? k_parts<0, true, W> : b->sPartition == 1 ? k_parts<1, true, W> : k_parts<2, true, W>)
@@ -1058,7 +1059,8 @@ static int batchRunOne(cmb_batch* b) {
             }
             // k_exact: k = 0 one lane per read x strand; otherwise the ExactTasks k_parts left — their number is on the device, a small
             // grid loops over them (none in the common case: every search of the multiple_opt schemes has one exact phase)
-            const uint32_t eSlots = b->k ? 256u * 256u : (uint32_t)std::min<uint64_t>((((uint64_t)tasks + 255) / 256) * 256, 256ull * 4096ull);
+            const uint32_t eSlots = capSlots(b->k ? 256u * 256u : (uint32_t)std::min<uint64_t>((((uint64_t)tasks + 255) / 256) * 256, 256ull * 4096ull));
+            if (!b->k) gridLine(verbose, "k_exact", tasks, eSlots); // (k > 0: the number of its tasks is on the device until the prologue is read back)
             const size_t eLds = stratBytes + (pParts + rdWords) * 256 * sizeof(uint32_t);
             if (b->wide)
                 hipLaunchKernelGGL((longReads ? k_exact<true, MAXP_WIDE> : k_exact<false, MAXP_WIDE>), dim3(eSlots / 256), dim3(256), eLds, s, ix->d,
@@ -1097,11 +1099,12 @@ static int batchRunOne(cmb_batch* b) {
                 uint32_t pass = 0, peakQ = 0;
                 bool drained = false;
                 auto kNaive = edit ? k_naive_pass<true, false> : k_naive_pass<false, false>;
+                const uint32_t nvGrid = capBlocks(BFS_GRID); // (k_naive_start above takes one lane per read x strand and does not loop: no cap)
                 if (b->geoX) kNaive = k_naive_pass<true, true>;
                 while (!drained && pass < maxPassN) {
                     const uint32_t upTo = std::min(pass + 16u, maxPassN);
                     for (; pass < upTo; pass++)
-                        hipLaunchKernelGGL(kNaive, dim3(BFS_GRID), dim3(256), 0, s, ix->d, N,
+                        hipLaunchKernelGGL(kNaive, dim3(nvGrid), dim3(256), 0, s, ix->d, N,
                                            pass, b->offs.p, b->gw, b->G.p, b->seq.p, b->maxLen, b->k, q);
                     HIPCHK(hipMemcpyAsync(hc.data(), b->nvCnt.p, cntWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
                     HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
@@ -1111,6 +1114,7 @@ static int batchRunOne(cmb_batch* b) {
                 }
                 for (uint32_t p2 = 0; p2 <= pass && p2 < cntWords; p2++) peakQ = std::max(peakQ, hc[p2]);
                 if (verbose) fprintf(stderr, "[naive] %u roots, %u passes, peak frontier %u\n", hc[0], pass, peakQ);
+                gridLine(verbose, "k_naive_pass", peakQ, 256ull * nvGrid); // (the largest frontier of a pass)
                 tm.end("k_naive");
                 HIPCHK(hipGetLastError());
                 flags = hcnt[3];
@@ -1129,6 +1133,7 @@ static int batchRunOne(cmb_batch* b) {
                             "the k-mer size, e.g. at 4 for kuch2 and 01*0: alignparameters.cpp:1070-1114, :1275-1278)");
             const uint32_t nDfs = hcnt[5];
             if (verbose && b->k) fprintf(stderr, "[prologue] %u items, %u search tasks, %u searches with further exact phases\n", hcnt[0], nDfs, hcnt[4]);
+            if (b->k) gridLine(verbose, "k_exact", hcnt[4], eSlots);
             if (!(flags & (FLAG_ITEM_OVERFLOW | FLAG_DFS_OVERFLOW | FLAG_EXACT_OVERFLOW)) && nDfs) {
                 tm.begin();
                 if (b->metric == CMB_METRIC_EDIT) {
@@ -1178,9 +1183,8 @@ static int batchRunOne(cmb_batch* b) {
                     B.ctxMblk = b->geoX ? CTX_MBLK_X : ctxMblkFor(b->maxLen);
                     B.aCap = cap32(b->bfsA.n);
                     B.chain = getenv("CMB_BFS_CHAIN") ? (uint32_t)std::max(1, atoi(getenv("CMB_BFS_CHAIN"))) : BFS_CHAIN;
-                    B.gridX = getenv("CMB_BFS_GRID") ? (uint32_t)std::min<int>(BFS_GRID_CNT, std::max(1, atoi(getenv("CMB_BFS_GRID"))))
-                                                     : BFS_GRID_X;
-                    B.gridEv = getenv("CMB_BFS_GRID_EV") ? (uint32_t)std::max(1, atoi(getenv("CMB_BFS_GRID_EV"))) : BFS_GRID_EV;
+                    B.gridX = capBlocks(std::min<uint32_t>(BFS_GRID_CNT, envBlocks("CMB_BFS_GRID", BFS_GRID_X)));
+                    B.gridEv = capBlocks(envBlocks("CMB_BFS_GRID_EV", BFS_GRID_EV));
                     // (CMB_TEST_NARROW_WV: tests lower the bound so that the re-run on the 64-bit geometry is exercised)
                     B.narrowWv = getenv("CMB_TEST_NARROW_WV") ? (uint32_t)std::max(0, atoi(getenv("CMB_TEST_NARROW_WV"))) : 0xFFFFu;
                     B.nq = b->bfsCnt.p;
@@ -1190,17 +1194,19 @@ static int batchRunOne(cmb_batch* b) {
                     // up to 6 errors the frontier carries the in-index matrix on 32-bit words (GeoN32, dev_matrix.hpp: MXS_*); CMB_MATRIX64=1
                     // keeps the reference's 64-bit words (GeoN), as does a batch one of whose phases did not fit the small matrix
                     const bool small32 = !b->wide && b->k <= MXS_MAX_ED && !b->noSmallMatrix && !getenv("CMB_MATRIX64");
+                    const uint32_t startGrid = capBlocks(std::min<uint32_t>((nDfs + 255) / 256, BFS_GRID));
+                    gridLine(verbose, "k_bfs_start", nDfs, 256ull * startGrid);
                     if (b->geoX)
-                        hipLaunchKernelGGL(k_bfs_start<GeoX>, dim3(std::min<uint32_t>((nDfs + 255) / 256, BFS_GRID)), dim3(256), 0, s,
+                        hipLaunchKernelGGL(k_bfs_start<GeoX>, dim3(startGrid), dim3(256), 0, s,
                                            ix->d, b->stratW.p, B, b->dfs.p, nDfs, b->offs.p, b->gw, b->G.p, b->partsW.p, q);
                     else if (b->wide)
-                        hipLaunchKernelGGL(k_bfs_start<GeoW>, dim3(std::min<uint32_t>((nDfs + 255) / 256, BFS_GRID)), dim3(256), 0, s,
+                        hipLaunchKernelGGL(k_bfs_start<GeoW>, dim3(startGrid), dim3(256), 0, s,
                                            ix->d, b->stratW.p, B, b->dfs.p, nDfs, b->offs.p, b->gw, b->G.p, b->partsW.p, q);
                     else if (small32)
-                        hipLaunchKernelGGL(k_bfs_start<GeoN32>, dim3(std::min<uint32_t>((nDfs + 255) / 256, BFS_GRID)), dim3(256), 0, s,
+                        hipLaunchKernelGGL(k_bfs_start<GeoN32>, dim3(startGrid), dim3(256), 0, s,
                                            ix->d, b->strat.p, B, b->dfs.p, nDfs, b->offs.p, b->gw, b->G.p, b->parts.p, q);
                     else
-                        hipLaunchKernelGGL(k_bfs_start<GeoN>, dim3(std::min<uint32_t>((nDfs + 255) / 256, BFS_GRID)), dim3(256), 0, s,
+                        hipLaunchKernelGGL(k_bfs_start<GeoN>, dim3(startGrid), dim3(256), 0, s,
                                        ix->d, b->strat.p, B, b->dfs.p, nDfs, b->offs.p, b->gw, b->G.p, b->parts.p, q);
                     std::vector<uint32_t> hc(cntWords);
                     // passes between two looks at the queue sizes (a pass on a drained frontier costs the device ~4 us, a look costs the host a round trip)
@@ -1237,6 +1243,8 @@ static int batchRunOne(cmb_batch* b) {
                     if (getenv("CMB_VERBOSE"))
                         fprintf(stderr, "[bfs] %u tasks, %u passes, peak frontier %u, peak events %u, F %u, contexts %u, arena %u\n",
                                 nDfs, pass, peakQ, peakEv, pool[0], pool[1], pool[2]);
+                    gridLine(verbose, "k_bfs_pass", peakQ, 256ull * B.gridX); // (the largest frontier and the most events of a pass)
+                    gridLine(verbose, "k_bfs_pass_events", peakEv, 256ull * B.gridEv);
                     if (getenv("CMB_VERBOSE") && atoi(getenv("CMB_VERBOSE")) > 1)
                         for (uint32_t p2 = 0; p2 <= pass; p2++)
                             fprintf(stderr, "  pass %u: %u nodes, %u events\n", p2, hc[p2], hc[maxPass + 2 + p2]);
@@ -1284,11 +1292,13 @@ static int batchRunOne(cmb_batch* b) {
                     H.nq = b->bfsCnt.p;
                     H.blockCnt = b->bfsBlockCnt.p;
                     const uint32_t hLds = stratBytes;
+                    const uint32_t startGrid = capBlocks(std::min<uint32_t>((nDfs + 255) / 256, BFS_GRID)), passGrid = capBlocks(BFS_GRID);
+                    gridLine(verbose, "k_hbfs_start", nDfs, 256ull * startGrid);
                     if (b->wide)
-                        hipLaunchKernelGGL((k_hbfs<true, MAXP_WIDE>), dim3(std::min<uint32_t>((nDfs + 255) / 256, BFS_GRID)), dim3(256), hLds, s,
+                        hipLaunchKernelGGL((k_hbfs<true, MAXP_WIDE>), dim3(startGrid), dim3(256), hLds, s,
                                            ix->d, b->stratW.p, H, 0u, b->dfs.p, nDfs, b->maxLen, b->seq.p, b->partsW.p, q);
                     else
-                        hipLaunchKernelGGL(k_hbfs<true>, dim3(std::min<uint32_t>((nDfs + 255) / 256, BFS_GRID)), dim3(256), hLds, s,
+                        hipLaunchKernelGGL(k_hbfs<true>, dim3(startGrid), dim3(256), hLds, s,
                                        ix->d, b->strat.p, H, 0u, b->dfs.p, nDfs, b->maxLen, b->seq.p, b->parts.p, q);
                     std::vector<uint32_t> hc(cntWords);
                     uint32_t pass = 0, peakQ = 0;
@@ -1297,10 +1307,10 @@ static int batchRunOne(cmb_batch* b) {
                         const uint32_t upTo = std::min(pass + 16u, maxPass);
                         for (; pass < upTo; pass++)
                             if (b->wide)
-                                hipLaunchKernelGGL((k_hbfs<false, MAXP_WIDE>), dim3(BFS_GRID), dim3(256), hLds, s, ix->d, b->stratW.p, H, pass,
+                                hipLaunchKernelGGL((k_hbfs<false, MAXP_WIDE>), dim3(passGrid), dim3(256), hLds, s, ix->d, b->stratW.p, H, pass,
                                                    (const DfsTask*)nullptr, 0u, b->maxLen, b->seq.p, b->partsW.p, q);
                             else
-                                hipLaunchKernelGGL(k_hbfs<false>, dim3(BFS_GRID), dim3(256), hLds, s, ix->d, b->strat.p, H, pass,
+                                hipLaunchKernelGGL(k_hbfs<false>, dim3(passGrid), dim3(256), hLds, s, ix->d, b->strat.p, H, pass,
                                                (const DfsTask*)nullptr, 0u, b->maxLen, b->seq.p, b->parts.p, q);
                         HIPCHK(hipMemcpyAsync(hc.data(), b->bfsCnt.p, cntWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
                         HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
@@ -1310,6 +1320,7 @@ static int batchRunOne(cmb_batch* b) {
                     }
                     for (uint32_t p2 = 0; p2 <= pass && p2 < cntWords; p2++) peakQ = std::max(peakQ, hc[p2]);
                     if (getenv("CMB_VERBOSE")) fprintf(stderr, "[hbfs] %u tasks, %u passes, peak frontier %u\n", nDfs, pass, peakQ);
+                    gridLine(verbose, "k_hbfs_pass", peakQ, 256ull * passGrid); // (the largest frontier of a pass)
                     BfsBufs Bf{};
                     Bf.blockCnt = b->bfsBlockCnt.p;
                     hipLaunchKernelGGL(k_bfs_finish, dim3(1), dim3(256), 0, s, Bf, q);
@@ -1391,8 +1402,9 @@ static int batchRunOne(cmb_batch* b) {
             HIPCHK(hipStreamSynchronize(s));
             if (nItems) {
                 // (lanes of k_verify: 128 k / 256 k / 512 k -> 34.8 / 32.0 / 35.9 ms of the locate group on the headline workload, round 4)
-                const uint32_t vCap = getenv("CMB_V_SLOTS") ? (uint32_t)std::min(256 * 2048, std::max(256, atoi(getenv("CMB_V_SLOTS")))) / 256u * 256u : 256u * 1024u;
+                const uint32_t vCap = capSlots(envSlots("CMB_V_SLOTS", 256u * 1024u, 256u * 2048u));
                 const uint32_t vSlots = std::min<uint32_t>(((nItems + 255) / 256) * 256, vCap);
+                gridLine(verbose, "k_verify", nItems, vSlots);
                 // Edit distance: identical verifications (same read x strand, text window and bounds — the parts of
                 // one read seeding the same alignment) are performed once: k_verify only locates and emits a key per
                 // candidate, the keys are sorted and run-length encoded, k_verify_edit verifies the distinct ones and
@@ -1440,7 +1452,8 @@ static int batchRunOne(cmb_batch* b) {
                     if (nRuns && b->wideEdit) {
                         // 8 ... 13 errors: the band (up to 53 columns) needs the wide left margins of the 64-bit in-text matrix (dev_matrix.hpp:
                         // MXX_*, MXY_*): k_wide_filter sorts out the candidates that never reach their final column, k_verify_wide<true> verifies the rest
-                        const uint32_t fGrid = std::min<uint32_t>((nRuns + 255) / 256, 2048u);
+                        const uint32_t fGrid = capBlocks(std::min<uint32_t>((nRuns + 255) / 256, 2048u));
+                        gridLine(verbose, "k_wide_filter", nRuns, 256ull * fGrid);
                         // (every key, the slots a wavefront leaves unused when it retires a chunk — fewer than 64 of 256 —, a chunk per wavefront)
                         const size_t listNeed = (size_t)nRuns + nRuns / 3 + (size_t)fGrid * 4 * 256 + 512;
                         if (b->dpList.n < listNeed) b->dpList.alloc(listNeed + listNeed / 8);
@@ -1453,7 +1466,7 @@ static int batchRunOne(cmb_batch* b) {
                                            b->dpWork.p, b->dpList.p, cap32(b->dpList.n), q);
                         const uint32_t slotBytes = (vwRows(b->maxLen) + 1u) * VW_ROW_BYTES;
                         // (six wavefronts per SIMD: 1024 SIMDs x 6 x 64 lanes — forward pass and traceback wait for memory; a slot is 3 - 8 KB)
-                        const uint32_t dSlots = std::min<uint32_t>(((nRuns + 255) / 256) * 256, getenv("CMB_VW_SLOTS") ? (uint32_t)atoi(getenv("CMB_VW_SLOTS")) : 256u * 1536u);
+                        const uint32_t dSlots = std::min<uint32_t>(((nRuns + 255) / 256) * 256, capSlots(envSlots("CMB_VW_SLOTS", 256u * 1536u)));
                         if (b->dpSlab.n < (size_t)slotBytes * dSlots) b->dpSlab.alloc((size_t)slotBytes * dSlots);
                         hipLaunchKernelGGL(kWide, dim3(dSlots / 256), dim3(256), 0, s, ix->d, b->offs.p, b->maxLen, b->seq.p, b->G.p, b->gw,
                                            (const uint4*)nullptr, cap32(b->dpList.n), b->vkeysA.p, b->vcounts.p, b->dpList.p, b->dpWork.p + 1, b->dpSlab.p, slotBytes, q);
@@ -1462,6 +1475,7 @@ static int batchRunOne(cmb_batch* b) {
                             HIPCHK(hipMemcpyAsync(hw, b->dpWork.p, sizeof(hw), hipMemcpyDeviceToHost, s));
                             HIPCHK(hipStreamSynchronize(s));
                             fprintf(stderr, "[verify] %u list slots (survivors and holes) for %u distinct candidates\n", hw[1], nRuns);
+                            gridLine(verbose, "k_verify_wide", hw[1], dSlots); // (it loops over the list the filter left)
                         }
                     } else if (nRuns) {
                         // staged verification (kernels.hpp: k_verify_stage): one launch per nb 32-row matrix blocks,
@@ -1481,8 +1495,9 @@ static int batchRunOne(cmb_batch* b) {
                         if (b->vsN.n < nStages + 2) b->vsN.alloc(nStages + 2);
                         HIPCHK(hipMemsetAsync(b->vsN.p, 0, (nStages + 2) * sizeof(uint32_t), s));
                         const uint32_t listCap = cap32(b->vsC[0].n);
-                        const uint32_t gridCap = getenv("CMB_STAGE_GRID") ? (uint32_t)std::max(256, atoi(getenv("CMB_STAGE_GRID"))) : 8192u;
+                        const uint32_t gridCap = capBlocks(envBlocks("CMB_STAGE_GRID", 8192u));
                         const uint32_t grid = std::min<uint32_t>((nRuns + 255) / 256, gridCap);
+                        gridLine(verbose, "k_verify_stage", nRuns, 256ull * grid); // (the first stage: the later ones take its survivors)
                         VStageList L0{b->vsA[0].p, b->vsB[0].p, b->vsC[0].p}, L1{b->vsA[1].p, b->vsB[1].p, b->vsC[1].p};
                         // k <= 4: the matrix on 32-bit words (dev_matrix.hpp); CMB_MATRIX_WIDE=1 keeps the 64-bit words
                         const bool w32 = b->k <= MX32_MAX_ED && !getenv("CMB_MATRIX_WIDE");
@@ -1533,8 +1548,9 @@ static int batchRunOne(cmb_batch* b) {
                 HIPCHK(hipStreamSynchronize(s));
                 const uint32_t nTb = hcnt[7];
                 if (nTb) {
-                    const uint32_t slotCap = getenv("CMB_TB_SLOTS") ? (uint32_t)std::max(256, atoi(getenv("CMB_TB_SLOTS"))) / 256u * 256u : 512u * 1024u; // (measured 64 k … 2 M slots: 84 / 49 / 34.4 / 32.8 / 31 / 29 ms alone; 512 k best beside other sub-batches)
+                    const uint32_t slotCap = capSlots(envSlots("CMB_TB_SLOTS", 512u * 1024u)); // (measured 64 k … 2 M slots: 84 / 49 / 34.4 / 32.8 / 31 / 29 ms alone; 512 k best beside other sub-batches)
                     const uint32_t tSlots = std::min<uint32_t>(((nTb + 255) / 256) * 256, slotCap);
+                    gridLine(verbose, "k_traceback", nTb, tSlots);
                     // 64-byte lines of 16 narrow (k <= 4) or 8 wide trace rows (a group is written whole)
                     const bool narrow = b->k <= TBN_MAX_ED && !getenv("CMB_TRACE_WIDE");
                     const uint32_t tLines = narrow ? (vRows(b->maxLen) + 15u) / 16u + 2u : (vRows(b->maxLen) + 7u) / 8u + 2u;
@@ -1709,7 +1725,7 @@ static int batchRunOne(cmb_batch* b) {
                     b->alnOps.alloc(b->alnRec.n * std::max<size_t>(b->alnStride, 2u * 7u + 3u));
                 }
                 if (total) {
-                    const uint32_t cSlots = (uint32_t)std::min<uint64_t>(((total + 255) / 256) * 256, 512u * 1024u);
+                    const uint32_t cSlots = capSlots((uint32_t)std::min<uint64_t>(((total + 255) / 256) * 256, 512u * 1024u));
                     const bool narrow = b->k <= TBN_MAX_ED && !getenv("CMB_TRACE_WIDE");
                     const uint32_t tLines = narrow ? (vRows(b->maxLen) + 15u) / 16u + 2u : (vRows(b->maxLen) + 7u) / 8u + 2u;
                     if (b->vW.n < (size_t)tLines * 8 * cSlots) b->vW.alloc((size_t)tLines * 8 * cSlots);
@@ -1725,14 +1741,17 @@ static int batchRunOne(cmb_batch* b) {
                         // (k_cigar's match words reach 9 columns right of the diagonal: kernels.hpp, k_cigar_wide)
                         const uint32_t wSlots = std::min<uint32_t>(cSlots, 256u * 256u);
                         const uint32_t slotBytes = (vwRows(b->maxLen) + 1u) * VW_ROW_BYTES;
+                        gridLine(verbose, "k_cigar_wide", total, wSlots);
                         if (b->dpSlab.n < (size_t)slotBytes * wSlots) b->dpSlab.alloc((size_t)slotBytes * wSlots);
                         hipLaunchKernelGGL(k_cigar_wide, dim3(wSlots / 256), dim3(256), 0, s, ix->d, b->offs.p, b->G.p, b->gw, b->fout.p, b->foutRead.p,
                                            (uint64_t)total, b->dpSlab.p, slotBytes, ix->seqStartsDev.p, ix->nSeqsDev, b->alnOps.p, b->alnStride,
                                            b->alnRec.p, b->cnt.p + 3, 0u);
-                    } else
-                    hipLaunchKernelGGL(kc, dim3(cSlots / 256), dim3(256), 0, s, ix->d, b->offs.p, mfc, b->fout.p, b->foutRead.p,
-                                       (uint64_t)total, vp, ix->seqStartsDev.p, ix->nSeqsDev, b->alnOps.p, b->alnStride, b->alnRec.p,
-                                       b->cnt.p + 3, (b->metric != CMB_METRIC_EDIT || b->k == 0) ? 1u : 0u);
+                    } else {
+                        gridLine(verbose, "k_cigar", total, cSlots);
+                        hipLaunchKernelGGL(kc, dim3(cSlots / 256), dim3(256), 0, s, ix->d, b->offs.p, mfc, b->fout.p, b->foutRead.p,
+                                           (uint64_t)total, vp, ix->seqStartsDev.p, ix->nSeqsDev, b->alnOps.p, b->alnStride, b->alnRec.p,
+                                           b->cnt.p + 3, (b->metric != CMB_METRIC_EDIT || b->k == 0) ? 1u : 0u);
+                    }
                 }
                 tm.end("k_cigar");
                 HIPCHK(hipGetLastError());
@@ -1798,7 +1817,8 @@ int moveCigarsOnText(cmb_index* textIndex, hipStream_t s, const uint64_t* offs, 
             hipLaunchKernelGGL(k_match_words, dim3((unsigned)((nW + 255) / 256)), dim3(256), 0, s, G, gw, offs, 2 * nReads, mf.nBlk, mfull.p);
             mf.p = mfull.p;
         }
-        const uint32_t cSlots = (uint32_t)std::min<uint64_t>(((nOcc + 255) / 256) * 256, 512u * 1024u);
+        const uint32_t cSlots = capSlots((uint32_t)std::min<uint64_t>(((nOcc + 255) / 256) * 256, 512u * 1024u));
+        const bool verbose = getenv("CMB_VERBOSE") != nullptr;
         if (!gapless && k > CIGAR_BLOCK_WORDS_MAX_ED) {
             // beyond 9 errors (k_cigar's match words reach 9 columns right of the diagonal): the matrix with the wide left margin, as for
             // the FM-index batches (kernels.hpp: k_cigar_wide; match words straight from the read's bit-strings)
@@ -1806,6 +1826,7 @@ int moveCigarsOnText(cmb_index* textIndex, hipStream_t s, const uint64_t* offs, 
             const uint32_t slotBytes = (vwRows(maxLen) + 1u) * VW_ROW_BYTES;
             DevBuf<uint8_t> slab;
             slab.alloc((size_t)slotBytes * wSlots);
+            gridLine(verbose, "k_cigar_wide", nOcc, wSlots);
             hipLaunchKernelGGL(k_cigar_wide, dim3(wSlots / 256), dim3(256), 0, s, d, offs, G, gw, (const uint4*)occs, occRead, nOcc, slab.p, slotBytes,
                                seqStartsDev, nSeqs, ops, stride, (AlnRec*)aln, flagWord, 0u);
             HIPCHK(hipGetLastError());
@@ -1820,6 +1841,7 @@ int moveCigarsOnText(cmb_index* textIndex, hipStream_t s, const uint64_t* offs, 
         auto kc = k_cigar<false, false>;
         if (narrow) kc = text2 ? k_cigar<true, true> : k_cigar<true, false>;
         else if (text2) kc = k_cigar<false, true>;
+        gridLine(verbose, "k_cigar", nOcc, cSlots);
         hipLaunchKernelGGL(kc, dim3(cSlots / 256), dim3(256), 0, s, d, offs, mf, (const uint4*)occs, occRead, nOcc, vp, seqStartsDev, nSeqs, ops,
                            stride, (AlnRec*)aln, flagWord, gapless ? 1u : 0u);
         HIPCHK(hipGetLastError());
@@ -2244,7 +2266,8 @@ static int verifyDirect(cmb_index* idx, const char* pattern, uint32_t plen, cons
         ctr.alloc(CMB_CNT_MAX);
         HIPCHK(hipMemset(cnt.p, 0, 32));
         HIPCHK(hipMemset(ctr.p, 0, CMB_CNT_MAX * 8));
-        const uint32_t slots = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(((n + 255) / 256) * 256, 256), 65536);
+        const uint32_t slots = capSlots((uint32_t)std::min<uint64_t>(std::max<uint64_t>(((n + 255) / 256) * 256, 256), 65536));
+        const bool verbose = getenv("CMB_VERBOSE") != nullptr;
         const bool narrow = max_ed <= TBN_MAX_ED && !getenv("CMB_TRACE_WIDE");
         const uint32_t tLines = narrow ? ((uint32_t)VROWS + 15u) / 16u + 2u : ((uint32_t)VROWS + 7u) / 8u + 2u;
         vW.alloc((size_t)tLines * 8 * slots);
@@ -2267,8 +2290,9 @@ static int verifyDirect(cmb_index* idx, const char* pattern, uint32_t plen, cons
         if (n && dp) {
             DevBuf<uint8_t> slab;
             const uint32_t slotBytes = (vwRows(mlen) + 1u) * VW_ROW_BYTES;
-            const uint32_t dSlots = (uint32_t)std::min<uint64_t>(((n + 255) / 256) * 256, 256u * 64u);
+            const uint32_t dSlots = capSlots((uint32_t)std::min<uint64_t>(((n + 255) / 256) * 256, 256u * 64u));
             slab.alloc((size_t)slotBytes * dSlots);
+            gridLine(verbose, "k_verify_wide", n, dSlots);
             auto kWide = k_verify_wide<false, WxTen>;
             if (max_ed > MX_MAX_ED) kWide = k_verify_wide<false, WxThirteen>;
             hipLaunchKernelGGL(kWide, dim3(dSlots / 256), dim3(256), 0, 0, idx->d, offs.p, mlen, seq.p, G.p, gw, items.p, (uint32_t)n,
@@ -2276,12 +2300,14 @@ static int verifyDirect(cmb_index* idx, const char* pattern, uint32_t plen, cons
                                slotBytes, q);
             HIPCHK(hipDeviceSynchronize());
         } else if (n) {
+            gridLine(verbose, "k_verify", n, slots);
             hipLaunchKernelGGL(k_verify<false>, dim3(slots / 256), dim3(256), 0, 0, idx->d, offs.p, mlen, gw, seq.p, mf,
                                items.p, (uint32_t)n, tbq.p, (uint32_t)tbq.n, (unsigned long long*)nullptr, q);
             HIPCHK(hipMemcpy(hc, cnt.p, 32, hipMemcpyDeviceToHost));
             if (hc[7]) {
                 auto kTrace = k_traceback<false, false>;
                 if (narrow) kTrace = idx->d.text2 ? k_traceback<true, true> : k_traceback<true, false>;
+                gridLine(verbose, "k_traceback", hc[7], slots);
                 hipLaunchKernelGGL(kTrace, dim3(slots / 256), dim3(256), 0, 0,
                                    idx->d, offs.p, mf, tbq.p, hc[7], vp, q, 0u);
             }

@@ -12,6 +12,8 @@
 
 #include <rocprim/device/device_scan.hpp> // (after <cstring>: its headers call memset unqualified)
 
+#include "host_grid.hpp" // CMB_TEST_GRID_CAP and the clamps of the geometry knobs (no HIP: a CPU program tests it)
+
 #define HIPCHK(expr)                                                                                  \
     do {                                                                                              \
         hipError_t _e = (expr);                                                                       \

@@ -1032,6 +1032,7 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
             sx.kmerSize = ix->kmerSize;
         }
         uint32_t hcnt[8];
+        const bool verbose = getenv("CMB_VERBOSE") != nullptr;
         if ((b->wide ? b->partsW.n : b->parts.n) < (size_t)2 * nReads) { // per-read scratch of a slice
             b->seq.alloc((size_t)2 * nReads * b->maxLen);
             b->G.alloc((size_t)nReads * 8 * b->gw);
@@ -1058,9 +1059,11 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
             // ---- prologue
             tm.begin();
             {
-                const unsigned grid = (unsigned)std::min<uint64_t>(((uint64_t)tasksRS + 63) / 64, 256 * 64);
+                const unsigned grid = capBlocks((unsigned)std::min<uint64_t>(((uint64_t)tasksRS + 63) / 64, 256 * 64));
                 const uint64_t nWork = (uint64_t)tasksRS * maxSearches;
-                const unsigned gridE = (unsigned)std::min<uint64_t>((nWork + 63) / 64, 256 * 64);
+                const unsigned gridE = capBlocks((unsigned)std::min<uint64_t>((nWork + 63) / 64, 256 * 64));
+                gridLine(verbose, "k_mvs_parts", tasksRS, 64ull * grid);
+                gridLine(verbose, "k_mvs_exact", nWork, 64ull * gridE);
                 const size_t exLdsBytes = (size_t)P * 3 * 64 * sizeof(uint4);
                 if (b->wide) {
                     auto kp = b->sPartition == 0 ? k_mvs_parts<0, MAXP_WIDE> : b->sPartition == 1 ? k_mvs_parts<1, MAXP_WIDE> : k_mvs_parts<2, MAXP_WIDE>;
@@ -1107,7 +1110,9 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                 auto kNaiveStart = edit ? k_mvs_naive<true, true, false> : k_mvs_naive<false, true, false>;
                 auto kNaivePass = edit ? k_mvs_naive<true, false, false> : k_mvs_naive<false, false, false>;
                 if (edit && b->k > MX_MAX_ED) kNaiveStart = k_mvs_naive<true, true, true>, kNaivePass = k_mvs_naive<true, false, true>;
-                hipLaunchKernelGGL(kNaiveStart, dim3((tasksRS + 255) / 256), dim3(256), 0, s, ix->d, N, 0u,
+                const uint32_t nvStart = capBlocks((tasksRS + 255) / 256), nvGrid = capBlocks(BFS_GRID);
+                gridLine(verbose, "k_mvs_naive_start", tasksRS, 256ull * nvStart);
+                hipLaunchKernelGGL(kNaiveStart, dim3(nvStart), dim3(256), 0, s, ix->d, N, 0u,
                                    (const uint8_t*)b->psel.p, tasksRS, dOffs, b->gw, b->G.p, b->seq.p, b->maxLen, b->k, q);
                 std::vector<uint32_t> hc(cntWords);
                 uint32_t pass = 0, peakQ = 0;
@@ -1115,7 +1120,7 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                 while (!drained && pass < maxPassN) {
                     const uint32_t upTo = std::min(pass + 16u, maxPassN);
                     for (; pass < upTo; pass++)
-                        hipLaunchKernelGGL(kNaivePass, dim3(BFS_GRID), dim3(256), 0, s, ix->d, N, pass,
+                        hipLaunchKernelGGL(kNaivePass, dim3(nvGrid), dim3(256), 0, s, ix->d, N, pass,
                                            (const uint8_t*)b->psel.p, tasksRS, dOffs, b->gw, b->G.p, b->seq.p, b->maxLen, b->k, q);
                     HIPCHK(hipMemcpyAsync(hc.data(), b->nvCnt.p, cntWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
                     HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
@@ -1124,6 +1129,7 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                     drained = hc[pass] == 0;
                 }
                 for (uint32_t p2 = 0; p2 <= pass && p2 < cntWords; p2++) peakQ = std::max(peakQ, hc[p2]);
+                gridLine(verbose, "k_mvs_naive_pass", peakQ, 256ull * nvGrid); // (the largest frontier of a pass)
                 tm.end("k_naive");
                 HIPCHK(hipGetLastError());
                 if (hcnt[3] & MVS_NAIVE_STOP) {
@@ -1156,11 +1162,13 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                 H.nq = b->bfsCnt.p;
                 H.blockCnt = b->blockCnt.p;
                 H.fmX = b->fm.p;
+                const uint32_t startGrid = capBlocks(std::min<uint32_t>((nTasks + 255) / 256, BFS_GRID)), passGrid = capBlocks(BFS_GRID);
+                gridLine(verbose, "k_mvs_hbfs_start", nTasks, 256ull * startGrid);
                 if (b->wide)
-                    hipLaunchKernelGGL((k_mvs_hbfs<true, MAXP_WIDE>), dim3(std::min<uint32_t>((nTasks + 255) / 256, BFS_GRID)), dim3(256), 0, s, ix->d, b->stratW.p,
+                    hipLaunchKernelGGL((k_mvs_hbfs<true, MAXP_WIDE>), dim3(startGrid), dim3(256), 0, s, ix->d, b->stratW.p,
                                        H, 0u, b->tasks.p, nTasks, b->maxLen, b->seq.p, b->partsW.p, q);
                 else
-                    hipLaunchKernelGGL((k_mvs_hbfs<true, MAXP>), dim3(std::min<uint32_t>((nTasks + 255) / 256, BFS_GRID)), dim3(256), 0, s, ix->d, b->strat.p, H, 0u,
+                    hipLaunchKernelGGL((k_mvs_hbfs<true, MAXP>), dim3(startGrid), dim3(256), 0, s, ix->d, b->strat.p, H, 0u,
                                        b->tasks.p, nTasks, b->maxLen, b->seq.p, b->parts.p, q);
                 std::vector<uint32_t> hc(cntWords);
                 uint32_t pass = 0, peakQ = 0;
@@ -1169,10 +1177,10 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                     const uint32_t upTo = std::min(pass + 16u, maxPass);
                     for (; pass < upTo; pass++)
                         if (b->wide)
-                            hipLaunchKernelGGL((k_mvs_hbfs<false, MAXP_WIDE>), dim3(BFS_GRID), dim3(256), 0, s, ix->d, b->stratW.p, H, pass, (const MvTask*)nullptr,
+                            hipLaunchKernelGGL((k_mvs_hbfs<false, MAXP_WIDE>), dim3(passGrid), dim3(256), 0, s, ix->d, b->stratW.p, H, pass, (const MvTask*)nullptr,
                                                0u, b->maxLen, b->seq.p, b->partsW.p, q);
                         else
-                            hipLaunchKernelGGL((k_mvs_hbfs<false, MAXP>), dim3(BFS_GRID), dim3(256), 0, s, ix->d, b->strat.p, H, pass, (const MvTask*)nullptr, 0u,
+                            hipLaunchKernelGGL((k_mvs_hbfs<false, MAXP>), dim3(passGrid), dim3(256), 0, s, ix->d, b->strat.p, H, pass, (const MvTask*)nullptr, 0u,
                                                b->maxLen, b->seq.p, b->parts.p, q);
                     HIPCHK(hipMemcpyAsync(hc.data(), b->bfsCnt.p, cntWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
                     HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
@@ -1181,6 +1189,7 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                     drained = hc[pass] == 0;
                 }
                 for (uint32_t p2 = 0; p2 <= pass && p2 < cntWords; p2++) peakQ = std::max(peakQ, hc[p2]);
+                gridLine(verbose, "k_mvs_hbfs_pass", peakQ, 256ull * passGrid); // (the largest frontier of a pass)
                 MvBufs Bf{};
                 Bf.blockCnt = b->blockCnt.p;
                 hipLaunchKernelGGL(k_mvs_finish, dim3(1), dim3(256), 0, s, Bf, q);
@@ -1240,9 +1249,8 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                 // the children in slots (mvExpandSlots; CMB_MOVE_POS64=1: the general 40-bit path)
                 const bool smallPos = !b->wide && ix->d.n < 0xFFFFFFF0ull && ix->d.fwd.runs < 0xFFFFFFF0ull && ix->d.rev.runs < 0xFFFFFFF0ull && !getenv("CMB_MOVE_POS64");
                 B.chain = getenv("CMB_MVS_CHAIN") ? (uint32_t)std::max(1, atoi(getenv("CMB_MVS_CHAIN"))) : (smallPos ? MVS_CHAIN_SMALL : MVS_CHAIN);
-                B.gridX = getenv("CMB_MVS_GRID") ? (uint32_t)std::min<int>(BFS_GRID, std::max(1, atoi(getenv("CMB_MVS_GRID"))))
-                                                 : (b->wide ? MVS_GRID_X_WIDE : smallPos ? MVS_GRID_X_SMALL : MVS_GRID_X);
-                B.gridEv = BFS_GRID_EV;
+                B.gridX = capBlocks(std::min<uint32_t>(BFS_GRID, envBlocks("CMB_MVS_GRID", b->wide ? MVS_GRID_X_WIDE : smallPos ? MVS_GRID_X_SMALL : MVS_GRID_X)));
+                B.gridEv = capBlocks(BFS_GRID_EV);
                 B.nq = b->bfsCnt.p;
                 B.ne = b->bfsCnt.p + (maxPass + 2);
                 B.pool = b->bfsCnt.p + 2 * (maxPass + 2);
@@ -1252,7 +1260,8 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                 B.narrowWv = getenv("CMB_TEST_NARROW_WV") ? (uint32_t)std::max(0, atoi(getenv("CMB_TEST_NARROW_WV"))) : 0xFFFFu;
                 // up to 6 errors the in-index matrix runs on 32-bit words (GeoN32, dev_matrix.hpp: MXS_*) unless a phase did not fit it (CMB_MATRIX64=1: never)
                 const bool small32 = !b->wide && b->k <= MXS_MAX_ED && !b->noSmallMatrix && !getenv("CMB_MATRIX64");
-                const dim3 gStart(std::min<uint32_t>((nTasks + 255) / 256, BFS_GRID));
+                const dim3 gStart(capBlocks(std::min<uint32_t>((nTasks + 255) / 256, BFS_GRID)));
+                gridLine(verbose, "k_mvs_start", nTasks, 256ull * gStart.x);
                 if (geoX)
                     hipLaunchKernelGGL(k_mvs_start<GeoX>, gStart, dim3(256), 0, s, b->stratW.p, B, b->tasks.p, nTasks, dOffs, b->gw, b->G.p, b->partsW.p, q);
                 else if (b->wide)
@@ -1290,6 +1299,8 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                     peakEv = std::max(peakEv, hc[maxPass + 2 + p2]);
                 }
                 const uint32_t* pool = hc.data() + 2 * (maxPass + 2);
+                gridLine(verbose, "k_mvs_pass", peakQ, 256ull * B.gridX); // (the largest frontier and the most events of a pass)
+                gridLine(verbose, "k_mvs_pass_events", peakEv, 256ull * B.gridEv);
                 if (getenv("CMB_VERBOSE"))
                     fprintf(stderr, "[mvs] %u tasks, %u passes, peak frontier %u, peak events %u, F %u, contexts %u, arena %u\n", nTasks, pass, peakQ, peakEv,
                             pool[0], pool[1], pool[2]);

@@ -504,8 +504,6 @@ def test_alignments_cigar_and_sequence(world, oracle_built, spec, metric, k):
     """SURVEY.md §8f rank 1 on the device: the CIGAR of every final occurrence (k_cigar) is what the reference's
     findCIGAR gives for (read on its strand, text[begin, end), distance) — asked of the oracle's restatement, which is
     pinned to the reference's findCIGAR by the golden vectors — and the sequence assignment is findSeqName's."""
-    import os
-    import subprocess
     g = world["genome"]
     reads = synth.sample_reads(g, 1500, 150, seed=700 + k, n_frac=0.01)
     # reads across sequence boundaries and with edits at their very ends
@@ -513,12 +511,21 @@ def test_alignments_cigar_and_sequence(world, oracle_built, spec, metric, k):
     for s in starts[1:-1][:20]:
         reads.append(g[int(s) - 70:int(s) + 80].tobytes())
     reads += _edge_reads(g, 200, max(k, 1), seed=71)
+    _check_alignments(world, oracle_built, spec, metric, k, reads, 1000 if k else 300)
+
+
+def _check_alignments(world, oracle_built, spec, metric, k, reads, min_occ):
+    """the assertions of test_alignments_cigar_and_sequence on a read set with more than min_occ occurrences; returns their number"""
+    import os
+    import subprocess
+    g = world["genome"]
+    starts = np.asarray(world["ix"].seq_starts, dtype=np.int64)
     b = ca.Batch(world["dev"], ca.SearchStrategy(spec, metric, "dynamic"), k, reads)
     b.want_alignments()
     b.run()
     occ, offs, _ = b.results()
     aln, ops = b.alignments()
-    assert len(aln) == len(occ) > (1000 if k else 300)
+    assert len(aln) == len(occ) > min_occ
     text = g.tobytes()
     comp = bytes.maketrans(b"ACGT", b"TGCA")
     cmds, who = [], []
@@ -554,6 +561,7 @@ def test_alignments_cigar_and_sequence(world, oracle_built, spec, metric, k):
     o2, f2, _ = ca.match_batch(world["dev"], ca.SearchStrategy(spec, metric, "dynamic"), k, reads)
     assert np.array_equal(o2, occ) and np.array_equal(f2, offs)
     b.close()
+    return len(occ)
 
 
 @pytest.mark.parametrize("spec,metric,x,min_identity", [("columba", "edit", 0, 96), ("columba", "edit", 1, 96),
