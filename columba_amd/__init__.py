@@ -48,7 +48,7 @@ EXPORTS = [
     "cmb_sam_pe", "cmb_sam_unpaired", "cmb_sam_unmapped_pe", "cmb_pair_sam", "cmb_pair_infer",
     "cmb_pair_best_create", "cmb_pair_best_set_trim", "cmb_pair_best_cutoff", "cmb_pair_best_seed", "cmb_pair_best_advance", "cmb_pair_best_supply", "cmb_pair_best_sam",
     "cmb_pair_best_destroy",
-    "cmb_read_prepare", "cmb_batch_sam", "cmb_batch_sam_device", "cmb_sam_device_mapq", "cmb_batch_filter_per_strand", "cmb_match_best", "cmb_best_sizes", "cmb_best_results",
+    "cmb_read_prepare", "cmb_batch_sam", "cmb_batch_sam_device", "cmb_pair_sam_device", "cmb_sam_device_mapq", "cmb_batch_filter_per_strand", "cmb_match_best", "cmb_best_sizes", "cmb_best_results",
     "cmb_best_destroy", "cmb_match_best_device", "cmb_best_host_reads", "cmb_best_sam_device", "cmb_best_timings",
     "cmb_move_create", "cmb_move_destroy", "cmb_move_device_bytes", "cmb_move_info", "cmb_move_complete_range", "cmb_move_rows",
     "cmb_move_extend_batch", "cmb_move_extend_bench", "cmb_move_locate_batch", "cmb_move_match_exact", "cmb_move_last_timings", "cmb_move_kmer_table",
@@ -171,6 +171,10 @@ class PairParams(C.Structure):
                 ("unmapped_records", C.c_int)]
 
 
+class PairDeviceStats(C.Structure):
+    _fields_ = [("host_pairs", C.c_uint64), ("mapped_pairs", C.c_uint64), ("device_records", C.c_uint64)]
+
+
 class PairInferred(C.Structure):
     """cmb_pair_inferred"""
     _fields_ = [("n_pairs", C.c_uint64), ("inferred", C.c_uint32), ("orientation", C.c_uint32), ("max_insert", C.c_uint32),
@@ -281,6 +285,8 @@ def lib():
         L.cmb_batch_sam.restype = C.c_int64
         L.cmb_batch_sam.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, u64]
         L.cmb_batch_sam_device.argtypes = [vp, C.POINTER(SamInputs), i32, i32, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
+        L.cmb_pair_sam_device.argtypes = [vp, vp, C.POINTER(PairParams), C.POINTER(SamInputs), C.POINTER(SamInputs), C.POINTER(vp), C.POINTER(u64),
+                                          C.POINTER(PairDeviceStats)]
         L.cmb_sam_device_mapq.argtypes = [u32, vp]
         L.cmb_batch_filter_per_strand.argtypes = [vp, i32]
         L.cmb_trim_occurrence.argtypes = [vp, vp, u32, u32, i32, vp, vp, vp, u32, C.POINTER(u32), C.POINTER(i32)]
@@ -1348,6 +1354,52 @@ def pair_chunk_sam(index: "Index", strategy: "SearchStrategy", max_distance: int
         text.append(t)
         mapped_pairs += n > 0
     return "".join(text), mapped_pairs
+
+
+def pair_batches_sam_device(batch1: "Batch", batch2: "Batch", ids1, ids2, quals1, quals2, seq_names, orientation: int = ORIENTATION_FR,
+                            max_frag: int = 500, min_frag: int = 0, discordant_allowed: bool = True, unmapped_records: bool = True):
+    """cmb_pair_sam_device on two batches that have run (read 1 and read 2 of every pair, with alignments, every strand filtered
+    by itself): (SAM text as bytes, {"host_pairs", "mapped_pairs", "device_records"}).  ids / quals / seq_names as for
+    Batch.sam_device_bytes; quals None or an empty entry: an empty quality."""
+    keep, inputs = [], []
+    for b, ids, quals in ((batch1, ids1, quals1), (batch2, ids2, quals2)):
+        bi, oi = pack_fields(ids)
+        bn, on = pack_fields(seq_names)
+        bq, oq = pack_fields(quals) if quals is not None else (None, None)
+        if oi.shape[0] - 1 != b.n_reads or (oq is not None and oq.shape[0] - 1 != b.n_reads):
+            raise ValueError("one identifier and one quality per read")
+        keep.append((bi, oi, bn, on, bq, oq))
+        inputs.append(SamInputs(_p(b._packed[0]), _p(bi), _p(oi), _p(bq) if bq is not None else None, _p(oq) if oq is not None else None,
+                                _p(bn), _p(on), on.shape[0] - 1))
+    prm = PairParams(orientation, max_frag, min_frag, int(discordant_allowed), int(unmapped_records))
+    text, n, st = C.c_void_p(), C.c_uint64(), PairDeviceStats()
+    _chk(lib().cmb_pair_sam_device(batch1.h, batch2.h, C.byref(prm), C.byref(inputs[0]), C.byref(inputs[1]), C.byref(text), C.byref(n), C.byref(st)))
+    out = C.string_at(text.value, n.value) if n.value else b""
+    return out, {"host_pairs": int(st.host_pairs), "mapped_pairs": int(st.mapped_pairs), "device_records": int(st.device_records)}
+
+
+def pair_chunk_sam_device(index: "Index", strategy: "SearchStrategy", max_distance: int, reads1, reads2, ids1, ids2, quals1, quals2, seq_names,
+                          orientation: int = ORIENTATION_FR, max_frag: int = 500, min_frag: int = 0, discordant_allowed: bool = True,
+                          unmapped_records: bool = True):
+    """pair_chunk_sam(..., per_strand=True) with the pairing and the records on the device (cmb_pair_sam_device): both mates through
+    the GPU matcher (one batch each, with alignments, every strand filtered by itself), their lists stay in HBM, the concordant and
+    the both-unmapped pairs are written there and the others go through cmb_pair_sam on the host.  quals1 / quals2: one quality
+    per read (an empty one prints as pair_chunk_sam prints it), or None for no qualities.  Returns (SAM text, number of properly or
+    discordantly mapped pairs, {"host_pairs", "mapped_pairs", "device_records"})."""
+    batches = []
+    try:
+        for reads in (reads1, reads2):
+            b = Batch(index, strategy, max_distance, reads=reads)
+            batches.append(b)
+            b.want_alignments()
+            _chk(lib().cmb_batch_filter_per_strand(b.h, 1))
+            b.run()
+        text, stats = pair_batches_sam_device(batches[0], batches[1], ids1, ids2, quals1, quals2, seq_names, orientation, max_frag, min_frag,
+                                              discordant_allowed, unmapped_records)
+        return text.decode(), stats["mapped_pairs"], stats
+    finally:
+        for b in batches:
+            b.close()
 
 
 def pair_chunk_sam_best(index: "Index", strategy: "SearchStrategy", reads1, reads2, ids1, ids2, quals1, quals2, seq_names, x: int = 0,

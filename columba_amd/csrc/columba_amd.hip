@@ -6,6 +6,7 @@
 #include "host_util.hpp"
 #include "kernels.hpp"
 #include "dev_sam.hpp"
+#include "dev_pair.hpp"
 #include "dev_best.hpp"
 
 #include <chrono>
@@ -612,6 +613,11 @@ struct cmb_batch {
     SamDeviceBufs sam;
     DevBuf<uint32_t> samHostList;
     PinnedBuf<char> samOut;
+    // cmb_pair_sam_device (this batch holds read 1 of every pair): the plan of the concordant pairs; per pair the SAM lines the device
+    // writes and whether it counts as mapped, and the scan that sums either (64 bits: no field of a packed word to run over)
+    DevBuf<PairPlan> pairPlan;
+    DevBuf<uint64_t> pairRecords, pairSums;
+    DevBuf<uint32_t> pairMapped;
     // cmb_verify_batch_staged: candidates given by the caller take the place of the search's in-text items, and the
     // raw text occurrences (before the filter) are what is handed back
     std::vector<uint4> presetItems;
@@ -2794,6 +2800,182 @@ extern "C" int cmb_batch_sam_device(cmb_batch* b, const cmb_sam_inputs* in, int 
             parts.push_back(std::move(p));
         }
         return samDeviceOver(b->ix, parts, in, unmapped_records, xa_tag, b->samOut, text, length, host_reads);
+    } catch (const std::exception& e) {
+        return fail(CMB_ERR_DEVICE, e.what());
+    }
+}
+
+// ---- read pairs in ALL mode: both mates' lists stay in HBM, the pairs are formed and their records written there (dev_pair.hpp).  The
+// driver is the single-end one — inputs up (samUpload, once per mate), plan, the host's pairs spliced in (samSplice), scan (samScan),
+// write — with sub-batch j of the two batches on the stream of read 1's.  A pair the device does not handle (an occurrence over the
+// end of its sequence or without a sequence, or lists without a concordant pair) is formatted by cmb_pair_sam from the batches' host
+// copies, trimmed as the host adapters do (cmb_trim_occurrence with edit distance).
+namespace {
+struct PairHostRead { // one mate as cmb_pair_sam takes it
+    std::string id, seq, rc, qual, rq;
+    std::vector<BestOcc> occs;
+    std::vector<cmb_pair_occ> po;
+    cmb_pair_read view() const { return cmb_pair_read{id.c_str(), seq.c_str(), rc.c_str(), qual.c_str(), rq.c_str(), po.data(), (uint32_t)po.size()}; }
+};
+void pairHostRead(PairHostRead& h, cmb_index* idx, const cmb_batch* c, uint32_t i, const cmb_sam_inputs* in, uint64_t gi, uint64_t charBase) {
+    const uint64_t o0 = charBase + c->hostOffs[i], o1 = charBase + c->hostOffs[i + 1];
+    h.seq = cleanReadSeq(std::string(in->seqs + o0, in->seqs + o1));
+    h.rc = revComplWithN(h.seq);
+    h.id = cleanSeqID(std::string(in->ids + in->id_offs[gi], in->ids + in->id_offs[gi + 1]));
+    h.qual = in->quals ? std::string(in->quals + in->qual_offs[gi], in->quals + in->qual_offs[gi + 1]) : std::string();
+    h.rq = h.qual;
+    std::reverse(h.rq.begin(), h.rq.end());
+    h.occs = occsOfBatchRead(c, i);
+    h.po.clear();
+    for (BestOcc& o : h.occs) {
+        if (o.aln.spans == 1 && !trimOccurrence(idx, o.occ.strand ? h.rc : h.seq, c->k, CMB_METRIC_EDIT, o, nullptr)) continue; // NOT_FOUND
+        h.po.push_back(cmb_pair_occ{o.aln.seq_id, o.aln.seq_begin, o.aln.seq_begin + (o.occ.end - o.occ.begin), o.occ.begin, o.occ.distance,
+                                    o.occ.strand, o.ops.data(), (uint32_t)o.ops.size()});
+    }
+}
+const char* pairBatchRefusal(const cmb_batch* b) {
+    if (b->ix == nullptr) return "a batch without an index";
+    if (!b->done) return "batch has not been run";
+    if (!b->wantAln) return "alignments were not requested (cmb_batch_want_alignments)";
+    if (!b->perStrand) return "the strands were not filtered each by itself (cmb_batch_filter_per_strand)";
+    return nullptr;
+}
+} // namespace
+
+extern "C" int cmb_pair_sam_device(cmb_batch* mates1, cmb_batch* mates2, const cmb_pair_params* params, const cmb_sam_inputs* in1,
+                                   const cmb_sam_inputs* in2, const char** text, uint64_t* length, cmb_pair_device_stats* stats) {
+    if (!mates1 || !mates2 || !params || !text || !length || !samInputsOk(in1) || !samInputsOk(in2)) return fail(CMB_ERR_INVALID, "null argument");
+    if (mates1 == mates2) return fail(CMB_ERR_INVALID, "the two mates need a batch each");
+    if (params->orientation > 2) return fail(CMB_ERR_INVALID, "orientation must be one of CMB_ORIENTATION_*");
+    for (const cmb_batch* b : {(const cmb_batch*)mates1, (const cmb_batch*)mates2})
+        if (const char* why = pairBatchRefusal(b)) return fail(CMB_ERR_INVALID, why);
+    if (mates1->ix != mates2->ix || mates1->k != mates2->k || mates1->metric != mates2->metric)
+        return fail(CMB_ERR_INVALID, "the mates' batches differ in index, metric or maximal distance");
+    if (mates1->nReads != mates2->nReads) return fail(CMB_ERR_INVALID, "the mates' batches do not hold the same number of reads");
+    if (mates1->subBound != mates2->subBound) return fail(CMB_ERR_INVALID, "the mates' batches are split into different sub-batches");
+    if (in1->n_seqs != in2->n_seqs) return fail(CMB_ERR_INVALID, "the mates' inputs name different numbers of sequences");
+    try {
+        cmb_index* idx = mates1->ix;
+        useDevice(idx->device);
+        std::vector<cmb_batch*> subs1, subs2;
+        if (mates1->subs.empty()) subs1.push_back(mates1), subs2.push_back(mates2);
+        else subs1 = mates1->subs, subs2 = mates2->subs;
+        const size_t P = subs1.size();
+        const cmb_sam_inputs* in[2] = {in1, in2};
+        std::vector<uint64_t> readBase(P + 1, 0), charBase1(P + 1, 0), charBase2(P + 1, 0), partBytes(P, 0), partRecords(P, 0), partMapped(P, 0);
+        std::vector<uint32_t> nHost(P, 0);
+        std::vector<PairCtx> ctx(P);
+        for (size_t j = 0; j < P; j++) {
+            if (subs1[j]->nReads != subs2[j]->nReads) return fail(CMB_ERR_INVALID, "the mates' batches are split into different sub-batches");
+            const uint32_t n = subs1[j]->nReads;
+            readBase[j + 1] = readBase[j] + n;
+            charBase1[j + 1] = charBase1[j] + (n ? subs1[j]->hostOffs[n] : 0);
+            charBase2[j + 1] = charBase2[j] + (n ? subs2[j]->hostOffs[n] : 0);
+        }
+        // ---- plan: inputs of both mates up, one wavefront per pair
+        for (size_t j = 0; j < P; j++) {
+            cmb_batch* c[2] = {subs1[j], subs2[j]};
+            const uint32_t n = c[0]->nReads;
+            if (!n) continue;
+            hipStream_t s = c[0]->stream;
+            PairCtx& pc = ctx[j];
+            pc.orientation = params->orientation, pc.maxFrag = params->max_frag, pc.minFrag = params->min_frag;
+            for (int m = 0; m < 2; m++) {
+                pc.m[m] = SamCtx{c[m]->reads.p, c[m]->offs.p, c[m]->foffs.p, 2u, c[m]->fout.p, c[m]->alnRec.p, c[m]->alnOps.p, c[m]->alnStride};
+                if (int rc = samUpload(c[m]->sam, in[m], readBase[j], n, s, pc.m[m])) return rc;
+            }
+            growTo(c[0]->pairPlan, n);
+            growTo(c[0]->pairRecords, (size_t)n + 1);
+            growTo(c[0]->pairMapped, (size_t)n + 1);
+            growTo(c[0]->pairSums, (size_t)n + 1);
+            growTo(c[0]->samHostList, (size_t)n + 1);
+            HIPCHK(hipMemsetAsync(c[0]->samHostList.p, 0, sizeof(uint32_t), s));
+            HIPCHK(hipMemsetAsync(c[0]->pairRecords.p + n, 0, sizeof(uint64_t), s));
+            HIPCHK(hipMemsetAsync(c[0]->pairMapped.p + n, 0, sizeof(uint32_t), s));
+            hipLaunchKernelGGL(k_pair_plan, dim3((n + 3u) / 4u), dim3(256), 0, s, pc, params->unmapped_records ? 1u : 0u, c[0]->sam.plan.p,
+                               c[0]->pairPlan.p, c[0]->sam.len.p, c[0]->pairRecords.p, c[0]->pairMapped.p, c[0]->samHostList.p);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(&nHost[j], c[0]->samHostList.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        }
+        // ---- the pairs the host formats, then the position of every pair in its sub-batch's text
+        std::vector<std::string> names;
+        std::vector<const char*> namePtrs;
+        uint64_t nHostAll = 0, hostMapped = 0;
+        for (size_t j = 0; j < P; j++) {
+            cmb_batch* c[2] = {subs1[j], subs2[j]};
+            const uint32_t n = c[0]->nReads;
+            if (!n) continue;
+            hipStream_t s = c[0]->stream;
+            HIPCHK(hipStreamSynchronize(s));
+            if (nHost[j]) {
+                if (names.empty()) {
+                    names = samNamesOf(in1);
+                    for (const std::string& nm : names) namePtrs.push_back(nm.c_str());
+                }
+                std::vector<uint32_t> list(nHost[j]);
+                HIPCHK(hipMemcpy(list.data(), c[0]->samHostList.p + 1, (size_t)nHost[j] * sizeof(uint32_t), hipMemcpyDeviceToHost));
+                std::sort(list.begin(), list.end());
+                PairHostRead h[2];
+                std::vector<char> buf;
+                samSplice(c[0]->sam, list, s, [&](uint32_t i, std::string& side) {
+                    pairHostRead(h[0], idx, c[0], i, in1, readBase[j] + i, charBase1[j]);
+                    pairHostRead(h[1], idx, c[1], i, in2, readBase[j] + i, charBase2[j]);
+                    const cmb_pair_read r1 = h[0].view(), r2 = h[1].view();
+                    uint32_t nPairs = 0;
+                    const int64_t len = cmb_pair_sam(params, &r1, &r2, namePtrs.data(), nullptr, 0, &nPairs);
+                    if (len < 0) throw std::runtime_error(g_err);
+                    buf.resize((size_t)len + 1);
+                    cmb_pair_sam(params, &r1, &r2, namePtrs.data(), buf.data(), (uint64_t)len + 1, &nPairs);
+                    side.append(buf.data(), (size_t)len);
+                    hostMapped += nPairs > 0;
+                });
+                nHostAll += nHost[j];
+            }
+            samScan(c[0]->sam, c[0]->scanTmp, n, &partBytes[j], s);
+            // the records the device writes and the pairs it maps: a 64-bit sum each, through the same scan buffer one after the other
+            scanExclusive(c[0]->scanTmp, c[0]->pairRecords.p, c[0]->pairSums.p, (size_t)n + 1, s);
+            HIPCHK(hipMemcpyAsync(&partRecords[j], c[0]->pairSums.p + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+            scanExclusive(c[0]->scanTmp, c[0]->pairMapped.p, c[0]->pairSums.p, (size_t)n + 1, s);
+            HIPCHK(hipMemcpyAsync(&partMapped[j], c[0]->pairSums.p + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        }
+        uint64_t total = 0, deviceRecords = 0, deviceMapped = 0;
+        for (size_t j = 0; j < P; j++) {
+            if (subs1[j]->nReads) HIPCHK(hipStreamSynchronize(subs1[j]->stream));
+            total += partBytes[j];
+            deviceRecords += partRecords[j];
+            deviceMapped += partMapped[j];
+        }
+        // ---- write: every sub-batch its piece, copied to its place in the text of read 1's batch
+        PinnedBuf<char>& samOut = mates1->samOut;
+        samOut.resize((size_t)total + 1);
+        samOut.p[total] = '\0';
+        uint64_t at = 0;
+        for (size_t j = 0; j < P; j++) {
+            const uint32_t n = subs1[j]->nReads;
+            if (!n || !partBytes[j]) continue;
+            SamDeviceBufs& d = subs1[j]->sam;
+            hipStream_t s = subs1[j]->stream;
+            growTo(d.text, (size_t)partBytes[j] + 16);
+            hipLaunchKernelGGL(k_pair_write, dim3((n + PAIR_PER_WAVE - 1u) / PAIR_PER_WAVE), dim3(64), 0, s, ctx[j], d.plan.p, subs1[j]->pairPlan.p,
+                               d.offs.p, d.side.p, d.text.p);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(samOut.p + at, d.text.p, (size_t)partBytes[j], hipMemcpyDeviceToHost, s));
+            at += partBytes[j];
+        }
+        for (size_t j = 0; j < P; j++)
+            if (subs1[j]->nReads && partBytes[j]) HIPCHK(hipStreamSynchronize(subs1[j]->stream));
+        *text = samOut.p;
+        *length = total;
+        if (getenv("CMB_VERBOSE"))
+            fprintf(stderr, "[host] pair sam: %llu pairs, %llu of them formatted on the host, %llu records from the device\n",
+                    (unsigned long long)readBase[P], (unsigned long long)nHostAll,
+                    (unsigned long long)deviceRecords);
+        if (stats) {
+            stats->host_pairs = nHostAll;
+            stats->mapped_pairs = hostMapped + deviceMapped;
+            stats->device_records = deviceRecords;
+        }
+        return CMB_OK;
     } catch (const std::exception& e) {
         return fail(CMB_ERR_DEVICE, e.what());
     }

@@ -57,6 +57,19 @@ __device__ __forceinline__ unsigned long long waveSum64(unsigned long long v) {
     return v;
 }
 
+// wave-wide exclusive prefix sum of 64-bit values (byte counts inside a read pair's text: dev_pair.hpp; all 64 lanes must call)
+__device__ __forceinline__ unsigned long long waveExclusiveScan64(unsigned long long v, unsigned long long& total) {
+    const uint32_t lane = threadIdx.x & 63u;
+    unsigned long long x = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned long long y = __shfl_up(x, d);
+        if ((int)lane >= d) x += y;
+    }
+    total = __shfl(x, 63);
+    return x - v;
+}
+
 // one atomic per wavefront: returns this lane's first slot for its `n` records in a queue
 __device__ __forceinline__ uint32_t waveAppend(uint32_t* counter, uint32_t n, uint32_t& total) {
     const uint32_t off = waveExclusiveScan(n, total);

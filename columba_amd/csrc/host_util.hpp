@@ -135,6 +135,14 @@ struct SamPlan { // per read (32 bytes; dev_sam.hpp)
     uint32_t pad;
     uint64_t sideOff; // SAM_HOST: where the read's text lies in the side buffer
 };
+// per read pair with a concordant combination (dev_pair.hpp).  A candidate pair is (combination of the orientation, index in the up
+// list, index in the down list): the primary — the first pair of minimal summed distance — and the first pair, which changes places with it
+struct PairPlan {
+    uint32_t primCombo, primU, primD;
+    uint32_t firstCombo, firstU, firstD;
+    uint32_t minDist, nPairs; // the minimal summed distance and how many pairs have it
+    uint32_t idLen[2];        // cleaned identifiers of read 1 and read 2
+};
 // What the device SAM driver (columba_amd.hip: samUpload, samSplice, samScan, samWrite) keeps in HBM for one (sub-)batch or one BEST result:
 // the chunk's packed identifiers, qualities and sequence names with their offsets, the plan, length and position of every read in the
 // text, the text of the reads the host formatted with its offsets and read numbers, the text itself (the scan's scratch is the owner's)

@@ -456,7 +456,8 @@ int64_t cmb_batch_sam(const cmb_batch* b, const char* seqs, const char* const* r
  * every sub-batch on its own stream; the text is in read order.  MAPQ (TextOcc::getMapQ, src/indexhelpers.h:378-388) comes from
  * a table on the device: 60, 3, 2, then 1 up to nine and 0 from ten occurrences of minimal distance on.
  * ALL mode, single-end reads, FM-index batches: BEST mode has cmb_best_sam_device (below) on a result of cmb_match_best_device, the
- * b-move flavour cmb_move_batch_sam_device; results of cmb_match_best and read pairs (cmb_pair_sam) keep the host formatter. */
+ * b-move flavour cmb_move_batch_sam_device, read pairs in ALL mode cmb_pair_sam_device (below); results of cmb_match_best, read pairs
+ * in BEST mode (cmb_pair_best_sam) and pairs that start from the inference phase's lists keep the host formatter. */
 typedef struct {
     const char* seqs;
     const char* ids;
@@ -469,6 +470,29 @@ typedef struct {
 } cmb_sam_inputs;
 int cmb_batch_sam_device(cmb_batch* b, const cmb_sam_inputs* in, int unmapped_records, int xa_tag, const char** text,
                          uint64_t* length, uint64_t* host_reads);
+/* The SAM text of a chunk of read PAIRS in ALL mode, paired and written on the device: byte for byte the concatenation over the pairs
+ * of what cmb_pair_sam returns for them (SearchStrategy::pairSingleEndedMatchesAll + generateSAMPairedEnd), from the lists the two
+ * mates' runs left in HBM.  mates1 / mates2: read 1 and read 2 of every pair, FM-index batches of the same index, strategy metric and
+ * maximal distance with the same number of reads, both run with cmb_batch_want_alignments and cmb_batch_filter_per_strand; anything
+ * else, composite batches that are split differently included, is CMB_ERR_INVALID, checked before any work.  (The split into
+ * sub-batches depends only on the read count and the environment, so the two batches of one chunk split alike.)  Sub-batch j of
+ * mates1 is paired with sub-batch j of mates2 on its own stream; the text is in pair order.
+ * in1 / in2: the packed inputs of the two mates as for cmb_batch_sam_device, with one difference: quals == NULL or an empty entry is
+ * an EMPTY quality, as a NULL or empty cmb_pair_read.qual is — "*" on a mapped record, nothing on an unmapped one.  The sequence
+ * names are taken from in1 (in2 must name as many).
+ * The device pairs the two classes that make up almost every chunk: both mates without an occurrence (two unmapped records, or
+ * nothing without params->unmapped_records), and pairs with at least one concordant combination.  A pair with an occurrence that runs
+ * over the end of its sequence or has none assigned (cmb_aln.spans != 0: IndexInterface::findSeqName trims, verifies again and may
+ * drop it), or whose lists are not both empty and hold no concordant pair (discordant pairs, unpaired records, one mate unmapped), is
+ * formatted by cmb_pair_sam from the batches' host copies, trimmed with cmb_trim_occurrence, and spliced in at its place.
+ * *text (page-locked, owned by mates1, *length bytes + a terminating 0) stays valid until the next cmb_batch_run, SAM call or
+ * cmb_batch_destroy on either batch.  stats (may be NULL): host_pairs = the pairs formatted through cmb_pair_sam; mapped_pairs = the
+ * pairs whose n_pairs_out is not 0; device_records = the SAM lines the device wrote. */
+typedef struct {
+    uint64_t host_pairs, mapped_pairs, device_records;
+} cmb_pair_device_stats;
+int cmb_pair_sam_device(cmb_batch* mates1, cmb_batch* mates2, const cmb_pair_params* params, const cmb_sam_inputs* in1,
+                        const cmb_sam_inputs* in2, const char** text, uint64_t* length, cmb_pair_device_stats* stats /* may be NULL */);
 /* The SAM text of a chunk matched with cmb_match_best_device, written on the device from the result's lists: byte for byte what
  * generateOutputSingleEnd + generateSE_SAM / generateSE_SAM_XATag (src/searchstrategy.cpp:1824-1902, src/searchstrategy.h:1612-1641)
  * give for BEST mode, i.e. what the host formatter (include/columba_amd_best.hpp: samOfBest) builds from cmb_best_results.  The

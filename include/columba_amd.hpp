@@ -31,6 +31,7 @@
 #include <fstream>
 #include <stdexcept>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -464,6 +465,43 @@ class SearchStrategy {
         check(cmb_pair_infer(samples.data(), samples.size(), &inf.inferred));
         return inf;
     }
+    // samOfChunkPairedAll with the pairing and the records on the device (CMB_PAIR_DEVICE=1; the host path stays the default:
+    // DESIGN.md §4.7 has what the two cost): two batches whose lists stay in HBM, the fields packed once per mate, cmb_pair_sam_device
+    template <class Record>
+    std::string samOfChunkPairedDevice(const std::vector<Record>& mates1, const std::vector<Record>& mates2, const std::vector<const char*>& seqNames,
+                                       length_t maxED, uint32_t orientation, uint32_t maxFragSize, uint32_t minFragSize, bool discordantAllowed,
+                                       bool unmappedRecords, size_t& mappedPairs) {
+        const std::vector<Record>* in[2] = {&mates1, &mates2};
+        struct Guard {
+            cmb_batch* b[2] = {nullptr, nullptr};
+            ~Guard() {
+                for (cmb_batch* x : b)
+                    if (x) cmb_batch_destroy(x);
+            }
+        } guard;
+        std::string seqs[2];
+        std::unique_ptr<SamPacked> packed[2];
+        cmb_sam_inputs inputs[2];
+        for (int m = 0; m < 2; m++) {
+            const std::vector<Record>& recs = *in[m];
+            std::vector<uint64_t> offs(recs.size() + 1, 0);
+            for (size_t j = 0; j < recs.size(); j++) seqs[m] += recs[j].read, offs[j + 1] = seqs[m].size();
+            check(cmb_batch_create(index.handle(), h, maxED, seqs[m].data(), offs.data(), (uint32_t)recs.size(), &guard.b[m]));
+            check(cmb_batch_want_alignments(guard.b[m], 1));
+            check(cmb_batch_filter_per_strand(guard.b[m], 1));
+            check(cmb_batch_run(guard.b[m]));
+            packed[m].reset(new SamPacked(recs.size(), seqNames, [&](size_t i) -> const std::string& { return recs[i].seqID; }, false,
+                                          [&](size_t i) -> const std::string& { return recs[i].qual; }));
+            inputs[m] = packed[m]->inputs(seqs[m]);
+        }
+        const cmb_pair_params prm = {orientation, maxFragSize, minFragSize, discordantAllowed ? 1 : 0, unmappedRecords ? 1 : 0};
+        const char* text = nullptr;
+        uint64_t length = 0;
+        cmb_pair_device_stats stats{};
+        check(cmb_pair_sam_device(guard.b[0], guard.b[1], &prm, &inputs[0], &inputs[1], &text, &length, &stats));
+        mappedPairs += (size_t)stats.mapped_pairs;
+        return std::string(text, (size_t)length);
+    }
     // the SAM text of a chunk of read PAIRS in ALL mode: both mates matched single-ended (one batch each, every strand filtered by itself as
     // matchApproxPairedEndAll's mapRead does, searchstrategy.cpp:746-776), then paired as SearchStrategy::pairSingleEndedMatchesAll does
     // (searchstrategy.cpp:1345-1399) with the records of generateSAMPairedEnd.  orientation: CMB_ORIENTATION_*.  startFrom: the lists of the
@@ -478,6 +516,9 @@ class SearchStrategy {
         std::vector<size_t> all(n);
         for (size_t i = 0; i < n; i++) all[i] = i;
         if (!startFrom) {
+            if (const char* e = getenv("CMB_PAIR_DEVICE"); e && atoi(e) != 0) // paired and written on the device (cmb_pair_sam_device)
+                return samOfChunkPairedDevice(mates1, mates2, seqNames, maxED, orientation, maxFragSize, minFragSize, discordantAllowed,
+                                              unmappedRecords, mappedPairs);
             MateLists L1 = listsOfMate(mates1, all, maxED, true), L2 = listsOfMate(mates2, all, maxED, true);
             return pairListsAll(mates1, mates2, L1, L2, seqNames, orientation, maxFragSize, minFragSize, discordantAllowed, unmappedRecords, mappedPairs);
         }
