@@ -192,6 +192,9 @@ extern "C" int cmb_index_create(const cmb_index_desc* desc, int device, cmb_inde
         // candidate has ended keep prefetching while their wavefront runs (at most MAX_READ + 3 k rows + 48 bytes)
         constexpr uint64_t TEXT_PAD = 640;
         static_assert(TEXT_PAD >= (uint64_t)VROWS + 64, "text padding must cover the longest verification window");
+        // ... and the CIGAR kernels' reads of text[begin, end) for an occurrence that ends beyond the text: begin < n,
+        // end - begin <= MAX_READ + 13 (MAX_K), and forwardPass prefetches up to 64 bytes past the longest window of its wavefront
+        static_assert(TEXT_PAD >= (uint64_t)MAX_READ + 13 + 64, "text padding must cover an occurrence that begins on the last character");
         ix->text.alloc(n + TEXT_PAD);
         HIPCHK(hipMemset(ix->text.p, 0, n + TEXT_PAD));
         HIPCHK(hipMemcpy(ix->text.p, desc->text, n, hipMemcpyHostToDevice));
@@ -302,7 +305,8 @@ extern "C" int cmb_index_create_text_only(const char* text, uint64_t n, const ui
         std::unique_ptr<cmb_index> ix(new cmb_index());
         ix->device = device;
         ix->textOnly = true;
-        constexpr uint64_t TEXT_PAD = 640;
+        constexpr uint64_t TEXT_PAD = 640; // (as in cmb_index_create: the windows of k_cigar / k_cigar_wide, also of occurrences that end beyond the text)
+        static_assert(TEXT_PAD >= (uint64_t)VROWS + 64 && TEXT_PAD >= (uint64_t)MAX_READ + 13 + 64, "text padding must cover the longest window");
         ix->text.alloc(n + TEXT_PAD);
         HIPCHK(hipMemset(ix->text.p, 0, n + TEXT_PAD));
         HIPCHK(hipMemcpy(ix->text.p, text, n, hipMemcpyHostToDevice));
