@@ -552,7 +552,6 @@ struct cmb_batch {
     // of k_parts / k_exact / k_hbfs (Hamming distance; the edit-distance matcher stops at 7 errors)
     bool wide = false;
     bool wideEdit = false; // edit distance 8 ... 13: wide records AND the wide layout of the filter keys
-    bool geoX = false;     // ... 11 ... 13: the in-index matrix with 16-row blocks (GeoX), the in-text matrix with 8-row blocks
     bool noSmallMatrix = false; // a phase of an earlier run did not fit the 32-bit in-index matrix (GeoN32): this batch stays on GeoN
     DevStrategyKT<MAXP_WIDE> hostStratW{};
     DevBuf<DevStrategyKT<MAXP_WIDE>> stratW;
@@ -603,7 +602,6 @@ struct cmb_batch {
     uint32_t nSlots = 0;
     std::vector<uint64_t> hostOffs;
     bool perStrand = false; // every strand filtered by itself (BEST mode: mapRead, searchstrategy.h:490-523)
-    bool allowUnsupported = false; // (cmb_batch_allow_unsupported: no effect any more)
     // alignments of the final occurrences (cmb_batch_want_alignments): CIGAR runs + sequence assignment
     bool wantAln = false;
     DevBuf<uint32_t> foutRead;
@@ -758,37 +756,22 @@ static int batchCreateOne(cmb_index* idx, const cmb_strategy* st, uint32_t max_d
             // 64-bit in-index matrix; GeoX with its 16-row blocks beyond); the staged in-text matrices stop at 7, candidates are verified by
             // k_wide_filter + k_verify_wide
             b->wideEdit = st->metric == CMB_METRIC_EDIT && 3 * max_distance + 1 > MXW_LEFT;
-            b->geoX = b->wideEdit && max_distance > MX_MAX_ED; // (beyond the reference's 64-bit in-index matrix: dev_matrix.hpp, MXN_*)
             try {
                 b->wide = st->numPartsFor(max_distance) > (uint32_t)MAXP || b->wideEdit;
                 if (max_distance > 13) return fail(CMB_ERR_UNSUPPORTED, "more than 13 errors (MAX_K, definitions.h:50)");
-                if (b->wide) {
-                    b->hostStratW = st->flatten<MAXP_WIDE>(max_distance);
-                    b->sNumParts = b->hostStratW.numParts, b->sPartition = b->hostStratW.partition, b->sNSchemes = b->hostStratW.nSchemes;
-                    for (int i = 0; i < b->hostStratW.nSchemes; i++) b->sMaxSearches = std::max<uint32_t>(b->sMaxSearches, b->hostStratW.sch[i].nSearches);
-                } else {
-                    b->hostStrat = st->flatten<MAXP>(max_distance);
-                    b->sNumParts = b->hostStrat.numParts, b->sPartition = b->hostStrat.partition, b->sNSchemes = b->hostStrat.nSchemes;
-                    for (int i = 0; i < b->hostStrat.nSchemes; i++) b->sMaxSearches = std::max<uint32_t>(b->sMaxSearches, b->hostStrat.sch[i].nSearches);
-                }
+                adoptStrategy(b.get(), st, max_distance);
             } catch (const std::exception& e) {
                 return fail(CMB_ERR_INVALID, e.what());
             }
         }
         if ((uint64_t)n_reads >= (1ull << groupBits(b.get()))) // (wide keys: 22 group bits)
             return fail(CMB_ERR_UNSUPPORTED, "more than 2^" + std::to_string(groupBits(b.get())) + " reads in one sub-batch at this distance");
-        uint32_t maxLen = 1, minLen = ~0u;
-        for (uint32_t i = 0; i < n_reads; i++) {
-            if (offs[i + 1] < offs[i]) return fail(CMB_ERR_INVALID, "read offsets must be non-decreasing");
-            maxLen = std::max<uint32_t>(maxLen, (uint32_t)(offs[i + 1] - offs[i]));
-            minLen = std::min<uint32_t>(minLen, (uint32_t)(offs[i + 1] - offs[i]));
-        }
+        uint32_t maxLen, minLen;
+        if (!readLengths(offs, n_reads, minLen, maxLen)) return fail(CMB_ERR_INVALID, "read offsets must be non-decreasing");
         b->minLen = n_reads ? minLen : 0u;
         if (maxLen > (uint32_t)MAX_READ)
             return fail(CMB_ERR_UNSUPPORTED, "reads longer than " + std::to_string(MAX_READ) + " are not supported");
-        // rows of per-read arrays are padded to a multiple of 16 bytes (16-byte stores in k_prep); the number of
-        // 32-character words per read does not change
-        maxLen = (maxLen + 15u) & ~15u;
+        maxLen = paddedLen(maxLen);
         b->maxLen = maxLen;
         b->gw = gWords(maxLen);
         b->hostOffs.assign(offs, offs + n_reads + 1);
@@ -878,20 +861,7 @@ extern "C" int cmb_batch_run(cmb_batch* b) {
     for (auto& t : th) t.join();
     for (size_t j = 0; j < rc.size(); j++)
         if (rc[j] != CMB_OK) return fail(rc[j], err[j]);
-    memset(b->cnts, 0, sizeof(b->cnts));
-    b->times.clear();
-    for (cmb_batch* c : b->subs) {
-        for (int i = 0; i < CMB_CNT_MAX; i++) b->cnts[i] += c->cnts[i];
-        for (const auto& t : c->times) { // busy time per kernel group, summed over the concurrent sub-batches
-            bool found = false;
-            for (auto& u : b->times)
-                if (!strcmp(u.name, t.name)) {
-                    u.ms += t.ms;
-                    found = true;
-                }
-            if (!found) b->times.push_back(t);
-        }
-    }
+    foldSubBatches(b);
     b->done = true;
     return CMB_OK;
 }
@@ -912,12 +882,8 @@ extern "C" int cmb_batch_stage_reads(cmb_batch* b, const char* seqs, const uint6
         }
         return CMB_OK;
     }
-    uint32_t maxLen = 1, minLen = ~0u;
-    for (uint32_t i = 0; i < n_reads; i++) {
-        if (offs[i + 1] < offs[i]) return fail(CMB_ERR_INVALID, "read offsets must be non-decreasing");
-        maxLen = std::max<uint32_t>(maxLen, (uint32_t)(offs[i + 1] - offs[i]));
-        minLen = std::min<uint32_t>(minLen, (uint32_t)(offs[i + 1] - offs[i]));
-    }
+    uint32_t maxLen, minLen;
+    if (!readLengths(offs, n_reads, minLen, maxLen)) return fail(CMB_ERR_INVALID, "read offsets must be non-decreasing");
     b->minLen = std::min(b->minLen, n_reads ? minLen : 0u);
     if (maxLen > b->maxLen) return fail(CMB_ERR_INVALID, "a staged read is longer than the batch was created for");
     if (b->pending) return fail(CMB_ERR_INVALID, "a chunk is already registered for the next run");
@@ -946,6 +912,63 @@ static void startStagedUpload(cmb_batch* b) {
     HIPCHK(hipEventRecord(b->copyDone, b->copyStream));
     b->pending = false;
     b->staged = true;
+}
+
+// ---- launches that more than one function makes ---------------------------------------------------------------------------------
+// 64-byte lines of the trace rows of one slot: 16 narrow (k <= TBN_MAX_ED) or 8 wide rows to a line (a group is written whole)
+static uint32_t traceLines(bool narrow, uint32_t rows) { return narrow ? (rows + 15u) / 16u + 2u : (rows + 7u) / 8u + 2u; }
+
+// k_traceback over the nTb tasks of tbq (batchRunOne, verifyDirect): the instance of the trace rows and of the text — packed or bytes;
+// the wide rows read either text through one instance
+static void launchTraceback(hipStream_t s, const DevIndex& d, bool narrow, const uint64_t* offs, MFull mf, const uint4* tbq, uint32_t nTb, VPlanes vp,
+                            Queues q, uint32_t rowMin) {
+    auto kTrace = withBools([](auto nrw, auto packed) { return k_traceback<nrw(), nrw() && packed()>; }, narrow, d.text2 != nullptr);
+    hipLaunchKernelGGL(kTrace, dim3(vp.nSlots / 256), dim3(256), 0, s, d, offs, mf, tbq, nTb, vp, q, rowMin);
+}
+
+// The CIGAR step of batchRunOne, cmb::moveCigarsOnText and cmb_cigar_windows: CIGAR and sequence assignment of nOcc occurrences
+// {begin, end, distance, strand} of the reads occRead (device pointers throughout).  wide: k_cigar_wide, the matrix with the wide left margin
+// (k_cigar's match words reach 9 columns right of the diagonal: beyond CIGAR_BLOCK_WORDS_MAX_ED errors), at most 64 k slots of `slab`;
+// otherwise the k_cigar instance of the trace rows (narrow or wide, for `rows` matrix rows per slot of vW) and of the text.  The caller says
+// which, owns the scratch — it grows to what the launch needs — and counts the slots
+struct CigarJob {
+    const uint64_t* offs;
+    const uint32_t* G;
+    uint32_t gw, maxLen;
+    MFull mf;
+    const uint4* occs;
+    const uint32_t* occRead;
+    uint64_t nOcc;
+    uint16_t* ops;
+    uint32_t stride;
+    AlnRec* aln;
+    uint32_t* flagWord;
+    uint32_t gapless;
+};
+static void launchCigar(cmb_index* ix, hipStream_t s, const CigarJob& j, bool wide, bool narrow, uint32_t rows, uint32_t slots, DevBuf<uint64_t>& vW,
+                        DevBuf<uint8_t>& slab, bool verbose) {
+    if (wide) {
+        const uint32_t wSlots = std::min<uint32_t>(slots, 256u * 256u);
+        const uint32_t slotBytes = (vwRows(j.maxLen) + 1u) * VW_ROW_BYTES;
+        gridLine(verbose, "k_cigar_wide", j.nOcc, wSlots);
+        if (slab.n < (size_t)slotBytes * wSlots) slab.alloc((size_t)slotBytes * wSlots);
+        hipLaunchKernelGGL(k_cigar_wide, dim3(wSlots / 256), dim3(256), 0, s, ix->d, j.offs, j.G, j.gw, j.occs, j.occRead, j.nOcc, slab.p, slotBytes,
+                           ix->seqStartsDev.p, ix->nSeqsDev, j.ops, j.stride, j.aln, j.flagWord, 0u);
+        return;
+    }
+    const uint32_t tLines = traceLines(narrow, rows);
+    if (vW.n < (size_t)tLines * 8 * slots) vW.alloc((size_t)tLines * 8 * slots);
+    VPlanes vp{vW.p, slots, tLines};
+    auto kc = withBools([](auto nrw, auto packed) { return k_cigar<nrw(), packed()>; }, narrow, ix->d.text2 != nullptr);
+    gridLine(verbose, "k_cigar", j.nOcc, slots);
+    hipLaunchKernelGGL(kc, dim3(slots / 256), dim3(256), 0, s, ix->d, j.offs, j.mf, j.occs, j.occRead, j.nOcc, vp, ix->seqStartsDev.p, ix->nSeqsDev, j.ops,
+                       j.stride, j.aln, j.flagWord, j.gapless);
+}
+
+// one level of the frontier search, as the pass loop of batchRunOne launches it
+template <class Geo> static void launchBfsPass(cmb_batch* b, const BfsBufs& B, uint32_t pass, const Queues& q) {
+    hipLaunchKernelGGL(k_bfs_pass<Geo>, dim3(B.gridX + B.gridEv), dim3(256), 0, b->stream, b->ix->d, stratOf<Geo::MP>(b), B, pass, b->offs.p, b->gw, b->G.p,
+                       partsOf<Geo::MP>(b), q);
 }
 
 static int batchRunOne(cmb_batch* b) {
@@ -981,7 +1004,12 @@ static int batchRunOne(cmb_batch* b) {
             return CMB_OK;
         }
         uint32_t hcnt[8];
-        const bool verbose = getenv("CMB_VERBOSE") != nullptr;
+        // (both read per run, not per process: tests set them between runs)
+        const char* verboseEnv = getenv("CMB_VERBOSE");
+        const bool verbose = verboseEnv != nullptr, smallPools = getenv("CMB_TEST_SMALL_POOLS") != nullptr;
+        // 11 ... 13 errors: the in-index matrix with 16-row blocks (GeoX, beyond the reference's 64-bit in-index matrix: dev_matrix.hpp, MXN_*),
+        // the in-text matrix with 8-row blocks
+        const bool geoX = b->wideEdit && frontierGeoOf(b) == FrontierGeo::X;
         auto t0 = std::chrono::steady_clock::now();
         auto lap = [&](const char* what) {
             if (!verbose) return;
@@ -1052,34 +1080,32 @@ static int batchRunOne(cmb_batch* b) {
                 if (b->psel.n < tasks) b->psel.alloc(tasks);
                 const size_t pLds = stratBytes + (5 * pParts + rdWords) * 256 * sizeof(uint32_t);
                 gridLine(verbose, "k_parts", tasks, pSlots);
-                if (b->wide) {
-                    constexpr int W = MAXP_WIDE;
-                    auto kp = longReads ? (b->sPartition == 0 ? k_parts<0, true, W> : b->sPartition == 1 ? k_parts<1, true, W> : k_parts<2, true, W>)
-                                        : (b->sPartition == 0 ? k_parts<0, false, W> : b->sPartition == 1 ? k_parts<1, false, W> : k_parts<2, false, W>);
-                    if (pLds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void*)kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pLds));
-                    hipLaunchKernelGGL(kp, dim3(pSlots / 256), dim3(256), pLds, s, ix->d, b->stratW.p, nReads, b->k, b->maxLen, b->seq.p,
-                                       (const uint4*)b->rec.p, b->recW / 4, b->partsW.p, b->psel.p, b->dfs.p, dfsCap, b->exq.p, exCap, q);
-                } else {
-                    auto kp = longReads ? (b->sPartition == 0 ? k_parts<0, true> : b->sPartition == 1 ? k_parts<1, true> : k_parts<2, true>)
-                                        : (b->sPartition == 0 ? k_parts<0, false> : b->sPartition == 1 ? k_parts<1, false> : k_parts<2, false>);
-                    hipLaunchKernelGGL(kp, dim3(pSlots / 256), dim3(256), pLds, s, ix->d, b->strat.p, nReads,
-                                   b->k, b->maxLen, b->seq.p, (const uint4*)b->rec.p, b->recW / 4, b->parts.p, b->psel.p,
-                                   b->dfs.p, dfsCap, b->exq.p, exCap, q);
-                }
+                withTables(b, [&](auto mp) {
+                    withInt<3>((int)b->sPartition, [&](auto part) {
+                        withBools(
+                            [&](auto lng) {
+                                constexpr int MP = decltype(mp)::value;
+                                auto kp = k_parts<decltype(part)::value, decltype(lng)::value, MP>;
+                                if (MP != MAXP && pLds > 64 * 1024)
+                                    HIPCHK(hipFuncSetAttribute((const void*)kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pLds));
+                                hipLaunchKernelGGL(kp, dim3(pSlots / 256), dim3(256), pLds, s, ix->d, stratOf<MP>(b), nReads, b->k, b->maxLen, b->seq.p,
+                                                   (const uint4*)b->rec.p, b->recW / 4, partsOf<MP>(b), b->psel.p, b->dfs.p, dfsCap, b->exq.p, exCap, q);
+                            },
+                            longReads);
+                    });
+                });
             }
             // k_exact: k = 0 one lane per read x strand; otherwise the ExactTasks k_parts left — their number is on the device, a small
             // grid loops over them (none in the common case: every search of the multiple_opt schemes has one exact phase)
             const uint32_t eSlots = capSlots(b->k ? 256u * 256u : (uint32_t)std::min<uint64_t>((((uint64_t)tasks + 255) / 256) * 256, 256ull * 4096ull));
             if (!b->k) gridLine(verbose, "k_exact", tasks, eSlots); // (k > 0: the number of its tasks is on the device until the prologue is read back)
             const size_t eLds = stratBytes + (pParts + rdWords) * 256 * sizeof(uint32_t);
-            if (b->wide)
-                hipLaunchKernelGGL((longReads ? k_exact<true, MAXP_WIDE> : k_exact<false, MAXP_WIDE>), dim3(eSlots / 256), dim3(256), eLds, s, ix->d,
-                                   b->stratW.p, nReads, b->k, b->maxLen, b->seq.p, (const uint4*)b->rec.p, b->recW / 4, b->partsW.p,
-                                   b->exq.p, exCap, b->dfs.p, dfsCap, q);
-            else
-                hipLaunchKernelGGL(longReads ? k_exact<true> : k_exact<false>, dim3(eSlots / 256), dim3(256), eLds,
-                               s, ix->d, b->strat.p, nReads, b->k, b->maxLen, b->seq.p, (const uint4*)b->rec.p,
-                               b->recW / 4, b->parts.p, b->exq.p, exCap, b->dfs.p, dfsCap, q);
+            withTables(b, [&](auto mp) {
+                constexpr int MP = decltype(mp)::value;
+                auto ke = withBools([](auto lng) { return k_exact<lng(), MP>; }, longReads);
+                hipLaunchKernelGGL(ke, dim3(eSlots / 256), dim3(256), eLds, s, ix->d, stratOf<MP>(b), nReads, b->k, b->maxLen, b->seq.p,
+                                   (const uint4*)b->rec.p, b->recW / 4, partsOf<MP>(b), b->exq.p, exCap, b->dfs.p, dfsCap, q);
+            });
             tm.end("k_partition");
             HIPCHK(hipGetLastError());
             HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
@@ -1091,7 +1117,7 @@ static int batchRunOne(cmb_batch* b) {
             if (b->hasNaive) {
                 tm.begin();
                 const uint32_t maxPassN = b->maxLen + 2 * b->k + 4; // (rows of the matrix: len + 2 k + 1 at most)
-                if (!b->nvQCap) b->nvQCap = getenv("CMB_TEST_SMALL_POOLS") ? 64 : 16384;
+                if (!b->nvQCap) b->nvQCap = smallPools ? 64 : 16384;
                 for (int j = 0; j < 2; j++)
                     if (b->nvQ[j].n < 3 * b->nvQCap) b->nvQ[j].alloc(3 * b->nvQCap);
                 const size_t cntWords = (size_t)maxPassN + 2;
@@ -1104,13 +1130,13 @@ static int batchRunOne(cmb_batch* b) {
                 N.nq = b->nvCnt.p;
                 const bool edit = b->metric == CMB_METRIC_EDIT;
                 hipLaunchKernelGGL(k_naive_start, dim3((tasks + 255) / 256), dim3(256), 0, s, ix->d, b->psel.p, b->offs.p, tasks,
-                                   b->k, edit ? 0u : 1u, N, q, b->geoX ? 1u : 0u);
+                                   b->k, edit ? 0u : 1u, N, q, geoX ? 1u : 0u);
                 std::vector<uint32_t> hc(cntWords);
                 uint32_t pass = 0, peakQ = 0;
                 bool drained = false;
-                auto kNaive = edit ? k_naive_pass<true, false> : k_naive_pass<false, false>;
+                // (the matrix of 11 ... 13 errors is the edit distance's alone)
+                auto kNaive = withBools([](auto e, auto x) { return k_naive_pass<e(), e() && x()>; }, edit, geoX);
                 const uint32_t nvGrid = capBlocks(BFS_GRID); // (k_naive_start above takes one lane per read x strand and does not loop: no cap)
-                if (b->geoX) kNaive = k_naive_pass<true, true>;
                 while (!drained && pass < maxPassN) {
                     const uint32_t upTo = std::min(pass + 16u, maxPassN);
                     for (; pass < upTo; pass++)
@@ -1154,8 +1180,8 @@ static int batchRunOne(cmb_batch* b) {
                     if (!b->bfsQCap) {
                         // first guess; every pool grows (and the search re-runs) when it turns out too small.
                         // CMB_TEST_SMALL_POOLS starts from almost nothing so that tests exercise that path.
-                        const size_t slack = getenv("CMB_TEST_SMALL_POOLS") ? 64 : 65536;
-                        const size_t per = getenv("CMB_TEST_SMALL_POOLS") ? 0 : 1;
+                        const size_t slack = smallPools ? 64 : 65536;
+                        const size_t per = smallPools ? 0 : 1;
                         b->bfsQCap = per * (size_t)nReads * 2 + slack;
                         b->bfsEvCap = per * (size_t)nReads / 2 + slack;
                         b->bfsFCap = per * (size_t)nReads * 16 + slack;
@@ -1169,7 +1195,7 @@ static int batchRunOne(cmb_batch* b) {
                     }
                     if (b->bfsF.n < F_U4 * b->bfsFCap) b->bfsF.alloc(F_U4 * b->bfsFCap);
                     // (GeoX: blocks of 16 rows — up to 32 of them for 480 + 26 rows, two uint4 of match words each)
-                    const uint32_t ctxU4 = b->geoX ? CTX_U4_X : ctxU4For(b->maxLen);
+                    const uint32_t ctxU4 = geoX ? CTX_U4_X : ctxU4For(b->maxLen);
                     if (b->bfsC.n < (size_t)ctxU4 * b->bfsCCap) b->bfsC.alloc((size_t)ctxU4 * b->bfsCCap);
                     if (b->bfsA.n < b->bfsACap) b->bfsA.alloc(b->bfsACap);
                     const size_t cntWords = 2 * ((size_t)maxPass + 2) + 4;
@@ -1190,7 +1216,7 @@ static int batchRunOne(cmb_batch* b) {
                     B.fCap = cap32(b->bfsF.n / F_U4);
                     B.cCap = cap32(b->bfsC.n / ctxU4);
                     B.ctxU4 = ctxU4;
-                    B.ctxMblk = b->geoX ? CTX_MBLK_X : ctxMblkFor(b->maxLen);
+                    B.ctxMblk = geoX ? CTX_MBLK_X : ctxMblkFor(b->maxLen);
                     B.aCap = cap32(b->bfsA.n);
                     B.chain = getenv("CMB_BFS_CHAIN") ? (uint32_t)std::max(1, atoi(getenv("CMB_BFS_CHAIN"))) : BFS_CHAIN;
                     B.gridX = capBlocks(std::min<uint32_t>(BFS_GRID_CNT, envBlocks("CMB_BFS_GRID", BFS_GRID_X)));
@@ -1203,21 +1229,16 @@ static int batchRunOne(cmb_batch* b) {
                     B.blockCnt = b->bfsBlockCnt.p;
                     // up to 6 errors the frontier carries the in-index matrix on 32-bit words (GeoN32, dev_matrix.hpp: MXS_*); CMB_MATRIX64=1
                     // keeps the reference's 64-bit words (GeoN), as does a batch one of whose phases did not fit the small matrix
-                    const bool small32 = !b->wide && b->k <= MXS_MAX_ED && !b->noSmallMatrix && !getenv("CMB_MATRIX64");
+                    const FrontierGeo geo = frontierGeoOf(b);
                     const uint32_t startGrid = capBlocks(std::min<uint32_t>((nDfs + 255) / 256, BFS_GRID));
                     gridLine(verbose, "k_bfs_start", nDfs, 256ull * startGrid);
-                    if (b->geoX)
-                        hipLaunchKernelGGL(k_bfs_start<GeoX>, dim3(startGrid), dim3(256), 0, s,
-                                           ix->d, b->stratW.p, B, b->dfs.p, nDfs, b->offs.p, b->gw, b->G.p, b->partsW.p, q);
-                    else if (b->wide)
-                        hipLaunchKernelGGL(k_bfs_start<GeoW>, dim3(startGrid), dim3(256), 0, s,
-                                           ix->d, b->stratW.p, B, b->dfs.p, nDfs, b->offs.p, b->gw, b->G.p, b->partsW.p, q);
-                    else if (small32)
-                        hipLaunchKernelGGL(k_bfs_start<GeoN32>, dim3(startGrid), dim3(256), 0, s,
-                                           ix->d, b->strat.p, B, b->dfs.p, nDfs, b->offs.p, b->gw, b->G.p, b->parts.p, q);
-                    else
-                        hipLaunchKernelGGL(k_bfs_start<GeoN>, dim3(startGrid), dim3(256), 0, s,
-                                       ix->d, b->strat.p, B, b->dfs.p, nDfs, b->offs.p, b->gw, b->G.p, b->parts.p, q);
+                    withGeo(geo, [&](auto g) {
+                        using Geo = typename decltype(g)::type;
+                        hipLaunchKernelGGL(k_bfs_start<Geo>, dim3(startGrid), dim3(256), 0, s, ix->d, stratOf<Geo::MP>(b), B, b->dfs.p, nDfs, b->offs.p,
+                                           b->gw, b->G.p, partsOf<Geo::MP>(b), q);
+                    });
+                    // (the instance of a pass is chosen here, once per attempt: the loop below calls through a pointer)
+                    const auto bfsPass = withGeo(geo, [](auto g) { return &launchBfsPass<typename decltype(g)::type>; });
                     std::vector<uint32_t> hc(cntWords);
                     // passes between two looks at the queue sizes (a pass on a drained frontier costs the device ~4 us, a look costs the host a round trip)
                     const uint32_t CHECK = getenv("CMB_BFS_CHECK") ? (uint32_t)std::max(1, atoi(getenv("CMB_BFS_CHECK"))) : 16;
@@ -1225,20 +1246,7 @@ static int batchRunOne(cmb_batch* b) {
                     bool drained = false;
                     while (!drained && pass < maxPass) {
                         const uint32_t upTo = std::min(pass + CHECK, maxPass);
-                        for (; pass < upTo; pass++) {
-                            if (b->geoX)
-                                hipLaunchKernelGGL(k_bfs_pass<GeoX>, dim3(B.gridX + B.gridEv), dim3(256), 0, s, ix->d, b->stratW.p, B,
-                                                   pass, b->offs.p, b->gw, b->G.p, b->partsW.p, q);
-                            else if (b->wide)
-                                hipLaunchKernelGGL(k_bfs_pass<GeoW>, dim3(B.gridX + B.gridEv), dim3(256), 0, s, ix->d, b->stratW.p, B,
-                                                   pass, b->offs.p, b->gw, b->G.p, b->partsW.p, q);
-                            else if (small32)
-                                hipLaunchKernelGGL(k_bfs_pass<GeoN32>, dim3(B.gridX + B.gridEv), dim3(256), 0, s, ix->d, b->strat.p, B,
-                                                   pass, b->offs.p, b->gw, b->G.p, b->parts.p, q);
-                            else
-                                hipLaunchKernelGGL(k_bfs_pass<GeoN>, dim3(B.gridX + B.gridEv), dim3(256), 0, s, ix->d, b->strat.p, B,
-                                               pass, b->offs.p, b->gw, b->G.p, b->parts.p, q);
-                        }
+                        for (; pass < upTo; pass++) bfsPass(b, B, pass, q);
                         HIPCHK(hipMemcpyAsync(hc.data(), b->bfsCnt.p, cntWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
                         HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
                         HIPCHK(hipStreamSynchronize(s));
@@ -1250,12 +1258,12 @@ static int batchRunOne(cmb_batch* b) {
                         peakEv = std::max(peakEv, hc[maxPass + 2 + p2]);
                     }
                     const uint32_t* pool = hc.data() + 2 * (maxPass + 2);
-                    if (getenv("CMB_VERBOSE"))
+                    if (verbose)
                         fprintf(stderr, "[bfs] %u tasks, %u passes, peak frontier %u, peak events %u, F %u, contexts %u, arena %u\n",
                                 nDfs, pass, peakQ, peakEv, pool[0], pool[1], pool[2]);
                     gridLine(verbose, "k_bfs_pass", peakQ, 256ull * B.gridX); // (the largest frontier and the most events of a pass)
                     gridLine(verbose, "k_bfs_pass_events", peakEv, 256ull * B.gridEv);
-                    if (getenv("CMB_VERBOSE") && atoi(getenv("CMB_VERBOSE")) > 1)
+                    if (verbose && atoi(verboseEnv) > 1)
                         for (uint32_t p2 = 0; p2 <= pass; p2++)
                             fprintf(stderr, "  pass %u: %u nodes, %u events\n", p2, hc[p2], hc[maxPass + 2 + p2]);
                     hipLaunchKernelGGL(k_bfs_finish, dim3(1), dim3(256), 0, s, B, q);
@@ -1286,7 +1294,7 @@ static int batchRunOne(cmb_batch* b) {
                 } else {
                     // ---- Hamming distance: the same frontier idea without a matrix (dev_bfs_hamming.hpp)
                     const uint32_t maxPass = b->maxLen + 2 * (b->wide ? MAXP_WIDE : MAXP) + 16;
-                    if (!b->bfsQCap) b->bfsQCap = (getenv("CMB_TEST_SMALL_POOLS") ? 0 : (size_t)nReads * 4) + 1024;
+                    if (!b->bfsQCap) b->bfsQCap = (smallPools ? 0 : (size_t)nReads * 4) + 1024;
                     b->bfsQCap = std::max<size_t>(b->bfsQCap, (size_t)nDfs + 1024);
                     for (int j = 0; j < 2; j++)
                         if (b->bfsQ[j].n < 2 * b->bfsQCap) b->bfsQ[j].alloc(2 * b->bfsQCap);
@@ -1304,24 +1312,22 @@ static int batchRunOne(cmb_batch* b) {
                     const uint32_t hLds = stratBytes;
                     const uint32_t startGrid = capBlocks(std::min<uint32_t>((nDfs + 255) / 256, BFS_GRID)), passGrid = capBlocks(BFS_GRID);
                     gridLine(verbose, "k_hbfs_start", nDfs, 256ull * startGrid);
-                    if (b->wide)
-                        hipLaunchKernelGGL((k_hbfs<true, MAXP_WIDE>), dim3(startGrid), dim3(256), hLds, s,
-                                           ix->d, b->stratW.p, H, 0u, b->dfs.p, nDfs, b->maxLen, b->seq.p, b->partsW.p, q);
-                    else
-                        hipLaunchKernelGGL(k_hbfs<true>, dim3(startGrid), dim3(256), hLds, s,
-                                       ix->d, b->strat.p, H, 0u, b->dfs.p, nDfs, b->maxLen, b->seq.p, b->parts.p, q);
+                    withTables(b, [&](auto mp) {
+                        constexpr int MP = decltype(mp)::value;
+                        hipLaunchKernelGGL((k_hbfs<true, MP>), dim3(startGrid), dim3(256), hLds, s, ix->d, stratOf<MP>(b), H, 0u, b->dfs.p, nDfs, b->maxLen,
+                                           b->seq.p, partsOf<MP>(b), q);
+                    });
                     std::vector<uint32_t> hc(cntWords);
                     uint32_t pass = 0, peakQ = 0;
                     bool drained = false;
                     while (!drained && pass < maxPass) {
                         const uint32_t upTo = std::min(pass + 16u, maxPass);
                         for (; pass < upTo; pass++)
-                            if (b->wide)
-                                hipLaunchKernelGGL((k_hbfs<false, MAXP_WIDE>), dim3(passGrid), dim3(256), hLds, s, ix->d, b->stratW.p, H, pass,
-                                                   (const DfsTask*)nullptr, 0u, b->maxLen, b->seq.p, b->partsW.p, q);
-                            else
-                                hipLaunchKernelGGL(k_hbfs<false>, dim3(passGrid), dim3(256), hLds, s, ix->d, b->strat.p, H, pass,
-                                               (const DfsTask*)nullptr, 0u, b->maxLen, b->seq.p, b->parts.p, q);
+                            withTables(b, [&](auto mp) {
+                                constexpr int MP = decltype(mp)::value;
+                                hipLaunchKernelGGL((k_hbfs<false, MP>), dim3(passGrid), dim3(256), hLds, s, ix->d, stratOf<MP>(b), H, pass,
+                                                   (const DfsTask*)nullptr, 0u, b->maxLen, b->seq.p, partsOf<MP>(b), q);
+                            });
                         HIPCHK(hipMemcpyAsync(hc.data(), b->bfsCnt.p, cntWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
                         HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
                         HIPCHK(hipStreamSynchronize(s));
@@ -1329,7 +1335,7 @@ static int batchRunOne(cmb_batch* b) {
                         drained = hc[pass] == 0;
                     }
                     for (uint32_t p2 = 0; p2 <= pass && p2 < cntWords; p2++) peakQ = std::max(peakQ, hc[p2]);
-                    if (getenv("CMB_VERBOSE")) fprintf(stderr, "[hbfs] %u tasks, %u passes, peak frontier %u\n", nDfs, pass, peakQ);
+                    if (verbose) fprintf(stderr, "[hbfs] %u tasks, %u passes, peak frontier %u\n", nDfs, pass, peakQ);
                     gridLine(verbose, "k_hbfs_pass", peakQ, 256ull * passGrid); // (the largest frontier of a pass)
                     BfsBufs Bf{};
                     Bf.blockCnt = b->bfsBlockCnt.p;
@@ -1384,12 +1390,7 @@ static int batchRunOne(cmb_batch* b) {
             if (b->fmN.n < 1) b->fmN.alloc(1);
             HIPCHK(hipMemsetAsync(b->fmN.p, 0, sizeof(uint32_t), s));
             hipLaunchKernelGGL(k_fm_keys, dim3((nFm + 255) / 256), dim3(256), 0, s, b->fm.p, nFm, b->fmKeysA.p, b->fmIdxA.p);
-            size_t tmpBytes = 0;
-            HIPCHK(rocprim::radix_sort_pairs(nullptr, tmpBytes, b->fmKeysA.p, b->fmKeysB.p, b->fmIdxA.p, b->fmIdxB.p, nFm, 0,
-                                             64, s));
-            if (b->sortTmp.n < tmpBytes) b->sortTmp.alloc(tmpBytes + 256);
-            HIPCHK(rocprim::radix_sort_pairs(b->sortTmp.p, tmpBytes, b->fmKeysA.p, b->fmKeysB.p, b->fmIdxA.p, b->fmIdxB.p,
-                                             nFm, 0, 64, s));
+            sortPairs(b->sortTmp, b->fmKeysA.p, b->fmKeysB.p, b->fmIdxA.p, b->fmIdxB.p, nFm, 0, 64, s);
             hipLaunchKernelGGL(k_fm_unique, dim3((nFm + 255) / 256), dim3(256), 0, s, b->fm.p, b->fmKeysB.p, b->fmIdxB.p, nFm,
                                b->fmUniq.p, b->fmN.p, q);
             HIPCHK(hipMemcpyAsync(&nFmUniq, b->fmN.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -1426,39 +1427,26 @@ static int batchRunOne(cmb_batch* b) {
                 const uint32_t tbCap = cap32(b->tbq.n);
                 const char* vGroup = "k_verify";
                 tm.begin();
-                if (dedup && b->vkeysA.n < nItems) {
-                    b->vkeysA.alloc((size_t)nItems + nItems / 8 + 256);
-                    b->vkeysB.alloc((size_t)nItems + nItems / 8 + 256);
-                    b->vcounts.alloc((size_t)nItems + nItems / 8 + 256);
-                    b->vruns.alloc(4);
-                }
-                auto kv = dedup ? k_verify<true> : k_verify<false>;
+                if (dedup) growTo(b->vkeysA, nItems), growTo(b->vkeysB, nItems), growTo(b->vcounts, nItems), growTo(b->vruns, 4);
+                auto kv = withBools([](auto keys) { return k_verify<keys()>; }, dedup);
                 hipLaunchKernelGGL(kv, dim3(vSlots / 256), dim3(256), 0, s, ix->d, b->offs.p, b->maxLen, b->gw,
                                    b->seq.p, mf, b->items.p, nItems, b->tbq.p, tbCap,
                                    dedup ? b->vkeysA.p : (unsigned long long*)nullptr, q, b->wideEdit ? 1u : 0u); // (1: the wide key layout)
                 if (dedup) {
                     uint32_t nRuns = 0;
-                    size_t tmpBytes = 0;
                     // sorted bits: low VK_LOW bits of the start, the bounds, read x strand (2 nReads < 2^rsBits, so
                     // that the all-ones key of the other items sorts behind every real key) — see packVerifyKey
                     uint32_t rsBits = 1;
                     while ((1ull << rsBits) <= 2ull * nReads) rsBits++;
                     const uint32_t bit0 = 32u - VK_LOW, bit1 = (b->wideEdit ? VKW_RS : 39u) + rsBits;
-                    HIPCHK(rocprim::radix_sort_keys(nullptr, tmpBytes, b->vkeysA.p, b->vkeysB.p, nItems, bit0, bit1, s));
-                    if (b->sortTmp.n < tmpBytes) b->sortTmp.alloc(tmpBytes + 256);
-                    HIPCHK(rocprim::radix_sort_keys(b->sortTmp.p, tmpBytes, b->vkeysA.p, b->vkeysB.p, nItems, bit0, bit1, s));
-                    size_t rleBytes = 0;
-                    HIPCHK(rocprim::run_length_encode(nullptr, rleBytes, b->vkeysB.p, nItems, b->vkeysA.p, b->vcounts.p,
-                                                      b->vruns.p, s));
-                    if (b->scanTmp.n < rleBytes) b->scanTmp.alloc(rleBytes + 256);
-                    HIPCHK(rocprim::run_length_encode(b->scanTmp.p, rleBytes, b->vkeysB.p, nItems, b->vkeysA.p,
-                                                      b->vcounts.p, b->vruns.p, s));
+                    sortKeys(b->sortTmp, b->vkeysA.p, b->vkeysB.p, nItems, bit0, bit1, s);
+                    runLengthEncode(b->scanTmp, b->vkeysB.p, nItems, b->vkeysA.p, b->vcounts.p, b->vruns.p, s);
                     HIPCHK(hipMemcpyAsync(&nRuns, b->vruns.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
                     HIPCHK(hipStreamSynchronize(s));
                     tm.end("k_verify"); // locate + key sort + run-length encode; the matrix stages are timed apart
                     vGroup = "k_verify_edit";
                     tm.begin();
-                    if (getenv("CMB_VERBOSE")) fprintf(stderr, "[verify] %u items, %u distinct keys\n", nItems, nRuns);
+                    if (verbose) fprintf(stderr, "[verify] %u items, %u distinct keys\n", nItems, nRuns);
                     if (nRuns && b->wideEdit) {
                         // 8 ... 13 errors: the band (up to 53 columns) needs the wide left margins of the 64-bit in-text matrix (dev_matrix.hpp:
                         // MXX_*, MXY_*): k_wide_filter sorts out the candidates that never reach their final column, k_verify_wide<true> verifies the rest
@@ -1471,7 +1459,7 @@ static int batchRunOne(cmb_batch* b) {
                         HIPCHK(hipMemsetAsync(b->dpWork.p, 0, 4 * sizeof(uint32_t), s));
                         auto kFilter = k_wide_filter<WxTen>;
                         auto kWide = k_verify_wide<true, WxTen>;
-                        if (b->geoX) kFilter = k_wide_filter<WxThirteen>, kWide = k_verify_wide<true, WxThirteen>;
+                        if (geoX) kFilter = k_wide_filter<WxThirteen>, kWide = k_verify_wide<true, WxThirteen>;
                         hipLaunchKernelGGL(kFilter, dim3(fGrid), dim3(256), 0, s, ix->d, b->offs.p, b->G.p, b->gw, b->vkeysA.p, b->vcounts.p, nRuns,
                                            b->dpWork.p, b->dpList.p, cap32(b->dpList.n), q);
                         const uint32_t slotBytes = (vwRows(b->maxLen) + 1u) * VW_ROW_BYTES;
@@ -1516,25 +1504,7 @@ static int batchRunOne(cmb_batch* b) {
                         // maxED <= 7) run the instance without final-column code
                         auto needsFinal = [&](uint32_t st) { return 32u * nb * (st + 1u) - 1u + 8u >= b->minLen; };
                         auto stageKernel = [&](bool first, bool fin) {
-                            const int sel = (first ? 8 : 0) | (w32 ? 4 : 0) | (packed ? 2 : 0) | (fin ? 1 : 0);
-                            switch (sel) {
-                            case 0: return k_verify_stage<false, false, false, false>;
-                            case 1: return k_verify_stage<false, false, false, true>;
-                            case 2: return k_verify_stage<false, false, true, false>;
-                            case 3: return k_verify_stage<false, false, true, true>;
-                            case 4: return k_verify_stage<false, true, false, false>;
-                            case 5: return k_verify_stage<false, true, false, true>;
-                            case 6: return k_verify_stage<false, true, true, false>;
-                            case 7: return k_verify_stage<false, true, true, true>;
-                            case 8: return k_verify_stage<true, false, false, false>;
-                            case 9: return k_verify_stage<true, false, false, true>;
-                            case 10: return k_verify_stage<true, false, true, false>;
-                            case 11: return k_verify_stage<true, false, true, true>;
-                            case 12: return k_verify_stage<true, true, false, false>;
-                            case 13: return k_verify_stage<true, true, false, true>;
-                            case 14: return k_verify_stage<true, true, true, false>;
-                            default: return k_verify_stage<true, true, true, true>;
-                            }
+                            return withBools([](auto f, auto w, auto p, auto c) { return k_verify_stage<f(), w(), p(), c()>; }, first, w32, packed, fin);
                         };
                         hipLaunchKernelGGL(stageKernel(true, needsFinal(0)), dim3(grid), dim3(256), 0, s, ix->d, b->offs.p, mf,
                                            b->vkeysA.p, b->vcounts.p, nRuns, L0, L1, b->vsN.p, listCap, 0u, nb, b->tbq.p, tbCap, q);
@@ -1563,16 +1533,13 @@ static int batchRunOne(cmb_batch* b) {
                     gridLine(verbose, "k_traceback", nTb, tSlots);
                     // 64-byte lines of 16 narrow (k <= 4) or 8 wide trace rows (a group is written whole)
                     const bool narrow = b->k <= TBN_MAX_ED && !getenv("CMB_TRACE_WIDE");
-                    const uint32_t tLines = narrow ? (vRows(b->maxLen) + 15u) / 16u + 2u : (vRows(b->maxLen) + 7u) / 8u + 2u;
+                    const uint32_t tLines = traceLines(narrow, vRows(b->maxLen));
                     if (b->vW.n < (size_t)tLines * 8 * tSlots) b->vW.alloc((size_t)tLines * 8 * tSlots);
                     VPlanes vp{b->vW.p, tSlots, tLines};
                     tm.begin();
-                    auto kTrace = k_traceback<false, false>;
-                    if (narrow) kTrace = ix->d.text2 ? k_traceback<true, true> : k_traceback<true, false>;
                     // no final-column row (> len - maxED - 1, maxED <= 7) at or before this row, for any read of the batch
                     const uint32_t rowMin = b->minLen > 8u ? b->minLen - 8u : 0u;
-                    hipLaunchKernelGGL(kTrace, dim3(tSlots / 256), dim3(256), 0, s, ix->d, b->offs.p, mf, b->tbq.p, nTb,
-                                       vp, q, rowMin);
+                    launchTraceback(s, ix->d, narrow, b->offs.p, mf, b->tbq.p, nTb, vp, q, rowMin);
                     tm.end("k_traceback");
                 }
             }
@@ -1591,9 +1558,7 @@ static int batchRunOne(cmb_batch* b) {
                 if (attempt >= 3) return fail(CMB_ERR_INTERNAL, "text occurrence queue keeps overflowing");
                 b->text.alloc((size_t)hcnt[2] + hcnt[2] / 8 + 1024);
                 HIPCHK(hipMemcpy(b->counters.p, keep, sizeof(keep), hipMemcpyHostToDevice));
-                uint32_t z = 0; // clear the overflow flag for the retry
-                uint32_t fl = hcnt[3] & ~(uint32_t)FLAG_TEXT_OVERFLOW;
-                (void)z;
+                uint32_t fl = hcnt[3] & ~(uint32_t)FLAG_TEXT_OVERFLOW; // clear the overflow flag for the retry
                 HIPCHK(hipMemcpy(b->cnt.p + 3, &fl, sizeof(uint32_t), hipMemcpyHostToDevice));
                 continue;
             }
@@ -1620,23 +1585,17 @@ static int batchRunOne(cmb_batch* b) {
             tm.begin();
             const uint32_t nG = 2u * nReads;
             if (nG >= (1u << (64u - groupShift))) return fail(CMB_ERR_UNSUPPORTED, "more than 2^23 reads in a sub-batch with reads matched by naive backtracking");
-            if (b->keysA.n < nText) {
-                b->keysA.alloc((size_t)nText + nText / 8 + 256);
-                b->keysB.alloc((size_t)nText + nText / 8 + 256);
-            }
+            growTo(b->keysA, nText), growTo(b->keysB, nText);
             if (b->fcounts.n < (size_t)nG + 1) {
                 b->fcounts.alloc((size_t)nG + 1);
                 b->foffs.alloc((size_t)nG + 1);
                 b->fsegB.alloc((size_t)nG + 1);
                 b->fsegE.alloc((size_t)nG + 1);
             }
-            if (b->frank.n < nText) b->frank.alloc((size_t)nText + nText / 8 + 256);
+            growTo(b->frank, nText);
             hipLaunchKernelGGL(k_pack_keys, dim3((nText + 255) / 256), dim3(256), 0, s, b->text.p, nText, b->offs.p, b->k, b->keysA.p,
                                b->cnt.p, 1u, (const uint8_t*)b->psel.p, keyLayout);
-            size_t tmpBytes = 0;
-            HIPCHK(rocprim::radix_sort_keys(nullptr, tmpBytes, b->keysA.p, b->keysB.p, nText, 0, 64, s));
-            if (b->sortTmp.n < tmpBytes) b->sortTmp.alloc(tmpBytes + 256);
-            HIPCHK(rocprim::radix_sort_keys(b->sortTmp.p, tmpBytes, b->keysA.p, b->keysB.p, nText, 0, 64, s));
+            sortKeys(b->sortTmp, b->keysA.p, b->keysB.p, nText, 0, 64, s);
             const int mode = b->metric == CMB_METRIC_HAMMING ? 1 : 2;
             HIPCHK(hipMemsetAsync(b->fcounts.p, 0, ((size_t)nG + 1) * sizeof(uint32_t), s));
             HIPCHK(hipMemsetAsync(b->fsegB.p, 0xFF, ((size_t)nG + 1) * sizeof(uint32_t), s));
@@ -1680,10 +1639,7 @@ static int batchRunOne(cmb_batch* b) {
         if (nGroups > (1u << (64u - groupShift))) return fail(CMB_ERR_UNSUPPORTED, "more filter groups in one sub-batch than the keys number");
         {
             tm.begin();
-            if (b->keysA.n < nText) {
-                b->keysA.alloc((size_t)nText + nText / 8 + 256);
-                b->keysB.alloc((size_t)nText + nText / 8 + 256);
-            }
+            growTo(b->keysA, nText), growTo(b->keysB, nText);
             if (b->fcounts.n < (size_t)nGroups + 1) {
                 b->fcounts.alloc((size_t)nGroups + 1);
                 b->foffs.alloc((size_t)nGroups + 1);
@@ -1694,10 +1650,7 @@ static int batchRunOne(cmb_batch* b) {
                 hipLaunchKernelGGL(k_pack_keys, dim3((nText + 255) / 256), dim3(256), 0, s, b->text.p, nText, b->offs.p,
                                    b->k, b->keysA.p, b->cnt.p, b->perStrand ? 1u : 0u, (const uint8_t*)nullptr,
                                    keyLayout);
-                size_t tmpBytes = 0;
-                HIPCHK(rocprim::radix_sort_keys(nullptr, tmpBytes, b->keysA.p, b->keysB.p, nText, 0, 64, s));
-                if (b->sortTmp.n < tmpBytes) b->sortTmp.alloc(tmpBytes + 256);
-                HIPCHK(rocprim::radix_sort_keys(b->sortTmp.p, tmpBytes, b->keysA.p, b->keysB.p, nText, 0, 64, s));
+                sortKeys(b->sortTmp, b->keysA.p, b->keysB.p, nText, 0, 64, s);
             }
             const int mode = b->k == 0 ? 0 : (b->metric == CMB_METRIC_HAMMING ? 1 : 2);
             HIPCHK(hipMemsetAsync(b->fcounts.p, 0, ((size_t)nGroups + 1) * sizeof(uint32_t), s));
@@ -1705,7 +1658,7 @@ static int batchRunOne(cmb_batch* b) {
             if (nText)
                 hipLaunchKernelGGL(k_filter_segments, dim3((nText + 255) / 256), dim3(256), 0, s, b->keysB.p, nText, b->fsegB.p,
                                    b->fsegE.p, groupShift);
-            if (b->frank.n < nText) b->frank.alloc((size_t)nText + nText / 8 + 256);
+            growTo(b->frank, nText);
             if (nText) HIPCHK(hipMemsetAsync(b->frank.p, 0xFF, (size_t)nText * sizeof(uint32_t), s));
             hipLaunchKernelGGL(k_filter_mark, dim3((nGroups + 255) / 256), dim3(256), 0, s, b->keysB.p, nGroups, b->k, mode,
                                b->fcounts.p, b->frank.p, b->fsegB.p, b->fsegE.p, keyLayout);
@@ -1718,8 +1671,8 @@ static int batchRunOne(cmb_batch* b) {
                 return fail(CMB_ERR_INTERNAL, "a traceback read a band-edge bit the narrow trace rows take as implied");
             if (hcnt[3] & FLAG_CAPACITY)
                 return fail(CMB_ERR_INTERNAL, "occurrence does not fit the filter key (width / distance range) or a traceback left the band");
-            if (b->fout.n < total) b->fout.alloc((size_t)total + total / 8 + 256);
-            if (b->wantAln && b->foutRead.n < total) b->foutRead.alloc((size_t)total + total / 8 + 256);
+            growTo(b->fout, total);
+            if (b->wantAln) growTo(b->foutRead, total);
             if (total)
                 hipLaunchKernelGGL(k_filter_write, dim3((nText + 255) / 256), dim3(256), 0, s, b->keysB.p, nText, b->offs.p,
                                    b->k, b->frank.p, b->foffs.p, b->fout.p, b->wantAln ? b->foutRead.p : (uint32_t*)nullptr,
@@ -1736,32 +1689,12 @@ static int batchRunOne(cmb_batch* b) {
                 }
                 if (total) {
                     const uint32_t cSlots = capSlots((uint32_t)std::min<uint64_t>(((total + 255) / 256) * 256, 512u * 1024u));
-                    const bool narrow = b->k <= TBN_MAX_ED && !getenv("CMB_TRACE_WIDE");
-                    const uint32_t tLines = narrow ? (vRows(b->maxLen) + 15u) / 16u + 2u : (vRows(b->maxLen) + 7u) / 8u + 2u;
-                    if (b->vW.n < (size_t)tLines * 8 * cSlots) b->vW.alloc((size_t)tLines * 8 * cSlots);
-                    VPlanes vp{b->vW.p, cSlots, tLines};
                     MFull mfc = mf;
-                    if (!mfc.p) { // (Hamming / exact batches have no match words: every CIGAR is len x M, nothing is traced)
-                        mfc.nBlk = 0;
-                    }
-                    auto kc = k_cigar<false, false>;
-                    if (narrow) kc = ix->d.text2 ? k_cigar<true, true> : k_cigar<true, false>;
-                    else if (ix->d.text2) kc = k_cigar<false, true>;
-                    if (b->metric == CMB_METRIC_EDIT && b->k > CIGAR_BLOCK_WORDS_MAX_ED) {
-                        // (k_cigar's match words reach 9 columns right of the diagonal: kernels.hpp, k_cigar_wide)
-                        const uint32_t wSlots = std::min<uint32_t>(cSlots, 256u * 256u);
-                        const uint32_t slotBytes = (vwRows(b->maxLen) + 1u) * VW_ROW_BYTES;
-                        gridLine(verbose, "k_cigar_wide", total, wSlots);
-                        if (b->dpSlab.n < (size_t)slotBytes * wSlots) b->dpSlab.alloc((size_t)slotBytes * wSlots);
-                        hipLaunchKernelGGL(k_cigar_wide, dim3(wSlots / 256), dim3(256), 0, s, ix->d, b->offs.p, b->G.p, b->gw, b->fout.p, b->foutRead.p,
-                                           (uint64_t)total, b->dpSlab.p, slotBytes, ix->seqStartsDev.p, ix->nSeqsDev, b->alnOps.p, b->alnStride,
-                                           b->alnRec.p, b->cnt.p + 3, 0u);
-                    } else {
-                        gridLine(verbose, "k_cigar", total, cSlots);
-                        hipLaunchKernelGGL(kc, dim3(cSlots / 256), dim3(256), 0, s, ix->d, b->offs.p, mfc, b->fout.p, b->foutRead.p,
-                                           (uint64_t)total, vp, ix->seqStartsDev.p, ix->nSeqsDev, b->alnOps.p, b->alnStride, b->alnRec.p,
-                                           b->cnt.p + 3, (b->metric != CMB_METRIC_EDIT || b->k == 0) ? 1u : 0u);
-                    }
+                    if (!mfc.p) mfc.nBlk = 0; // (Hamming / exact batches have no match words: every CIGAR is len x M, nothing is traced)
+                    const CigarJob job{b->offs.p, b->G.p, b->gw, b->maxLen, mfc, b->fout.p, b->foutRead.p, (uint64_t)total, b->alnOps.p, b->alnStride,
+                                       b->alnRec.p, b->cnt.p + 3, (b->metric != CMB_METRIC_EDIT || b->k == 0) ? 1u : 0u};
+                    launchCigar(ix, s, job, b->metric == CMB_METRIC_EDIT && b->k > CIGAR_BLOCK_WORDS_MAX_ED, b->k <= TBN_MAX_ED && !getenv("CMB_TRACE_WIDE"),
+                                vRows(b->maxLen), cSlots, b->vW, b->dpSlab, verbose);
                 }
                 tm.end("k_cigar");
                 HIPCHK(hipGetLastError());
@@ -1814,10 +1747,6 @@ int moveCigarsOnText(cmb_index* textIndex, hipStream_t s, const uint64_t* offs, 
     try {
         HIPCHK(hipSetDevice(textIndex->device));
         if (!nOcc) return CMB_OK;
-        const DevIndex& d = textIndex->d;
-        const uint32_t* text2 = d.text2;
-        const uint32_t* seqStartsDev = textIndex->seqStartsDev.p;
-        const uint32_t nSeqs = textIndex->nSeqsDev;
         DevBuf<uint4> mfull;
         MFull mf{nullptr, 0};
         if (!gapless) {
@@ -1828,32 +1757,12 @@ int moveCigarsOnText(cmb_index* textIndex, hipStream_t s, const uint64_t* offs, 
             mf.p = mfull.p;
         }
         const uint32_t cSlots = capSlots((uint32_t)std::min<uint64_t>(((nOcc + 255) / 256) * 256, 512u * 1024u));
-        const bool verbose = getenv("CMB_VERBOSE") != nullptr;
-        if (!gapless && k > CIGAR_BLOCK_WORDS_MAX_ED) {
-            // beyond 9 errors (k_cigar's match words reach 9 columns right of the diagonal): the matrix with the wide left margin, as for
-            // the FM-index batches (kernels.hpp: k_cigar_wide; match words straight from the read's bit-strings)
-            const uint32_t wSlots = std::min<uint32_t>(cSlots, 256u * 256u);
-            const uint32_t slotBytes = (vwRows(maxLen) + 1u) * VW_ROW_BYTES;
-            DevBuf<uint8_t> slab;
-            slab.alloc((size_t)slotBytes * wSlots);
-            gridLine(verbose, "k_cigar_wide", nOcc, wSlots);
-            hipLaunchKernelGGL(k_cigar_wide, dim3(wSlots / 256), dim3(256), 0, s, d, offs, G, gw, (const uint4*)occs, occRead, nOcc, slab.p, slotBytes,
-                               seqStartsDev, nSeqs, ops, stride, (AlnRec*)aln, flagWord, 0u);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(s)); // (the slab goes out of scope)
-            return CMB_OK;
-        }
-        const bool narrow = k <= TBN_MAX_ED;
-        const uint32_t tLines = narrow ? (vRows(maxLen) + 15u) / 16u + 2u : (vRows(maxLen) + 7u) / 8u + 2u;
+        // (beyond 9 errors the matrix with the wide left margin, as for the FM-index batches; match words straight from the read's bit-strings)
         DevBuf<uint64_t> vW;
-        vW.alloc((size_t)tLines * 8 * cSlots);
-        VPlanes vp{vW.p, cSlots, tLines};
-        auto kc = k_cigar<false, false>;
-        if (narrow) kc = text2 ? k_cigar<true, true> : k_cigar<true, false>;
-        else if (text2) kc = k_cigar<false, true>;
-        gridLine(verbose, "k_cigar", nOcc, cSlots);
-        hipLaunchKernelGGL(kc, dim3(cSlots / 256), dim3(256), 0, s, d, offs, mf, (const uint4*)occs, occRead, nOcc, vp, seqStartsDev, nSeqs, ops,
-                           stride, (AlnRec*)aln, flagWord, gapless ? 1u : 0u);
+        DevBuf<uint8_t> slab;
+        const CigarJob job{offs, G, gw, maxLen, mf, (const uint4*)occs, occRead, nOcc, ops, stride, (AlnRec*)aln, flagWord, gapless ? 1u : 0u};
+        launchCigar(textIndex, s, job, !gapless && k > CIGAR_BLOCK_WORDS_MAX_ED, k <= TBN_MAX_ED, vRows(maxLen), cSlots, vW, slab,
+                    getenv("CMB_VERBOSE") != nullptr);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(s)); // (the temporaries above go out of scope)
         return CMB_OK;
@@ -1965,9 +1874,8 @@ extern "C" int cmb_batch_timings(const cmb_batch* b, const char** names, float* 
 // backtracking, as in the reference (searchstrategy.cpp:148-152, :442-459; indexinterface.cpp:1055-1210 -> dev_bfs_naive.hpp).
 // cmb_batch_read_status says which reads took that path; cmb_batch_allow_unsupported is kept for older callers and has no effect.
 extern "C" int cmb_batch_allow_unsupported(cmb_batch* b, int on) {
+    (void)on;
     if (!b) return fail(CMB_ERR_INVALID, "null argument");
-    b->allowUnsupported = on != 0;
-    for (cmb_batch* c : b->subs) c->allowUnsupported = on != 0;
     return CMB_OK;
 }
 static uint32_t readStatusOne(const cmb_batch* b, uint8_t* status) {
@@ -2279,7 +2187,7 @@ static int verifyDirect(cmb_index* idx, const char* pattern, uint32_t plen, cons
         const uint32_t slots = capSlots((uint32_t)std::min<uint64_t>(std::max<uint64_t>(((n + 255) / 256) * 256, 256), 65536));
         const bool verbose = getenv("CMB_VERBOSE") != nullptr;
         const bool narrow = max_ed <= TBN_MAX_ED && !getenv("CMB_TRACE_WIDE");
-        const uint32_t tLines = narrow ? ((uint32_t)VROWS + 15u) / 16u + 2u : ((uint32_t)VROWS + 7u) / 8u + 2u;
+        const uint32_t tLines = traceLines(narrow, (uint32_t)VROWS);
         vW.alloc((size_t)tLines * 8 * slots);
         tbq.alloc(n + (size_t)(slots / 64 + 1) * 256);
         VPlanes vp{vW.p, slots, tLines};
@@ -2315,11 +2223,8 @@ static int verifyDirect(cmb_index* idx, const char* pattern, uint32_t plen, cons
                                items.p, (uint32_t)n, tbq.p, (uint32_t)tbq.n, (unsigned long long*)nullptr, q);
             HIPCHK(hipMemcpy(hc, cnt.p, 32, hipMemcpyDeviceToHost));
             if (hc[7]) {
-                auto kTrace = k_traceback<false, false>;
-                if (narrow) kTrace = idx->d.text2 ? k_traceback<true, true> : k_traceback<true, false>;
                 gridLine(verbose, "k_traceback", hc[7], slots);
-                hipLaunchKernelGGL(kTrace, dim3(slots / 256), dim3(256), 0, 0,
-                                   idx->d, offs.p, mf, tbq.p, hc[7], vp, q, 0u);
+                launchTraceback(0, idx->d, narrow, offs.p, mf, tbq.p, hc[7], vp, q, 0u);
             }
         }
         HIPCHK(hipGetLastError());
@@ -2395,24 +2300,11 @@ extern "C" int cmb_cigar_windows(cmb_index* idx, const char* pattern, uint32_t p
         flag.alloc(1);
         HIPCHK(hipMemset(flag.p, 0, sizeof(uint32_t)));
         const uint32_t slots = (uint32_t)std::min<uint64_t>(((n + 255) / 256) * 256, 65536);
-        const bool narrow = maxD <= TBN_MAX_ED;
-        const uint32_t tLines = narrow ? ((uint32_t)VROWS + 15u) / 16u + 2u : ((uint32_t)VROWS + 7u) / 8u + 2u;
-        vW.alloc((size_t)tLines * 8 * slots);
         ops.alloc(n * stride);
         aln.alloc(n);
-        VPlanes vp{vW.p, slots, tLines};
-        auto kc = k_cigar<false, false>;
-        if (narrow) kc = idx->d.text2 ? k_cigar<true, true> : k_cigar<true, false>;
-        else if (idx->d.text2) kc = k_cigar<false, true>;
         DevBuf<uint8_t> slab;
-        if (maxD > CIGAR_BLOCK_WORDS_MAX_ED) { // (k_cigar's match words reach 9 columns right of the diagonal: kernels.hpp, k_cigar_wide)
-            const uint32_t slotBytes = (vwRows(mlen) + 1u) * VW_ROW_BYTES;
-            slab.alloc((size_t)slotBytes * slots);
-            hipLaunchKernelGGL(k_cigar_wide, dim3(slots / 256), dim3(256), 0, 0, idx->d, offs.p, G.p, gw, occs.p, occRead.p, n, slab.p, slotBytes,
-                               idx->seqStartsDev.p, idx->nSeqsDev, ops.p, stride, aln.p, flag.p, 0u);
-        } else
-        hipLaunchKernelGGL(kc, dim3(slots / 256), dim3(256), 0, 0, idx->d, offs.p, mf, occs.p, occRead.p, n, vp, idx->seqStartsDev.p,
-                           idx->nSeqsDev, ops.p, stride, aln.p, flag.p, 0u);
+        const CigarJob job{offs.p, G.p, gw, mlen, mf, occs.p, occRead.p, n, ops.p, stride, aln.p, flag.p, 0u};
+        launchCigar(idx, 0, job, maxD > CIGAR_BLOCK_WORDS_MAX_ED, maxD <= TBN_MAX_ED, (uint32_t)VROWS, slots, vW, slab, false);
         HIPCHK(hipGetLastError());
         uint32_t hf = 0;
         HIPCHK(hipMemcpy(&hf, flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -3565,10 +3457,9 @@ int matchBestDeviceWith(cmb_index* idx, const cmb_strategy* st, bool trimCounter
             HIPCHK(hipGetLastError());
             // order: distance, strand, (sequence, begin inside it), the order in which the records were found — the last key makes the
             // order total, so the (stable) merge sort has no ties to keep
-            size_t bytes = 0;
-            HIPCHK(rocprim::merge_sort(nullptr, bytes, keysA.p, keysB.p, (size_t)nSel, BestKeyLess(), (hipStream_t)0));
-            if (tmp.n < bytes || !tmp.p) tmp.alloc(bytes + 256);
-            HIPCHK(rocprim::merge_sort(tmp.p, bytes, keysA.p, keysB.p, (size_t)nSel, BestKeyLess(), (hipStream_t)0));
+            withScratch(tmp, [&](void* p, size_t& bytes) {
+                return rocprim::merge_sort(p, bytes, keysA.p, keysB.p, (size_t)nSel, BestKeyLess(), (hipStream_t)0);
+            });
             HIPCHK(hipMemset(dUflag.p + nSel, 0, sizeof(uint64_t)));
             hipLaunchKernelGGL(k_best_uniq, dim3((uint32_t)((nSel + 255u) / 256u)), dim3(256), 0, 0, keysB.p, nSel, dUflag.p, dPerRead.p);
             HIPCHK(hipGetLastError());

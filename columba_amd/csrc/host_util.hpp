@@ -1,5 +1,6 @@
 // Host-side HIP plumbing shared by the library's translation units (columba_amd.hip, move_backend.hip): the error check, owning device
-// and page-locked buffers, the 64-bit exclusive scan and the event timer behind cmb_batch_timings / cmb_move_batch_timings.
+// and page-locked buffers, the device primitives (sorts, scan, run-length encode: rocPRIM), which geometry and tables a batch runs on,
+// what both backends do when a batch is created, and the event timer behind cmb_batch_timings / cmb_move_batch_timings.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,9 +11,14 @@
 #include <string>
 #include <vector>
 
-#include <rocprim/device/device_scan.hpp> // (after <cstring>: its headers call memset unqualified)
+#include <rocprim/device/device_radix_sort.hpp> // (after <cstring>: its headers call memset unqualified)
+#include <rocprim/device/device_run_length_encode.hpp>
+#include <rocprim/device/device_scan.hpp>
 
-#include "host_grid.hpp" // CMB_TEST_GRID_CAP and the clamps of the geometry knobs (no HIP: a CPU program tests it)
+#include "dev_bfs_edit.hpp"  // the record geometries of the frontier (GeoX, GeoW, GeoN32, GeoN)
+#include "host_dispatch.hpp" // runtime values to template arguments, the geometry rule (no HIP: a CPU program tests it)
+#include "host_grid.hpp"     // CMB_TEST_GRID_CAP and the clamps of the geometry knobs (no HIP: a CPU program tests it)
+#include "host_schemes.hpp"
 
 #define HIPCHK(expr)                                                                                  \
     do {                                                                                              \
@@ -87,13 +93,86 @@ template <typename T> struct PinnedBuf {
     const T* data() const { return p; }
 };
 
-// out[i] = in[0] + ... + in[i - 1] in 64 bits, on stream s; tmp is rocPRIM's scratch and grows as needed
-template <typename T> void scanExclusive(DevBuf<uint8_t>& tmp, const T* in, uint64_t* out, size_t n, hipStream_t s) {
+// rocPRIM's two-call idiom — a size query, the scratch, the run — in one place: call(scratch, bytes) is the primitive; tmp is its scratch
+// and grows as needed (a quarter to spare: the slices of a b-move chunk differ in size)
+template <typename Call> void withScratch(DevBuf<uint8_t>& tmp, Call&& call) {
     size_t bytes = 0;
-    HIPCHK(rocprim::exclusive_scan(nullptr, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), s));
-    if (tmp.n < bytes || !tmp.p) tmp.alloc(bytes + 256);
-    HIPCHK(rocprim::exclusive_scan(tmp.p, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), s));
+    HIPCHK(call((void*)nullptr, bytes));
+    if (tmp.n < bytes || !tmp.p) tmp.alloc(bytes + bytes / 4 + 256);
+    HIPCHK(call((void*)tmp.p, bytes));
 }
+// out[i] = in[0] + ... + in[i - 1] in the width of `out` (64 bits; 32 for the keep -> slot scan of the b-move backend), on stream s
+template <typename T, typename O> void scanExclusive(DevBuf<uint8_t>& tmp, const T* in, O* out, size_t n, hipStream_t s) {
+    withScratch(tmp, [&](void* p, size_t& bytes) { return rocprim::exclusive_scan(p, bytes, in, out, (O)0, n, rocprim::plus<O>(), s); });
+}
+// radix sorts on the key bits [bit0, bit1), keys alone or with a value each (fewer than 2^31 of them: the callers refuse more before;
+// the input stays as it is — plain pointers, so that rocPRIM instantiates what it did for the direct calls)
+template <typename K> void sortKeys(DevBuf<uint8_t>& tmp, K* in, K* out, uint32_t n, uint32_t bit0, uint32_t bit1, hipStream_t s) {
+    withScratch(tmp, [&](void* p, size_t& bytes) { return rocprim::radix_sort_keys(p, bytes, in, out, n, bit0, bit1, s); });
+}
+template <typename K, typename V>
+void sortPairs(DevBuf<uint8_t>& tmp, K* kIn, K* kOut, V* vIn, V* vOut, uint32_t n, uint32_t bit0, uint32_t bit1, hipStream_t s) {
+    withScratch(tmp, [&](void* p, size_t& bytes) { return rocprim::radix_sort_pairs(p, bytes, kIn, kOut, vIn, vOut, n, bit0, bit1, s); });
+}
+// the distinct keys of a sorted list, how often each occurs, and (nRuns[0]) how many there are
+template <typename K> void runLengthEncode(DevBuf<uint8_t>& tmp, K* in, uint32_t n, K* uniq, uint32_t* counts, uint32_t* nRuns, hipStream_t s) {
+    withScratch(tmp, [&](void* p, size_t& bytes) { return rocprim::run_length_encode(p, bytes, in, n, uniq, counts, nRuns, s); });
+}
+
+// ---- which instance a batch runs (both batch structs use the same member names)
+// the geometry of a batch's frontier (host_dispatch.hpp: frontierGeo); read per attempt: noSmallMatrix changes between two
+template <typename Batch> FrontierGeo frontierGeoOf(const Batch* b) {
+    return frontierGeo(b->wide, b->k, b->noSmallMatrix, getenv("CMB_MATRIX64") != nullptr, MX_MAX_ED, MXS_MAX_ED);
+}
+template <typename T> struct TypeTag {
+    using type = T;
+};
+// f(TypeTag<Geo>{}): the geometry as a type
+template <typename F> decltype(auto) withGeo(FrontierGeo g, F&& f) {
+    switch (g) {
+    case FrontierGeo::X: return f(TypeTag<GeoX>{});
+    case FrontierGeo::W: return f(TypeTag<GeoW>{});
+    case FrontierGeo::N32: return f(TypeTag<GeoN32>{});
+    default: return f(TypeTag<GeoN>{});
+    }
+}
+// f(std::integral_constant<int, MP>{}): the table size of the batch's width, for the kernels that depend on nothing else
+template <typename Batch, typename F> decltype(auto) withTables(const Batch* b, F&& f) {
+    return b->wide ? f(std::integral_constant<int, MAXP_WIDE>{}) : f(std::integral_constant<int, MAXP>{});
+}
+// ... and the tables of that size (Geo::MP of a geometry)
+template <int MP, typename Batch> auto stratOf(Batch* b) {
+    if constexpr (MP == MAXP) return b->strat.p;
+    else return b->stratW.p;
+}
+template <int MP, typename Batch> auto partsOf(Batch* b) {
+    if constexpr (MP == MAXP) return b->parts.p;
+    else return b->partsW.p;
+}
+
+// ---- what both backends do when a batch is created
+// the strategy flattened at k errors into the narrow or the wide table of the batch, and what the run needs to know of either
+template <typename Batch> void adoptStrategy(Batch* b, const cmb_strategy* st, uint32_t k) {
+    auto summary = [&](const auto& t) {
+        b->sNumParts = t.numParts, b->sPartition = t.partition, b->sNSchemes = t.nSchemes;
+        for (int i = 0; i < t.nSchemes; i++) b->sMaxSearches = std::max<uint32_t>(b->sMaxSearches, t.sch[i].nSearches);
+    };
+    if (b->wide) summary(b->hostStratW = st->template flatten<MAXP_WIDE>(k));
+    else summary(b->hostStrat = st->template flatten<MAXP>(k));
+}
+// the shortest and the longest of n reads given by their offsets (maxLen at least 1; minLen ~0 without reads); false: offsets decrease
+inline bool readLengths(const uint64_t* offs, uint32_t n, uint32_t& minLen, uint32_t& maxLen) {
+    maxLen = 1, minLen = ~0u;
+    for (uint32_t i = 0; i < n; i++) {
+        if (offs[i + 1] < offs[i]) return false;
+        maxLen = std::max<uint32_t>(maxLen, (uint32_t)(offs[i + 1] - offs[i]));
+        minLen = std::min<uint32_t>(minLen, (uint32_t)(offs[i + 1] - offs[i]));
+    }
+    return true;
+}
+// rows of per-read arrays are padded to a multiple of 16 bytes (16-byte stores in k_prep); the number of 32-character words per read
+// does not change
+inline uint32_t paddedLen(uint32_t maxLen) { return (maxLen + 15u) & ~15u; }
 
 // device time per kernel group of a run: end(name) waits for the stream and adds the time since begin() to the record of that name
 struct KernelTime {
@@ -126,6 +205,20 @@ struct Timer {
         out.push_back({name, ms});
     }
 };
+
+// a composite batch's counters and busy time per kernel group: those of its parts summed (the parts overlap on the device)
+template <typename Batch> void foldSubBatches(Batch* b) {
+    memset(b->cnts, 0, sizeof(b->cnts));
+    b->times.clear();
+    for (const Batch* c : b->subs) {
+        for (size_t i = 0; i < sizeof(b->cnts) / sizeof(b->cnts[0]); i++) b->cnts[i] += c->cnts[i];
+        for (const KernelTime& t : c->times) {
+            auto u = std::find_if(b->times.begin(), b->times.end(), [&](const KernelTime& x) { return !strcmp(x.name, t.name); });
+            if (u == b->times.end()) b->times.push_back(t);
+            else u->ms += t.ms;
+        }
+    }
+}
 
 struct SamPlan { // per read (32 bytes; dev_sam.hpp)
     uint32_t kind;    // SAM_*

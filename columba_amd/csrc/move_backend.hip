@@ -5,8 +5,6 @@
 #include "host_util.hpp"
 #include "move_search.hpp"
 
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -23,12 +21,12 @@ int failWith(int code, const std::string& msg); // columba_amd.hip: sets the cal
 }
 using namespace cmb;
 
-// hipcub takes its element counts as int: a count of 2^31 or more is refused here instead of being truncated by the cast
-#define MV_CUB_COUNT(n, what)                                                                                                  \
-    do {                                                                                                                       \
-        if ((uint64_t)(n) >= (1ull << 31))                                                                                     \
-            return failWith(CMB_ERR_UNSUPPORTED, std::string(what) + ": " + std::to_string((uint64_t)(n)) + " elements, hipcub " \
-                                                                  "takes 2^31 - 1 at most");                                   \
+// limits of the backend: 2^31 text positions and 2^31 records per slice (the sorts and scans below count in 32 bits)
+#define MV_COUNT_LIMIT(n, what)                                                                                                      \
+    do {                                                                                                                             \
+        if ((uint64_t)(n) >= (1ull << 31))                                                                                           \
+            return failWith(CMB_ERR_UNSUPPORTED, std::string(what) + ": " + std::to_string((uint64_t)(n)) + " elements, the backend " \
+                                                                  "takes 2^31 - 1 at most");                                         \
     } while (0)
 
 namespace {
@@ -455,12 +453,9 @@ extern "C" int cmb_move_match_exact(const cmb_move_index* idx, const char* reads
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ev[1], 0));
         // offsets of the tasks' occurrences: exclusive prefix sum over nTasks + 1 widths (the last one is zero)
-        size_t tmpBytes = 0;
-        MV_CUB_COUNT(nTasks + 1, "exact-match tasks"); // (below 2^31: 2^30 reads per call at most)
-        HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmpBytes, dWidth.p, dTaskOff.p, (int)(nTasks + 1)));
+        MV_COUNT_LIMIT(nTasks + 1, "exact-match tasks"); // (below 2^31: 2^30 reads per call at most)
         DevBuf<uint8_t> tmp;
-        tmp.alloc(tmpBytes);
-        HIPCHK(hipcub::DeviceScan::ExclusiveSum(tmp.p, tmpBytes, dWidth.p, dTaskOff.p, (int)(nTasks + 1)));
+        scanExclusive(tmp, dWidth.p, dTaskOff.p, nTasks + 1, (hipStream_t)0);
         HIPCHK(hipEventRecord(ev[2], 0));
         uint64_t total = 0;
         HIPCHK(hipMemcpy(&total, dTaskOff.p + nTasks, sizeof(total), hipMemcpyDeviceToHost));
@@ -817,28 +812,17 @@ static int moveBatchCreateOne(cmb_move_index* idx, const cmb_strategy* st, uint3
             try {
                 // (edit distance beyond 7 errors: the wide record geometries of the frontier, GeoW / GeoX, on the wide tables)
                 b->wide = st->numPartsFor(max_distance) > (uint32_t)MAXP || (st->metric == CMB_METRIC_EDIT && max_distance > 7);
-                if (b->wide) {
-                    b->hostStratW = st->flatten<MAXP_WIDE>(max_distance);
-                    b->sNumParts = b->hostStratW.numParts, b->sPartition = b->hostStratW.partition, b->sNSchemes = b->hostStratW.nSchemes;
-                    for (int i = 0; i < b->hostStratW.nSchemes; i++) b->sMaxSearches = std::max<uint32_t>(b->sMaxSearches, b->hostStratW.sch[i].nSearches);
-                } else {
-                    b->hostStrat = st->flatten(max_distance);
-                    b->sNumParts = b->hostStrat.numParts, b->sPartition = b->hostStrat.partition, b->sNSchemes = b->hostStrat.nSchemes;
-                    for (int i = 0; i < b->hostStrat.nSchemes; i++) b->sMaxSearches = std::max<uint32_t>(b->sMaxSearches, b->hostStrat.sch[i].nSearches);
-                }
+                adoptStrategy(b.get(), st, max_distance);
             } catch (const std::exception& e) {
                 return failWith(CMB_ERR_INVALID, e.what());
             }
             const int rc = ensureKmerTable(idx, kmer_size);
             if (rc != CMB_OK) return rc;
         }
-        uint32_t maxLen = 1;
-        for (uint32_t i = 0; i < n_reads; i++) {
-            if (offs[i + 1] < offs[i]) return failWith(CMB_ERR_INVALID, "read offsets must be non-decreasing");
-            maxLen = std::max<uint32_t>(maxLen, (uint32_t)(offs[i + 1] - offs[i]));
-        }
+        uint32_t maxLen, minLen;
+        if (!readLengths(offs, n_reads, minLen, maxLen)) return failWith(CMB_ERR_INVALID, "read offsets must be non-decreasing");
         if (maxLen > (uint32_t)MAX_READ) return failWith(CMB_ERR_UNSUPPORTED, "reads longer than " + std::to_string(MAX_READ) + " are not supported");
-        maxLen = (maxLen + 15u) & ~15u;
+        maxLen = paddedLen(maxLen);
         b->maxLen = maxLen;
         b->gw = gWords(maxLen);
         b->hostOffs.assign(offs, offs + n_reads + 1);
@@ -901,17 +885,7 @@ extern "C" int cmb_move_batch_run(cmb_move_batch* b) {
                                                  ? " (the chunk is matched as " + std::to_string(b->subs.size()) + " concurrent parts with pools of their own: "
                                                    "CMB_MOVE_SUBBATCHES=1 matches it as one batch)"
                                                  : ""));
-    memset(b->cnts, 0, sizeof(b->cnts));
-    b->times.clear();
-    for (const cmb_move_batch* c : b->subs) {
-        for (int i = 0; i < CMB_CNT_MAX; i++) b->cnts[i] += c->cnts[i];
-        for (const auto& t : c->times) { // busy time per kernel group, summed over the halves (they overlap on the device)
-            bool found = false;
-            for (auto& u : b->times)
-                if (!strcmp(u.name, t.name)) u.ms += t.ms, found = true;
-            if (!found) b->times.push_back(t);
-        }
-    }
+    foldSubBatches(b);
     b->done = true;
     return CMB_OK;
 }
@@ -956,6 +930,13 @@ static int moveBatchRunOne(cmb_move_batch* b) {
     b->waitForCopies();
     b->done = true;
     return CMB_OK;
+}
+
+// one level of the frontier search, as the pass loop of runSlice launches it (SMALL: 32-bit positions, on the narrow tables alone)
+template <class Geo, bool SMALL>
+static void launchMvsPass(cmb_move_batch* b, const MvBufs& B, uint32_t pass, const uint64_t* dOffs, const Queues& q) {
+    hipLaunchKernelGGL((k_mvs_pass<Geo, SMALL && Geo::MP == MAXP>), dim3(B.gridX + B.gridEv), dim3(256), 0, b->stream, b->ix->d, stratOf<Geo::MP>(b), B, pass,
+                       dOffs, b->gw, b->G.p, partsOf<Geo::MP>(b), q);
 }
 
 static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
@@ -1032,7 +1013,10 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
             sx.kmerSize = ix->kmerSize;
         }
         uint32_t hcnt[8];
-        const bool verbose = getenv("CMB_VERBOSE") != nullptr;
+        // (both read per run, not per process: tests set them between runs)
+        const bool verbose = getenv("CMB_VERBOSE") != nullptr, smallPools = getenv("CMB_TEST_SMALL_POOLS") != nullptr;
+        const bool edit = b->metric == CMB_METRIC_EDIT;
+        const bool geoX = edit && frontierGeoOf(b) == FrontierGeo::X; // (11 ... 13 errors: the in-index matrix with 16-row blocks)
         if ((b->wide ? b->partsW.n : b->parts.n) < (size_t)2 * nReads) { // per-read scratch of a slice
             b->seq.alloc((size_t)2 * nReads * b->maxLen);
             b->G.alloc((size_t)nReads * 8 * b->gw);
@@ -1065,19 +1049,14 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                 gridLine(verbose, "k_mvs_parts", tasksRS, 64ull * grid);
                 gridLine(verbose, "k_mvs_exact", nWork, 64ull * gridE);
                 const size_t exLdsBytes = (size_t)P * 3 * 64 * sizeof(uint4);
-                if (b->wide) {
-                    auto kp = b->sPartition == 0 ? k_mvs_parts<0, MAXP_WIDE> : b->sPartition == 1 ? k_mvs_parts<1, MAXP_WIDE> : k_mvs_parts<2, MAXP_WIDE>;
-                    hipLaunchKernelGGL(kp, dim3(grid), dim3(64), exLdsBytes, s, sx, b->stratW.p, nReads, b->maxLen, b->seq.p, dOffs, b->partsW.p, b->exr.p,
+                withTables(b, [&](auto mp) {
+                    constexpr int MP = decltype(mp)::value;
+                    auto kp = withInt<3>((int)b->sPartition, [](auto part) { return k_mvs_parts<part(), MP>; });
+                    hipLaunchKernelGGL(kp, dim3(grid), dim3(64), exLdsBytes, s, sx, stratOf<MP>(b), nReads, b->maxLen, b->seq.p, dOffs, partsOf<MP>(b), b->exr.p,
                                        b->psel.p, q);
-                    hipLaunchKernelGGL(k_mvs_exact<MAXP_WIDE>, dim3(gridE), dim3(64), 0, s, sx, b->stratW.p, nReads, b->maxLen, maxSearches, b->seq.p, b->partsW.p,
+                    hipLaunchKernelGGL(k_mvs_exact<MP>, dim3(gridE), dim3(64), 0, s, sx, stratOf<MP>(b), nReads, b->maxLen, maxSearches, b->seq.p, partsOf<MP>(b),
                                        b->exr.p, b->psel.p, b->tasks.p, cap32(b->tasks.n), q);
-                } else {
-                    auto kp = b->sPartition == 0 ? k_mvs_parts<0, MAXP> : b->sPartition == 1 ? k_mvs_parts<1, MAXP> : k_mvs_parts<2, MAXP>;
-                    hipLaunchKernelGGL(kp, dim3(grid), dim3(64), exLdsBytes, s, sx, b->strat.p, nReads, b->maxLen, b->seq.p, dOffs, b->parts.p, b->exr.p,
-                                       b->psel.p, q);
-                    hipLaunchKernelGGL(k_mvs_exact<MAXP>, dim3(gridE), dim3(64), 0, s, sx, b->strat.p, nReads, b->maxLen, maxSearches, b->seq.p, b->parts.p,
-                                       b->exr.p, b->psel.p, b->tasks.p, cap32(b->tasks.n), q);
-                }
+                });
             }
             tm.end("k_partition");
             HIPCHK(hipGetLastError());
@@ -1091,10 +1070,9 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
             if (hasNaive) {
                 // ---- reads not longer than the number of parts / one-part strategies: naive backtracking (k_mvs_naive)
                 tm.begin();
-                const bool edit = b->metric == CMB_METRIC_EDIT;
                 const uint32_t maxPassN = b->maxLen + 2 * b->k + 4;
                 constexpr uint32_t PU = MvTraits::PAIR_U4;
-                if (!b->nvQCap) b->nvQCap = getenv("CMB_TEST_SMALL_POOLS") ? 64 : 16384;
+                if (!b->nvQCap) b->nvQCap = smallPools ? 64 : 16384;
                 for (int j = 0; j < 2; j++)
                     if (b->nvQ[j].n < (PU + 2) * b->nvQCap) b->nvQ[j].alloc((PU + 2) * b->nvQCap);
                 const size_t cntWords = (size_t)maxPassN + 2;
@@ -1107,9 +1085,11 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                 N.nq = b->nvCnt.p;
                 N.blockCnt = nullptr;
                 N.fmX = b->fm.p;
-                auto kNaiveStart = edit ? k_mvs_naive<true, true, false> : k_mvs_naive<false, true, false>;
-                auto kNaivePass = edit ? k_mvs_naive<true, false, false> : k_mvs_naive<false, false, false>;
-                if (edit && b->k > MX_MAX_ED) kNaiveStart = k_mvs_naive<true, true, true>, kNaivePass = k_mvs_naive<true, false, true>;
+                // (the matrix of 11 ... 13 errors is the edit distance's alone)
+                auto naiveKernel = [&](bool start) {
+                    return withBools([](auto e, auto st, auto x) { return k_mvs_naive<e(), st(), e() && x()>; }, edit, start, geoX);
+                };
+                auto kNaiveStart = naiveKernel(true), kNaivePass = naiveKernel(false);
                 const uint32_t nvStart = capBlocks((tasksRS + 255) / 256), nvGrid = capBlocks(BFS_GRID);
                 gridLine(verbose, "k_mvs_naive_start", tasksRS, 256ull * nvStart);
                 hipLaunchKernelGGL(kNaiveStart, dim3(nvStart), dim3(256), 0, s, ix->d, N, 0u,
@@ -1146,7 +1126,7 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                 tm.begin();
                 const uint32_t maxPass = b->maxLen + 2 * (b->wide ? MAXP_WIDE : MAXP) + 16;
                 constexpr uint32_t PU = MvTraits::PAIR_U4;
-                if (!b->qCap) b->qCap = (getenv("CMB_TEST_SMALL_POOLS") ? 0 : (size_t)nReads * 8) + 1024;
+                if (!b->qCap) b->qCap = (smallPools ? 0 : (size_t)nReads * 8) + 1024;
                 b->qCap = std::max<size_t>(b->qCap, (size_t)nTasks + 1024);
                 for (int j = 0; j < 2; j++)
                     if (b->Q[j].n < (PU + 1) * b->qCap) b->Q[j].alloc((PU + 1) * b->qCap);
@@ -1164,24 +1144,22 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                 H.fmX = b->fm.p;
                 const uint32_t startGrid = capBlocks(std::min<uint32_t>((nTasks + 255) / 256, BFS_GRID)), passGrid = capBlocks(BFS_GRID);
                 gridLine(verbose, "k_mvs_hbfs_start", nTasks, 256ull * startGrid);
-                if (b->wide)
-                    hipLaunchKernelGGL((k_mvs_hbfs<true, MAXP_WIDE>), dim3(startGrid), dim3(256), 0, s, ix->d, b->stratW.p,
-                                       H, 0u, b->tasks.p, nTasks, b->maxLen, b->seq.p, b->partsW.p, q);
-                else
-                    hipLaunchKernelGGL((k_mvs_hbfs<true, MAXP>), dim3(startGrid), dim3(256), 0, s, ix->d, b->strat.p, H, 0u,
-                                       b->tasks.p, nTasks, b->maxLen, b->seq.p, b->parts.p, q);
+                withTables(b, [&](auto mp) {
+                    constexpr int MP = decltype(mp)::value;
+                    hipLaunchKernelGGL((k_mvs_hbfs<true, MP>), dim3(startGrid), dim3(256), 0, s, ix->d, stratOf<MP>(b), H, 0u, b->tasks.p, nTasks, b->maxLen,
+                                       b->seq.p, partsOf<MP>(b), q);
+                });
                 std::vector<uint32_t> hc(cntWords);
                 uint32_t pass = 0, peakQ = 0;
                 bool drained = false;
                 while (!drained && pass < maxPass) {
                     const uint32_t upTo = std::min(pass + 16u, maxPass);
                     for (; pass < upTo; pass++)
-                        if (b->wide)
-                            hipLaunchKernelGGL((k_mvs_hbfs<false, MAXP_WIDE>), dim3(passGrid), dim3(256), 0, s, ix->d, b->stratW.p, H, pass, (const MvTask*)nullptr,
-                                               0u, b->maxLen, b->seq.p, b->partsW.p, q);
-                        else
-                            hipLaunchKernelGGL((k_mvs_hbfs<false, MAXP>), dim3(passGrid), dim3(256), 0, s, ix->d, b->strat.p, H, pass, (const MvTask*)nullptr, 0u,
-                                               b->maxLen, b->seq.p, b->parts.p, q);
+                        withTables(b, [&](auto mp) {
+                            constexpr int MP = decltype(mp)::value;
+                            hipLaunchKernelGGL((k_mvs_hbfs<false, MP>), dim3(passGrid), dim3(256), 0, s, ix->d, stratOf<MP>(b), H, pass, (const MvTask*)nullptr,
+                                               0u, b->maxLen, b->seq.p, partsOf<MP>(b), q);
+                        });
                     HIPCHK(hipMemcpyAsync(hc.data(), b->bfsCnt.p, cntWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
                     HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
                     HIPCHK(hipStreamSynchronize(s));
@@ -1204,11 +1182,10 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
             } else if (nTasks) {
                 tm.begin();
                 const uint32_t maxPass = 2 * b->maxLen + 8 * (b->wide ? MAXP_WIDE : MAXP) + 64;
-                const bool geoX = b->wide && b->k > MX_MAX_ED; // (11 ... 13 errors: the in-index matrix with 16-row blocks)
                 const uint32_t pkU4 = b->wide ? GeoW::PK_U4 : GeoN::PK_U4; // planes of a node's final-column pack / uint4 of an event's
                 if (!b->qCap) {
-                    const size_t slack = getenv("CMB_TEST_SMALL_POOLS") ? 64 : 65536;
-                    const size_t per = getenv("CMB_TEST_SMALL_POOLS") ? 0 : 1;
+                    const size_t slack = smallPools ? 64 : 65536;
+                    const size_t per = smallPools ? 0 : 1;
                     b->qCap = per * (size_t)nReads * 4 + slack;
                     b->evCap = per * (size_t)nReads + slack;
                     b->fCap = per * (size_t)nReads * 16 + slack;
@@ -1258,36 +1235,24 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                 B.fmX = b->fm.p;
                 B.rowSteps = nullptr;
                 B.narrowWv = getenv("CMB_TEST_NARROW_WV") ? (uint32_t)std::max(0, atoi(getenv("CMB_TEST_NARROW_WV"))) : 0xFFFFu;
-                // up to 6 errors the in-index matrix runs on 32-bit words (GeoN32, dev_matrix.hpp: MXS_*) unless a phase did not fit it (CMB_MATRIX64=1: never)
-                const bool small32 = !b->wide && b->k <= MXS_MAX_ED && !b->noSmallMatrix && !getenv("CMB_MATRIX64");
+                const FrontierGeo geo = frontierGeoOf(b);
                 const dim3 gStart(capBlocks(std::min<uint32_t>((nTasks + 255) / 256, BFS_GRID)));
                 gridLine(verbose, "k_mvs_start", nTasks, 256ull * gStart.x);
-                if (geoX)
-                    hipLaunchKernelGGL(k_mvs_start<GeoX>, gStart, dim3(256), 0, s, b->stratW.p, B, b->tasks.p, nTasks, dOffs, b->gw, b->G.p, b->partsW.p, q);
-                else if (b->wide)
-                    hipLaunchKernelGGL(k_mvs_start<GeoW>, gStart, dim3(256), 0, s, b->stratW.p, B, b->tasks.p, nTasks, dOffs, b->gw, b->G.p, b->partsW.p, q);
-                else if (small32)
-                    hipLaunchKernelGGL(k_mvs_start<GeoN32>, gStart, dim3(256), 0, s, b->strat.p, B, b->tasks.p, nTasks, dOffs, b->gw, b->G.p, b->parts.p, q);
-                else
-                    hipLaunchKernelGGL(k_mvs_start<GeoN>, gStart, dim3(256), 0, s, b->strat.p, B, b->tasks.p, nTasks, dOffs, b->gw, b->G.p, b->parts.p, q);
+                withGeo(geo, [&](auto g) {
+                    using Geo = typename decltype(g)::type;
+                    hipLaunchKernelGGL(k_mvs_start<Geo>, gStart, dim3(256), 0, s, stratOf<Geo::MP>(b), B, b->tasks.p, nTasks, dOffs, b->gw, b->G.p,
+                                       partsOf<Geo::MP>(b), q);
+                });
+                // (the instance of a pass is chosen here, once per attempt: the loop below calls through a pointer)
+                const auto mvsPass = withGeo(geo, [&](auto g) {
+                    return withBools([](auto small) { return &launchMvsPass<typename decltype(g)::type, decltype(small)::value>; }, smallPos);
+                });
                 std::vector<uint32_t> hc(cntWords);
                 uint32_t pass = 0, peakQ = 0, peakEv = 0;
                 bool drained = false;
                 while (!drained && pass < maxPass) {
                     const uint32_t upTo = std::min(pass + 16u, maxPass);
-                    for (; pass < upTo; pass++)
-                        if (geoX)
-                            hipLaunchKernelGGL(k_mvs_pass<GeoX>, dim3(B.gridX + B.gridEv), dim3(256), 0, s, ix->d, b->stratW.p, B, pass, dOffs, b->gw, b->G.p,
-                                               b->partsW.p, q);
-                        else if (b->wide)
-                            hipLaunchKernelGGL(k_mvs_pass<GeoW>, dim3(B.gridX + B.gridEv), dim3(256), 0, s, ix->d, b->stratW.p, B, pass, dOffs, b->gw, b->G.p,
-                                               b->partsW.p, q);
-                        else if (small32)
-                            hipLaunchKernelGGL((smallPos ? k_mvs_pass<GeoN32, true> : k_mvs_pass<GeoN32, false>), dim3(B.gridX + B.gridEv), dim3(256), 0, s, ix->d,
-                                               b->strat.p, B, pass, dOffs, b->gw, b->G.p, b->parts.p, q);
-                        else
-                            hipLaunchKernelGGL((smallPos ? k_mvs_pass<GeoN, true> : k_mvs_pass<GeoN, false>), dim3(B.gridX + B.gridEv), dim3(256), 0, s, ix->d,
-                                               b->strat.p, B, pass, dOffs, b->gw, b->G.p, b->parts.p, q);
+                    for (; pass < upTo; pass++) mvsPass(b, B, pass, dOffs, q);
                     HIPCHK(hipMemcpyAsync(hc.data(), b->bfsCnt.p, cntWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
                     HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
                     HIPCHK(hipStreamSynchronize(s));
@@ -1301,7 +1266,7 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                 const uint32_t* pool = hc.data() + 2 * (maxPass + 2);
                 gridLine(verbose, "k_mvs_pass", peakQ, 256ull * B.gridX); // (the largest frontier and the most events of a pass)
                 gridLine(verbose, "k_mvs_pass_events", peakEv, 256ull * B.gridEv);
-                if (getenv("CMB_VERBOSE"))
+                if (verbose)
                     fprintf(stderr, "[mvs] %u tasks, %u passes, peak frontier %u, peak events %u, F %u, contexts %u, arena %u\n", nTasks, pass, peakQ, peakEv,
                             pool[0], pool[1], pool[2]);
                 hipLaunchKernelGGL(k_mvs_finish, dim3(1), dim3(256), 0, s, B, q);
@@ -1336,17 +1301,11 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                 b->keysA.alloc(c), b->keysB.alloc(c), b->fmIdxA.alloc(c), b->fmIdxB.alloc(c), b->keep.alloc(c + 1), b->slot.alloc(c + 1), b->widths.alloc(c + 1);
             }
             hipLaunchKernelGGL(k_mvs_fm_keys, dim3(gridFor(nFm)), dim3(256), 0, s, b->fm.p, nFm, b->keysA.p, b->fmIdxA.p);
-            size_t tb = 0;
-            MV_CUB_COUNT((uint64_t)nFm + 1, "in-index occurrences of one slice"); // (2^31 records of 96 bytes would not fit the HBM)
-            HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, b->keysA.p, b->keysB.p, b->fmIdxA.p, b->fmIdxB.p, (int)nFm, 0, 64, s));
-            if (b->sortTmp.n < tb) b->sortTmp.alloc(tb + tb / 4);
-            HIPCHK(hipcub::DeviceRadixSort::SortPairs(b->sortTmp.p, tb, b->keysA.p, b->keysB.p, b->fmIdxA.p, b->fmIdxB.p, (int)nFm, 0, 64, s));
+            MV_COUNT_LIMIT((uint64_t)nFm + 1, "in-index occurrences of one slice"); // (2^31 records of 96 bytes would not fit the HBM)
+            sortPairs(b->sortTmp, b->keysA.p, b->keysB.p, b->fmIdxA.p, b->fmIdxB.p, nFm, 0, 64, s);
             hipLaunchKernelGGL(k_mvs_fm_unique, dim3(gridFor(nFm)), dim3(256), 0, s, b->fm.p, b->fmIdxB.p, nFm, b->keep.p, b->widths.p);
             HIPCHK(hipMemsetAsync(b->keep.p + nFm, 0, sizeof(uint32_t), s));
-            tb = 0;
-            HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, b->keep.p, b->slot.p, (int)(nFm + 1), s));
-            if (b->sortTmp.n < tb) b->sortTmp.alloc(tb + tb / 4);
-            HIPCHK(hipcub::DeviceScan::ExclusiveSum(b->sortTmp.p, tb, b->keep.p, b->slot.p, (int)(nFm + 1), s));
+            scanExclusive(b->sortTmp, b->keep.p, b->slot.p, (size_t)nFm + 1, s);
             HIPCHK(hipMemcpyAsync(&nUniq, b->slot.p + nFm, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
             if (nUniq) {
@@ -1357,11 +1316,8 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                 hipLaunchKernelGGL(k_mvs_fm_compact, dim3(gridFor(nFm)), dim3(256), 0, s, b->fm.p, b->fmIdxB.p, b->keep.p, b->slot.p, nFm, b->locRanges.p,
                                    b->locMeta.p, b->locWidths.p);
                 HIPCHK(hipMemsetAsync(b->locWidths.p + nUniq, 0, sizeof(uint64_t), s));
-                tb = 0;
-                MV_CUB_COUNT((uint64_t)nUniq + 1, "distinct in-index occurrences of one slice"); // (nUniq <= nFm)
-                HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, b->locWidths.p, b->locOff.p, (int)(nUniq + 1), s));
-                if (b->sortTmp.n < tb) b->sortTmp.alloc(tb + tb / 4);
-                HIPCHK(hipcub::DeviceScan::ExclusiveSum(b->sortTmp.p, tb, b->locWidths.p, b->locOff.p, (int)(nUniq + 1), s));
+                MV_COUNT_LIMIT((uint64_t)nUniq + 1, "distinct in-index occurrences of one slice"); // (nUniq <= nFm)
+                scanExclusive(b->sortTmp, b->locWidths.p, b->locOff.p, (size_t)nUniq + 1, s);
                 HIPCHK(hipMemcpyAsync(&totalPos, b->locOff.p + nUniq, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
                 HIPCHK(hipStreamSynchronize(s));
             }
@@ -1387,19 +1343,13 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
         const uint32_t uniqueOnly = b->metric == CMB_METRIC_EDIT ? 0u : 1u; // (getTextOccHamming, indexinterface.cpp:1331-1371: no redundancy filter)
         auto sortAndFilter = [&](uint64_t nKeys, uint32_t nGroups, DevBuf<MoveOccOut>& dst, uint64_t& kept) -> int {
             // (nKeys < 2^31: the refusals of 2^31 text positions per slice; nGroups <= 2^24: 2^23 reads per batch)
-            MV_CUB_COUNT(nKeys, "text occurrences of one slice");
-            MV_CUB_COUNT((uint64_t)nGroups + 1, "filter groups of one slice");
-            size_t tb = 0;
-            HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, b->keysA.p, b->keysB.p, b->vals.p, b->valsB.p, (int)nKeys, 0, 64, s));
-            if (b->sortTmp.n < tb) b->sortTmp.alloc(tb + tb / 4);
-            HIPCHK(hipcub::DeviceRadixSort::SortPairs(b->sortTmp.p, tb, b->keysA.p, b->keysB.p, b->vals.p, b->valsB.p, (int)nKeys, 0, 64, s));
+            MV_COUNT_LIMIT(nKeys, "text occurrences of one slice");
+            MV_COUNT_LIMIT((uint64_t)nGroups + 1, "filter groups of one slice");
+            sortPairs(b->sortTmp, b->keysA.p, b->keysB.p, b->vals.p, b->valsB.p, (uint32_t)nKeys, 0, 64, s);
             HIPCHK(hipMemsetAsync(b->readCnt.p, 0, ((size_t)nGroups + 1) * sizeof(uint64_t), s));
             hipLaunchKernelGGL(k_mvs_filter<false>, dim3(gridFor(nGroups)), dim3(256), 0, s, b->keysB.p, b->valsB.p, nKeys, nGroups, window, b->readCnt.p,
                                (const uint64_t*)nullptr, (MoveOccOut*)nullptr, uniqueOnly);
-            tb = 0;
-            HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, b->readCnt.p, b->readOff.p, (int)(nGroups + 1), s));
-            if (b->sortTmp.n < tb) b->sortTmp.alloc(tb + tb / 4);
-            HIPCHK(hipcub::DeviceScan::ExclusiveSum(b->sortTmp.p, tb, b->readCnt.p, b->readOff.p, (int)(nGroups + 1), s));
+            scanExclusive(b->sortTmp, b->readCnt.p, b->readOff.p, (size_t)nGroups + 1, s);
             HIPCHK(hipMemcpyAsync(&kept, b->readOff.p + nGroups, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
             if (dst.n < kept) dst.alloc(kept + kept / 4 + 256);
