@@ -16,7 +16,6 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CMB_LIB") or os.path.join(_HERE, "libcolumba_amd.so")  # (CMB_LIB: a variant build, for A/B runs)
-_SRC = os.path.join(_HERE, "csrc", "columba_amd.hip")
 
 CMB_OK = 0
 CMB_ERR_INVALID, CMB_ERR_DEVICE, CMB_ERR_UNSUPPORTED, CMB_ERR_OVERFLOW, CMB_ERR_INTERNAL = -1, -2, -3, -4, -5
@@ -68,34 +67,56 @@ class CmbError(RuntimeError):
         self.code = code
 
 
+_CSRC = os.path.join(_HERE, "csrc")
+_OBJDIR = os.path.join(_HERE, "_build")
+
+
+def build_units() -> list:
+    """The library's translation units: every *.hip in csrc."""
+    return sorted(f for f in os.listdir(_CSRC) if f.endswith(".hip"))
+
+
+def unit_dependencies(unit: str) -> Optional[list]:
+    """The files the last compilation of a unit read, as the compiler recorded them (-MD) beside its object; None: not recorded."""
+    try:
+        with open(os.path.join(_OBJDIR, unit.replace(".hip", ".d"))) as f:
+            words = f.read().replace("\\\n", " ").split()
+    except OSError:
+        return None
+    return [os.path.normpath(os.path.join(_CSRC, w)) for w in words[1:]]  # (words[0]: the target; the project's files relative to csrc)
+
+
 def build_library(force: bool = False) -> str:
-    """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU): one object per translation unit
-    (the matcher; the b-move backend; the paired-end records; the pairing in BEST mode), linked into one shared library."""
-    csrc = os.path.join(_HERE, "csrc")
-    header = os.path.join(os.path.dirname(_HERE), "include", "columba_amd.h")
-    units = {"columba_amd.hip": [f for f in os.listdir(csrc) if not f.startswith(("move_", "pair_"))],
-             # (the b-move backend shares the event handler, the matrix and the wave helpers with the matcher)
-             "move_backend.hip": [f for f in os.listdir(csrc) if not f.startswith("pair_") and f != "columba_amd.hip"],
-             "pair_sam.hip": ["pair_sam.hip", "host_sam.hpp"],
-             "pair_best.hip": ["pair_best.hip", "host_best.hpp", "host_sam.hpp"]}
-    every = [os.path.join(csrc, f) for f in os.listdir(csrc)] + [header]
-    if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in every):
-        return LIB_PATH  # (the objects are build scratch: only the library travels to the GPU box)
+    """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU): one object per translation unit (every
+    *.hip in csrc), the stale ones concurrently, linked into one shared library.  A unit is stale when a file its last compilation
+    read is newer than its object."""
+    every = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC)] + [os.path.join(os.path.dirname(_HERE), "include", "columba_amd.h")]
+    units = build_units()
+    deps = {u: unit_dependencies(u) for u in units}
+    if (not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in every)
+            and all(deps.values())):
+        return LIB_PATH  # (the objects are build scratch: only the library and the recorded dependencies travel to the GPU box)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    objdir = os.path.join(_HERE, "_build")
-    os.makedirs(objdir, exist_ok=True)
-    objs, relink = [], force or not os.path.exists(LIB_PATH)
-    for unit, deps in units.items():
-        obj = os.path.join(objdir, unit.replace(".hip", ".o"))
-        srcs = [os.path.join(csrc, f) for f in deps] + [header]
-        if force or not os.path.exists(obj) or any(os.path.getmtime(obj) < os.path.getmtime(s) for s in srcs):
-            subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
-                                   "-Wno-unused-variable", "-c", "-o", obj, os.path.join(csrc, unit)])
-            relink = True
-        relink = relink or os.path.getmtime(obj) > os.path.getmtime(LIB_PATH)
-        objs.append(obj)
-    if relink:
-        subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs)
+    os.makedirs(_OBJDIR, exist_ok=True)
+    obj = {u: os.path.join(_OBJDIR, u.replace(".hip", ".o")) for u in units}
+
+    def stale(u):
+        if force or not deps[u] or not os.path.exists(obj[u]):
+            return True
+        return any(not os.path.exists(s) or os.path.getmtime(obj[u]) < os.path.getmtime(s) for s in deps[u])
+
+    def compile_unit(u):
+        subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-variable",
+                               "-MD", "-MF", obj[u][:-2] + ".d", "-c", "-o", obj[u], u], cwd=_CSRC)
+
+    todo = [u for u in units if stale(u)]
+    if todo:
+        from concurrent.futures import ThreadPoolExecutor
+        jobs = os.environ.get("MAX_JOBS", "")
+        with ThreadPoolExecutor(max(1, min(len(todo), int(jobs) if jobs.isdigit() else 8))) as pool:  # (never sized by the CPU count)
+            list(pool.map(compile_unit, todo))
+    if todo or not os.path.exists(LIB_PATH) or any(os.path.getmtime(obj[u]) > os.path.getmtime(LIB_PATH) for u in units):
+        subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + [obj[u] for u in units])
     return LIB_PATH
 
 

@@ -1,17 +1,12 @@
 // C-ABI implementation (include/columba_amd.h) on top of the HIP kernels.  gfx950 only.
 #include "../../include/columba_amd.h"
-#include "host_best.hpp"
-#include "host_sam.hpp"
 #include "host_schemes.hpp"
 #include "host_util.hpp"
 #include "kernels.hpp"
-#include "dev_sam.hpp"
-#include "dev_pair.hpp"
-#include "dev_best.hpp"
+#include "units.hpp"
 
 #include <chrono>
 #include <cstring>
-#include <functional>
 #include <memory>
 #include <mutex>
 #include <thread>
@@ -26,7 +21,7 @@ static int fail(int code, const std::string& msg) {
     return code;
 }
 namespace cmb {
-int failWith(int code, const std::string& msg) { return fail(code, msg); } // for the library's other translation units
+int failWith(int code, const std::string& msg) { return fail(code, msg); } // for the library's other translation units (host_error.hpp)
 }
 // ------------------------------------------------------------------------------------ index
 struct cmb_index {
@@ -610,16 +605,7 @@ struct cmb_batch {
     uint32_t alnStride = 0;
     PinnedBuf<uint16_t> hAlnOps;
     PinnedBuf<AlnRec> hAlnRec;
-    // cmb_batch_sam_device: the sub-batch's buffers of the SAM driver; samHostList: the reads k_sam_plan leaves to the host ([0]: how
-    // many); samOut: the finished text of the whole batch in page-locked memory (the composite's own, or the single batch's)
-    SamDeviceBufs sam;
-    DevBuf<uint32_t> samHostList;
-    PinnedBuf<char> samOut;
-    // cmb_pair_sam_device (this batch holds read 1 of every pair): the plan of the concordant pairs; per pair the SAM lines the device
-    // writes and whether it counts as mapped, and the scan that sums either (64 bits: no field of a packed word to run over)
-    DevBuf<PairPlan> pairPlan;
-    DevBuf<uint64_t> pairRecords, pairSums;
-    DevBuf<uint32_t> pairMapped;
+    SamBufs samBufs; // (what the SAM and pair drivers keep with this part: cmb_batch_sam_device, cmb_pair_sam_device, sam.hip)
     // cmb_verify_batch_staged: candidates given by the caller take the place of the search's in-text items, and the
     // raw text occurrences (before the filter) are what is handed back
     std::vector<uint4> presetItems;
@@ -1737,12 +1723,38 @@ static int batchRunOne(cmb_batch* b) {
 // 64 human haplotypes next to ~130 GB of tables), and the matched string of an occurrence IS text[begin, end): findCIGAR on that
 // window (k_cigar) gives the reference's CIGAR without carrying anything through the frontier.
 namespace cmb {
+int deviceOfIndex(const cmb_index* ix) { return ix->device; }
+bool indexIsTextOnly(const cmb_index* ix) { return ix->textOnly; }
 const std::vector<uint32_t>& seqStartsOfIndex(const cmb_index* textIndex) { return textIndex->seqStarts; }
-// CIGAR and sequence assignment of nOcc occurrences {begin, end, distance, strand} of the reads `occRead` on a text: the k_cigar launch
-// of batchRunOne for a caller that has the pieces (device pointers throughout; aln: nOcc x 16 bytes {seqId, seqBegin, nOps, spans};
-// ops: nOcc x stride, stored end to begin as for cmb_batch_alignments).
+// The final lists of a batch that has run with alignments, one view per part, for the SAM and pair drivers and the strata of BEST mode
+int batchListViews(cmb_batch* b, bool perStrand, std::vector<ListView>& out) {
+    if (!b) return fail(CMB_ERR_INVALID, "null argument");
+    if (perStrand && b->ix == nullptr) return fail(CMB_ERR_INVALID, "a batch without an index");
+    if (!b->done) return fail(CMB_ERR_INVALID, "batch has not been run");
+    if (!b->wantAln) return fail(CMB_ERR_INVALID, "alignments were not requested (cmb_batch_want_alignments)");
+    if (perStrand && !b->perStrand) return fail(CMB_ERR_INVALID, "the strands were not filtered each by itself (cmb_batch_filter_per_strand)");
+    std::vector<cmb_batch*> parts = b->subs;
+    if (parts.empty()) parts.push_back(b);
+    out.clear();
+    for (cmb_batch* c : parts) {
+        ListView v;
+        v.nReads = c->nReads, v.k = c->k, v.metric = c->metric, v.textIndex = c->ix;
+        v.reads = c->reads.p, v.offs = c->offs.p;
+        v.goffs = c->foffs.p, v.groupStride = c->perStrand ? 2u : 1u;
+        v.occ = c->fout.p, v.aln = c->alnRec.p, v.ops = c->alnOps.p, v.stride = c->alnStride;
+        v.stream = c->stream;
+        v.hostOffs = c->hostOffs.data();
+        v.hOcc = c->occs.data(), v.hOccBytes = sizeof(cmb_occ), v.hOccOffs = c->occOffs.data(), v.hOffsPerGroup = true;
+        v.hAln = c->hAlnRec.data(), v.hOps = c->hAlnOps.data();
+        v.cnts = c->cnts, v.times = &c->times;
+        v.bufs = &c->samBufs, v.scanTmp = &c->scanTmp;
+        out.push_back(v);
+    }
+    return CMB_OK;
+}
+// (declared in units.hpp; the k_cigar launch of batchRunOne)
 int moveCigarsOnText(cmb_index* textIndex, hipStream_t s, const uint64_t* offs, const uint32_t* G, uint32_t gw, uint32_t nReads, uint32_t maxLen,
-                     uint32_t k, int gapless, const void* occs, const uint32_t* occRead, uint64_t nOcc, void* aln, uint16_t* ops, uint32_t stride,
+                     uint32_t k, int gapless, const uint4* occs, const uint32_t* occRead, uint64_t nOcc, AlnRec* aln, uint16_t* ops, uint32_t stride,
                      uint32_t* flagWord) {
     try {
         HIPCHK(hipSetDevice(textIndex->device));
@@ -1760,7 +1772,7 @@ int moveCigarsOnText(cmb_index* textIndex, hipStream_t s, const uint64_t* offs, 
         // (beyond 9 errors the matrix with the wide left margin, as for the FM-index batches; match words straight from the read's bit-strings)
         DevBuf<uint64_t> vW;
         DevBuf<uint8_t> slab;
-        const CigarJob job{offs, G, gw, maxLen, mf, (const uint4*)occs, occRead, nOcc, ops, stride, (AlnRec*)aln, flagWord, gapless ? 1u : 0u};
+        const CigarJob job{offs, G, gw, maxLen, mf, occs, occRead, nOcc, ops, stride, aln, flagWord, gapless ? 1u : 0u};
         launchCigar(textIndex, s, job, !gapless && k > CIGAR_BLOCK_WORDS_MAX_ED, k <= TBN_MAX_ED, vRows(maxLen), cSlots, vW, slab,
                     getenv("CMB_VERBOSE") != nullptr);
         HIPCHK(hipGetLastError());
@@ -1920,49 +1932,6 @@ extern "C" int cmb_match_batch(cmb_index* idx, const cmb_strategy* st, uint32_t 
     }
     cmb_batch_destroy(b);
     return rc;
-}
-
-// ------------------------------------------------------------------------- output records (host-only)
-static int64_t putString(const std::string& s, char* out, uint64_t cap) {
-    if (out && cap > s.size()) memcpy(out, s.c_str(), s.size() + 1);
-    return (int64_t)s.size();
-}
-static SamHit toHit(const cmb_sam_hit& h) {
-    SamHit r;
-    r.seqName = h.seq_name ? h.seq_name : "*";
-    r.cigar = cigarString(h.cigar_ops, h.n_ops);
-    r.pos0 = h.pos0;
-    r.distance = h.distance;
-    r.revCompl = h.revcomp != 0;
-    return r;
-}
-extern "C" int64_t cmb_sam_se(const char* read_id, const cmb_sam_hit* hit, int primary, uint32_t n_hits, uint32_t min_score,
-                              const char* print_seq, const char* print_qual, char* out, uint64_t cap) {
-    if (!read_id || !hit || !print_seq || !print_qual) return fail(CMB_ERR_INVALID, "null argument");
-    return putString(samLineSE(read_id, toHit(*hit), primary != 0, n_hits, min_score, print_seq, print_qual), out, cap);
-}
-extern "C" int64_t cmb_sam_se_xa(const char* read_id, const cmb_sam_hit* hits, uint32_t n, uint32_t n_hits, const char* print_seq,
-                                 const char* print_qual, char* out, uint64_t cap) {
-    if (!read_id || !hits || n == 0 || !print_seq || !print_qual) return fail(CMB_ERR_INVALID, "null argument");
-    std::vector<SamHit> v;
-    for (uint32_t i = 0; i < n; i++) v.push_back(toHit(hits[i]));
-    return putString(samLineSEWithXA(read_id, v, n_hits, print_seq, print_qual), out, cap);
-}
-extern "C" int64_t cmb_sam_unmapped_se(const char* read_id, const char* seq, const char* qual, char* out, uint64_t cap) {
-    if (!read_id || !seq || !qual) return fail(CMB_ERR_INVALID, "null argument");
-    return putString(samLineUnmappedSE(read_id, seq, qual), out, cap);
-}
-extern "C" int cmb_read_prepare(const char* id, const char* seq, const char* qual, char* id_out, char* seq_out, char* revcomp_out,
-                                char* revqual_out) {
-    if (!id || !seq) return fail(CMB_ERR_INVALID, "null argument");
-    const std::string cid = cleanSeqID(id), cs = cleanReadSeq(seq), rc = revComplWithN(cs);
-    std::string rq = qual ? qual : "";
-    std::reverse(rq.begin(), rq.end());
-    if (id_out) memcpy(id_out, cid.c_str(), cid.size() + 1);
-    if (seq_out) memcpy(seq_out, cs.c_str(), cs.size() + 1);
-    if (revcomp_out) memcpy(revcomp_out, rc.c_str(), rc.size() + 1);
-    if (revqual_out) memcpy(revqual_out, rq.c_str(), rq.size() + 1);
-    return CMB_OK;
 }
 
 // ------------------------------------------------------------------------- fine-grained hooks
@@ -2323,1466 +2292,3 @@ extern "C" int cmb_cigar_windows(cmb_index* idx, const char* pattern, uint32_t p
     }
 }
 
-namespace {
-
-// IndexInterface::findSeqName for an occurrence that runs over the end of its sequence (indexinterface.cpp:833-899):
-// trim to the sequence it mostly lies in and verify again inside that window (edit distance only)
-static bool trimOccurrence(cmb_index* idx, const std::string& seq, uint32_t largestStratum, int metric, BestOcc& o,
-                           uint64_t* counters) {
-    if (metric == CMB_METRIC_HAMMING) return false;
-    const std::vector<uint32_t>& sp = idx->seqStarts;
-    const uint32_t index = o.aln.seq_id;
-    if (sp.size() < 2 || index + 1 >= sp.size()) return false;
-    uint32_t b = o.occ.begin, e = o.occ.end, seqId = index;
-    if (sp[index + 1] - b <= largestStratum) { // option 1: begin is just before the end of the sequence
-        seqId = index + 1;
-        if (seqId + 1 >= sp.size()) return false;
-        b = sp[seqId];
-        e = std::min(e, sp[seqId + 1]);
-    } else if (e - sp[index + 1] <= largestStratum) { // option 2: end is just over the start of the next sequence
-        e = sp[index + 1];
-    } else {
-        return false;
-    }
-    if (e <= b) return false;
-    cmb_occ res[64];
-    uint64_t n = 0, cnt[CMB_CNT_MAX];
-    if (cmb_verify_window(idx, seq.data(), (uint32_t)seq.size(), b, e, largestStratum, 0, res, 64, &n, cnt) != CMB_OK) return false;
-    for (int i = 0; counters && i < CMB_CNT_MAX; i++) counters[i] += cnt[i];
-    if (n == 0) return false;
-    // the minimal occurrence under TextOcc::operator< (begin, distance, width; indexhelpers.h:779-795)
-    const cmb_occ* bestO = &res[0];
-    for (uint64_t i = 1; i < n; i++) {
-        const cmb_occ& c = res[i];
-        const uint32_t wc = c.end - c.begin, wb = bestO->end - bestO->begin;
-        if (c.begin != bestO->begin ? c.begin < bestO->begin
-                                    : c.distance != bestO->distance ? c.distance < bestO->distance : wc < wb)
-            bestO = &c;
-    }
-    o.occ.begin = bestO->begin;
-    o.occ.end = bestO->end;
-    o.occ.distance = bestO->distance;
-    o.aln.seq_id = seqId;
-    o.aln.seq_begin = bestO->begin - sp[seqId];
-    o.aln.spans = 2; // found with trimming
-    uint16_t opsBuf[2 * 13 + 3];
-    uint32_t nOps = 0;
-    o.ops.clear();
-    if (cmb_cigar_windows(idx, seq.data(), (uint32_t)seq.size(), &o.occ.begin, &o.occ.end, &o.occ.distance, 1, opsBuf, 2 * 13 + 3,
-                          &nOps) != CMB_OK)
-        return false;
-    o.ops.assign(opsBuf, opsBuf + nOps);
-    return true;
-}
-
-} // namespace
-
-// IndexInterface::findSeqName for ONE occurrence that runs over the end of its sequence (cmb_aln.spans == 1), for host layers
-// that build their own records (paired reads): FOUND_WITH_TRIMMING -> *found = 1 and occ / aln / CIGAR updated; NOT_FOUND -> 0.
-extern "C" int cmb_trim_occurrence(cmb_index* idx, const char* pattern, uint32_t plen, uint32_t largest_stratum, int metric, cmb_occ* occ,
-                                   cmb_aln* aln, uint16_t* cigar_ops, uint32_t ops_cap, uint32_t* n_ops, int* found) {
-    if (!idx || !pattern || !occ || !aln || !found) return fail(CMB_ERR_INVALID, "null argument");
-    try {
-        BestOcc o;
-        o.occ = *occ;
-        o.aln = *aln;
-        const bool ok = trimOccurrence(idx, std::string(pattern, plen), largest_stratum, metric, o, nullptr);
-        *found = ok ? 1 : 0;
-        if (ok) {
-            if (o.ops.size() > ops_cap) return fail(CMB_ERR_OVERFLOW, "room for the CIGAR operations of the trimmed occurrence");
-            *occ = o.occ;
-            *aln = o.aln;
-            aln->cigar_len = (uint16_t)o.ops.size();
-            for (size_t i = 0; i < o.ops.size() && cigar_ops; i++) cigar_ops[i] = o.ops[i];
-            if (n_ops) *n_ops = (uint32_t)o.ops.size();
-        }
-        return CMB_OK;
-    } catch (const std::exception& e) {
-        return fail(CMB_ERR_DEVICE, e.what());
-    }
-}
-
-// SAM text of a whole chunk in ALL mode: matchApproxAllMap D) -> SearchStrategy::generateOutputSingleEnd
-// (searchstrategy.cpp:530-533, :1824-1902) -> generateSE_SAM / generateSE_SAM_XATag (searchstrategy.h:1612-1641), from the
-// occurrences, CIGARs and sequence assignments the device produced (cmb_batch_want_alignments before cmb_batch_run).
-// Occurrences that run over the end of their sequence are trimmed and verified again (findSeqName,
-// indexinterface.cpp:833-899) through the device hooks.
-// the SAM records of one read from its occurrences with alignments (generateOutputSingleEnd, searchstrategy.cpp:1824-1902)
-static void samOfRead(std::string& text, cmb_index* idx, uint32_t k, int metric, const std::string& read, const std::string& revC,
-                      const std::string& sid, const std::string& qual, std::vector<BestOcc>& occs, const char* const* seq_names,
-                      int unmapped_records, int xa_tag) {
-    std::string revQ = qual;
-    std::reverse(revQ.begin(), revQ.end());
-    std::vector<SamHit> hits;
-    for (BestOcc& o : occs) {
-        if (o.aln.spans == 1 && !trimOccurrence(idx, o.occ.strand ? revC : read, k, metric, o, nullptr)) continue; // NOT_FOUND
-        SamHit h;
-        h.seqName = seq_names[o.aln.seq_id];
-        h.cigar = cigarString(o.ops.data(), (uint32_t)o.ops.size());
-        h.pos0 = o.aln.seq_begin;
-        h.distance = o.occ.distance;
-        h.revCompl = o.occ.strand != 0;
-        hits.push_back(h);
-    }
-    if (hits.empty()) {
-        if (unmapped_records) text += samLineUnmappedSE(sid, read, qual);
-        return;
-    }
-    // primary = the first occurrence of minimal distance, swapped to the front (:1883-1899)
-    size_t mi = 0;
-    for (size_t j = 1; j < hits.size(); j++)
-        if (hits[j].distance < hits[mi].distance) mi = j;
-    const uint32_t minScore = hits[mi].distance;
-    uint32_t nHits = 0;
-    for (const SamHit& h : hits) nHits += h.distance == minScore;
-    if (mi != 0) std::swap(hits[0], hits[mi]);
-    const bool rcFirst = hits[0].revCompl;
-    if (xa_tag) {
-        text += samLineSEWithXA(sid, hits, nHits, rcFirst ? revC : read, rcFirst ? revQ : qual);
-    } else {
-        text += samLineSE(sid, hits[0], true, nHits, minScore, rcFirst ? revC : read, rcFirst ? revQ : qual);
-        for (size_t j = 1; j < hits.size(); j++) text += samLineSE(sid, hits[j], false, nHits, minScore, "*", "*");
-    }
-}
-
-// the occurrences of read i of a (sub-)batch with their alignments, as the run left them on the host
-static std::vector<BestOcc> occsOfBatchRead(const cmb_batch* c, uint32_t i) {
-    std::vector<BestOcc> occs;
-    const uint64_t q0 = c->occOffs.data()[c->perStrand ? 2 * (size_t)i : i], q1 = c->occOffs.data()[c->perStrand ? 2 * (size_t)i + 2 : i + 1];
-    for (uint64_t q2 = q0; q2 < q1; q2++) {
-        BestOcc o;
-        o.occ = c->occs.data()[q2];
-        const AlnRec& ar = c->hAlnRec.data()[q2];
-        o.aln = cmb_aln{ar.seqId, ar.seqBegin, 0, (uint16_t)ar.nOps, (uint16_t)ar.spans, 0};
-        const uint16_t* src = c->hAlnOps.data() + q2 * c->alnStride;
-        for (uint32_t j = 0; j < ar.nOps; j++) o.ops.push_back(src[ar.nOps - 1 - j]);
-        occs.push_back(std::move(o));
-    }
-    return occs;
-}
-
-extern "C" int64_t cmb_batch_sam(const cmb_batch* b, const char* seqs, const char* const* read_ids, const char* const* quals,
-                                 const char* const* seq_names, int unmapped_records, int xa_tag, char* out, uint64_t cap) {
-    if (!b || !seqs || !read_ids || !seq_names) return fail(CMB_ERR_INVALID, "null argument");
-    if (!b->done) return fail(CMB_ERR_INVALID, "batch has not been run");
-    if (!b->wantAln) return fail(CMB_ERR_INVALID, "alignments were not requested (cmb_batch_want_alignments)");
-    try {
-        std::vector<const cmb_batch*> parts;
-        if (b->subs.empty()) parts.push_back(b);
-        else
-            for (const cmb_batch* c : b->subs) parts.push_back(c);
-        cmb_index* idx = b->ix;
-        std::string text;
-        uint64_t readBase = 0, charBase = 0;
-        for (const cmb_batch* c : parts) {
-            for (uint32_t i = 0; i < c->nReads; i++) {
-                const uint64_t gi = readBase + i;
-                const uint64_t o0 = charBase + c->hostOffs[i], o1 = charBase + c->hostOffs[i + 1];
-                const std::string read = cleanReadSeq(std::string(seqs + o0, seqs + o1)), revC = revComplWithN(read);
-                const std::string sid = cleanSeqID(read_ids[gi]);
-                const std::string qual = quals && quals[gi] ? quals[gi] : "*";
-                std::vector<BestOcc> occs = occsOfBatchRead(c, i);
-                samOfRead(text, idx, c->k, c->metric, read, revC, sid, qual, occs, seq_names, unmapped_records, xa_tag);
-            }
-            readBase += c->nReads;
-            charBase += c->hostOffs[c->nReads];
-        }
-        return putString(text, out, cap);
-    } catch (const std::exception& e) {
-        return fail(CMB_ERR_DEVICE, e.what());
-    }
-}
-
-// The same text written on the device (dev_sam.hpp): plan -> lengths of the host-formatted reads -> scan -> write, every sub-batch on
-// its own stream, the finished text in one page-locked buffer of the batch.  Reads with an occurrence that runs over the end of its
-// sequence (AlnRec::spans == 1) go through samOfRead on the host — findSeqName trims them and may drop them — and their bytes are
-// copied into place by the write kernel; nothing else is formatted on the host.
-// The driver's steps, shared with cmb_best_sam_device; every one works on the stream it is given.
-// 1. The slice [r0, r0 + n) of the packed inputs goes up, the plan's arrays are sized and the length behind the last read is cleared;
-//    cx gets the input fields of the context (the packed bytes stay where they are: idBase / qualBase are subtracted on the device).
-static int samUpload(SamDeviceBufs& d, const cmb_sam_inputs* in, uint64_t r0, uint32_t n, hipStream_t s, SamCtx& cx) {
-    const size_t offBytes = ((size_t)n + 1) * sizeof(uint64_t);
-    const uint64_t idLo = in->id_offs[r0], idHi = in->id_offs[r0 + n];
-    if (idHi < idLo) return fail(CMB_ERR_INVALID, "identifier offsets must be non-decreasing");
-    growTo(d.ids, idHi - idLo + 1); // (+ 1: the cleaned identifier starts at byte 1, also of an empty line)
-    growTo(d.idOffs, (size_t)n + 1);
-    if (idHi > idLo) HIPCHK(hipMemcpyAsync(d.ids.p, in->ids + idLo, idHi - idLo, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d.idOffs.p, in->id_offs + r0, offBytes, hipMemcpyHostToDevice, s));
-    uint64_t qLo = 0;
-    if (in->quals) {
-        qLo = in->qual_offs[r0];
-        const uint64_t qHi = in->qual_offs[r0 + n];
-        if (qHi < qLo) return fail(CMB_ERR_INVALID, "quality offsets must be non-decreasing");
-        growTo(d.quals, qHi - qLo);
-        growTo(d.qualOffs, (size_t)n + 1);
-        if (qHi > qLo) HIPCHK(hipMemcpyAsync(d.quals.p, in->quals + qLo, qHi - qLo, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(d.qualOffs.p, in->qual_offs + r0, offBytes, hipMemcpyHostToDevice, s));
-    }
-    const uint64_t nameBytes = in->n_seqs ? in->seq_name_offs[in->n_seqs] : 0;
-    growTo(d.names, nameBytes);
-    growTo(d.nameOffs, (size_t)in->n_seqs + 1);
-    if (nameBytes) HIPCHK(hipMemcpyAsync(d.names.p, in->seq_names, nameBytes, hipMemcpyHostToDevice, s));
-    if (in->n_seqs) HIPCHK(hipMemcpyAsync(d.nameOffs.p, in->seq_name_offs, ((size_t)in->n_seqs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    growTo(d.plan, n);
-    growTo(d.len, (size_t)n + 1);
-    growTo(d.offs, (size_t)n + 1);
-    HIPCHK(hipMemsetAsync(d.len.p + n, 0, sizeof(uint64_t), s));
-    cx.ids = d.ids.p, cx.idOffs = d.idOffs.p, cx.idBase = idLo;
-    cx.quals = in->quals ? d.quals.p : nullptr, cx.qualOffs = d.qualOffs.p, cx.qualBase = qLo;
-    cx.names = d.names.p, cx.nameOffs = d.nameOffs.p, cx.nSeqs = in->n_seqs, cx.nReads = n;
-    return CMB_OK;
-}
-// 2. The reads of `list` (ascending) are formatted on the host — format(i, text) appends the records of read i — and spliced in: their
-//    text goes up and k_sam_override puts their lengths over the plan's.  The stream must have been waited for if `list` came from it.
-template <class F> static void samSplice(SamDeviceBufs& d, const std::vector<uint32_t>& list, hipStream_t s, F format) {
-    std::string side;
-    std::vector<uint64_t> sideOffs(list.size() + 1, 0);
-    for (size_t q = 0; q < list.size(); q++) {
-        format(list[q], side);
-        sideOffs[q + 1] = side.size();
-    }
-    growTo(d.side, side.size());
-    growTo(d.sideOffs, sideOffs.size());
-    growTo(d.sideReads, list.size());
-    if (!side.empty()) HIPCHK(hipMemcpy(d.side.p, side.data(), side.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d.sideOffs.p, sideOffs.data(), sideOffs.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d.sideReads.p, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_sam_override, dim3(((uint32_t)list.size() + 255u) / 256u), dim3(256), 0, s, d.sideReads.p, d.sideOffs.p, (uint32_t)list.size(),
-                       d.plan.p, d.len.p);
-    HIPCHK(hipGetLastError());
-}
-// 3. The position of every read in the text; *total (the text's length) is valid once the stream has been waited for ...
-static void samScan(SamDeviceBufs& d, DevBuf<uint8_t>& scanTmp, uint32_t n, uint64_t* total, hipStream_t s) {
-    scanExclusive(scanTmp, d.len.p, d.offs.p, (size_t)n + 1, s);
-    HIPCHK(hipMemcpyAsync(total, d.offs.p + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-}
-//    ... and then the text is written and copied to dst (page-locked); the caller waits for the stream once more.
-static void samWrite(SamDeviceBufs& d, const SamCtx& cx, uint64_t total, char* dst, hipStream_t s) {
-    growTo(d.text, (size_t)total + 16);
-    hipLaunchKernelGGL(k_sam_write, dim3((cx.nReads + SAM_READS_PER_WAVE - 1u) / SAM_READS_PER_WAVE), dim3(64), 0, s, cx, d.plan.p, d.offs.p, d.side.p,
-                       d.text.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(dst, d.text.p, (size_t)total, hipMemcpyDeviceToHost, s));
-}
-// the sequence names of packed inputs as the host formatters take them
-static std::vector<std::string> samNamesOf(const cmb_sam_inputs* in) {
-    std::vector<std::string> names;
-    for (uint32_t q = 0; q < in->n_seqs; q++) names.emplace_back(in->seq_names + in->seq_name_offs[q], in->seq_names + in->seq_name_offs[q + 1]);
-    return names;
-}
-
-// One part of a chunk as the driver sees it: a (sub-)batch of either flavour with its lists in HBM (cx: the list fields of the context),
-// the buffers it keeps for the driver, and its occurrences on the host for the reads the host formats
-struct SamPart {
-    uint32_t n = 0, k = 0;
-    int metric = 1;
-    hipStream_t s = nullptr;
-    SamCtx cx{};
-    SamDeviceBufs* sam = nullptr;
-    DevBuf<uint32_t>* hostList = nullptr;
-    DevBuf<uint8_t>* scanTmp = nullptr;
-    const uint64_t* hostOffs = nullptr; // read offsets of the part, from 0
-    std::function<std::vector<BestOcc>(uint32_t)> occsOf;
-};
-// idx: the index whose text and sequence starts serve the trimming of the host-formatted reads
-static int samDeviceOver(cmb_index* idx, std::vector<SamPart>& parts, const cmb_sam_inputs* in, int unmapped_records, int xa_tag,
-                         PinnedBuf<char>& samOut, const char** text, uint64_t* length, uint64_t* host_reads) {
-    useDevice(idx->device);
-    const size_t P = parts.size();
-    const bool verbose = getenv("CMB_VERBOSE") != nullptr;
-    auto t0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (!verbose) return;
-        auto t1 = std::chrono::steady_clock::now();
-        fprintf(stderr, "[host] sam: %-28s %7.3f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count());
-        t0 = t1;
-    };
-    std::vector<uint64_t> readBase(P + 1, 0), charBase(P + 1, 0), partBytes(P, 0);
-    std::vector<uint32_t> nHost(P, 0);
-    for (size_t j = 0; j < P; j++) {
-        readBase[j + 1] = readBase[j] + parts[j].n;
-        charBase[j + 1] = charBase[j] + (parts[j].n ? parts[j].hostOffs[parts[j].n] : 0);
-    }
-    // ---- plan: inputs up, one wavefront per read
-    for (size_t j = 0; j < P; j++) {
-        SamPart& c = parts[j];
-        const uint32_t n = c.n;
-        if (!n) continue;
-        hipStream_t s = c.s;
-        SamCtx& cx = c.cx;
-        cx.unmapped = unmapped_records ? 1u : 0u, cx.xa = xa_tag ? 1u : 0u;
-        if (int rc = samUpload(*c.sam, in, readBase[j], n, s, cx)) return rc;
-        growTo(*c.hostList, (size_t)n + 1);
-        HIPCHK(hipMemsetAsync(c.hostList->p, 0, sizeof(uint32_t), s));
-        hipLaunchKernelGGL(k_sam_plan, dim3((n + 3u) / 4u), dim3(256), 0, s, cx, c.sam->plan.p, c.sam->len.p, c.hostList->p);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(&nHost[j], c.hostList->p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    }
-    lap("inputs up, plan started");
-    // ---- the reads the host formats (k_sam_plan listed them), then the position of every read in its sub-batch's text
-    std::vector<std::string> names;
-    std::vector<const char*> namePtrs;
-    uint64_t nHostAll = 0;
-    for (size_t j = 0; j < P; j++) {
-        SamPart& c = parts[j];
-        const uint32_t n = c.n;
-        if (!n) continue;
-        hipStream_t s = c.s;
-        HIPCHK(hipStreamSynchronize(s));
-        if (nHost[j]) {
-            if (names.empty()) names = samNamesOf(in);
-            if (namePtrs.empty())
-                for (const std::string& nm : names) namePtrs.push_back(nm.c_str());
-            std::vector<uint32_t> list(nHost[j]);
-            HIPCHK(hipMemcpy(list.data(), c.hostList->p + 1, (size_t)nHost[j] * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            std::sort(list.begin(), list.end());
-            samSplice(*c.sam, list, s, [&](uint32_t i, std::string& side) {
-                const uint64_t gi = readBase[j] + i;
-                const uint64_t o0 = charBase[j] + c.hostOffs[i], o1 = charBase[j] + c.hostOffs[i + 1];
-                const std::string read = cleanReadSeq(std::string(in->seqs + o0, in->seqs + o1)), revC = revComplWithN(read);
-                const std::string sid = cleanSeqID(std::string(in->ids + in->id_offs[gi], in->ids + in->id_offs[gi + 1]));
-                const std::string qual = in->quals ? std::string(in->quals + in->qual_offs[gi], in->quals + in->qual_offs[gi + 1]) : "*";
-                std::vector<BestOcc> occs = c.occsOf(i);
-                samOfRead(side, idx, c.k, c.metric, read, revC, sid, qual, occs, namePtrs.data(), unmapped_records, xa_tag);
-            });
-            nHostAll += nHost[j];
-        }
-        samScan(*c.sam, *c.scanTmp, n, &partBytes[j], s);
-    }
-    uint64_t total = 0;
-    for (size_t j = 0; j < P; j++) {
-        if (parts[j].n) HIPCHK(hipStreamSynchronize(parts[j].s));
-        total += partBytes[j];
-    }
-    lap("plan, host reads, scan");
-    // ---- write: every sub-batch its piece, copied to its place in the batch's text
-    samOut.resize((size_t)total + 1);
-    samOut.p[total] = '\0';
-    uint64_t at = 0;
-    for (size_t j = 0; j < P; j++) {
-        if (!parts[j].n || !partBytes[j]) continue;
-        samWrite(*parts[j].sam, parts[j].cx, partBytes[j], samOut.p + at, parts[j].s);
-        at += partBytes[j];
-    }
-    for (size_t j = 0; j < P; j++)
-        if (parts[j].n && partBytes[j]) HIPCHK(hipStreamSynchronize(parts[j].s));
-    lap("write, text down");
-    *text = samOut.p;
-    *length = total;
-    if (host_reads) *host_reads = nHostAll;
-    return CMB_OK;
-}
-static bool samInputsOk(const cmb_sam_inputs* in) {
-    return in && in->seqs && in->ids && in->id_offs && (!in->quals || in->qual_offs) && (!in->n_seqs || (in->seq_names && in->seq_name_offs));
-}
-
-extern "C" int cmb_batch_sam_device(cmb_batch* b, const cmb_sam_inputs* in, int unmapped_records, int xa_tag, const char** text,
-                                    uint64_t* length, uint64_t* host_reads) {
-    if (!b || !text || !length || !samInputsOk(in)) return fail(CMB_ERR_INVALID, "null argument");
-    if (!b->done) return fail(CMB_ERR_INVALID, "batch has not been run");
-    if (!b->wantAln) return fail(CMB_ERR_INVALID, "alignments were not requested (cmb_batch_want_alignments)");
-    try {
-        std::vector<cmb_batch*> subs;
-        if (b->subs.empty()) subs.push_back(b);
-        else subs = b->subs;
-        std::vector<SamPart> parts;
-        for (cmb_batch* c : subs) {
-            SamPart p;
-            p.n = c->nReads, p.k = c->k, p.metric = c->metric, p.s = c->stream;
-            p.cx = SamCtx{c->reads.p, c->offs.p, c->foffs.p, c->perStrand ? 2u : 1u, c->fout.p, c->alnRec.p, c->alnOps.p, c->alnStride};
-            p.sam = &c->sam, p.hostList = &c->samHostList, p.scanTmp = &c->scanTmp;
-            p.hostOffs = c->hostOffs.data();
-            p.occsOf = [c](uint32_t i) { return occsOfBatchRead(c, i); };
-            parts.push_back(std::move(p));
-        }
-        return samDeviceOver(b->ix, parts, in, unmapped_records, xa_tag, b->samOut, text, length, host_reads);
-    } catch (const std::exception& e) {
-        return fail(CMB_ERR_DEVICE, e.what());
-    }
-}
-
-// ---- read pairs in ALL mode: both mates' lists stay in HBM, the pairs are formed and their records written there (dev_pair.hpp).  The
-// driver is the single-end one — inputs up (samUpload, once per mate), plan, the host's pairs spliced in (samSplice), scan (samScan),
-// write — with sub-batch j of the two batches on the stream of read 1's.  A pair the device does not handle (an occurrence over the
-// end of its sequence or without a sequence, or lists without a concordant pair) is formatted by cmb_pair_sam from the batches' host
-// copies, trimmed as the host adapters do (cmb_trim_occurrence with edit distance).
-namespace {
-struct PairHostRead { // one mate as cmb_pair_sam takes it
-    std::string id, seq, rc, qual, rq;
-    std::vector<BestOcc> occs;
-    std::vector<cmb_pair_occ> po;
-    cmb_pair_read view() const { return cmb_pair_read{id.c_str(), seq.c_str(), rc.c_str(), qual.c_str(), rq.c_str(), po.data(), (uint32_t)po.size()}; }
-};
-void pairHostRead(PairHostRead& h, cmb_index* idx, const cmb_batch* c, uint32_t i, const cmb_sam_inputs* in, uint64_t gi, uint64_t charBase) {
-    const uint64_t o0 = charBase + c->hostOffs[i], o1 = charBase + c->hostOffs[i + 1];
-    h.seq = cleanReadSeq(std::string(in->seqs + o0, in->seqs + o1));
-    h.rc = revComplWithN(h.seq);
-    h.id = cleanSeqID(std::string(in->ids + in->id_offs[gi], in->ids + in->id_offs[gi + 1]));
-    h.qual = in->quals ? std::string(in->quals + in->qual_offs[gi], in->quals + in->qual_offs[gi + 1]) : std::string();
-    h.rq = h.qual;
-    std::reverse(h.rq.begin(), h.rq.end());
-    h.occs = occsOfBatchRead(c, i);
-    h.po.clear();
-    for (BestOcc& o : h.occs) {
-        if (o.aln.spans == 1 && !trimOccurrence(idx, o.occ.strand ? h.rc : h.seq, c->k, CMB_METRIC_EDIT, o, nullptr)) continue; // NOT_FOUND
-        h.po.push_back(cmb_pair_occ{o.aln.seq_id, o.aln.seq_begin, o.aln.seq_begin + (o.occ.end - o.occ.begin), o.occ.begin, o.occ.distance,
-                                    o.occ.strand, o.ops.data(), (uint32_t)o.ops.size()});
-    }
-}
-const char* pairBatchRefusal(const cmb_batch* b) {
-    if (b->ix == nullptr) return "a batch without an index";
-    if (!b->done) return "batch has not been run";
-    if (!b->wantAln) return "alignments were not requested (cmb_batch_want_alignments)";
-    if (!b->perStrand) return "the strands were not filtered each by itself (cmb_batch_filter_per_strand)";
-    return nullptr;
-}
-} // namespace
-
-extern "C" int cmb_pair_sam_device(cmb_batch* mates1, cmb_batch* mates2, const cmb_pair_params* params, const cmb_sam_inputs* in1,
-                                   const cmb_sam_inputs* in2, const char** text, uint64_t* length, cmb_pair_device_stats* stats) {
-    if (!mates1 || !mates2 || !params || !text || !length || !samInputsOk(in1) || !samInputsOk(in2)) return fail(CMB_ERR_INVALID, "null argument");
-    if (mates1 == mates2) return fail(CMB_ERR_INVALID, "the two mates need a batch each");
-    if (params->orientation > 2) return fail(CMB_ERR_INVALID, "orientation must be one of CMB_ORIENTATION_*");
-    for (const cmb_batch* b : {(const cmb_batch*)mates1, (const cmb_batch*)mates2})
-        if (const char* why = pairBatchRefusal(b)) return fail(CMB_ERR_INVALID, why);
-    if (mates1->ix != mates2->ix || mates1->k != mates2->k || mates1->metric != mates2->metric)
-        return fail(CMB_ERR_INVALID, "the mates' batches differ in index, metric or maximal distance");
-    if (mates1->nReads != mates2->nReads) return fail(CMB_ERR_INVALID, "the mates' batches do not hold the same number of reads");
-    if (mates1->subBound != mates2->subBound) return fail(CMB_ERR_INVALID, "the mates' batches are split into different sub-batches");
-    if (in1->n_seqs != in2->n_seqs) return fail(CMB_ERR_INVALID, "the mates' inputs name different numbers of sequences");
-    try {
-        cmb_index* idx = mates1->ix;
-        useDevice(idx->device);
-        std::vector<cmb_batch*> subs1, subs2;
-        if (mates1->subs.empty()) subs1.push_back(mates1), subs2.push_back(mates2);
-        else subs1 = mates1->subs, subs2 = mates2->subs;
-        const size_t P = subs1.size();
-        const cmb_sam_inputs* in[2] = {in1, in2};
-        std::vector<uint64_t> readBase(P + 1, 0), charBase1(P + 1, 0), charBase2(P + 1, 0), partBytes(P, 0), partRecords(P, 0), partMapped(P, 0);
-        std::vector<uint32_t> nHost(P, 0);
-        std::vector<PairCtx> ctx(P);
-        for (size_t j = 0; j < P; j++) {
-            if (subs1[j]->nReads != subs2[j]->nReads) return fail(CMB_ERR_INVALID, "the mates' batches are split into different sub-batches");
-            const uint32_t n = subs1[j]->nReads;
-            readBase[j + 1] = readBase[j] + n;
-            charBase1[j + 1] = charBase1[j] + (n ? subs1[j]->hostOffs[n] : 0);
-            charBase2[j + 1] = charBase2[j] + (n ? subs2[j]->hostOffs[n] : 0);
-        }
-        // ---- plan: inputs of both mates up, one wavefront per pair
-        for (size_t j = 0; j < P; j++) {
-            cmb_batch* c[2] = {subs1[j], subs2[j]};
-            const uint32_t n = c[0]->nReads;
-            if (!n) continue;
-            hipStream_t s = c[0]->stream;
-            PairCtx& pc = ctx[j];
-            pc.orientation = params->orientation, pc.maxFrag = params->max_frag, pc.minFrag = params->min_frag;
-            for (int m = 0; m < 2; m++) {
-                pc.m[m] = SamCtx{c[m]->reads.p, c[m]->offs.p, c[m]->foffs.p, 2u, c[m]->fout.p, c[m]->alnRec.p, c[m]->alnOps.p, c[m]->alnStride};
-                if (int rc = samUpload(c[m]->sam, in[m], readBase[j], n, s, pc.m[m])) return rc;
-            }
-            growTo(c[0]->pairPlan, n);
-            growTo(c[0]->pairRecords, (size_t)n + 1);
-            growTo(c[0]->pairMapped, (size_t)n + 1);
-            growTo(c[0]->pairSums, (size_t)n + 1);
-            growTo(c[0]->samHostList, (size_t)n + 1);
-            HIPCHK(hipMemsetAsync(c[0]->samHostList.p, 0, sizeof(uint32_t), s));
-            HIPCHK(hipMemsetAsync(c[0]->pairRecords.p + n, 0, sizeof(uint64_t), s));
-            HIPCHK(hipMemsetAsync(c[0]->pairMapped.p + n, 0, sizeof(uint32_t), s));
-            hipLaunchKernelGGL(k_pair_plan, dim3((n + 3u) / 4u), dim3(256), 0, s, pc, params->unmapped_records ? 1u : 0u, c[0]->sam.plan.p,
-                               c[0]->pairPlan.p, c[0]->sam.len.p, c[0]->pairRecords.p, c[0]->pairMapped.p, c[0]->samHostList.p);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(&nHost[j], c[0]->samHostList.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        }
-        // ---- the pairs the host formats, then the position of every pair in its sub-batch's text
-        std::vector<std::string> names;
-        std::vector<const char*> namePtrs;
-        uint64_t nHostAll = 0, hostMapped = 0;
-        for (size_t j = 0; j < P; j++) {
-            cmb_batch* c[2] = {subs1[j], subs2[j]};
-            const uint32_t n = c[0]->nReads;
-            if (!n) continue;
-            hipStream_t s = c[0]->stream;
-            HIPCHK(hipStreamSynchronize(s));
-            if (nHost[j]) {
-                if (names.empty()) {
-                    names = samNamesOf(in1);
-                    for (const std::string& nm : names) namePtrs.push_back(nm.c_str());
-                }
-                std::vector<uint32_t> list(nHost[j]);
-                HIPCHK(hipMemcpy(list.data(), c[0]->samHostList.p + 1, (size_t)nHost[j] * sizeof(uint32_t), hipMemcpyDeviceToHost));
-                std::sort(list.begin(), list.end());
-                PairHostRead h[2];
-                std::vector<char> buf;
-                samSplice(c[0]->sam, list, s, [&](uint32_t i, std::string& side) {
-                    pairHostRead(h[0], idx, c[0], i, in1, readBase[j] + i, charBase1[j]);
-                    pairHostRead(h[1], idx, c[1], i, in2, readBase[j] + i, charBase2[j]);
-                    const cmb_pair_read r1 = h[0].view(), r2 = h[1].view();
-                    uint32_t nPairs = 0;
-                    const int64_t len = cmb_pair_sam(params, &r1, &r2, namePtrs.data(), nullptr, 0, &nPairs);
-                    if (len < 0) throw std::runtime_error(g_err);
-                    buf.resize((size_t)len + 1);
-                    cmb_pair_sam(params, &r1, &r2, namePtrs.data(), buf.data(), (uint64_t)len + 1, &nPairs);
-                    side.append(buf.data(), (size_t)len);
-                    hostMapped += nPairs > 0;
-                });
-                nHostAll += nHost[j];
-            }
-            samScan(c[0]->sam, c[0]->scanTmp, n, &partBytes[j], s);
-            // the records the device writes and the pairs it maps: a 64-bit sum each, through the same scan buffer one after the other
-            scanExclusive(c[0]->scanTmp, c[0]->pairRecords.p, c[0]->pairSums.p, (size_t)n + 1, s);
-            HIPCHK(hipMemcpyAsync(&partRecords[j], c[0]->pairSums.p + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-            scanExclusive(c[0]->scanTmp, c[0]->pairMapped.p, c[0]->pairSums.p, (size_t)n + 1, s);
-            HIPCHK(hipMemcpyAsync(&partMapped[j], c[0]->pairSums.p + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        }
-        uint64_t total = 0, deviceRecords = 0, deviceMapped = 0;
-        for (size_t j = 0; j < P; j++) {
-            if (subs1[j]->nReads) HIPCHK(hipStreamSynchronize(subs1[j]->stream));
-            total += partBytes[j];
-            deviceRecords += partRecords[j];
-            deviceMapped += partMapped[j];
-        }
-        // ---- write: every sub-batch its piece, copied to its place in the text of read 1's batch
-        PinnedBuf<char>& samOut = mates1->samOut;
-        samOut.resize((size_t)total + 1);
-        samOut.p[total] = '\0';
-        uint64_t at = 0;
-        for (size_t j = 0; j < P; j++) {
-            const uint32_t n = subs1[j]->nReads;
-            if (!n || !partBytes[j]) continue;
-            SamDeviceBufs& d = subs1[j]->sam;
-            hipStream_t s = subs1[j]->stream;
-            growTo(d.text, (size_t)partBytes[j] + 16);
-            hipLaunchKernelGGL(k_pair_write, dim3((n + PAIR_PER_WAVE - 1u) / PAIR_PER_WAVE), dim3(64), 0, s, ctx[j], d.plan.p, subs1[j]->pairPlan.p,
-                               d.offs.p, d.side.p, d.text.p);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(samOut.p + at, d.text.p, (size_t)partBytes[j], hipMemcpyDeviceToHost, s));
-            at += partBytes[j];
-        }
-        for (size_t j = 0; j < P; j++)
-            if (subs1[j]->nReads && partBytes[j]) HIPCHK(hipStreamSynchronize(subs1[j]->stream));
-        *text = samOut.p;
-        *length = total;
-        if (getenv("CMB_VERBOSE"))
-            fprintf(stderr, "[host] pair sam: %llu pairs, %llu of them formatted on the host, %llu records from the device\n",
-                    (unsigned long long)readBase[P], (unsigned long long)nHostAll,
-                    (unsigned long long)deviceRecords);
-        if (stats) {
-            stats->host_pairs = nHostAll;
-            stats->mapped_pairs = hostMapped + deviceMapped;
-            stats->device_records = deviceRecords;
-        }
-        return CMB_OK;
-    } catch (const std::exception& e) {
-        return fail(CMB_ERR_DEVICE, e.what());
-    }
-}
-
-// ---- the same on a b-move batch whose final lists stayed in HBM (cmb_move_batch_keep_device_lists; move_backend.hip) -----------------
-namespace cmb {
-int moveBatchListViews(cmb_move_batch* b, std::vector<MoveListView>& out);
-cmb_index* moveTextIndexOfBatch(const cmb_move_batch* b);
-} // namespace cmb
-extern "C" int cmb_move_batch_sam_device(cmb_move_batch* b, const cmb_sam_inputs* in, int unmapped_records, int xa_tag, const char** text,
-                                         uint64_t* length, uint64_t* host_reads) {
-    if (!b || !text || !length || !samInputsOk(in)) return fail(CMB_ERR_INVALID, "null argument");
-    try {
-        std::vector<MoveListView> views;
-        if (int rc = moveBatchListViews(b, views)) return rc;
-        cmb_index* idx = moveTextIndexOfBatch(b);
-        if (!idx) return fail(CMB_ERR_INVALID, "the batch's index has no text beside it (cmb_move_attach_text)");
-        useDevice(idx->device);
-        std::vector<SamPart> parts;
-        for (const MoveListView& v : views) {
-            MoveSamBufs* st = v.samBufs;
-            SamPart p;
-            p.n = v.nReads, p.k = v.k, p.metric = v.metric, p.s = v.stream;
-            p.cx = SamCtx{v.reads, v.offs, v.goffs, v.groupStride, v.occ, (const AlnRec*)v.aln, v.ops, v.stride};
-            p.sam = &st->sam, p.hostList = &st->hostList, p.scanTmp = &st->scanTmp;
-            p.hostOffs = v.hostOffs;
-            p.occsOf = [v](uint32_t i) { // (texts below 2^32: cmb_move_attach_text)
-                std::vector<BestOcc> occs;
-                const cmb_move_occ* ho = (const cmb_move_occ*)v.hOcc;
-                for (uint64_t q = v.hOccOffs[i]; q < v.hOccOffs[i + 1]; q++) {
-                    BestOcc o;
-                    o.occ = cmb_occ{(uint32_t)ho[q].begin, (uint32_t)ho[q].end, ho[q].distance, ho[q].strand};
-                    const uint4& ar = v.hAln[q];
-                    o.aln = cmb_aln{ar.x, ar.y, 0, (uint16_t)ar.z, (uint16_t)ar.w, 0};
-                    const uint16_t* src = v.hOps + q * v.stride;
-                    for (uint32_t j = 0; j < ar.z; j++) o.ops.push_back(src[ar.z - 1 - j]);
-                    occs.push_back(std::move(o));
-                }
-                return occs;
-            };
-            parts.push_back(std::move(p));
-        }
-        return samDeviceOver(idx, parts, in, unmapped_records, xa_tag, views[0].samBufs->samOut, text, length, host_reads);
-    } catch (const std::exception& e) {
-        return fail(CMB_ERR_DEVICE, e.what());
-    }
-}
-// test hook: the MAPQ the device path prints for 1 ... n occurrences of minimal distance (dev_sam.hpp: samMapQ)
-extern "C" int cmb_sam_device_mapq(uint32_t n, uint32_t* out) {
-    if (!out && n) return fail(CMB_ERR_INVALID, "null argument");
-    try {
-        if (!n) return CMB_OK;
-        DevBuf<uint32_t> d;
-        d.alloc(n);
-        hipLaunchKernelGGL(k_sam_mapq, dim3((n + 255u) / 256u), dim3(256), 0, 0, n, d.p);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpy(out, d.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        return CMB_OK;
-    } catch (const std::exception& e) {
-        return fail(CMB_ERR_DEVICE, e.what());
-    }
-}
-
-// The same for occurrences and alignments the caller holds (cmb_batch_results + cmb_batch_alignments, or their b-move
-// counterparts with the text-only index of cmb_move_text_index): occ_offs[n_reads + 1], aln[i].cigar_off into cigar_ops.
-extern "C" int64_t cmb_sam_chunk(cmb_index* idx, uint32_t max_distance, int metric, const char* seqs, const uint64_t* offs, uint32_t n_reads,
-                                 const char* const* read_ids, const char* const* quals, const char* const* seq_names, const cmb_occ* occ,
-                                 const uint64_t* occ_offs, const cmb_aln* aln, const uint16_t* cigar_ops, int unmapped_records, int xa_tag,
-                                 char* out, uint64_t cap) {
-    if (!idx || !seqs || !offs || !read_ids || !seq_names || !occ_offs || (occ_offs[n_reads] && (!occ || !aln || !cigar_ops)))
-        return fail(CMB_ERR_INVALID, "null argument");
-    try {
-        std::string text;
-        for (uint32_t i = 0; i < n_reads; i++) {
-            const std::string read = cleanReadSeq(std::string(seqs + offs[i], seqs + offs[i + 1])), revC = revComplWithN(read);
-            const std::string sid = cleanSeqID(read_ids[i]);
-            const std::string qual = quals && quals[i] ? quals[i] : "*";
-            std::vector<BestOcc> occs;
-            for (uint64_t q2 = occ_offs[i]; q2 < occ_offs[i + 1]; q2++) {
-                BestOcc o;
-                o.occ = occ[q2];
-                o.aln = aln[q2];
-                o.ops.assign(cigar_ops + aln[q2].cigar_off, cigar_ops + aln[q2].cigar_off + aln[q2].cigar_len);
-                occs.push_back(std::move(o));
-            }
-            samOfRead(text, idx, max_distance, metric, read, revC, sid, qual, occs, seq_names, unmapped_records, xa_tag);
-        }
-        return putString(text, out, cap);
-    } catch (const std::exception& e) {
-        return fail(CMB_ERR_DEVICE, e.what());
-    }
-}
-
-// ------------------------------------------------------------------------- BEST (+x strata) mode
-// SearchStrategy::matchApproxBestPlusX / findBestAlignments / processSeq / mapRead / checkAlignments /
-// combineOccVectors (reference src/searchstrategy.cpp:623-760, :791-812, :536-620; src/searchstrategy.h:490-523).
-// The reference walks every read through its strata on its own: exact matches, then k = 1, 3, 5, 9, 13 (k + x + 2 below
-// 5, + 4 above) up to the identity cut-off, until a stratum holds an alignment; every stratum is one ALL-mode search
-// of ONE strand (mapRead) whose occurrences below the first unprocessed distance are dropped.  Here a stratum is one
-// device batch over all reads that are still looking at that distance: both strands at once, each strand filtered
-// by itself (cmb_batch_filter_per_strand), CIGARs and sequence assignment from the device (k_cigar); the per-read
-// bookkeeping below is the reference's.
-
-struct cmb_best {
-    std::vector<cmb_occ> occ;
-    std::vector<cmb_aln> aln;
-    std::vector<uint16_t> ops;
-    std::vector<uint64_t> offs;
-    std::vector<uint32_t> best, nHits;
-    uint64_t cnts[CMB_CNT_MAX];
-    // cmb_match_best_device: the final lists in HBM, in the layout k_sam_write reads (SamCtx: occurrences as uint4, AlnRec, CIGAR runs
-    // at BEST_OPS_STRIDE stored end to begin, 64-bit offsets per read); occ / aln / ops above are filled from them on first use
-    bool onDevice = false, fetched = false;
-    cmb_index* ix = nullptr;
-    int metric = 1;
-    uint32_t nReads = 0, x = 0;
-    uint64_t nOcc = 0;
-    DevBuf<uint4> dOcc;
-    DevBuf<AlnRec> dAln;
-    DevBuf<uint16_t> dOps;
-    DevBuf<uint64_t> dOffs;
-    DevBuf<uint32_t> dBest, dHits;
-    std::vector<uint8_t> hostRead; // reads whose bookkeeping went through the host (an occurrence over a sequence end, edit distance)
-    uint32_t nHostReads = 0;
-    // cmb_best_sam_device: the SAM driver's buffers, the chunk's raw reads (the batches of the strata are gone), the reads the host
-    // formats as a flag per read (k_sam_plan_best), the finished text
-    SamDeviceBufs sam;
-    DevBuf<uint8_t> samReads, samHostFlag, scanTmp;
-    DevBuf<uint64_t> samReadOffs;
-    PinnedBuf<char> samOut;
-    std::vector<uint64_t> readOffs; // the chunk's read offsets, as given to cmb_match_best_device
-    // cmb_best_timings: host time per phase of the call (every phase ends in a synchronise) and, summed over the strata, the
-    // device time of the batches' kernels as cmb_batch_timings names them
-    std::vector<std::pair<std::string, double>> times;
-    void addTime(const std::string& name, double ms) {
-        for (auto& t : times)
-            if (t.first == name) {
-                t.second += ms;
-                return;
-            }
-        times.push_back({name, ms});
-    }
-    bool readsUp = false;
-};
-
-namespace {
-// what one stratum returns: the ALL-mode lists of a set of reads at distance k, both strands, every strand filtered by itself
-struct StratumOut {
-    std::vector<cmb_occ> oc;
-    std::vector<cmb_aln> al;
-    std::vector<uint16_t> ops;
-    std::vector<uint64_t> oo, cnt;
-};
-typedef std::function<int(const char* cat, const uint64_t* o, uint32_t n, uint32_t k, StratumOut& r)> StratumRunner;
-
-// The strata loop's store (host_best.hpp) with every read's occurrences in host vectors.
-// idx: the index whose text and sequence starts serve the trimming (the FM-index itself, or the text beside a b-move index);
-// trimCounters: the in-text counters of a trimming count (FM-index flavour: inTextVerificationOneString; the b-move flavour's
-// checkTrimmedMatch counts nothing, indexinterface.cpp:722-796)
-struct BestHostStore {
-    cmb_index* idx;
-    const cmb_strategy* st;
-    bool trimCounters;
-    const StratumRunner& runOn;
-    const char* seqs;
-    const uint64_t* offs;
-    cmb_best* R;
-    std::vector<BestCursor> cur;
-    std::vector<BestHostRead> rd;
-
-    BestCursor& cursor(uint32_t i) { return cur[i]; }
-    bool nonEmpty(uint32_t i, int s2, uint32_t d) const { return rd[i].nonEmpty(s2, d); }
-    void check(uint32_t i, int s2, uint32_t l, uint32_t cutOffTrim) {
-        bestCheckHost(rd[i], cur[i].best, s2, l, cutOffTrim, [&](const std::string& seq, BestOcc& o, uint32_t cutOff) {
-            return trimOccurrence(idx, seq, cutOff, st->metric, o, trimCounters ? R->cnts : nullptr);
-        });
-    }
-    // one stratum for a set of reads: ALL-mode search of both strands at distance k, every strand filtered by itself
-    int run(const std::vector<uint32_t>& ids, uint32_t k) {
-        std::string cat;
-        std::vector<uint64_t> o;
-        bestGatherReads(seqs, offs, ids, cat, o);
-        StratumOut so;
-        if (const int rcode = runOn(cat.data(), o.data(), (uint32_t)ids.size(), k, so)) return rcode;
-        for (int i = 0; i < CMB_CNT_MAX; i++) R->cnts[i] += so.cnt[i];
-        for (size_t j = 0; j < ids.size(); j++) {
-            const uint32_t minD = std::min<uint32_t>(cur[ids[j]].proc, k); // processSeq (:791-812): the first distance not processed yet
-            for (uint64_t q2 = so.oo[j]; q2 < so.oo[j + 1]; q2++) {
-                const cmb_aln& a = so.al[q2];
-                if (so.oc[q2].distance >= minD)
-                    rd[ids[j]].add(BestOcc{so.oc[q2], a, std::vector<uint16_t>(so.ops.begin() + a.cigar_off, so.ops.begin() + a.cigar_off + a.cigar_len)});
-            }
-        }
-        return CMB_OK;
-    }
-};
-
-// deviceCap: the largest distance the flavour's device path runs
-int matchBestWith(cmb_index* idx, const cmb_strategy* st, uint32_t deviceCap, bool trimCounters, const StratumRunner& runOn, uint32_t x,
-                  uint32_t min_identity, const char* seqs, const uint64_t* offs, uint32_t n_reads, cmb_best** out) {
-    if (!idx || !st || !offs || !out || (!seqs && n_reads)) return fail(CMB_ERR_INVALID, "null argument");
-    if (min_identity < 50 || min_identity > 100) return fail(CMB_ERR_INVALID, "the minimal identity lies between 50 and 100");
-    try {
-        const uint32_t maxSupported = bestMaxSupported(st->schemes, deviceCap);
-        std::unique_ptr<cmb_best> R(new cmb_best());
-        memset(R->cnts, 0, sizeof(R->cnts));
-        BestHostStore S{idx, st, trimCounters, runOn, seqs, offs, R.get(), std::vector<BestCursor>(n_reads), std::vector<BestHostRead>(n_reads)};
-        for (uint32_t i = 0; i < n_reads; i++) {
-            S.cur[i] = bestCursor(bestMaxED(maxSupported, (uint32_t)(offs[i + 1] - offs[i]), min_identity));
-            S.rd[i].fw = cleanReadSeq(std::string(seqs + offs[i], seqs + offs[i + 1]));
-            S.rd[i].rc = revComplWithN(S.rd[i].fw);
-            S.rd[i].start(S.cur[i].cutOff);
-        }
-        if (const int rcode = bestStrataLoop(S, n_reads, x)) return rcode;
-        // ---- results: combineOccVectors (:573-620) per read
-        R->offs.assign(n_reads + 1, 0);
-        R->best.assign(n_reads, 0xFFFFFFFFu);
-        R->nHits.assign(n_reads, 0);
-        for (uint32_t i = 0; i < n_reads; i++) {
-            const BestCursor& r = S.cur[i];
-            R->offs[i] = R->occ.size();
-            if (!r.bestFound) continue;
-            R->best[i] = r.best;
-            R->nHits[i] = S.rd[i].hitsAt(r.best);
-            bestCombineHost(S.rd[i], r.best, std::min<uint32_t>(r.best + x, r.cutOff), [&](const BestOcc& o) {
-                cmb_aln a = o.aln;
-                a.cigar_off = R->ops.size();
-                a.cigar_len = (uint16_t)o.ops.size();
-                a.spans = o.aln.spans == 2 ? 2 : 0;
-                R->ops.insert(R->ops.end(), o.ops.begin(), o.ops.end());
-                R->occ.push_back(o.occ);
-                R->aln.push_back(a);
-            });
-        }
-        R->offs[n_reads] = R->occ.size();
-        *out = R.release();
-        return CMB_OK;
-    } catch (const std::exception& e) {
-        return fail(CMB_ERR_DEVICE, e.what());
-    }
-}
-} // namespace
-
-extern "C" int cmb_match_best(cmb_index* idx, const cmb_strategy* st, uint32_t x, uint32_t min_identity, const char* seqs,
-                              const uint64_t* offs, uint32_t n_reads, cmb_best** out) {
-    if (!idx || !st) return fail(CMB_ERR_INVALID, "null argument");
-    const StratumRunner run = [&](const char* cat, const uint64_t* o, uint32_t n, uint32_t k, StratumOut& r) -> int {
-        cmb_batch* b = nullptr;
-        int rcode = cmb_batch_create(idx, st, k, cat, o, n, &b);
-        if (rcode) return rcode;
-        struct Guard {
-            cmb_batch* b;
-            ~Guard() { cmb_batch_destroy(b); }
-        } guard{b};
-        cmb_batch_filter_per_strand(b, 1);
-        cmb_batch_want_alignments(b, 1);
-        if ((rcode = cmb_batch_run(b))) return rcode;
-        uint64_t nOcc = 0, nOps = 0;
-        cmb_batch_result_size(b, &nOcc);
-        r.oc.resize(nOcc ? nOcc : 1);
-        r.al.resize(nOcc ? nOcc : 1);
-        r.oo.resize((size_t)n + 1);
-        r.cnt.assign(CMB_CNT_MAX, 0);
-        if ((rcode = cmb_batch_results(b, r.oc.data(), r.oc.size(), r.oo.data(), r.cnt.data()))) return rcode;
-        (void)cmb_batch_alignments(b, r.al.data(), 0, nullptr, 0, &nOps);
-        r.ops.resize(nOps ? nOps : 1);
-        return cmb_batch_alignments(b, r.al.data(), r.al.size(), r.ops.data(), r.ops.size(), &nOps);
-    };
-    // (MAX_K, definitions.h:50)
-    return matchBestWith(idx, st, 13u, true, run, x, min_identity, seqs, offs, n_reads, out);
-}
-// ---- BEST mode with the bookkeeping on the device (dev_best.hpp) ------------------------------------------------------------------
-// The strata loop and every per-read decision are the ones matchBestWith runs (host_best.hpp; searchstrategy.cpp:623-712); what that
-// keeps in vectors per read, strand and distance is here a pool of records in HBM plus, per read, a few words on the host: which
-// distances hold an occurrence / an occurrence inside one sequence (from k_best_scan), which went through checkAlignments, and the
-// cursor.  The host touches those words once per read and stratum and no occurrence — except for the reads that keep an occurrence over a sequence end
-// under edit distance: trimming verifies again and moves the occurrence to another distance (checkAlignments, :536-571), so from that
-// stratum on such a read's lists live in host vectors as in matchBestWith, and its final records are spliced into the device lists.
-namespace {
-struct BestDevRead {
-    BestCursor c;
-    bool host = false; // its lists live in a BestHostRead
-    uint16_t any[2] = {0, 0}, asg[2] = {0, 0}, chk[2] = {0, 0};
-};
-struct BestPoolBufs {
-    DevBuf<uint4> occ;
-    DevBuf<AlnRec> aln;
-    DevBuf<uint16_t> ops;
-    DevBuf<uint32_t> read;
-    uint64_t n = 0, cap = 0;
-    BestPool at(uint64_t i) { return BestPool{occ.p + i, aln.p + i, ops.p + i * BEST_OPS_STRIDE, read.p + i}; }
-    void reserve(uint64_t want) { // (the exact size is known before a record is written: the pool never overflows)
-        if (want <= cap) return;
-        const uint64_t c = want + want / 2 + 4096;
-        BestPoolBufs f;
-        f.occ.alloc(c), f.aln.alloc(c), f.ops.alloc(c * BEST_OPS_STRIDE), f.read.alloc(c);
-        if (n) {
-            HIPCHK(hipMemcpy(f.occ.p, occ.p, n * sizeof(uint4), hipMemcpyDeviceToDevice));
-            HIPCHK(hipMemcpy(f.aln.p, aln.p, n * sizeof(AlnRec), hipMemcpyDeviceToDevice));
-            HIPCHK(hipMemcpy(f.ops.p, ops.p, n * BEST_OPS_STRIDE * sizeof(uint16_t), hipMemcpyDeviceToDevice));
-            HIPCHK(hipMemcpy(f.read.p, read.p, n * sizeof(uint32_t), hipMemcpyDeviceToDevice));
-        }
-        std::swap(occ.p, f.occ.p), std::swap(occ.n, f.occ.n);
-        std::swap(aln.p, f.aln.p), std::swap(aln.n, f.aln.n);
-        std::swap(ops.p, f.ops.p), std::swap(ops.n, f.ops.n);
-        std::swap(read.p, f.read.p), std::swap(read.n, f.read.n);
-        cap = c;
-    }
-};
-inline BestOcc bestOccOf(const uint4& o, const AlnRec& a, const uint16_t* ops) { // (CIGAR runs are stored end to begin)
-    BestOcc b;
-    b.occ = cmb_occ{o.x, o.y, o.z, o.w};
-    const uint32_t nOps = std::min<uint32_t>(a.nOps, BEST_OPS_STRIDE);
-    b.aln = cmb_aln{a.seqId, a.seqBegin, 0, (uint16_t)nOps, (uint16_t)a.spans, 0};
-    for (uint32_t j = 0; j < nOps; j++) b.ops.push_back(ops[nOps - 1 - j]);
-    return b;
-}
-} // namespace
-
-namespace {
-// What one stratum leaves in HBM, whichever flavour matched it: per part the lists k_best_scan / k_best_append read (two filter groups
-// per read), the counters and kernel times of its run, and how to let go of the batch that owns the lists.
-struct StratumLists {
-    uint32_t nReads;
-    const uint64_t* foffs;
-    const uint4* fout;
-    const AlnRec* aln;
-    const uint16_t* ops;
-    uint32_t stride;
-};
-struct DevStratum {
-    std::vector<StratumLists> parts;
-    uint64_t cnts[CMB_CNT_MAX] = {};
-    std::vector<KernelTime> times;
-    std::function<void()> destroy;
-    ~DevStratum() {
-        if (destroy) destroy();
-    }
-};
-// create, per-strand filter, alignments, run: an ALL-mode search of both strands of `n` reads at distance k whose lists stay on the device
-typedef std::function<int(const char* cat, const uint64_t* o, uint32_t n, uint32_t k, DevStratum& r, const std::function<void(const char*)>& lap)>
-    DevStratumRunner;
-
-// The strata loop's store (host_best.hpp) with the occurrences in a pool in HBM and, per read, masks of the distances that hold one;
-// the reads that trimming takes to the host keep theirs in a BestHostRead.
-// idx: the index whose text and sequence starts serve the trimming (the FM-index itself, or the text beside a b-move index);
-// trimCounters: as for BestHostStore
-struct BestDevStore {
-    cmb_index* idx;
-    const cmb_strategy* st;
-    bool trimCounters;
-    const DevStratumRunner& runOn;
-    const char* seqs;
-    const uint64_t* offs;
-    uint32_t nReads;
-    cmb_best* R;
-    bool edit;
-    std::vector<BestDevRead> rd;
-    std::map<uint32_t, BestHostRead> hr;
-    BestPoolBufs pool, stage;
-    DevBuf<uint8_t> dMinD, dMode, tmp;
-    DevBuf<uint32_t> dIds, dList;
-    DevBuf<unsigned long long> dMasks;
-    DevBuf<uint64_t> dCnt, dPoff;
-    std::vector<uint8_t> hMinD, hMode;
-    std::vector<unsigned long long> hMasks;
-
-    BestCursor& cursor(uint32_t i) { return rd[i].c; }
-    bool nonEmpty(uint32_t i, int s2, uint32_t d) { return rd[i].host ? hr[i].nonEmpty(s2, d) : ((rd[i].any[s2] >> d) & 1u) != 0; }
-    // checkAlignments (:536-571).  On the device's side an occurrence is assigned (it lies inside one sequence) or dropped
-    // (Hamming distance never trims); on the host's side it is BestHostStore's.
-    void check(uint32_t i, int s2, uint32_t l, uint32_t cutOffTrim) {
-        BestDevRead& r = rd[i];
-        if (l > r.c.cutOff) return;
-        if (r.host) {
-            bestCheckHost(hr[i], r.c.best, s2, l, cutOffTrim, [&](const std::string& seq, BestOcc& o, uint32_t cutOff) {
-                return trimOccurrence(idx, seq, cutOff, st->metric, o, trimCounters ? R->cnts : nullptr);
-            });
-            return;
-        }
-        const uint16_t bit = (uint16_t)(1u << l);
-        r.any[s2] = (uint16_t)((r.any[s2] & ~bit) | (r.asg[s2] & bit));
-        r.chk[s2] |= bit;
-        if ((r.asg[s2] & bit) && l < r.c.best) r.c.best = (uint8_t)l;
-    }
-    // one stratum for a set of reads: ALL-mode search of both strands at distance k, every strand filtered by itself; the batch's
-    // lists stay where they are
-    int run(const std::vector<uint32_t>& ids, uint32_t k) {
-        const uint32_t n = (uint32_t)ids.size();
-        auto t0 = std::chrono::steady_clock::now();
-        auto lap = [&](const char* what) {
-            auto t1 = std::chrono::steady_clock::now();
-            R->addTime(what, std::chrono::duration<double, std::milli>(t1 - t0).count());
-            t0 = t1;
-        };
-        std::string cat;
-        std::vector<uint64_t> o;
-        bestGatherReads(seqs, offs, ids, cat, o);
-        lap("host: gather of the stratum's reads");
-        DevStratum ds;
-        if (const int rcode = runOn(cat.data(), o.data(), n, k, ds, lap)) return rcode;
-        for (int i = 0; i < CMB_CNT_MAX; i++) R->cnts[i] += ds.cnts[i];
-        const std::vector<StratumLists>& parts = ds.parts;
-        for (const KernelTime& t : ds.times) R->addTime(std::string("strata: ") + t.name, t.ms);
-        // processSeq (:791-812): what lies below the first distance not processed yet is dropped
-        hMinD.resize(n);
-        for (uint32_t j = 0; j < n; j++) hMinD[j] = (uint8_t)std::min<uint32_t>(rd[ids[j]].c.proc, k);
-        growTo(dMinD, n), growTo(dIds, n), growTo(dMasks, n), growTo(dCnt, (size_t)n + 1), growTo(dPoff, (size_t)n + 1);
-        HIPCHK(hipMemcpy(dMinD.p, hMinD.data(), n, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dIds.p, ids.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
-        HIPCHK(hipMemset(dCnt.p + n, 0, sizeof(uint64_t)));
-        uint32_t base = 0;
-        for (const StratumLists& c : parts) {
-            if (c.nReads)
-                hipLaunchKernelGGL(k_best_scan, dim3((c.nReads + 3u) / 4u), dim3(256), 0, 0, c.foffs, c.fout, c.aln, c.nReads, dMinD.p + base,
-                                   dMasks.p + base, dCnt.p + base);
-            base += c.nReads;
-        }
-        HIPCHK(hipGetLastError());
-        scanExclusive(tmp, dCnt.p, dPoff.p, (size_t)n + 1, (hipStream_t)0);
-        uint64_t kept = 0;
-        hMasks.resize(n);
-        HIPCHK(hipMemcpy(&kept, dPoff.p + n, sizeof(uint64_t), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(hMasks.data(), dMasks.p, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        const uint64_t poolBase = pool.n;
-        if (poolBase + kept >= 0xFFFFFFFFull) return fail(CMB_ERR_UNSUPPORTED, "more than 2^32 occurrences in the strata of one chunk");
-        pool.reserve(poolBase + kept);
-        base = 0;
-        for (const StratumLists& c : parts) {
-            if (c.nReads && kept)
-                hipLaunchKernelGGL(k_best_append, dim3((c.nReads + 3u) / 4u), dim3(256), 0, 0, c.foffs, c.fout, c.aln, c.ops, c.stride, c.nReads,
-                                   dMinD.p + base, dIds.p + base, dPoff.p + base, pool.at(poolBase));
-            base += c.nReads;
-        }
-        HIPCHK(hipGetLastError());
-        pool.n = poolBase + kept;
-        // the words of every read; the reads that go to, or are with, the host
-        bool anyHost = false, anyNew = false;
-        for (uint32_t j = 0; j < n; j++) {
-            BestDevRead& r = rd[ids[j]];
-            const unsigned long long m = hMasks[j];
-            if (r.host) {
-                hMode[ids[j]] = 1, anyHost = true;
-                continue;
-            }
-            r.any[0] |= (uint16_t)((m >> BEST_ANY0) & 0x3FFFu), r.any[1] |= (uint16_t)((m >> BEST_ANY1) & 0x3FFFu);
-            r.asg[0] |= (uint16_t)((m >> BEST_ASG0) & 0x3FFFu), r.asg[1] |= (uint16_t)((m >> BEST_ASG1) & 0x3FFFu);
-            if (edit && ((m >> BEST_SPAN) & 1ull)) hMode[ids[j]] = 2, anyHost = anyNew = true;
-        }
-        if (anyHost) {
-            const uint64_t from = anyNew ? 0 : poolBase, span = pool.n - from;
-            growTo(dMode, nReads);
-            growTo(dList, (size_t)span + 1);
-            HIPCHK(hipMemcpy(dMode.p, hMode.data(), nReads, hipMemcpyHostToDevice));
-            HIPCHK(hipMemset(dList.p, 0, sizeof(uint32_t)));
-            uint32_t nList = 0;
-            if (span) {
-                hipLaunchKernelGGL(k_best_collect, dim3((uint32_t)((span + 255u) / 256u)), dim3(256), 0, 0, pool.read.p, from, pool.n, poolBase,
-                                   dMode.p, dList.p);
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipMemcpy(&nList, dList.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
-            }
-            std::vector<uint32_t> list(nList);
-            std::vector<uint4> go(nList);
-            std::vector<AlnRec> ga(nList);
-            std::vector<uint16_t> gp((size_t)nList * BEST_OPS_STRIDE);
-            std::vector<uint32_t> gr(nList);
-            if (nList) {
-                HIPCHK(hipMemcpy(list.data(), dList.p + 1, (size_t)nList * sizeof(uint32_t), hipMemcpyDeviceToHost));
-                std::sort(list.begin(), list.end()); // (the order in which the records were found)
-                HIPCHK(hipMemcpy(dList.p + 1, list.data(), (size_t)nList * sizeof(uint32_t), hipMemcpyHostToDevice));
-                growTo(stage.occ, nList), growTo(stage.aln, nList), growTo(stage.ops, (size_t)nList * BEST_OPS_STRIDE), growTo(stage.read, nList);
-                hipLaunchKernelGGL(k_best_gather, dim3((nList + 255u) / 256u), dim3(256), 0, 0, dList.p + 1, nList, pool.at(0), stage.at(0));
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipMemcpy(go.data(), stage.occ.p, (size_t)nList * sizeof(uint4), hipMemcpyDeviceToHost));
-                HIPCHK(hipMemcpy(ga.data(), stage.aln.p, (size_t)nList * sizeof(AlnRec), hipMemcpyDeviceToHost));
-                HIPCHK(hipMemcpy(gp.data(), stage.ops.p, gp.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
-                HIPCHK(hipMemcpy(gr.data(), stage.read.p, (size_t)nList * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            }
-            for (uint32_t j = 0; j < n; j++) {
-                const uint32_t i = ids[j];
-                if (hMode[i] == 2) {
-                    BestHostRead& h = hr[i];
-                    h.fw = cleanReadSeq(std::string(seqs + offs[i], seqs + offs[i + 1]));
-                    h.rc = revComplWithN(h.fw);
-                    h.start(rd[i].c.cutOff);
-                    rd[i].host = true;
-                }
-                hMode[i] = 0;
-            }
-            for (uint32_t t = 0; t < nList; t++) hr[gr[t]].add(bestOccOf(go[t], ga[t], gp.data() + (size_t)t * BEST_OPS_STRIDE));
-        }
-        HIPCHK(hipDeviceSynchronize()); // (the batch and its lists go away)
-        lap("host: strata bookkeeping (k_best_scan, k_best_append, host reads)");
-        ds.destroy();
-        ds.destroy = nullptr;
-        lap("host: cmb_batch_destroy");
-        return CMB_OK;
-    }
-};
-
-int matchBestDeviceWith(cmb_index* idx, const cmb_strategy* st, bool trimCounters, const DevStratumRunner& runOn, uint32_t x, uint32_t min_identity,
-                        const char* seqs, const uint64_t* offs, uint32_t n_reads, cmb_best** out) {
-    if (!idx || !st || !offs || !out || (!seqs && n_reads)) return fail(CMB_ERR_INVALID, "null argument");
-    if (min_identity < 50 || min_identity > 100) return fail(CMB_ERR_INVALID, "the minimal identity lies between 50 and 100");
-    try {
-        useDevice(idx->device);
-        const uint32_t maxSupported = bestMaxSupported(st->schemes, 13u); // (MAX_K, definitions.h:50)
-        std::unique_ptr<cmb_best> R(new cmb_best());
-        memset(R->cnts, 0, sizeof(R->cnts));
-        R->onDevice = true, R->ix = idx, R->metric = st->metric, R->nReads = n_reads, R->x = x;
-        R->readOffs.assign(offs, offs + n_reads + 1);
-        BestDevStore S{idx, st, trimCounters, runOn, seqs, offs, n_reads, R.get(), st->metric != CMB_METRIC_HAMMING};
-        S.rd.resize(n_reads), S.hMode.assign(n_reads, 0);
-        for (uint32_t i = 0; i < n_reads; i++) S.rd[i].c = bestCursor(bestMaxED(maxSupported, (uint32_t)(offs[i + 1] - offs[i]), min_identity));
-        if (const int rcode = bestStrataLoop(S, n_reads, x)) return rcode;
-        BestPoolBufs& pool = S.pool;
-        DevBuf<uint8_t>& tmp = S.tmp;
-        const auto tFinal = std::chrono::steady_clock::now();
-        // ---- results: combineOccVectors (:573-620).  Pool reads on the device; host reads as matchBestWith does
-        std::vector<unsigned long long> hState(n_reads, 0);
-        R->best.assign(n_reads, 0xFFFFFFFFu);
-        R->hostRead.assign(n_reads, 0);
-        for (uint32_t i = 0; i < n_reads; i++) {
-            const BestDevRead& r = S.rd[i];
-            if (r.host) R->hostRead[i] = 1, R->nHostReads++;
-            if (!r.c.bestFound) continue;
-            R->best[i] = r.c.best;
-            const unsigned long long hi = std::min<uint32_t>(r.c.best + x, r.c.cutOff);
-            if (!r.host)
-                hState[i] = (unsigned long long)r.c.best | (hi << 8) | (1ull << 16) | ((unsigned long long)(r.chk[0] & 0x3FFFu) << 32) |
-                            ((unsigned long long)(r.chk[1] & 0x3FFFu) << 46);
-        }
-        std::vector<uint4> sOcc; // the final records of the host reads, one read after the other
-        std::vector<AlnRec> sAln;
-        std::vector<uint16_t> sOps;
-        std::vector<uint32_t> hostHits;
-        std::vector<std::pair<uint32_t, uint64_t>> hostAt; // (read, its first record in sOcc)
-        for (auto& kv : S.hr) {
-            const uint32_t i = kv.first;
-            const BestCursor& r = S.rd[i].c;
-            BestHostRead& h = kv.second;
-            hostAt.push_back({i, sOcc.size()});
-            hostHits.push_back(0);
-            if (!r.bestFound) continue;
-            hostHits.back() = h.hitsAt(r.best);
-            bestCombineHost(h, r.best, std::min<uint32_t>(r.best + x, r.cutOff), [&](const BestOcc& o) {
-                const uint32_t nOps = (uint32_t)std::min<size_t>(o.ops.size(), BEST_OPS_STRIDE);
-                sOcc.push_back(uint4{o.occ.begin, o.occ.end, o.occ.distance, o.occ.strand});
-                sAln.push_back(AlnRec{o.aln.seq_id, o.aln.seq_begin, nOps, o.aln.spans == 2 ? 2u : 0u});
-                const size_t at = sOps.size();
-                sOps.resize(at + BEST_OPS_STRIDE, 0);
-                for (uint32_t j = 0; j < nOps; j++) sOps[at + j] = o.ops[nOps - 1 - j]; // (CIGAR runs are stored end to begin)
-            });
-        }
-        hostAt.push_back({n_reads, sOcc.size()});
-        DevBuf<unsigned long long> dState;
-        DevBuf<uint32_t> dFlag, dPerRead;
-        DevBuf<uint64_t> dPos, dUflag, dUpos, dDevBase;
-        DevBuf<BestKey> keysA, keysB;
-        const uint64_t nPool = pool.n;
-        growTo(dState, n_reads), growTo(R->dHits, n_reads), growTo(R->dBest, n_reads), growTo(dPerRead, n_reads);
-        growTo(dFlag, (size_t)nPool + 1), growTo(dPos, (size_t)nPool + 1);
-        if (n_reads) {
-            HIPCHK(hipMemcpy(dState.p, hState.data(), (size_t)n_reads * sizeof(unsigned long long), hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(R->dBest.p, R->best.data(), (size_t)n_reads * sizeof(uint32_t), hipMemcpyHostToDevice));
-            HIPCHK(hipMemset(R->dHits.p, 0, (size_t)n_reads * sizeof(uint32_t)));
-            HIPCHK(hipMemset(dPerRead.p, 0, (size_t)n_reads * sizeof(uint32_t)));
-        }
-        HIPCHK(hipMemset(dFlag.p + nPool, 0, sizeof(uint32_t)));
-        uint64_t nSel = 0, nDev = 0;
-        if (nPool) {
-            hipLaunchKernelGGL(k_best_flag, dim3((uint32_t)((nPool + 255u) / 256u)), dim3(256), 0, 0, pool.at(0), nPool, dState.p, dFlag.p, R->dHits.p);
-            HIPCHK(hipGetLastError());
-            scanExclusive(tmp, dFlag.p, dPos.p, (size_t)nPool + 1, (hipStream_t)0);
-            HIPCHK(hipMemcpy(&nSel, dPos.p + nPool, sizeof(uint64_t), hipMemcpyDeviceToHost));
-        }
-        growTo(dUflag, (size_t)nSel + 1), growTo(dUpos, (size_t)nSel + 1);
-        if (nSel) {
-            keysA.alloc(nSel), keysB.alloc(nSel);
-            hipLaunchKernelGGL(k_best_keys, dim3((uint32_t)((nPool + 255u) / 256u)), dim3(256), 0, 0, pool.at(0), nPool, dFlag.p, dPos.p, keysA.p);
-            HIPCHK(hipGetLastError());
-            // order: distance, strand, (sequence, begin inside it), the order in which the records were found — the last key makes the
-            // order total, so the (stable) merge sort has no ties to keep
-            withScratch(tmp, [&](void* p, size_t& bytes) {
-                return rocprim::merge_sort(p, bytes, keysA.p, keysB.p, (size_t)nSel, BestKeyLess(), (hipStream_t)0);
-            });
-            HIPCHK(hipMemset(dUflag.p + nSel, 0, sizeof(uint64_t)));
-            hipLaunchKernelGGL(k_best_uniq, dim3((uint32_t)((nSel + 255u) / 256u)), dim3(256), 0, 0, keysB.p, nSel, dUflag.p, dPerRead.p);
-            HIPCHK(hipGetLastError());
-            scanExclusive(tmp, dUflag.p, dUpos.p, (size_t)nSel + 1, (hipStream_t)0);
-            HIPCHK(hipMemcpy(&nDev, dUpos.p + nSel, sizeof(uint64_t), hipMemcpyDeviceToHost));
-        }
-        // every read's place in the final lists: a running sum over one word per read
-        std::vector<uint32_t> perRead(n_reads, 0);
-        R->nHits.assign(n_reads, 0);
-        if (n_reads) {
-            HIPCHK(hipMemcpy(perRead.data(), dPerRead.p, (size_t)n_reads * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(R->nHits.data(), R->dHits.p, (size_t)n_reads * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        }
-        std::vector<uint64_t> devBase((size_t)n_reads + 1, 0);
-        R->offs.assign((size_t)n_reads + 1, 0);
-        {
-            size_t h = 0;
-            for (uint32_t i = 0; i < n_reads; i++) {
-                uint64_t mine = perRead[i];
-                if (h + 1 < hostAt.size() && hostAt[h].first == i) {
-                    mine = hostAt[h + 1].second - hostAt[h].second;
-                    R->nHits[i] = hostHits[h];
-                    HIPCHK(hipMemcpy(R->dHits.p + i, &hostHits[h], sizeof(uint32_t), hipMemcpyHostToDevice));
-                    h++;
-                }
-                devBase[i + 1] = devBase[i] + perRead[i];
-                R->offs[i + 1] = R->offs[i] + mine;
-            }
-        }
-        const uint64_t total = R->offs[n_reads];
-        R->nOcc = total;
-        growTo(R->dOffs, (size_t)n_reads + 1), growTo(dDevBase, (size_t)n_reads + 1);
-        HIPCHK(hipMemcpy(R->dOffs.p, R->offs.data(), ((size_t)n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dDevBase.p, devBase.data(), ((size_t)n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-        R->dOcc.alloc(total), R->dAln.alloc(total), R->dOps.alloc(total * BEST_OPS_STRIDE);
-        const BestPool fin{R->dOcc.p, R->dAln.p, R->dOps.p, nullptr};
-        if (nSel) {
-            hipLaunchKernelGGL(k_best_emit, dim3((uint32_t)((nSel + 255u) / 256u)), dim3(256), 0, 0, keysB.p, nSel, dUflag.p, dUpos.p, dDevBase.p,
-                               R->dOffs.p, pool.at(0), fin);
-            HIPCHK(hipGetLastError());
-        }
-        for (size_t h = 0; h + 1 < hostAt.size(); h++) { // the host reads' records at their place
-            const uint64_t s0 = hostAt[h].second, cnt = hostAt[h + 1].second - s0, at = R->offs[hostAt[h].first];
-            if (!cnt) continue;
-            HIPCHK(hipMemcpy(R->dOcc.p + at, sOcc.data() + s0, cnt * sizeof(uint4), hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(R->dAln.p + at, sAln.data() + s0, cnt * sizeof(AlnRec), hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(R->dOps.p + at * BEST_OPS_STRIDE, sOps.data() + s0 * BEST_OPS_STRIDE, cnt * BEST_OPS_STRIDE * sizeof(uint16_t),
-                             hipMemcpyHostToDevice));
-        }
-        HIPCHK(hipDeviceSynchronize());
-        R->addTime("host: final selection, sort, lists", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tFinal).count());
-        *out = R.release();
-        return CMB_OK;
-    } catch (const std::exception& e) {
-        return fail(CMB_ERR_DEVICE, e.what());
-    }
-}
-} // namespace
-
-extern "C" int cmb_match_best_device(cmb_index* idx, const cmb_strategy* st, uint32_t x, uint32_t min_identity, const char* seqs,
-                                     const uint64_t* offs, uint32_t n_reads, cmb_best** out) {
-    if (!idx || !st || !offs || !out || (!seqs && n_reads)) return fail(CMB_ERR_INVALID, "null argument");
-    if (min_identity < 50 || min_identity > 100) return fail(CMB_ERR_INVALID, "the minimal identity lies between 50 and 100");
-    if (idx->textOnly) return fail(CMB_ERR_INVALID, "this index holds only the text (cmb_index_create_text_only): nothing can be matched on it");
-    const DevStratumRunner run = [&](const char* cat, const uint64_t* o, uint32_t n, uint32_t k, DevStratum& r,
-                                     const std::function<void(const char*)>& lap) -> int {
-        cmb_batch* b = nullptr;
-        int rcode = cmb_batch_create(idx, st, k, cat, o, n, &b);
-        if (rcode) return rcode;
-        r.destroy = [b] { cmb_batch_destroy(b); };
-        cmb_batch_filter_per_strand(b, 1);
-        cmb_batch_want_alignments(b, 1);
-        lap("host: cmb_batch_create");
-        if ((rcode = cmb_batch_run(b))) return rcode;
-        lap("host: cmb_batch_run");
-        for (int i = 0; i < CMB_CNT_MAX; i++) r.cnts[i] = b->cnts[i];
-        std::vector<cmb_batch*> parts;
-        if (b->subs.empty()) parts.push_back(b);
-        else parts = b->subs;
-        for (const cmb_batch* c : parts) {
-            r.parts.push_back(StratumLists{c->nReads, c->foffs.p, c->fout.p, c->alnRec.p, c->alnOps.p, c->alnStride});
-            r.times.insert(r.times.end(), c->times.begin(), c->times.end());
-        }
-        return CMB_OK;
-    };
-    return matchBestDeviceWith(idx, st, true, run, x, min_identity, seqs, offs, n_reads, out);
-}
-// The same on the b-move index: the strata are b-move batches whose final lists stay in HBM (cmb_move_batch_keep_device_lists), the
-// trimming of the host reads uses the text beside the index and counts nothing, as cmb_move_match_best; the result carries the text-only
-// index, so cmb_best_results, cmb_best_host_reads, cmb_best_timings and cmb_best_sam_device work on it as on an FM-index result.
-extern "C" int cmb_move_match_best_device(cmb_move_index* idx, const cmb_strategy* st, uint32_t x, uint32_t min_identity, uint32_t kmer_size,
-                                          const char* seqs, const uint64_t* offs, uint32_t n_reads, cmb_best** out) {
-    if (!idx || !st || !offs || !out || (!seqs && n_reads)) return fail(CMB_ERR_INVALID, "null argument");
-    cmb_index* text = cmb_move_text_index(idx);
-    if (!text) return fail(CMB_ERR_INVALID, "BEST mode on the b-move index needs the text beside it (cmb_move_attach_text)");
-    const DevStratumRunner run = [&](const char* cat, const uint64_t* o, uint32_t n, uint32_t k, DevStratum& r,
-                                     const std::function<void(const char*)>& lap) -> int {
-        cmb_move_batch* b = nullptr;
-        int rcode = cmb_move_batch_create(idx, st, k, kmer_size, cat, o, n, &b);
-        if (rcode) return rcode;
-        r.destroy = [b] { cmb_move_batch_destroy(b); };
-        cmb_move_batch_filter_per_strand(b, 1);
-        if ((rcode = cmb_move_batch_want_alignments(b, 1))) return rcode;
-        if ((rcode = cmb_move_batch_keep_device_lists(b, 1))) return rcode;
-        lap("host: cmb_batch_create");
-        if ((rcode = cmb_move_batch_run(b))) return rcode;
-        lap("host: cmb_batch_run");
-        std::vector<MoveListView> views;
-        if ((rcode = moveBatchListViews(b, views))) return rcode;
-        for (const MoveListView& v : views) {
-            for (int i = 0; i < CMB_CNT_MAX; i++) r.cnts[i] += v.cnts[i];
-            r.parts.push_back(StratumLists{v.nReads, v.goffs, v.occ, (const AlnRec*)v.aln, v.ops, v.stride});
-            r.times.insert(r.times.end(), v.times->begin(), v.times->end());
-        }
-        return CMB_OK;
-    };
-    return matchBestDeviceWith(text, st, false, run, x, min_identity, seqs, offs, n_reads, out);
-}
-// SAM text of a chunk from a device-resident BEST result, written on the device: the text samOfBest (include/columba_amd_best.hpp) puts
-// together from cmb_best_results with the record builders, byte for byte.  The final lists have the layout k_sam_write reads, so only
-// the plan differs (k_sam_plan_best); the reads whose bookkeeping went through the host are formatted by the record builders and
-// spliced in as cmb_batch_sam_device does.
-extern "C" int cmb_best_sam_device(cmb_best* r, const cmb_sam_inputs* in, int unmapped_records, int xa_tag, const char** text,
-                                   uint64_t* length, uint64_t* host_reads) {
-    if (!r || !in || !text || !length) return fail(CMB_ERR_INVALID, "null argument");
-    if (!r->onDevice) return fail(CMB_ERR_INVALID, "the result does not live on the device (cmb_match_best_device)");
-    const uint32_t n = r->nReads;
-    if (!in->id_offs || (!in->seqs && n && r->readOffs[n]) || (!in->ids && in->id_offs[n]) || (in->quals && !in->qual_offs) ||
-        (in->n_seqs && (!in->seq_names || !in->seq_name_offs)))
-        return fail(CMB_ERR_INVALID, "null argument");
-    try {
-        cmb_index* idx = r->ix;
-        useDevice(idx->device);
-        *text = "";
-        *length = 0;
-        if (host_reads) *host_reads = r->nHostReads;
-        if (!n) return CMB_OK;
-        hipStream_t s = 0;
-        if (!r->readsUp) { // the chunk's raw reads: once per handle
-            const uint64_t chars = r->readOffs[n];
-            growTo(r->samReads, chars + 1);
-            growTo(r->samReadOffs, (size_t)n + 1);
-            if (chars) HIPCHK(hipMemcpy(r->samReads.p, in->seqs, chars, hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(r->samReadOffs.p, r->readOffs.data(), ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-            growTo(r->samHostFlag, n);
-            HIPCHK(hipMemcpy(r->samHostFlag.p, r->hostRead.data(), n, hipMemcpyHostToDevice));
-            r->readsUp = true;
-        }
-        SamCtx cx{r->samReads.p, r->samReadOffs.p, r->dOffs.p, 1u, r->dOcc.p, r->dAln.p, r->dOps.p, BEST_OPS_STRIDE};
-        cx.unmapped = unmapped_records ? 1u : 0u, cx.xa = xa_tag ? 1u : 0u;
-        if (int rc = samUpload(r->sam, in, 0, n, s, cx)) return rc;
-        hipLaunchKernelGGL(k_sam_plan_best, dim3((n + 3u) / 4u), dim3(256), 0, s, cx, r->dBest.p, r->dHits.p, r->samHostFlag.p, r->sam.plan.p,
-                           r->sam.len.p);
-        HIPCHK(hipGetLastError());
-        // ---- the host reads (known from the strata bookkeeping) through the record builders: samOfBest's lines
-        if (r->nHostReads) {
-            const std::vector<std::string> nameStr = samNamesOf(in);
-            std::vector<uint32_t> list;
-            for (uint32_t i = 0; i < n; i++)
-                if (r->hostRead[i]) list.push_back(i);
-            samSplice(r->sam, list, s, [&](uint32_t i, std::string& side) {
-                const std::string read = cleanReadSeq(std::string(in->seqs + r->readOffs[i], in->seqs + r->readOffs[i + 1])), revC = revComplWithN(read);
-                const std::string sid = cleanSeqID(std::string(in->ids + in->id_offs[i], in->ids + in->id_offs[i + 1]));
-                const std::string qual = in->quals ? std::string(in->quals + in->qual_offs[i], in->quals + in->qual_offs[i + 1]) : "*";
-                const uint64_t o0 = r->offs[i], cnt = r->offs[i + 1] - o0;
-                if (!cnt) {
-                    if (unmapped_records) side += samLineUnmappedSE(sid, read, qual);
-                    return;
-                }
-                std::vector<uint4> oc(cnt);
-                std::vector<AlnRec> al(cnt);
-                std::vector<uint16_t> op(cnt * BEST_OPS_STRIDE);
-                HIPCHK(hipMemcpy(oc.data(), r->dOcc.p + o0, cnt * sizeof(uint4), hipMemcpyDeviceToHost));
-                HIPCHK(hipMemcpy(al.data(), r->dAln.p + o0, cnt * sizeof(AlnRec), hipMemcpyDeviceToHost));
-                HIPCHK(hipMemcpy(op.data(), r->dOps.p + o0 * BEST_OPS_STRIDE, op.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
-                std::vector<SamHit> hits;
-                for (uint64_t t = 0; t < cnt; t++) {
-                    const BestOcc bo = bestOccOf(oc[t], al[t], op.data() + t * BEST_OPS_STRIDE);
-                    SamHit h;
-                    h.seqName = bo.aln.seq_id < nameStr.size() ? nameStr[bo.aln.seq_id] : std::string();
-                    h.cigar = cigarString(bo.ops.data(), (uint32_t)bo.ops.size());
-                    h.pos0 = bo.aln.seq_begin;
-                    h.distance = bo.occ.distance;
-                    h.revCompl = bo.occ.strand != 0;
-                    hits.push_back(h);
-                }
-                std::string revQ = qual;
-                std::reverse(revQ.begin(), revQ.end());
-                const bool rcFirst = hits[0].revCompl;
-                if (xa_tag) {
-                    side += samLineSEWithXA(sid, hits, r->nHits[i], rcFirst ? revC : read, rcFirst ? revQ : qual);
-                } else {
-                    side += samLineSE(sid, hits[0], true, r->nHits[i], r->best[i], rcFirst ? revC : read, rcFirst ? revQ : qual);
-                    for (size_t j = 1; j < hits.size(); j++) side += samLineSE(sid, hits[j], false, r->nHits[i], r->best[i], "*", "*");
-                }
-            });
-        }
-        uint64_t total = 0;
-        samScan(r->sam, r->scanTmp, n, &total, s);
-        HIPCHK(hipStreamSynchronize(s));
-        r->samOut.resize((size_t)total + 1);
-        r->samOut.p[total] = '\0';
-        if (total) {
-            samWrite(r->sam, cx, total, r->samOut.p, s);
-            HIPCHK(hipStreamSynchronize(s));
-        }
-        *text = r->samOut.p;
-        *length = total;
-        return CMB_OK;
-    } catch (const std::exception& e) {
-        return fail(CMB_ERR_DEVICE, e.what());
-    }
-}
-// The same on the b-move index (the reference's RUN_LENGTH_COMPRESSION build runs the same matchApproxBestPlusX): the strata are
-// b-move batches, CIGARs and trimming read the matched string of an occurrence from the text beside the index (cmb_move_attach_text).
-extern "C" int cmb_move_match_best(cmb_move_index* idx, const cmb_strategy* st, uint32_t x, uint32_t min_identity, uint32_t kmer_size,
-                                   const char* seqs, const uint64_t* offs, uint32_t n_reads, cmb_best** out) {
-    if (!idx || !st) return fail(CMB_ERR_INVALID, "null argument");
-    cmb_index* text = cmb_move_text_index(idx);
-    if (!text) return fail(CMB_ERR_INVALID, "BEST mode on the b-move index needs the text beside it (cmb_move_attach_text)");
-    const StratumRunner run = [&](const char* cat, const uint64_t* o, uint32_t n, uint32_t k, StratumOut& r) -> int {
-        cmb_move_batch* b = nullptr;
-        int rcode = cmb_move_batch_create(idx, st, k, kmer_size, cat, o, n, &b);
-        if (rcode) return rcode;
-        struct Guard {
-            cmb_move_batch* b;
-            ~Guard() { cmb_move_batch_destroy(b); }
-        } guard{b};
-        cmb_move_batch_filter_per_strand(b, 1);
-        if ((rcode = cmb_move_batch_want_alignments(b, 1))) return rcode;
-        if ((rcode = cmb_move_batch_run(b))) return rcode;
-        uint64_t nOcc = 0, nOps = 0;
-        cmb_move_batch_result_size(b, &nOcc);
-        std::vector<cmb_move_occ> mo(nOcc ? nOcc : 1);
-        r.al.resize(nOcc ? nOcc : 1);
-        r.oo.resize((size_t)n + 1);
-        r.cnt.assign(CMB_CNT_MAX, 0);
-        if ((rcode = cmb_move_batch_results(b, mo.data(), mo.size(), r.oo.data(), r.cnt.data()))) return rcode;
-        r.oc.resize(nOcc ? nOcc : 1);
-        for (uint64_t i = 0; i < nOcc; i++) {
-            r.oc[i].begin = (uint32_t)mo[i].begin, r.oc[i].end = (uint32_t)mo[i].end; // (texts below 2^32: cmb_move_attach_text)
-            r.oc[i].distance = mo[i].distance, r.oc[i].strand = mo[i].strand;
-        }
-        (void)cmb_move_batch_alignments(b, r.al.data(), 0, nullptr, 0, &nOps);
-        r.ops.resize(nOps ? nOps : 1);
-        return cmb_move_batch_alignments(b, r.al.data(), r.al.size(), r.ops.data(), r.ops.size(), &nOps);
-    };
-    // (strata up to 13 errors, the reference's MAX_K, as on the FM-index: the b-move search runs that far since round 3, its alignments since round 4)
-    return matchBestWith(text, st, 13u, false, run, x, min_identity, seqs, offs, n_reads, out);
-}
-// the lists of a device-resident result on the host, packed as cmb_match_best packs them (CIGAR runs from the begin, one after the other)
-static void fetchBest(cmb_best* r) {
-    if (!r->onDevice || r->fetched) return;
-    useDevice(r->ix->device);
-    const uint64_t n = r->nOcc;
-    r->occ.resize(n);
-    r->aln.resize(n);
-    std::vector<AlnRec> ar(n);
-    std::vector<uint16_t> raw((size_t)n * BEST_OPS_STRIDE);
-    if (n) {
-        static_assert(sizeof(cmb_occ) == sizeof(uint4), "cmb_occ is the device's occurrence record");
-        HIPCHK(hipMemcpy(r->occ.data(), r->dOcc.p, n * sizeof(cmb_occ), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(ar.data(), r->dAln.p, n * sizeof(AlnRec), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(raw.data(), r->dOps.p, raw.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
-    }
-    uint64_t nOps = 0;
-    for (uint64_t i = 0; i < n; i++) nOps += ar[i].nOps;
-    r->ops.resize(nOps);
-    uint64_t po = 0;
-    for (uint64_t i = 0; i < n; i++) {
-        r->aln[i] = cmb_aln{ar[i].seqId, ar[i].seqBegin, po, (uint16_t)ar[i].nOps, (uint16_t)ar[i].spans, 0};
-        const uint16_t* src = raw.data() + i * BEST_OPS_STRIDE;
-        for (uint32_t j = 0; j < ar[i].nOps; j++) r->ops[po + j] = src[ar[i].nOps - 1 - j]; // (stored end to begin)
-        po += ar[i].nOps;
-    }
-    r->fetched = true;
-}
-extern "C" int cmb_best_sizes(const cmb_best* r, uint64_t* n_occ, uint64_t* n_ops) {
-    if (!r) return fail(CMB_ERR_INVALID, "null argument");
-    try {
-        fetchBest(const_cast<cmb_best*>(r));
-    } catch (const std::exception& e) {
-        return fail(CMB_ERR_DEVICE, e.what());
-    }
-    if (n_occ) *n_occ = r->occ.size();
-    if (n_ops) *n_ops = r->ops.size();
-    return CMB_OK;
-}
-extern "C" int cmb_best_results(const cmb_best* r, cmb_occ* occ, cmb_aln* aln, uint64_t cap, uint16_t* cigar_ops, uint64_t ops_cap,
-                                uint64_t* offs, uint32_t* best, uint32_t* n_hits, uint64_t* counters) {
-    if (!r) return fail(CMB_ERR_INVALID, "null argument");
-    const bool lists = occ || aln || cigar_ops; // (a device-resident result downloads its lists only when they are asked for)
-    try {
-        if (lists) fetchBest(const_cast<cmb_best*>(r));
-    } catch (const std::exception& e) {
-        return fail(CMB_ERR_DEVICE, e.what());
-    }
-    if ((lists || !r->onDevice) && (cap < r->occ.size() || ops_cap < r->ops.size())) return fail(CMB_ERR_OVERFLOW, "output buffer too small");
-    if (occ && !r->occ.empty()) memcpy(occ, r->occ.data(), r->occ.size() * sizeof(cmb_occ));
-    if (aln && !r->aln.empty()) memcpy(aln, r->aln.data(), r->aln.size() * sizeof(cmb_aln));
-    if (cigar_ops && !r->ops.empty()) memcpy(cigar_ops, r->ops.data(), r->ops.size() * sizeof(uint16_t));
-    if (offs) memcpy(offs, r->offs.data(), r->offs.size() * sizeof(uint64_t));
-    if (best) memcpy(best, r->best.data(), r->best.size() * sizeof(uint32_t));
-    if (n_hits) memcpy(n_hits, r->nHits.data(), r->nHits.size() * sizeof(uint32_t));
-    if (counters) memcpy(counters, r->cnts, sizeof(r->cnts));
-    return CMB_OK;
-}
-extern "C" int cmb_best_timings(const cmb_best* r, const char** names, float* ms, uint32_t cap) {
-    if (!r) return 0;
-    uint32_t n = 0;
-    for (const auto& t : r->times) {
-        if (n >= cap) break;
-        if (names) names[n] = t.first.c_str();
-        if (ms) ms[n] = (float)t.second;
-        n++;
-    }
-    return (int)n;
-}
-extern "C" int cmb_best_host_reads(const cmb_best* r, uint8_t* status, uint32_t* n) {
-    if (!r) return fail(CMB_ERR_INVALID, "null argument");
-    if (status)
-        for (size_t i = 0; i < r->offs.size() - 1; i++) status[i] = i < r->hostRead.size() ? r->hostRead[i] : 0;
-    if (n) *n = r->nHostReads;
-    return CMB_OK;
-}
-extern "C" void cmb_best_destroy(cmb_best* r) { delete r; }

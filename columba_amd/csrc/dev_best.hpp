@@ -1,4 +1,4 @@
-// BEST (+x strata) mode with the per-occurrence bookkeeping on the device (cmb_match_best_device): what matchBestWith (columba_amd.hip)
+// BEST (+x strata) mode with the per-occurrence bookkeeping on the device (cmb_match_best_device): what matchBestWith (best.hip)
 // does with host containers — processSeq's "keep what lies at or above the first distance not processed yet", the vectors per strand and
 // distance, combineOccVectors' sort / unique / copy (reference src/searchstrategy.cpp:573-620, :791-812) — on the arrays a stratum batch
 // leaves in HBM (foffs, two filter groups per read; fout; alnRec; alnOps at alnStride).
@@ -15,13 +15,11 @@
 //   k_best_uniq     a record that equals its predecessor in (read, distance, strand, sequence, begin) is dropped; records per read
 //   k_best_emit     the final lists, every read's records at its offset
 #pragma once
-#include "kernels.hpp"
+#include "host_util.hpp" // (AlnRec, BEST_OPS_STRIDE)
 
 #include <rocprim/device/device_merge_sort.hpp>
 
 namespace cmb {
-
-constexpr uint32_t BEST_OPS_STRIDE = 2u * 13u + 3u; // CIGAR runs of an occurrence with up to 13 errors (k_cigar: 2 k + 3)
 
 // per read of a stratum (k_best_scan): bits 0-13 / 14-27 "an occurrence at distance d" of the forward / reverse strand, 28-41 / 42-55
 // "an occurrence at distance d that lies inside one sequence", bit 56 "a kept occurrence runs over the end of its sequence"

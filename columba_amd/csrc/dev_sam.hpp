@@ -1,5 +1,5 @@
 // SAM text of a single-end chunk in ALL mode, written on the device (cmb_batch_sam_device): the lines host_sam.hpp and samOfRead
-// (columba_amd.hip) put together on the host, byte for byte, from what a run with alignments leaves in HBM — the read
+// (sam.hip) put together on the host, byte for byte, from what a run with alignments leaves in HBM — the read
 // characters, the final occurrences of every read (k_filter_write), their CIGAR runs and sequence assignment (k_cigar) — plus
 // the identifiers, qualities and sequence names of the chunk, packed.
 //
@@ -27,8 +27,7 @@
 //                   does not fit the window is emitted again, clipped, after the window went out — so a line (an XA line of a
 //                   repeat: tens of kilobytes) may be any number of windows long.
 #pragma once
-#include "host_util.hpp" // (SamPlan, SamDeviceBufs)
-#include "kernels.hpp"
+#include "host_util.hpp" // (SamPlan, SamDeviceBufs, AlnRec)
 
 namespace cmb {
 

@@ -1,7 +1,7 @@
 // BEST (+x strata) mode, the host side, once: the rule that decides which distance a read looks at next (findBestAlignments,
 // reference src/searchstrategy.cpp:623-712), the loop that walks a chunk of reads through their strata as batches, and the containers
 // of the reads whose occurrences live in host vectors (checkAlignments :536-568, combineOccVectors :570-621).  Plain C++17: no HIP, no
-// batch; columba_amd.hip puts a host store and a device store under the loop, pair_best.hip steps the rule for one read.
+// batch; best.hip puts a host store and a device store under the loop, pair_best.hip steps the rule for one read.
 #pragma once
 #include "../../include/columba_amd.h"
 

@@ -1,4 +1,4 @@
-// Host-side HIP plumbing shared by the library's translation units (columba_amd.hip, move_backend.hip): the error check, owning device
+// Host-side HIP plumbing shared by the library's translation units that use the device: the error check, owning device
 // and page-locked buffers, the device primitives (sorts, scan, run-length encode: rocPRIM), which geometry and tables a batch runs on,
 // what both backends do when a batch is created, and the event timer behind cmb_batch_timings / cmb_move_batch_timings.
 #pragma once
@@ -19,6 +19,8 @@
 #include "host_dispatch.hpp" // runtime values to template arguments, the geometry rule (no HIP: a CPU program tests it)
 #include "host_grid.hpp"     // CMB_TEST_GRID_CAP and the clamps of the geometry knobs (no HIP: a CPU program tests it)
 #include "host_schemes.hpp"
+
+struct cmb_index;
 
 #define HIPCHK(expr)                                                                                  \
     do {                                                                                              \
@@ -220,6 +222,14 @@ template <typename Batch> void foldSubBatches(Batch* b) {
     }
 }
 
+// CIGAR and sequence assignment of one occurrence (kernels.hpp: k_cigar): nOps runs of (length << 2 | op) stored END to BEGIN;
+// seqId = the sequence `begin` lies in (IndexInterface::findSeqName, indexinterface.cpp:799-832); spans = the occurrence runs over its
+// end (the host trims or drops those, :833-899)
+struct AlnRec {
+    uint32_t seqId, seqBegin, nOps, spans;
+};
+static_assert(sizeof(AlnRec) == 16, "AlnRec is copied between the device and the host as it stands");
+constexpr uint32_t BEST_OPS_STRIDE = 2u * 13u + 3u; // CIGAR runs of an occurrence with up to 13 errors (k_cigar: 2 k + 3)
 struct SamPlan { // per read (32 bytes; dev_sam.hpp)
     uint32_t kind;    // SAM_*
     uint32_t primary; // index of the primary among the read's occurrences
@@ -236,7 +246,7 @@ struct PairPlan {
     uint32_t minDist, nPairs; // the minimal summed distance and how many pairs have it
     uint32_t idLen[2];        // cleaned identifiers of read 1 and read 2
 };
-// What the device SAM driver (columba_amd.hip: samUpload, samSplice, samScan, samWrite) keeps in HBM for one (sub-)batch or one BEST result:
+// What the device SAM driver (sam.hip: samUpload, samSplice, samScan, samWrite) keeps in HBM for one (sub-)batch or one BEST result:
 // the chunk's packed identifiers, qualities and sequence names with their offsets, the plan, length and position of every read in the
 // text, the text of the reads the host formatted with its offsets and read numbers, the text itself (the scan's scratch is the owner's)
 struct SamDeviceBufs {
@@ -245,40 +255,46 @@ struct SamDeviceBufs {
     DevBuf<SamPlan> plan;
     DevBuf<uint32_t> sideReads;
 };
-// ... and what a b-move (sub-)batch owns for that driver (cmb_move_batch_sam_device): its buffers, the list of host-formatted reads, the
-// scan's scratch, and — in the first part — the finished text of the whole batch in page-locked memory
-struct MoveSamBufs {
+// ... and what a (sub-)batch of either backend owns for the SAM and pair drivers: the driver's buffers; the reads (pairs) the plan kernel
+// leaves to the host ([0]: how many); in the first part, the finished text of the whole batch; in a part with read 1 of every pair, the
+// plan of the concordant pairs, per pair the SAM lines the device writes and whether it counts as mapped, and the 64-bit scan of either
+struct SamBufs {
     SamDeviceBufs sam;
     DevBuf<uint32_t> hostList;
-    DevBuf<uint8_t> scanTmp;
     PinnedBuf<char> samOut;
+    DevBuf<PairPlan> pairPlan;
+    DevBuf<uint64_t> pairRecords, pairSums;
+    DevBuf<uint32_t> pairMapped;
 };
-// The final lists a b-move (sub-)batch keeps in HBM for its whole chunk (cmb_move_batch_keep_device_lists), as columba_amd.hip's SAM
-// driver and strata bookkeeping read them (dev_sam.hpp: SamCtx; dev_best.hpp: k_best_scan / k_best_append), beside the host copies the
-// host-formatted reads are taken from.  One view per part, in read order (move_backend.hip: moveBatchListViews).
-struct MoveListView {
+// The final lists a (sub-)batch of either backend holds in HBM for its whole chunk, as the SAM driver and the strata bookkeeping read
+// them (dev_sam.hpp: SamCtx; dev_best.hpp: k_best_scan / k_best_append), beside the host copies the host-formatted reads are taken
+// from.  One view per part, in read order (columba_amd.hip: batchListViews; move_backend.hip: moveBatchListViews).
+struct ListView {
     uint32_t nReads = 0, k = 0;
     int metric = 1;
+    cmb_index* textIndex = nullptr; // whose text and sequence starts the lists refer to (nullptr: a b-move index without its text)
     const uint8_t* reads = nullptr; // device: raw read characters of the part, and their offsets
     const uint64_t* offs = nullptr;
     const uint64_t* goffs = nullptr; // device: first record of every filter group, groupStride groups per read
     uint32_t groupStride = 1;
-    const uint4* occ = nullptr; // device: {begin, end, distance, strand}
-    const uint4* aln = nullptr; //         AlnRec {seqId, seqBegin, nOps, spans}
-    const uint16_t* ops = nullptr; //      CIGAR runs at `stride`, stored end to begin
+    const uint4* occ = nullptr;    // device: {begin, end, distance, strand}
+    const AlnRec* aln = nullptr;
+    const uint16_t* ops = nullptr; //         CIGAR runs at `stride`, stored end to begin
     uint32_t stride = 0;
-    uint64_t nOcc = 0;
     hipStream_t stream = nullptr;
-    // host: read offsets of the part (from 0), occurrences as {begin, end (64 bits), distance, strand} of 24 bytes with their offsets per
-    // read, AlnRec and CIGAR runs as on the device
+    // host: read offsets of the part (from 0); occurrences as records of hOccBytes (cmb_occ: 16, or cmb_move_occ with 64-bit begin and
+    // end: 24) with their offsets per filter group or per read; AlnRec and CIGAR runs as on the device
     const uint64_t* hostOffs = nullptr;
     const void* hOcc = nullptr;
+    uint32_t hOccBytes = 0;
     const uint64_t* hOccOffs = nullptr;
-    const uint4* hAln = nullptr;
+    bool hOffsPerGroup = false;
+    const AlnRec* hAln = nullptr;
     const uint16_t* hOps = nullptr;
     const uint64_t* cnts = nullptr; // counters and kernel times of the part's run
     const std::vector<KernelTime>* times = nullptr;
-    MoveSamBufs* samBufs = nullptr;
+    SamBufs* bufs = nullptr;
+    DevBuf<uint8_t>* scanTmp = nullptr; // the part's scratch for the drivers' scans
 };
 
 } // namespace cmb

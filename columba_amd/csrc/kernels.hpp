@@ -12,6 +12,7 @@
 //   k_fmocc       in-index occurrence -> text positions indexinterface.cpp:1385-1440, :1349-1366
 #pragma once
 #include "dev_partition.hpp"
+#include "host_util.hpp" // (AlnRec: the record k_cigar writes, shared with the units that read it)
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -2166,10 +2167,7 @@ k_filter_write(const unsigned long long* __restrict__ keys, uint32_t n, const ui
 // and take the same decisions (tests/test_oracle_golden.py checks it on the reference's own traceback vectors).
 // Output per occurrence: n runs of (length << 2 | op), op 0 M / 1 I / 2 D, stored END to BEGIN at ops[occ * stride + j].
 // Sequence assignment (IndexInterface::findSeqName, indexinterface.cpp:799-832): seq = the sequence `begin` lies in;
-// spans = the occurrence runs over its end (the host trims or drops those, :833-899).
-struct AlnRec {
-    uint32_t seqId, seqBegin, nOps, spans;
-};
+// spans = the occurrence runs over its end (the host trims or drops those, :833-899) — AlnRec, host_util.hpp.
 constexpr uint32_t CIG_M = 0, CIG_I = 1, CIG_D = 2;
 constexpr uint32_t CIGAR_BLOCK_WORDS_MAX_ED = 9; // k_cigar up to this distance, k_cigar_wide beyond (see there)
 template <bool NARROW, bool PACKED>

@@ -4,6 +4,7 @@
 #include "host_schemes.hpp"
 #include "host_util.hpp"
 #include "move_search.hpp"
+#include "units.hpp" // (failWith; the text kernels and k_cigar live in columba_amd.hip: moveCigarsOnText)
 
 #include <algorithm>
 #include <cmath>
@@ -16,9 +17,6 @@
 #include <thread>
 #include <vector>
 
-namespace cmb {
-int failWith(int code, const std::string& msg); // columba_amd.hip: sets the calling thread's cmb_last_error
-}
 using namespace cmb;
 
 // limits of the backend: 2^31 text positions and 2^31 records per slice (the sorts and scans below count in 32 bits)
@@ -101,13 +99,6 @@ struct TableHost {
 uint32_t bitsFor(double v) { return (uint32_t)std::ceil(std::log2(v)); } // moverepr.h:44-46
 
 } // namespace
-
-namespace cmb { // (columba_amd.hip: the text kernels and k_cigar live in that translation unit)
-int moveCigarsOnText(cmb_index* textIndex, hipStream_t s, const uint64_t* offs, const uint32_t* G, uint32_t gw, uint32_t nReads, uint32_t maxLen,
-                     uint32_t k, int gapless, const void* occs, const uint32_t* occRead, uint64_t nOcc, void* aln, uint16_t* ops, uint32_t stride,
-                     uint32_t* flagWord);
-const std::vector<uint32_t>& seqStartsOfIndex(const cmb_index* textIndex);
-} // namespace cmb
 
 struct cmb_move_index {
     int device = 0;
@@ -686,31 +677,35 @@ struct cmb_move_batch {
     // alignments of the final occurrences (cmb_move_batch_want_alignments; needs cmb_move_attach_text)
     bool wantAln = false;
     uint32_t alnStride = 0;
-    DevBuf<uint4> occ32, alnRec;
+    DevBuf<uint4> occ32;
+    DevBuf<AlnRec> alnRec;
     DevBuf<uint32_t> occRead;
     DevBuf<uint16_t> alnOps;
-    std::vector<uint4> hAlnRec; // {seqId, seqBegin, nOps, spans} per occurrence
+    std::vector<AlnRec> hAlnRec;
     std::vector<uint16_t> hAlnOps;
     // the same lists of the WHOLE chunk in HBM (cmb_move_batch_keep_device_lists): occ32 / alnRec / alnOps above are a slice's and are
     // reused by the next one; with the lists kept, k_mvs_occ32 and k_cigar write a slice's records straight behind those of the slices
     // before it (keepN records so far; the arrays grow with a copy of what they hold), and keepOff holds the group offsets of every
     // read — one group per read, or two with every strand filtered by itself — rebased to the chunk (k_mvs_keep_offsets)
     bool keepLists = false;
-    DevBuf<uint4> keepOcc, keepAln;
+    DevBuf<uint4> keepOcc;
+    DevBuf<AlnRec> keepAln;
     DevBuf<uint16_t> keepOps;
     DevBuf<uint64_t> keepOff;
     uint64_t keepN = 0, keepCap = 0;
     uint32_t keepStride = 1; // groups per read of the last run
-    MoveSamBufs samBufs; // (what the SAM driver keeps with this part: cmb_move_batch_sam_device, columba_amd.hip)
+    SamBufs samBufs; // (what the SAM driver keeps with this part, and its scan's scratch: cmb_move_batch_sam_device, sam.hip)
+    DevBuf<uint8_t> samScanTmp;
     void keepReserve(uint64_t want, hipStream_t s) {
         if (want <= keepCap) return;
         const uint64_t c = want + want / 2 + 4096;
-        DevBuf<uint4> o, a;
+        DevBuf<uint4> o;
+        DevBuf<AlnRec> a;
         DevBuf<uint16_t> p;
         o.alloc(c), a.alloc(c), p.alloc(c * alnStride);
         if (keepN) {
             HIPCHK(hipMemcpyAsync(o.p, keepOcc.p, keepN * sizeof(uint4), hipMemcpyDeviceToDevice, s));
-            HIPCHK(hipMemcpyAsync(a.p, keepAln.p, keepN * sizeof(uint4), hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(a.p, keepAln.p, keepN * sizeof(AlnRec), hipMemcpyDeviceToDevice, s));
             HIPCHK(hipMemcpyAsync(p.p, keepOps.p, keepN * alnStride * sizeof(uint16_t), hipMemcpyDeviceToDevice, s));
         }
         HIPCHK(hipStreamSynchronize(s)); // (the old arrays are freed below)
@@ -965,10 +960,10 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                 for (uint64_t i = 0; i < nOcc; i++) {
                     const cmb_move_occ& o = b->occs[i];
                     if (sp.size() < 2) { // one sequence
-                        b->hAlnRec[i] = make_uint4(0u, (uint32_t)o.begin, 1u, 0u);
+                        b->hAlnRec[i] = AlnRec{0u, (uint32_t)o.begin, 1u, 0u};
                     } else {
                         const uint32_t id = (uint32_t)(std::upper_bound(sp.begin(), sp.end() - 1, (uint32_t)o.begin) - sp.begin()) - 1;
-                        b->hAlnRec[i] = make_uint4(id, (uint32_t)o.begin - sp[id], 1u, o.end > sp[id + 1] ? 1u : 0u);
+                        b->hAlnRec[i] = AlnRec{id, (uint32_t)o.begin - sp[id], 1u, o.end > sp[id + 1] ? 1u : 0u};
                     }
                     b->hAlnOps[i * b->alnStride] = (uint16_t)(((o.end - o.begin) << 2) | 0u);
                 }
@@ -983,7 +978,7 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
                     go[(size_t)gs * nReads] = b->occOffs[nReads];
                     if (nOcc) {
                         HIPCHK(hipMemcpyAsync(b->keepOcc.p, o32.data(), nOcc * sizeof(uint4), hipMemcpyHostToDevice, s));
-                        HIPCHK(hipMemcpyAsync(b->keepAln.p, b->hAlnRec.data(), nOcc * sizeof(uint4), hipMemcpyHostToDevice, s));
+                        HIPCHK(hipMemcpyAsync(b->keepAln.p, b->hAlnRec.data(), nOcc * sizeof(AlnRec), hipMemcpyHostToDevice, s));
                         HIPCHK(hipMemcpyAsync(b->keepOps.p, b->hAlnOps.data(), nOcc * b->alnStride * sizeof(uint16_t), hipMemcpyHostToDevice, s));
                     }
                     HIPCHK(hipMemcpyAsync(b->keepOff.p, go.data(), go.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s));
@@ -1392,7 +1387,8 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
         HIPCHK(hipGetLastError());
         if (b->wantAln && nOut) { // CIGAR and sequence of every final occurrence: findCIGAR on text[begin, end) (k_cigar)
             tm.begin();
-            uint4 *dOcc = nullptr, *dAln = nullptr;
+            uint4* dOcc = nullptr;
+            AlnRec* dAln = nullptr;
             uint16_t* dOps = nullptr;
             if (b->keepLists) { // in place, behind the records of the slices before this one
                 b->keepReserve(b->keepN + nOut, s);
@@ -1414,7 +1410,7 @@ static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
             const size_t base = b->hAlnRec.size();
             b->hAlnRec.resize(base + nOut);
             b->hAlnOps.resize((base + nOut) * b->alnStride);
-            HIPCHK(hipMemcpyAsync(b->hAlnRec.data() + base, dAln, nOut * sizeof(uint4), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(b->hAlnRec.data() + base, dAln, nOut * sizeof(AlnRec), hipMemcpyDeviceToHost, s));
             HIPCHK(hipMemcpyAsync(b->hAlnOps.data() + base * b->alnStride, dOps, nOut * b->alnStride * sizeof(uint16_t), hipMemcpyDeviceToHost, s));
             uint32_t flagAfter = 0;
             HIPCHK(hipMemcpyAsync(&flagAfter, b->cnt.p + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -1517,8 +1513,8 @@ extern "C" int cmb_move_batch_keep_device_lists(cmb_move_batch* b, int on) {
     return CMB_OK;
 }
 namespace cmb {
-// one view per part of a batch that has run with its lists kept (columba_amd.hip: the SAM driver, the strata of BEST mode)
-int moveBatchListViews(cmb_move_batch* b, std::vector<MoveListView>& out) {
+// one view per part of a batch that has run with its lists kept (sam.hip: the SAM driver; best.hip: the strata of BEST mode)
+int moveBatchListViews(cmb_move_batch* b, std::vector<ListView>& out) {
     if (!b) return failWith(CMB_ERR_INVALID, "null argument");
     if (!b->done) return failWith(CMB_ERR_INVALID, "batch has not been run");
     if (!b->keepLists || !b->wantAln) return failWith(CMB_ERR_INVALID, "the lists were not kept on the device (cmb_move_batch_keep_device_lists)");
@@ -1526,21 +1522,21 @@ int moveBatchListViews(cmb_move_batch* b, std::vector<MoveListView>& out) {
     if (parts.empty()) parts.push_back(b);
     out.clear();
     for (cmb_move_batch* c : parts) {
-        MoveListView v;
-        v.nReads = c->nReads, v.k = c->k, v.metric = c->metric;
+        ListView v;
+        v.nReads = c->nReads, v.k = c->k, v.metric = c->metric, v.textIndex = c->ix->textIndex;
         v.reads = c->reads.p, v.offs = c->offs.p;
         v.goffs = c->keepOff.p, v.groupStride = c->keepStride;
-        v.occ = c->keepOcc.p, v.aln = c->keepAln.p, v.ops = c->keepOps.p, v.stride = c->alnStride, v.nOcc = c->keepN;
+        v.occ = c->keepOcc.p, v.aln = c->keepAln.p, v.ops = c->keepOps.p, v.stride = c->alnStride;
         v.stream = c->stream;
         v.hostOffs = c->hostOffs.data();
-        v.hOcc = c->occs.data(), v.hOccOffs = c->occOffs.data(), v.hAln = c->hAlnRec.data(), v.hOps = c->hAlnOps.data();
+        v.hOcc = c->occs.data(), v.hOccBytes = sizeof(cmb_move_occ), v.hOccOffs = c->occOffs.data(), v.hOffsPerGroup = false;
+        v.hAln = c->hAlnRec.data(), v.hOps = c->hAlnOps.data();
         v.cnts = c->cnts, v.times = &c->times;
-        v.samBufs = &c->samBufs;
+        v.bufs = &c->samBufs, v.scanTmp = &c->samScanTmp;
         out.push_back(v);
     }
     return CMB_OK;
 }
-cmb_index* moveTextIndexOfBatch(const cmb_move_batch* b) { return b ? b->ix->textIndex : nullptr; }
 } // namespace cmb
 // as cmb_batch_alignments: one record per occurrence of cmb_move_batch_results, CIGAR runs (length << 2 | op, op 0 M / 1 I / 2 D) in a pool
 extern "C" int cmb_move_batch_alignments(const cmb_move_batch* b, cmb_aln* out, uint64_t cap, uint16_t* cigar_ops, uint64_t ops_cap, uint64_t* n_ops) {
@@ -1552,18 +1548,18 @@ extern "C" int cmb_move_batch_alignments(const cmb_move_batch* b, cmb_aln* out, 
     uint64_t total = 0, ops = 0;
     for (const cmb_move_batch* c : parts) {
         total += c->hAlnRec.size();
-        for (const uint4& r : c->hAlnRec) ops += r.z;
+        for (const AlnRec& r : c->hAlnRec) ops += r.nOps;
     }
     if (n_ops) *n_ops = ops;
     if (cap < total || ops_cap < ops) return failWith(CMB_ERR_OVERFLOW, "output buffer too small");
     uint64_t po = 0, at = 0;
     for (const cmb_move_batch* c : parts)
         for (uint64_t i = 0; i < c->hAlnRec.size(); i++, at++) {
-            const uint4& r = c->hAlnRec[i];
-            out[at] = cmb_aln{r.x, r.y, po, (uint16_t)r.z, (uint16_t)r.w};
+            const AlnRec& r = c->hAlnRec[i];
+            out[at] = cmb_aln{r.seqId, r.seqBegin, po, (uint16_t)r.nOps, (uint16_t)r.spans};
             const uint16_t* src = c->hAlnOps.data() + i * c->alnStride;
-            for (uint32_t j = 0; j < r.z; j++) cigar_ops[po + j] = src[r.z - 1 - j]; // (stored end to begin)
-            po += r.z;
+            for (uint32_t j = 0; j < r.nOps; j++) cigar_ops[po + j] = src[r.nOps - 1 - j]; // (stored end to begin)
+            po += r.nOps;
         }
     return CMB_OK;
 }

@@ -17,6 +17,7 @@
 // itself (cmb_batch_filter_per_strand) and the alignments of cmb_batch_alignments.
 #include "../../include/columba_amd.h"
 #include "host_best.hpp"
+#include "host_error.hpp"
 #include "host_sam.hpp"
 
 #include <algorithm>
@@ -29,9 +30,6 @@
 #include <tuple>
 #include <vector>
 
-namespace cmb {
-int failWith(int code, const std::string& msg); // columba_amd.hip
-}
 using namespace cmb;
 
 namespace {

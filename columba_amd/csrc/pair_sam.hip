@@ -2,6 +2,7 @@
 // Reference: TextOcc::generateSAMPairedEnd (indexhelpers.cpp:114-166), createUnmappedSAMOccurrencePE (:186-213),
 // generateSAMUnpaired (:215-262), getFlagsPE (indexhelpers.h:340-371), getMapQ / getMapQPairedEnd (:378-410).
 #include "../../include/columba_amd.h"
+#include "host_error.hpp"
 #include "host_sam.hpp"
 
 #include <cmath>
@@ -9,9 +10,6 @@
 #include <functional>
 #include <string>
 
-namespace cmb {
-int failWith(int code, const std::string& msg); // columba_amd.hip
-}
 using namespace cmb;
 
 namespace {

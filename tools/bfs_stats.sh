@@ -5,7 +5,7 @@ set -e
 R=${GRAFT_REPO_ROOT:-$PWD}
 cd $R
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off -Wno-unused-variable -DCMB_BFS_STATS \
-    -o /tmp/libcolumba_amd_stats.so columba_amd/csrc/columba_amd.hip columba_amd/csrc/move_backend.hip columba_amd/csrc/pair_sam.hip columba_amd/csrc/pair_best.hip
+    -o /tmp/libcolumba_amd_stats.so columba_amd/csrc/*.hip
 python3 - "$@" <<'PY'
 import ctypes as C, sys, numpy as np, torch
 sys.path.insert(0, ".")

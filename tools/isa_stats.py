@@ -1,6 +1,8 @@
 """Instruction counts of device kernels from a hipcc -S listing (development helper):
    hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off --cuda-device-only -S -o /tmp/x.s columba_amd/csrc/columba_amd.hip
-   python3 tools/isa_stats.py /tmp/x.s k_bfs_pass [--loops]"""
+   python3 tools/isa_stats.py /tmp/x.s k_bfs_pass [--loops]
+(the unit that holds the kernel: columba_amd.hip for the matcher's (kernels.hpp), sam.hip for k_sam_* and k_pair_*, best.hip for
+k_best_*, move_backend.hip for k_mv*)"""
 import re, sys
 src = open(sys.argv[1]).read().split('\n')
 pat = sys.argv[2]
