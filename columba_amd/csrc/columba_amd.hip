@@ -560,7 +560,7 @@ struct cmb_batch {
     uint32_t recW = 0;
     DevBuf<uint64_t> offs;
     DevBuf<uint32_t> G;
-    DevBuf<uint4> mfull; // match words of the full reads per 32-row block (k_match_words)
+    DevBuf<uint4> mfull; // match words of the full reads per 32-row block (k_prep)
     DevBuf<DevStrategyK> strat;
     // frontier search (dev_bfs_edit.hpp): node / event double buffers, F records, contexts, list arena
     DevBuf<uint4> bfsQ[2], bfsEv[2], bfsF, bfsC, bfsA;
@@ -951,6 +951,21 @@ static void launchCigar(cmb_index* ix, hipStream_t s, const CigarJob& j, bool wi
                        j.stride, j.aln, j.flagWord, j.gapless);
 }
 
+// k_prep over nReads reads (batchRunOne, verifyDirect, cmb_cigar_windows): the codes, the bit-strings, the read records (rec, or null) and the
+// match words of the full reads (mfull with nBlk blocks per read x strand, or null) in one launch that leaves no word of them unwritten.
+// A block takes as many reads per pass as give it a (read, chunk) pair per thread; at most 64 k blocks loop over the passes
+static void launchPrep(hipStream_t s, const uint8_t* reads, const uint64_t* offs, uint32_t nReads, uint32_t maxLen, uint32_t gw, uint8_t* seq, uint32_t* G,
+                       uint32_t* rec, uint32_t recW, uint4* mfull, uint32_t nBlk, bool verbose) {
+    const uint32_t chunks = (maxLen + 31) / 32;
+    const uint32_t perPass = std::max(1u, 256u / chunks);
+    const uint32_t passes = (nReads + perPass - 1) / perPass;
+    const uint32_t blocks = capBlocks(std::min<uint32_t>(passes, 65536u));
+    gridLine(verbose, "k_prep", passes, (uint64_t)blocks * 256);
+    if (!blocks) return;
+    hipLaunchKernelGGL(k_prep, dim3(blocks), dim3(256), prepLdsWords(perPass, gw) * sizeof(uint32_t), s, reads, offs, nReads, maxLen, gw, chunks, perPass, seq,
+                       G, rec, recW, mfull, nBlk);
+}
+
 // one level of the frontier search, as the pass loop of batchRunOne launches it
 template <class Geo> static void launchBfsPass(cmb_batch* b, const BfsBufs& B, uint32_t pass, const Queues& q) {
     hipLaunchKernelGGL(k_bfs_pass<Geo>, dim3(B.gridX + B.gridEv), dim3(256), 0, b->stream, b->ix->d, stratOf<Geo::MP>(b), B, pass, b->offs.p, b->gw, b->G.p,
@@ -1009,23 +1024,15 @@ static int batchRunOne(cmb_batch* b) {
 
         HIPCHK(hipMemsetAsync(b->counters.p, 0, CMB_CNT_MAX * sizeof(unsigned long long), s));
         tm.begin();
-        {
-            HIPCHK(hipMemsetAsync(b->G.p, 0, b->G.bytes(), s));
-            HIPCHK(hipMemsetAsync(b->rec.p, 0, b->rec.bytes(), s));
-            const uint32_t chunks = (b->maxLen + 31) / 32;
-            const uint64_t nthr = (uint64_t)nReads * chunks;
-            hipLaunchKernelGGL(k_prep, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, b->reads.p, b->offs.p,
-                               nReads, b->maxLen, b->gw, chunks, b->seq.p, b->G.p, b->rec.p, b->recW);
-        }
         MFull mf{nullptr, 0};
-        if (b->metric == CMB_METRIC_EDIT && b->k > 0) {
+        if (b->metric == CMB_METRIC_EDIT && b->k > 0) { // (the match words of the full reads: k_prep writes them along with the rest)
             mf.nBlk = mfullBlocks(b->maxLen);
             const uint64_t nW = (uint64_t)tasks * mf.nBlk;
             if (b->mfull.n < 2 * nW) b->mfull.alloc(2 * nW);
-            hipLaunchKernelGGL(k_match_words, dim3((unsigned)((nW + 255) / 256)), dim3(256), 0, s, b->G.p, b->gw, b->offs.p, tasks,
-                               mf.nBlk, b->mfull.p);
             mf.p = b->mfull.p;
         }
+        launchPrep(s, b->reads.p, b->offs.p, nReads, b->maxLen, b->gw, b->seq.p, b->G.p, b->rec.p, b->recW, const_cast<uint4*>(mf.p),
+                   mf.nBlk, verbose);
         tm.end("k_prep");
 
         // ---- prologue + DFS (re-run with larger queues if they overflow: nothing is truncated)
@@ -2165,13 +2172,10 @@ static int verifyDirect(cmb_index* idx, const char* pattern, uint32_t plen, cons
         q.textCap = (uint32_t)cap;
         q.cnt = cnt.p;
         q.counters = ctr.p;
-        HIPCHK(hipMemset(G.p, 0, G.bytes()));
-        hipLaunchKernelGGL(k_prep, dim3(1), dim3(256), 0, 0, reads.p, offs.p, 1u, mlen, gw, (mlen + 31) / 32, seq.p,
-                           G.p, (uint32_t*)nullptr, 0u);
         DevBuf<uint4> mfull;
         MFull mf{nullptr, mfullBlocks(mlen)};
         mfull.alloc((size_t)2 * 2 * mf.nBlk);
-        hipLaunchKernelGGL(k_match_words, dim3(1), dim3(256), 0, 0, G.p, gw, offs.p, 2u, mf.nBlk, mfull.p);
+        launchPrep(0, reads.p, offs.p, 1u, mlen, gw, seq.p, G.p, nullptr, 0u, mfull.p, mf.nBlk, verbose);
         mf.p = mfull.p;
         uint32_t hc[8];
         if (n && dp) {
@@ -2254,12 +2258,9 @@ extern "C" int cmb_cigar_windows(cmb_index* idx, const char* pattern, uint32_t p
         offs.upload(ho, 2);
         seq.alloc(2 * (size_t)mlen);
         G.alloc(8 * (size_t)gw);
-        HIPCHK(hipMemset(G.p, 0, G.bytes()));
-        hipLaunchKernelGGL(k_prep, dim3(1), dim3(256), 0, 0, reads.p, offs.p, 1u, mlen, gw, (mlen + 31) / 32, seq.p, G.p,
-                           (uint32_t*)nullptr, 0u);
         MFull mf{nullptr, mfullBlocks(mlen)};
         mfull.alloc((size_t)2 * 2 * mf.nBlk);
-        hipLaunchKernelGGL(k_match_words, dim3(1), dim3(256), 0, 0, G.p, gw, offs.p, 2u, mf.nBlk, mfull.p);
+        launchPrep(0, reads.p, offs.p, 1u, mlen, gw, seq.p, G.p, nullptr, 0u, mfull.p, mf.nBlk, getenv("CMB_VERBOSE") != nullptr);
         mf.p = mfull.p;
         std::vector<uint4> ho4(n);
         for (uint64_t i = 0; i < n; i++) ho4[i] = make_uint4(begins[i], ends[i], distances[i], 0u);

@@ -2,7 +2,7 @@
 //
 //   k_kmer_table  populateTable                         src/indexinterface.cpp:294-335
 //   k_rank/k_extend/k_locate   fine-grained hooks       bitvec.h:356, fmindex.cpp:137-243, :53-60
-//   k_prep        read clean-up + reverse complement + match bit-strings
+//   k_prep        read clean-up + reverse complement + match bit-strings, read records and match words of the full reads
 //                                                       src/reads.h:43-58, nucleotide.h:250,
 //                                                       bitparallelmatrix.cpp:34-75
 //   k_parts / k_exact   partitioning, scheme selection, exact phases   dev_partition.hpp
@@ -174,30 +174,104 @@ __device__ __forceinline__ uint4 loadText16(const uint8_t* p) {
     return make_uint4(v.x, v.y, v.z, v.w);
 }
 // ------------------------------------------------------------------ read preparation
-// One thread per (read, 32-character chunk): writes the codes of both strands and the chunk's word of
-// the eight match bit-strings of both strands (forward / reversed read x A,C,G,T).  G must be zeroed
-// beforehand (padding words stay zero).  Both strands need the same two byte runs of the read:
+// Everything the later kernels read of a read, in one pass and with nothing zeroed beforehand: the codes of both strands (seq), the
+// eight match bit-strings (G: forward / reversed read x A,C,G,T), the read records of both strands (rec, unless null) and the match
+// words of the full read per 32-row block (out, unless null: what k_match_words computes from G).  A block takes `perPass` reads per
+// pass, perPass * chunks <= 256, and loops over the passes beyond the grid.  Per pass: one thread per (read, 32-character chunk)
+// writes the codes and puts the chunk's word of the eight strings into the LDS copy of the pass's stretch of G (zeroed before, so
+// that the padding words and the words behind a short read are zeros); then the whole block writes G, rec and the match words
+// from that copy with 16-byte stores that are contiguous over the reads of the pass.  Both strands need the same two byte runs:
 //   A = read[32w .. 32w+32)   and   B = read[L-1-32w-t], t = 0..31
+__device__ __forceinline__ void prepChunk(const uint8_t* __restrict__ rd, uint64_t off, uint32_t len, uint32_t w, uint32_t maxLen,
+                                          uint8_t* __restrict__ sF, uint8_t* __restrict__ sR, uint32_t fA[4], uint32_t fB[4]);
+constexpr uint32_t prepLdsWords(uint32_t perPass, uint32_t gw) { return perPass * 8u * gw + 3u * perPass; }
 __global__ void __launch_bounds__(256)
 k_prep(const uint8_t* __restrict__ reads, const uint64_t* __restrict__ offs, uint32_t nReads, uint32_t maxLen,
-       uint32_t gw, uint32_t chunks, uint8_t* __restrict__ seq, uint32_t* __restrict__ G, uint32_t* __restrict__ rec,
-       uint32_t recW) {
-    const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t r = gid / chunks, w = gid % chunks;
-    if (r >= nReads) return;
-    const uint8_t* rd = reads + offs[r];
-    const uint32_t len = (uint32_t)(offs[r + 1] - offs[r]);
-    if (len > maxLen) return;
-    if (32 * w >= len) {
-        if (w == 0 && rec) { // empty read: header only (rec is zeroed beforehand)
-            rec[(size_t)(2 * r) * recW] = 0;
-            rec[(size_t)(2 * r + 1) * recW] = 0;
+       uint32_t gw, uint32_t chunks, uint32_t perPass, uint8_t* __restrict__ seq, uint32_t* __restrict__ G,
+       uint32_t* __restrict__ rec, uint32_t recW, uint4* __restrict__ out, uint32_t nBlk) {
+    extern __shared__ uint4 prepLds[];
+    uint32_t* sG = reinterpret_cast<uint32_t*>(prepLds); // [read of the pass][string][gw]: the layout of G
+    uint32_t* sHdr = sG + perPass * 8u * gw;             // [read of the pass][strand]: hasN << 16
+    uint32_t* sLen = sHdr + 2u * perPass;                // [read of the pass]: its length (0: longer than maxLen, treated as empty)
+    const uint32_t tid = threadIdx.x;
+    const uint32_t gq = 2u * gw; // uint4 per read of G
+    for (uint64_t r0 = (uint64_t)blockIdx.x * perPass; r0 < nReads; r0 += (uint64_t)gridDim.x * perPass) {
+        const uint32_t nR = (uint32_t)min((uint64_t)perPass, (uint64_t)nReads - r0);
+        for (uint32_t i = tid; i < nR * gq; i += 256u) prepLds[i] = make_uint4(0, 0, 0, 0);
+        for (uint32_t i = tid; i < 2u * nR; i += 256u) sHdr[i] = 0;
+        __syncthreads();
+        if (tid < nR * chunks) {
+            const uint32_t lr = tid / chunks, w = tid % chunks;
+            const uint64_t r = r0 + lr;
+            const uint64_t off = offs[r];
+            uint32_t len = (uint32_t)(offs[r + 1] - off);
+            if (len > maxLen) len = 0;
+            if (w == 0) sLen[lr] = len;
+            if (32u * w < len) {
+                uint32_t fA[4], fB[4]; // bit t set: A[t] / B[t] is that nucleotide
+                prepChunk(reads + off, off, len, w, maxLen, seq + (size_t)(2 * r) * maxLen, seq + (size_t)(2 * r + 1) * maxLen, fA, fB);
+                // Eight bit-strings per READ: [0..3] the read's A,C,G,T bits, [4..7] those of the reversed read.  The
+                // reverse-complement strand needs no strings of its own (gString): its position i is comp(read[L-1-i]), i.e.
+                // string 4 + (3 - ch), and its reversed sequence is comp(read[ri]), i.e. string 3 - ch.
+                uint32_t* gF = sG + (size_t)lr * 8u * gw;
+#pragma unroll
+                for (int ch = 0; ch < 4; ch++) {
+                    gF[ch * gw + w] = fA[ch];       // position i : read[i]
+                    gF[(4 + ch) * gw + w] = fB[ch]; // position ri: read[L-1-ri]
+                }
+                const uint32_t nT = min(32u, len - 32u * w);
+                const uint32_t valid = nT >= 32 ? 0xFFFFFFFFu : ((1u << nT) - 1u);
+                if (valid & ~(fA[0] | fA[1] | fA[2] | fA[3])) atomicOr(&sHdr[2u * lr], 0x10000u);
+                if (valid & ~(fB[0] | fB[1] | fB[2] | fB[3])) atomicOr(&sHdr[2u * lr + 1u], 0x10000u);
+            }
         }
-        return;
+        __syncthreads();
+        {
+            uint4* dG = reinterpret_cast<uint4*>(G + (size_t)r0 * 8u * gw);
+            for (uint32_t i = tid; i < nR * gq; i += 256u) dG[i] = prepLds[i];
+        }
+        if (rec) {
+            // read record for k_partition: word 0 = len | hasN << 16, then per 32 characters the low / high bit of
+            // (code - 1): A=00 C=01 G=10 T=11; strand R position i is comp(read[L-1-i]); zeros behind the last chunk
+            const uint32_t rq = recW / 4u; // uint4 per record
+            uint4* dR = reinterpret_cast<uint4*>(rec + (size_t)(2 * r0) * recW);
+            for (uint32_t i = tid; i < 2u * nR * rq; i += 256u) {
+                const uint32_t ls = i / rq, j0 = (i % rq) * 4u; // read x strand of the pass, first word of the four
+                const uint32_t* g = sG + (size_t)(ls >> 1) * 8u * gw + ((ls & 1u) ? 4u * gw : 0u);
+                const uint32_t sLo = (ls & 1u) ? 2u : 1u, sHi = (ls & 1u) ? 1u : 2u, sBoth = (ls & 1u) ? 0u : 3u;
+                uint32_t v[4];
+#pragma unroll
+                for (uint32_t j = 0; j < 4; j++) {
+                    const uint32_t x = j0 + j;
+                    if (x == 0) v[j] = sLen[ls >> 1] | sHdr[ls];
+                    else if (x <= 2u * chunks) {
+                        const uint32_t w = (x - 1u) >> 1;
+                        v[j] = g[(((x - 1u) & 1u) ? sHi : sLo) * gw + w] | g[sBoth * gw + w];
+                    } else v[j] = 0;
+                }
+                dR[i] = make_uint4(v[0], v[1], v[2], v[3]);
+            }
+        }
+        if (out) { // (k_match_words, from the LDS copy of the strings)
+            uint4* dM = out + (size_t)(2 * r0) * nBlk * 2u;
+            for (uint32_t i = tid; i < 2u * nR * nBlk; i += 256u) {
+                const uint32_t ls = i / nBlk, b = i % nBlk;
+                const uint32_t len = sLen[ls >> 1];
+                uint64_t m[4];
+#pragma unroll
+                for (int ch = 0; ch < 4; ch++) m[ch] = matchWord<MXF_LEFT>(gString(sG, gw, ls, 0u, (uint32_t)ch), 0, len, b);
+                dM[2u * i] = make_uint4((uint32_t)m[0], (uint32_t)(m[0] >> 32), (uint32_t)m[1], (uint32_t)(m[1] >> 32));
+                dM[2u * i + 1u] = make_uint4((uint32_t)m[2], (uint32_t)(m[2] >> 32), (uint32_t)m[3], (uint32_t)(m[3] >> 32));
+            }
+        }
+        __syncthreads(); // (the next pass zeroes the copy)
     }
-    uint32_t fA[4] = {0, 0, 0, 0}, fB[4] = {0, 0, 0, 0}; // bit t set: A[t] / B[t] is that nucleotide
-    uint8_t* sF = seq + (size_t)(2 * r) * maxLen;
-    uint8_t* sR = seq + (size_t)(2 * r + 1) * maxLen;
+}
+// the codes of chunk w of both strands into their rows (sF, sR); fA / fB: the chunk's word of the strings of A and B
+__device__ __forceinline__ void prepChunk(const uint8_t* __restrict__ rd, uint64_t off, uint32_t len, uint32_t w, uint32_t maxLen,
+                                          uint8_t* __restrict__ sF, uint8_t* __restrict__ sR, uint32_t fA[4], uint32_t fB[4]) {
+#pragma unroll
+    for (int ch = 0; ch < 4; ch++) fA[ch] = fB[ch] = 0;
     const uint32_t nT = min(32u, len - 32 * w);
     // the 32 codes of both strands are collected in registers and written as two 16-byte stores each (maxLen
     // is a multiple of 16): single-byte stores cost a partial-line write each
@@ -211,7 +285,7 @@ k_prep(const uint8_t* __restrict__ reads, const uint64_t* __restrict__ offs, uin
         const uint4 x = loadText16(rd + 32 * w), y = loadText16(rd + 32 * w + 16);
         wa[0] = x.x, wa[1] = x.y, wa[2] = x.z, wa[3] = x.w, wa[4] = y.x, wa[5] = y.y, wa[6] = y.z, wa[7] = y.w;
     }
-    if (offs[r] + len >= 32ull * w + 32ull) {
+    if (off + len >= 32ull * w + 32ull) {
         const uint8_t* pb = rd + len - 32 * w - 32; // (pointer arithmetic inside the reads buffer)
         const uint4 x = loadText16(pb), y = loadText16(pb + 16);
         wb[0] = x.x, wb[1] = x.y, wb[2] = x.z, wb[3] = x.w, wb[4] = y.x, wb[5] = y.y, wb[6] = y.z, wb[7] = y.w;
@@ -245,32 +319,6 @@ k_prep(const uint8_t* __restrict__ reads, const uint64_t* __restrict__ offs, uin
             dF[1] = make_uint4(cF[4], cF[5], cF[6], cF[7]);
             dR[1] = make_uint4(cR[4], cR[5], cR[6], cR[7]);
         }
-    }
-    // Eight bit-strings per READ: [0..3] the read's A,C,G,T bits, [4..7] those of the reversed read.  The
-    // reverse-complement strand needs no strings of its own (gString): its position i is comp(read[L-1-i]), i.e.
-    // string 4 + (3 - ch), and its reversed sequence is comp(read[ri]), i.e. string 3 - ch.
-    uint32_t* gF = G + (size_t)r * 8 * gw;
-#pragma unroll
-    for (int ch = 0; ch < 4; ch++) {
-        gF[ch * gw + w] = fA[ch];       // position i : read[i]
-        gF[(4 + ch) * gw + w] = fB[ch]; // position ri: read[L-1-ri]
-    }
-    if (rec) {
-        // read record for k_partition: word 0 = len | hasN << 16 (rec zeroed beforehand, chunks OR into it),
-        // then per 32 characters the low / high bit of (code - 1): A=00 C=01 G=10 T=11
-        uint32_t* rF = rec + (size_t)(2 * r) * recW;
-        uint32_t* rR = rec + (size_t)(2 * r + 1) * recW;
-        const uint32_t valid = nT >= 32 ? 0xFFFFFFFFu : ((1u << nT) - 1u);
-        const uint32_t nA = valid & ~(fA[0] | fA[1] | fA[2] | fA[3]);
-        const uint32_t nB = valid & ~(fB[0] | fB[1] | fB[2] | fB[3]);
-        rF[1 + 2 * w] = fA[1] | fA[3];
-        rF[2 + 2 * w] = fA[2] | fA[3];
-        rR[1 + 2 * w] = fB[2] | fB[0]; // strand R position i is comp(read[L-1-i])
-        rR[2 + 2 * w] = fB[1] | fB[0];
-        const uint32_t hF = (w == 0 ? len : 0u) | (nA ? 0x10000u : 0u);
-        const uint32_t hR = (w == 0 ? len : 0u) | (nB ? 0x10000u : 0u);
-        if (hF) atomicOr(&rF[0], hF);
-        if (hR) atomicOr(&rR[0], hR);
     }
 }
 
@@ -705,7 +753,8 @@ constexpr uint32_t ML_WORDS = 5 * 256; // LDS match-word table of a 256-thread b
 
 // The match words of the FULL read (the matrix of the in-text verification has the whole read as its horizontal
 // sequence): for every read x strand and 32-row block the four 64-bit words, 32 bytes, computed once per batch
-// (k_match_words) — the verification stages, the traceback's forward pass and the trace itself fetch them with
+// (k_prep from its LDS copy of the bit-strings; k_match_words from the strings in HBM, for moveCigarsOnText) — the
+// verification stages, the traceback's forward pass and the trace itself fetch them with
 // two 16-byte loads instead of funnel-shifting twelve scattered 4-byte words of the bit-strings each time.
 struct MFull {
     const uint4* p; // [read x strand][block][2]
