@@ -57,6 +57,7 @@ EXPORTS = [
     "cmb_move_batch_timings", "cmb_move_batch_destroy", "cmb_move_attach_text", "cmb_move_text_index", "cmb_index_create_text_only", "cmb_sam_chunk", "cmb_move_batch_want_alignments",
     "cmb_move_batch_alignments", "cmb_move_batch_filter_per_strand", "cmb_move_match_best",
     "cmb_move_batch_keep_device_lists", "cmb_move_batch_sam_device", "cmb_move_match_best_device",
+    "cmb_pair_sam_device_classes", "cmb_move_pair_sam_device",
     "cmb_last_error", "cmb_version",
 ]
 
@@ -196,6 +197,15 @@ class PairDeviceStats(C.Structure):
     _fields_ = [("host_pairs", C.c_uint64), ("mapped_pairs", C.c_uint64), ("device_records", C.c_uint64)]
 
 
+PAIR_CLASS_ONE_UNMAPPED, PAIR_CLASS_DISCORDANT, PAIR_CLASS_UNPAIRED, PAIR_CLASS_OVER_LIMIT, PAIR_CLASS_ALL = 1, 2, 4, 8, 15
+PAIR_CLASS_STATS = ("host_pairs", "mapped_pairs", "device_records", "both_unmapped", "concordant", "one_unmapped", "discordant", "unpaired",
+                    "over_limit")
+
+
+class PairClassStats(C.Structure):  # cmb_pair_class_stats
+    _fields_ = [(f, C.c_uint64) for f in PAIR_CLASS_STATS]
+
+
 class PairInferred(C.Structure):
     """cmb_pair_inferred"""
     _fields_ = [("n_pairs", C.c_uint64), ("inferred", C.c_uint32), ("orientation", C.c_uint32), ("max_insert", C.c_uint32),
@@ -308,6 +318,9 @@ def lib():
         L.cmb_batch_sam_device.argtypes = [vp, C.POINTER(SamInputs), i32, i32, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
         L.cmb_pair_sam_device.argtypes = [vp, vp, C.POINTER(PairParams), C.POINTER(SamInputs), C.POINTER(SamInputs), C.POINTER(vp), C.POINTER(u64),
                                           C.POINTER(PairDeviceStats)]
+        for f in (L.cmb_pair_sam_device_classes, L.cmb_move_pair_sam_device):
+            f.argtypes = [vp, vp, C.POINTER(PairParams), C.POINTER(SamInputs), C.POINTER(SamInputs), u32, C.POINTER(vp), C.POINTER(u64),
+                          C.POINTER(PairClassStats)]
         L.cmb_sam_device_mapq.argtypes = [u32, vp]
         L.cmb_batch_filter_per_strand.argtypes = [vp, i32]
         L.cmb_trim_occurrence.argtypes = [vp, vp, u32, u32, i32, vp, vp, vp, u32, C.POINTER(u32), C.POINTER(i32)]
@@ -1330,58 +1343,77 @@ def pair_chunk_sam(index: "Index", strategy: "SearchStrategy", max_distance: int
     searchstrategy.h:753-774) — the default — instead of together (matchApproxAllMap; the view of pairSingleEndedMatchesAll).
     Occurrences that run past the end of their sequence (cmb_aln.spans) are trimmed and verified again as assignSequence ->
     findSeqName does (indexinterface.cpp:833-899: cmb_trim_occurrence) and paired with their trimmed coordinates, distance and
-    CIGAR; those for which that fails are dropped.  Returns (SAM text, number of properly or discordantly mapped pairs)."""
+    CIGAR; those for which that fails are dropped.  Returns (SAM text, number of properly or discordantly mapped pairs).
+    `index`: an Index, or a MoveIndex with its text attached (the b-move backend; occurrences are trimmed on the text beside it)."""
+    is_move = isinstance(index, MoveIndex)
+    trim_handle = index.h
+    if is_move:
+        trim_handle = C.c_void_p(lib().cmb_move_text_index(index.h))
+        if not trim_handle:
+            raise CmbError(-1, "pairs on the b-move index need the text beside it (MoveIndex.attach_text)")
     per_mate = []
     for reads in (reads1, reads2):
-        b = Batch(index, strategy, max_distance, reads=reads)
-        b.want_alignments()
-        if per_strand:
-            _chk(lib().cmb_batch_filter_per_strand(b.h, 1))
-        b.run()
-        occ, offs, _ = b.results()
-        aln, ops = b.alignments()
+        b = MoveBatch(index, strategy, max_distance, reads=reads) if is_move else Batch(index, strategy, max_distance, reads=reads)
+        try:
+            b.want_alignments()
+            if per_strand:
+                b.filter_per_strand() if is_move else _chk(lib().cmb_batch_filter_per_strand(b.h, 1))
+            b.run()
+            occ, offs, _ = b.results()
+            aln, ops = b.alignments()
+        finally:
+            b.close()
         per_mate.append((occ, offs, aln, ops))
-        b.close() if hasattr(b, "close") else None
-    starts = index.seq_starts()
     text, mapped_pairs = [], 0
     for i in range(len(reads1)):
         rd = []
         for m, (reads, ids, quals) in enumerate(((reads1, ids1, quals1), (reads2, ids2, quals2))):
-            occ, offs, aln, ops = per_mate[m]
             sid, seq, rc, rq = read_prepare(ids[i], reads[i].decode() if isinstance(reads[i], bytes) else reads[i], quals[i])
-            lst = []
-            for j in range(int(offs[i]), int(offs[i + 1])):
-                a = aln[j]
-                o = ops[int(a["cigar_off"]):int(a["cigar_off"]) + int(a["cigar_len"])]
-                width = int(occ["end"][j]) - int(occ["begin"][j])
-                if a["spans"]:
-                    oc1 = np.array([tuple(occ[j])], dtype=OCC_DTYPE)
-                    al1 = np.array([tuple(a)], dtype=ALN_DTYPE)
-                    ops1 = np.zeros(2 * max_distance + 8, np.uint16)
-                    nops, found = C.c_uint32(), C.c_int32()
-                    pat = (rc if int(occ["strand"][j]) else seq).encode()
-                    _chk(lib().cmb_trim_occurrence(index.h, pat, len(pat), max_distance, METRIC["edit"], _p(oc1), _p(al1), _p(ops1), ops1.shape[0],
-                                                   C.byref(nops), C.byref(found)))
-                    if not found.value:
-                        continue  # NOT_FOUND: the occurrence takes no part in the pairing
-                    w1 = int(oc1["end"][0]) - int(oc1["begin"][0])
-                    lst.append((int(al1["seq_id"][0]), int(al1["seq_begin"][0]), int(al1["seq_begin"][0]) + w1, int(oc1["begin"][0]),
-                                int(oc1["distance"][0]), int(oc1["strand"][0]), ops1[:nops.value].copy()))
-                else:
-                    lst.append((int(a["seq_id"]), int(a["seq_begin"]), int(a["seq_begin"]) + width, int(occ["begin"][j]),
-                                int(occ["distance"][j]), int(occ["strand"][j]), o))
-            rd.append((sid, seq, rc, quals[i], rq, lst))
+            rd.append((sid, seq, rc, quals[i], rq, _pair_list_of_read(trim_handle, max_distance, seq, rc, i, *per_mate[m])))
         t, n = pair_sam(rd[0], rd[1], seq_names, orientation, max_frag, min_frag, discordant_allowed, unmapped_records)
         text.append(t)
         mapped_pairs += n > 0
     return "".join(text), mapped_pairs
 
 
+def _pair_list_of_read(trim_handle, max_distance: int, seq: str, rc: str, i: int, occ, offs, aln, ops):
+    """the occurrences of read i of a batch's results (either backend's records) as pair_sam takes them: (seq_id, begin and end inside
+    the sequence, begin in the text, distance, strand, CIGAR runs); one over a sequence end is trimmed or dropped"""
+    lst = []
+    for j in range(int(offs[i]), int(offs[i + 1])):
+        a = aln[j]
+        o = ops[int(a["cigar_off"]):int(a["cigar_off"]) + int(a["cigar_len"])]
+        width = int(occ["end"][j]) - int(occ["begin"][j])
+        if a["spans"]:
+            oc1 = np.zeros(1, OCC_DTYPE)
+            for f in ("begin", "end", "distance", "strand"):
+                oc1[f][0] = occ[f][j]
+            al1 = np.array([tuple(a)], dtype=ALN_DTYPE)
+            ops1 = np.zeros(2 * max_distance + 8, np.uint16)
+            nops, found = C.c_uint32(), C.c_int32()
+            pat = (rc if int(occ["strand"][j]) else seq).encode()
+            _chk(lib().cmb_trim_occurrence(trim_handle, pat, len(pat), max_distance, METRIC["edit"], _p(oc1), _p(al1), _p(ops1), ops1.shape[0],
+                                           C.byref(nops), C.byref(found)))
+            if not found.value:
+                continue  # NOT_FOUND: the occurrence takes no part in the pairing
+            w1 = int(oc1["end"][0]) - int(oc1["begin"][0])
+            lst.append((int(al1["seq_id"][0]), int(al1["seq_begin"][0]), int(al1["seq_begin"][0]) + w1, int(oc1["begin"][0]),
+                        int(oc1["distance"][0]), int(oc1["strand"][0]), ops1[:nops.value].copy()))
+        else:
+            lst.append((int(a["seq_id"]), int(a["seq_begin"]), int(a["seq_begin"]) + width, int(occ["begin"][j]),
+                        int(occ["distance"][j]), int(occ["strand"][j]), o))
+    return lst
+
+
 def pair_batches_sam_device(batch1: "Batch", batch2: "Batch", ids1, ids2, quals1, quals2, seq_names, orientation: int = ORIENTATION_FR,
-                            max_frag: int = 500, min_frag: int = 0, discordant_allowed: bool = True, unmapped_records: bool = True):
+                            max_frag: int = 500, min_frag: int = 0, discordant_allowed: bool = True, unmapped_records: bool = True,
+                            classes: int = 0):
     """cmb_pair_sam_device on two batches that have run (read 1 and read 2 of every pair, with alignments, every strand filtered
     by itself): (SAM text as bytes, {"host_pairs", "mapped_pairs", "device_records"}).  ids / quals / seq_names as for
-    Batch.sam_device_bytes; quals None or an empty entry: an empty quality."""
+    Batch.sam_device_bytes; quals None or an empty entry: an empty quality.
+    classes (PAIR_CLASS_*) not 0: cmb_pair_sam_device_classes — those classes are formatted on the device as well, and the dict has the
+    nine fields of PAIR_CLASS_STATS.  Two MoveBatches (alignments, per-strand filter, kept lists): cmb_move_pair_sam_device, always
+    with the nine fields."""
     keep, inputs = [], []
     for b, ids, quals in ((batch1, ids1, quals1), (batch2, ids2, quals2)):
         bi, oi = pack_fields(ids)
@@ -1393,30 +1425,47 @@ def pair_batches_sam_device(batch1: "Batch", batch2: "Batch", ids1, ids2, quals1
         inputs.append(SamInputs(_p(b._packed[0]), _p(bi), _p(oi), _p(bq) if bq is not None else None, _p(oq) if oq is not None else None,
                                 _p(bn), _p(on), on.shape[0] - 1))
     prm = PairParams(orientation, max_frag, min_frag, int(discordant_allowed), int(unmapped_records))
-    text, n, st = C.c_void_p(), C.c_uint64(), PairDeviceStats()
-    _chk(lib().cmb_pair_sam_device(batch1.h, batch2.h, C.byref(prm), C.byref(inputs[0]), C.byref(inputs[1]), C.byref(text), C.byref(n), C.byref(st)))
+    text, n = C.c_void_p(), C.c_uint64()
+    is_move = isinstance(batch1, MoveBatch)
+    if is_move or classes:
+        st = PairClassStats()
+        entry = lib().cmb_move_pair_sam_device if is_move else lib().cmb_pair_sam_device_classes
+        _chk(entry(batch1.h, batch2.h, C.byref(prm), C.byref(inputs[0]), C.byref(inputs[1]), int(classes), C.byref(text), C.byref(n), C.byref(st)))
+        fields = PAIR_CLASS_STATS
+    else:
+        st = PairDeviceStats()
+        _chk(lib().cmb_pair_sam_device(batch1.h, batch2.h, C.byref(prm), C.byref(inputs[0]), C.byref(inputs[1]), C.byref(text), C.byref(n), C.byref(st)))
+        fields = PAIR_CLASS_STATS[:3]
     out = C.string_at(text.value, n.value) if n.value else b""
-    return out, {"host_pairs": int(st.host_pairs), "mapped_pairs": int(st.mapped_pairs), "device_records": int(st.device_records)}
+    return out, {f: int(getattr(st, f)) for f in fields}
 
 
 def pair_chunk_sam_device(index: "Index", strategy: "SearchStrategy", max_distance: int, reads1, reads2, ids1, ids2, quals1, quals2, seq_names,
                           orientation: int = ORIENTATION_FR, max_frag: int = 500, min_frag: int = 0, discordant_allowed: bool = True,
-                          unmapped_records: bool = True):
+                          unmapped_records: bool = True, classes: int = 0):
     """pair_chunk_sam(..., per_strand=True) with the pairing and the records on the device (cmb_pair_sam_device): both mates through
     the GPU matcher (one batch each, with alignments, every strand filtered by itself), their lists stay in HBM, the concordant and
     the both-unmapped pairs are written there and the others go through cmb_pair_sam on the host.  quals1 / quals2: one quality
     per read (an empty one prints as pair_chunk_sam prints it), or None for no qualities.  Returns (SAM text, number of properly or
-    discordantly mapped pairs, {"host_pairs", "mapped_pairs", "device_records"})."""
+    discordantly mapped pairs, {"host_pairs", "mapped_pairs", "device_records"}).  classes (PAIR_CLASS_*) and a MoveIndex with its
+    text attached: as for pair_batches_sam_device."""
     batches = []
     try:
         for reads in (reads1, reads2):
-            b = Batch(index, strategy, max_distance, reads=reads)
-            batches.append(b)
-            b.want_alignments()
-            _chk(lib().cmb_batch_filter_per_strand(b.h, 1))
+            if isinstance(index, MoveIndex):
+                b = MoveBatch(index, strategy, max_distance, reads=reads)
+                batches.append(b)
+                b.want_alignments()
+                b.filter_per_strand()
+                b.keep_device_lists()
+            else:
+                b = Batch(index, strategy, max_distance, reads=reads)
+                batches.append(b)
+                b.want_alignments()
+                _chk(lib().cmb_batch_filter_per_strand(b.h, 1))
             b.run()
         text, stats = pair_batches_sam_device(batches[0], batches[1], ids1, ids2, quals1, quals2, seq_names, orientation, max_frag, min_frag,
-                                              discordant_allowed, unmapped_records)
+                                              discordant_allowed, unmapped_records, classes)
         return text.decode(), stats["mapped_pairs"], stats
     finally:
         for b in batches:

@@ -235,11 +235,13 @@ struct SamPlan { // per read (32 bytes; dev_sam.hpp)
     uint32_t primary; // index of the primary among the read's occurrences
     uint32_t minScore, nHits;
     uint32_t idLen; // cleaned identifier: raw[1, idLen + 1)
-    uint32_t pad;
+    uint32_t cls;   // read pairs: the pair's PAIR_CLS_* (dev_pair.hpp; k_pair_class_write reads it); 0 for single reads
     uint64_t sideOff; // SAM_HOST: where the read's text lies in the side buffer
 };
 // per read pair with a concordant combination (dev_pair.hpp).  A candidate pair is (combination of the orientation, index in the up
-// list, index in the down list): the primary — the first pair of minimal summed distance — and the first pair, which changes places with it
+// list, index in the down list): the primary — the first pair of minimal summed distance — and the first pair, which changes places with it.
+// A discordant pair has one combination, (read 1's list, read 2's list); a pair with one mate unmapped has primU (the primary among the
+// mapped mate's occurrences), minDist and nPairs alone
 struct PairPlan {
     uint32_t primCombo, primU, primD;
     uint32_t firstCombo, firstU, firstD;
@@ -257,7 +259,9 @@ struct SamDeviceBufs {
 };
 // ... and what a (sub-)batch of either backend owns for the SAM and pair drivers: the driver's buffers; the reads (pairs) the plan kernel
 // leaves to the host ([0]: how many); in the first part, the finished text of the whole batch; in a part with read 1 of every pair, the
-// plan of the concordant pairs, per pair the SAM lines the device writes and whether it counts as mapped, and the 64-bit scan of either
+// plan of the concordant pairs, per pair the SAM lines the device writes and whether it counts as mapped, and the 64-bit scan of either;
+// for the pairs k_pair_class_write formats into the side buffer (cmb_pair_sam_device_classes): their list ([0]: how many), their byte
+// lengths (0 for every other pair) with the scan of those, and the number of pairs per device class
 struct SamBufs {
     SamDeviceBufs sam;
     DevBuf<uint32_t> hostList;
@@ -265,6 +269,8 @@ struct SamBufs {
     DevBuf<PairPlan> pairPlan;
     DevBuf<uint64_t> pairRecords, pairSums;
     DevBuf<uint32_t> pairMapped;
+    DevBuf<uint32_t> clsList, clsCount;
+    DevBuf<uint64_t> clsLen, clsOffs;
 };
 // The final lists a (sub-)batch of either backend holds in HBM for its whole chunk, as the SAM driver and the strata bookkeeping read
 // them (dev_sam.hpp: SamCtx; dev_best.hpp: k_best_scan / k_best_append), beside the host copies the host-formatted reads are taken

@@ -5,6 +5,7 @@
 #include "dev_sam.hpp"
 #include "dev_pair.hpp"
 
+#include <array>
 #include <chrono>
 
 using namespace cmb;
@@ -253,14 +254,15 @@ static int samUpload(SamDeviceBufs& d, const cmb_sam_inputs* in, uint64_t r0, ui
 }
 // 2. The reads of `list` (ascending) are formatted on the host — format(i, text) appends the records of read i — and spliced in: their
 //    text goes up and k_sam_override puts their lengths over the plan's.  The stream must have been waited for if `list` came from it.
-template <class F> static void samSplice(SamDeviceBufs& d, const std::vector<uint32_t>& list, hipStream_t s, F format) {
+//    -> the bytes of the host's text; roomBehind: bytes the side buffer must hold behind them (the pairs of k_pair_class_write)
+template <class F> static uint64_t samSplice(SamDeviceBufs& d, const std::vector<uint32_t>& list, hipStream_t s, F format, uint64_t roomBehind = 0) {
     std::string side;
     std::vector<uint64_t> sideOffs(list.size() + 1, 0);
     for (size_t q = 0; q < list.size(); q++) {
         format(list[q], side);
         sideOffs[q + 1] = side.size();
     }
-    growTo(d.side, side.size());
+    growTo(d.side, side.size() + roomBehind);
     growTo(d.sideOffs, sideOffs.size());
     growTo(d.sideReads, list.size());
     if (!side.empty()) HIPCHK(hipMemcpy(d.side.p, side.data(), side.size(), hipMemcpyHostToDevice));
@@ -269,6 +271,7 @@ template <class F> static void samSplice(SamDeviceBufs& d, const std::vector<uin
     hipLaunchKernelGGL(k_sam_override, dim3(((uint32_t)list.size() + 255u) / 256u), dim3(256), 0, s, d.sideReads.p, d.sideOffs.p, (uint32_t)list.size(),
                        d.plan.p, d.len.p);
     HIPCHK(hipGetLastError());
+    return side.size();
 }
 // 3. The position of every read in the text; *total (the text's length) is valid once the stream has been waited for ...
 static void samScan(SamDeviceBufs& d, DevBuf<uint8_t>& scanTmp, uint32_t n, uint64_t* total, hipStream_t s) {
@@ -441,17 +444,20 @@ void pairHostRead(PairHostRead& h, const ListView& c, uint32_t i, const cmb_sam_
                                     o.occ.strand, o.ops.data(), (uint32_t)o.ops.size()});
     }
 }
-} // namespace
-
-extern "C" int cmb_pair_sam_device(cmb_batch* mates1, cmb_batch* mates2, const cmb_pair_params* params, const cmb_sam_inputs* in1,
-                                   const cmb_sam_inputs* in2, const char** text, uint64_t* length, cmb_pair_device_stats* stats) {
+// the argument checks of the pair drivers that need no batch
+int pairArgsCheck(const void* mates1, const void* mates2, const cmb_pair_params* params, const cmb_sam_inputs* in1, const cmb_sam_inputs* in2,
+                  uint32_t classes, const char** text, uint64_t* length) {
     if (!mates1 || !mates2 || !params || !text || !length || !samInputsOk(in1) || !samInputsOk(in2)) return failWith(CMB_ERR_INVALID, "null argument");
     if (mates1 == mates2) return failWith(CMB_ERR_INVALID, "the two mates need a batch each");
     if (params->orientation > 2) return failWith(CMB_ERR_INVALID, "orientation must be one of CMB_ORIENTATION_*");
-    try {
-        std::vector<ListView> subs1, subs2; // (sub-batch j of the two batches)
-        if (int rc = batchListViews(mates1, true, subs1)) return rc;
-        if (int rc = batchListViews(mates2, true, subs2)) return rc;
+    if (classes > CMB_PAIR_CLASS_ALL) return failWith(CMB_ERR_INVALID, "classes must be a combination of CMB_PAIR_CLASS_*");
+    return CMB_OK;
+}
+// The driver over the parts of the two mates' batches, whichever backend matched them (subs1 / subs2: sub-batch j of the two).  classes:
+// the CMB_PAIR_CLASS_* that k_pair_class_write formats; the pairs of the others go to the host
+int pairDeviceOver(const std::vector<ListView>& subs1, const std::vector<ListView>& subs2, const cmb_pair_params* params, const cmb_sam_inputs* in1,
+                   const cmb_sam_inputs* in2, uint32_t classes, const char** text, uint64_t* length, cmb_pair_class_stats* stats) {
+    {
         if (subs1[0].textIndex != subs2[0].textIndex || subs1[0].k != subs2[0].k || subs1[0].metric != subs2[0].metric)
             return failWith(CMB_ERR_INVALID, "the mates' batches differ in index, metric or maximal distance");
         uint64_t total1 = 0, total2 = 0;
@@ -466,7 +472,8 @@ extern "C" int cmb_pair_sam_device(cmb_batch* mates1, cmb_batch* mates2, const c
         useDeviceOf(subs1[0].textIndex);
         const cmb_sam_inputs* in[2] = {in1, in2};
         std::vector<uint64_t> readBase(P + 1, 0), charBase1(P + 1, 0), charBase2(P + 1, 0), partBytes(P, 0), partRecords(P, 0), partMapped(P, 0);
-        std::vector<uint32_t> nHost(P, 0);
+        std::vector<uint32_t> nHost(P, 0), nCls(P, 0);
+        std::vector<std::array<uint32_t, PAIR_CLS_COUNTERS>> clsCount(P);
         std::vector<PairCtx> ctx(P);
         for (size_t j = 0; j < P; j++) {
             const uint32_t n = subs1[j].nReads;
@@ -495,15 +502,25 @@ extern "C" int cmb_pair_sam_device(cmb_batch* mates1, cmb_batch* mates2, const c
             HIPCHK(hipMemsetAsync(B.hostList.p, 0, sizeof(uint32_t), s));
             HIPCHK(hipMemsetAsync(B.pairRecords.p + n, 0, sizeof(uint64_t), s));
             HIPCHK(hipMemsetAsync(B.pairMapped.p + n, 0, sizeof(uint32_t), s));
+            growTo(B.clsList, (size_t)n + 1);
+            growTo(B.clsLen, (size_t)n + 1);
+            growTo(B.clsOffs, (size_t)n + 1);
+            growTo(B.clsCount, PAIR_CLS_COUNTERS);
+            HIPCHK(hipMemsetAsync(B.clsList.p, 0, sizeof(uint32_t), s));
+            HIPCHK(hipMemsetAsync(B.clsLen.p + n, 0, sizeof(uint64_t), s));
+            HIPCHK(hipMemsetAsync(B.clsCount.p, 0, PAIR_CLS_COUNTERS * sizeof(uint32_t), s));
             hipLaunchKernelGGL(k_pair_plan, dim3((n + 3u) / 4u), dim3(256), 0, s, pc, params->unmapped_records ? 1u : 0u, B.sam.plan.p,
-                               B.pairPlan.p, B.sam.len.p, B.pairRecords.p, B.pairMapped.p, B.hostList.p);
+                               B.pairPlan.p, B.sam.len.p, B.pairRecords.p, B.pairMapped.p, B.hostList.p, classes,
+                               params->discordant_allowed ? 1u : 0u, B.clsList.p, B.clsLen.p, B.clsCount.p);
             HIPCHK(hipGetLastError());
             HIPCHK(hipMemcpyAsync(&nHost[j], B.hostList.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(&nCls[j], B.clsList.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(clsCount[j].data(), B.clsCount.p, PAIR_CLS_COUNTERS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         }
         // ---- the pairs the host formats, then the position of every pair in its sub-batch's text
         std::vector<std::string> names;
         std::vector<const char*> namePtrs;
-        uint64_t nHostAll = 0, hostMapped = 0;
+        uint64_t nHostAll = 0, hostMapped = 0, clsAll[PAIR_CLS_COUNTERS] = {};
         for (size_t j = 0; j < P; j++) {
             const ListView* c[2] = {&subs1[j], &subs2[j]};
             const uint32_t n = c[0]->nReads;
@@ -511,6 +528,13 @@ extern "C" int cmb_pair_sam_device(cmb_batch* mates1, cmb_batch* mates2, const c
             hipStream_t s = c[0]->stream;
             SamBufs& B = *c[0]->bufs;
             HIPCHK(hipStreamSynchronize(s));
+            uint64_t clsBytes = 0, hostBytes = 0; // the side buffer: the host's text, then the text of k_pair_class_write's pairs
+            if (nCls[j]) {
+                scanExclusive(*c[0]->scanTmp, B.clsLen.p, B.clsOffs.p, (size_t)n + 1, s);
+                HIPCHK(hipMemcpyAsync(&clsBytes, B.clsOffs.p + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+                HIPCHK(hipStreamSynchronize(s));
+                if (!nHost[j]) growTo(B.sam.side, (size_t)clsBytes + 16);
+            }
             if (nHost[j]) {
                 if (names.empty()) {
                     names = samNamesOf(in1);
@@ -521,7 +545,7 @@ extern "C" int cmb_pair_sam_device(cmb_batch* mates1, cmb_batch* mates2, const c
                 std::sort(list.begin(), list.end());
                 PairHostRead h[2];
                 std::vector<char> buf;
-                samSplice(B.sam, list, s, [&](uint32_t i, std::string& side) {
+                hostBytes = samSplice(B.sam, list, s, [&](uint32_t i, std::string& side) {
                     pairHostRead(h[0], *c[0], i, in1, readBase[j] + i, charBase1[j]);
                     pairHostRead(h[1], *c[1], i, in2, readBase[j] + i, charBase2[j]);
                     const cmb_pair_read r1 = h[0].view(), r2 = h[1].view();
@@ -532,9 +556,15 @@ extern "C" int cmb_pair_sam_device(cmb_batch* mates1, cmb_batch* mates2, const c
                     cmb_pair_sam(params, &r1, &r2, namePtrs.data(), buf.data(), (uint64_t)len + 1, &nPairs);
                     side.append(buf.data(), (size_t)len);
                     hostMapped += nPairs > 0;
-                });
+                }, clsBytes ? clsBytes + 16 : 0);
                 nHostAll += nHost[j];
             }
+            if (nCls[j]) {
+                hipLaunchKernelGGL(k_pair_class_write, dim3(nCls[j]), dim3(64), 0, s, ctx[j], B.sam.plan.p, B.pairPlan.p, B.clsList.p, B.clsOffs.p,
+                                   hostBytes, B.sam.side.p);
+                HIPCHK(hipGetLastError());
+            }
+            for (uint32_t q = 0; q < PAIR_CLS_COUNTERS; q++) clsAll[q] += clsCount[j][q];
             samScan(B.sam, *c[0]->scanTmp, n, &partBytes[j], s);
             // the records the device writes and the pairs it maps: a 64-bit sum each, through the same scan buffer one after the other
             scanExclusive(*c[0]->scanTmp, B.pairRecords.p, B.pairSums.p, (size_t)n + 1, s);
@@ -571,15 +601,62 @@ extern "C" int cmb_pair_sam_device(cmb_batch* mates1, cmb_batch* mates2, const c
         *text = samOut.p;
         *length = total;
         if (getenv("CMB_VERBOSE"))
-            fprintf(stderr, "[host] pair sam: %llu pairs, %llu of them formatted on the host, %llu records from the device\n",
-                    (unsigned long long)readBase[P], (unsigned long long)nHostAll,
-                    (unsigned long long)deviceRecords);
+            fprintf(stderr,
+                    "[host] pair sam: %llu pairs, %llu of them formatted on the host, %llu records from the device; device pairs: %llu both "
+                    "unmapped, %llu concordant, %llu one unmapped, %llu discordant, %llu unpaired, %llu over the limit (classes %u)\n",
+                    (unsigned long long)readBase[P], (unsigned long long)nHostAll, (unsigned long long)deviceRecords,
+                    (unsigned long long)clsAll[PAIR_CLS_BOTH_UNMAPPED], (unsigned long long)clsAll[PAIR_CLS_CONCORDANT],
+                    (unsigned long long)clsAll[PAIR_CLS_ONE_UNMAPPED], (unsigned long long)clsAll[PAIR_CLS_DISCORDANT],
+                    (unsigned long long)clsAll[PAIR_CLS_UNPAIRED], (unsigned long long)clsAll[PAIR_CLS_OVER_LIMIT], classes);
         if (stats) {
             stats->host_pairs = nHostAll;
             stats->mapped_pairs = hostMapped + deviceMapped;
             stats->device_records = deviceRecords;
+            stats->both_unmapped = clsAll[PAIR_CLS_BOTH_UNMAPPED], stats->concordant = clsAll[PAIR_CLS_CONCORDANT];
+            stats->one_unmapped = clsAll[PAIR_CLS_ONE_UNMAPPED], stats->discordant = clsAll[PAIR_CLS_DISCORDANT];
+            stats->unpaired = clsAll[PAIR_CLS_UNPAIRED], stats->over_limit = clsAll[PAIR_CLS_OVER_LIMIT];
         }
         return CMB_OK;
+    }
+}
+} // namespace
+
+extern "C" int cmb_pair_sam_device_classes(cmb_batch* mates1, cmb_batch* mates2, const cmb_pair_params* params, const cmb_sam_inputs* in1,
+                                           const cmb_sam_inputs* in2, uint32_t classes, const char** text, uint64_t* length,
+                                           cmb_pair_class_stats* stats) {
+    if (int rc = pairArgsCheck(mates1, mates2, params, in1, in2, classes, text, length)) return rc;
+    try {
+        std::vector<ListView> subs1, subs2; // (sub-batch j of the two batches)
+        if (int rc = batchListViews(mates1, true, subs1)) return rc;
+        if (int rc = batchListViews(mates2, true, subs2)) return rc;
+        return pairDeviceOver(subs1, subs2, params, in1, in2, classes, text, length, stats);
+    } catch (const std::exception& e) {
+        return failWith(CMB_ERR_DEVICE, e.what());
+    }
+}
+extern "C" int cmb_pair_sam_device(cmb_batch* mates1, cmb_batch* mates2, const cmb_pair_params* params, const cmb_sam_inputs* in1,
+                                   const cmb_sam_inputs* in2, const char** text, uint64_t* length, cmb_pair_device_stats* stats) {
+    cmb_pair_class_stats cs{};
+    const int rc = cmb_pair_sam_device_classes(mates1, mates2, params, in1, in2, 0u, text, length, &cs);
+    if (rc == CMB_OK && stats) stats->host_pairs = cs.host_pairs, stats->mapped_pairs = cs.mapped_pairs, stats->device_records = cs.device_records;
+    return rc;
+}
+// the same on two b-move batches whose final lists stayed in HBM, every strand filtered by itself, on an index with its text beside it
+extern "C" int cmb_move_pair_sam_device(cmb_move_batch* mates1, cmb_move_batch* mates2, const cmb_pair_params* params, const cmb_sam_inputs* in1,
+                                        const cmb_sam_inputs* in2, uint32_t classes, const char** text, uint64_t* length,
+                                        cmb_pair_class_stats* stats) {
+    if (int rc = pairArgsCheck(mates1, mates2, params, in1, in2, classes, text, length)) return rc;
+    try {
+        std::vector<ListView> subs1, subs2;
+        if (int rc = moveBatchListViews(mates1, subs1)) return rc;
+        if (int rc = moveBatchListViews(mates2, subs2)) return rc;
+        for (const std::vector<ListView>* subs : {&subs1, &subs2})
+            for (const ListView& v : *subs) {
+                if (!v.textIndex) return failWith(CMB_ERR_INVALID, "the batch's index has no text beside it (cmb_move_attach_text)");
+                if (v.groupStride != 2u)
+                    return failWith(CMB_ERR_INVALID, "the strands were not filtered each by itself (cmb_move_batch_filter_per_strand)");
+            }
+        return pairDeviceOver(subs1, subs2, params, in1, in2, classes, text, length, stats);
     } catch (const std::exception& e) {
         return failWith(CMB_ERR_DEVICE, e.what());
     }

@@ -484,7 +484,8 @@ int cmb_batch_sam_device(cmb_batch* b, const cmb_sam_inputs* in, int unmapped_re
  * nothing without params->unmapped_records), and pairs with at least one concordant combination.  A pair with an occurrence that runs
  * over the end of its sequence or has none assigned (cmb_aln.spans != 0: IndexInterface::findSeqName trims, verifies again and may
  * drop it), or whose lists are not both empty and hold no concordant pair (discordant pairs, unpaired records, one mate unmapped), is
- * formatted by cmb_pair_sam from the batches' host copies, trimmed with cmb_trim_occurrence, and spliced in at its place.
+ * formatted by cmb_pair_sam from the batches' host copies, trimmed with cmb_trim_occurrence, and spliced in at its place
+ * (cmb_pair_sam_device_classes, below, keeps those classes on the device as well).
  * *text (page-locked, owned by mates1, *length bytes + a terminating 0) stays valid until the next cmb_batch_run, SAM call or
  * cmb_batch_destroy on either batch.  stats (may be NULL): host_pairs = the pairs formatted through cmb_pair_sam; mapped_pairs = the
  * pairs whose n_pairs_out is not 0; device_records = the SAM lines the device wrote. */
@@ -493,6 +494,34 @@ typedef struct {
 } cmb_pair_device_stats;
 int cmb_pair_sam_device(cmb_batch* mates1, cmb_batch* mates2, const cmb_pair_params* params, const cmb_sam_inputs* in1,
                         const cmb_sam_inputs* in2, const char** text, uint64_t* length, cmb_pair_device_stats* stats /* may be NULL */);
+/* The same call with more of the pairing on the device (cmb_pair_sam_device is this call with classes == 0).  `classes` selects which of
+ * the remaining classes of cmb_pair_sam's pairDiscordantly the device formats as well; a pair of a class that is not selected goes to
+ * the host as before, and so does, whatever is selected, every pair with an occurrence that has cmb_aln.spans != 0 or no sequence: with
+ * CMB_PAIR_CLASS_ALL only those pairs reach cmb_pair_sam.  Bits above CMB_PAIR_CLASS_ALL are CMB_ERR_INVALID; all argument checks of
+ * cmb_pair_sam_device apply, before any work.  The text is the same bytes for every value of `classes`.
+ *   ONE_UNMAPPED  exactly one mate has occurrences: the record of its first occurrence of minimal distance (flags 1 | 8 | 16 x strand
+ *                 | 64 / 128, RNEXT *, PNEXT 0, TLEN 0), ONE record of the unmapped mate (1 | 4 | 32 x the primary's strand | 64 / 128),
+ *                 then the other occurrences as secondary records; n + 1 records, the pair does not count as mapped
+ *   DISCORDANT    both mates have occurrences, no concordant combination, params->discordant_allowed, at most 10 000 combinations: the
+ *                 full cross product, read 1's list times read 2's, the record of the occurrence that begins first inside its sequence
+ *                 (read 2's on a tie) before its mate's; 2 n1 n2 records, the pair counts as mapped
+ *   UNPAIRED      the same without params->discordant_allowed: read 1's occurrences, then read 2's, each list stably sorted by
+ *                 distance, as cmb_sam_unpaired writes them; n1 + n2 records, not mapped
+ *   OVER_LIMIT    more than 10 000 combinations: the two records of a pair without any occurrence, or nothing
+ * stats: the three fields of cmb_pair_device_stats, then the number of pairs per class the DEVICE formatted; those six and host_pairs
+ * add up to the number of pairs. */
+#define CMB_PAIR_CLASS_ONE_UNMAPPED 1u /* addOneUnmapped */
+#define CMB_PAIR_CLASS_DISCORDANT 2u   /* addDiscPairs, at most 10 000 combinations */
+#define CMB_PAIR_CLASS_UNPAIRED 4u     /* addUnpairedMatches (discordant pairs not allowed) */
+#define CMB_PAIR_CLASS_OVER_LIMIT 8u   /* more than 10 000 combinations */
+#define CMB_PAIR_CLASS_ALL 15u
+typedef struct {
+    uint64_t host_pairs, mapped_pairs, device_records;                                  /* as cmb_pair_device_stats */
+    uint64_t both_unmapped, concordant, one_unmapped, discordant, unpaired, over_limit; /* pairs per device class */
+} cmb_pair_class_stats;
+int cmb_pair_sam_device_classes(cmb_batch* mates1, cmb_batch* mates2, const cmb_pair_params* params, const cmb_sam_inputs* in1,
+                                const cmb_sam_inputs* in2, uint32_t classes, const char** text, uint64_t* length,
+                                cmb_pair_class_stats* stats /* may be NULL */);
 /* The SAM text of a chunk matched with cmb_match_best_device, written on the device from the result's lists: byte for byte what
  * generateOutputSingleEnd + generateSE_SAM / generateSE_SAM_XATag (src/searchstrategy.cpp:1824-1902, src/searchstrategy.h:1612-1641)
  * give for BEST mode, i.e. what the host formatter (include/columba_amd_best.hpp: samOfBest) builds from cmb_best_results.  The
@@ -734,6 +763,15 @@ int cmb_move_batch_keep_device_lists(cmb_move_batch* b, int on);
  * next call on the batch.  CMB_ERR_INVALID: NULL arguments, a batch that has not run, lists that were not kept. */
 int cmb_move_batch_sam_device(cmb_move_batch* b, const cmb_sam_inputs* in, int unmapped_records, int xa_tag, const char** text,
                               uint64_t* length, uint64_t* host_reads);
+/* cmb_pair_sam_device_classes for two b-move batches (read 1 and read 2 of every pair) of one index with its text beside it
+ * (cmb_move_attach_text), both run with cmb_move_batch_want_alignments, cmb_move_batch_filter_per_strand and
+ * cmb_move_batch_keep_device_lists; anything else is CMB_ERR_INVALID with a message that names what is missing.  The b-move filter
+ * leaves a strand's occurrences in (begin, distance, width) order as the FM-index filter does, so the driver and the kernels are the
+ * same; the host's pairs are taken from the batches' host copies and trimmed on the text-only index.  Text, classes and stats as there;
+ * *text is owned by mates1. */
+int cmb_move_pair_sam_device(cmb_move_batch* mates1, cmb_move_batch* mates2, const cmb_pair_params* params, const cmb_sam_inputs* in1,
+                             const cmb_sam_inputs* in2, uint32_t classes, const char** text, uint64_t* length,
+                             cmb_pair_class_stats* stats /* may be NULL */);
 /* cmb_match_best_device on the b-move index (SearchStrategy::matchApproxBestPlusX, src/searchstrategy.cpp:623-746; checkAlignments,
  * :536-571; processSeq, :791-812; combineOccVectors, :573-620): the strata are b-move batches with kept lists, the bookkeeping is
  * cmb_match_best_device's, the trimming of the host reads is cmb_move_match_best's (checkTrimmedMatch, src/indexinterface.cpp:722-796:

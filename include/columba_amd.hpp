@@ -466,7 +466,8 @@ class SearchStrategy {
         return inf;
     }
     // samOfChunkPairedAll with the pairing and the records on the device (CMB_PAIR_DEVICE=1; the host path stays the default:
-    // DESIGN.md §4.7 has what the two cost): two batches whose lists stay in HBM, the fields packed once per mate, cmb_pair_sam_device
+    // DESIGN.md §4.7 has what the two cost): two batches whose lists stay in HBM, the fields packed once per mate,
+    // cmb_pair_sam_device_classes
     template <class Record>
     std::string samOfChunkPairedDevice(const std::vector<Record>& mates1, const std::vector<Record>& mates2, const std::vector<const char*>& seqNames,
                                        length_t maxED, uint32_t orientation, uint32_t maxFragSize, uint32_t minFragSize, bool discordantAllowed,
@@ -497,8 +498,11 @@ class SearchStrategy {
         const cmb_pair_params prm = {orientation, maxFragSize, minFragSize, discordantAllowed ? 1 : 0, unmappedRecords ? 1 : 0};
         const char* text = nullptr;
         uint64_t length = 0;
-        cmb_pair_device_stats stats{};
-        check(cmb_pair_sam_device(guard.b[0], guard.b[1], &prm, &inputs[0], &inputs[1], &text, &length, &stats));
+        // every class of pairs on the device; CMB_PAIR_DEVICE_CLASSES=<mask of CMB_PAIR_CLASS_*> overrides (0: cmb_pair_sam_device's split)
+        uint32_t classes = CMB_PAIR_CLASS_ALL;
+        if (const char* e = getenv("CMB_PAIR_DEVICE_CLASSES")) classes = (uint32_t)strtoul(e, nullptr, 0);
+        cmb_pair_class_stats stats{};
+        check(cmb_pair_sam_device_classes(guard.b[0], guard.b[1], &prm, &inputs[0], &inputs[1], classes, &text, &length, &stats));
         mappedPairs += (size_t)stats.mapped_pairs;
         return std::string(text, (size_t)length);
     }

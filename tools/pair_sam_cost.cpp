@@ -20,9 +20,9 @@ static double msSince(Clock::time_point t0) { return std::chrono::duration<doubl
 struct Strategy : NamedStrategy {
     using NamedStrategy::NamedStrategy;
     // the matching of both mates; bothAlive: the second batch is created and run while the first one lives (the device path), and
-    // *stats then gets what one cmb_pair_sam_device call on the two reports (outside the clock)
+    // *stats then gets what one cmb_pair_sam_device_classes call on the two reports (outside the clock)
     double matchMs(const std::vector<Rec>* mates[2], const std::vector<const char*>& seqNames, length_t k, const cmb_pair_params& prm, bool bothAlive,
-                   cmb_pair_device_stats* stats) {
+                   uint32_t classes, cmb_pair_class_stats* stats) {
         cmb_batch* b[2] = {nullptr, nullptr};
         std::string seqs[2];
         double ms = 0;
@@ -49,7 +49,7 @@ struct Strategy : NamedStrategy {
             }
             const char* text = nullptr;
             uint64_t length = 0;
-            const int rc = cmb_pair_sam_device(b[0], b[1], &prm, &in[0], &in[1], &text, &length, stats);
+            const int rc = cmb_pair_sam_device_classes(b[0], b[1], &prm, &in[0], &in[1], classes, &text, &length, stats);
             cmb_batch_destroy(b[0]);
             cmb_batch_destroy(b[1]);
             check(rc);
@@ -86,24 +86,30 @@ int main(int argc, char** argv) {
         const int reps = atoi(argv[8]);
         const char* e = getenv("CMB_PAIR_DEVICE");
         const bool device = e && atoi(e) != 0;
+        uint32_t classes = CMB_PAIR_CLASS_ALL; // (as samOfChunkPairedAll chooses them)
+        if (const char* c = getenv("CMB_PAIR_DEVICE_CLASSES")) classes = (uint32_t)strtoul(c, nullptr, 0);
         size_t mapped = 0, bytes = 0;
         uint64_t sum = 0;
         double totalMs = 0, matchMs = 0;
-        cmb_pair_device_stats stats{};
+        std::string each; // the cost behind the matching of every repetition, so that their spread shows
+        cmb_pair_class_stats stats{};
         for (int r = -1; r < reps; r++) { // (the first round warms up: buffers, page-locked memory)
             if (r == 0) totalMs = matchMs = 0, mapped = 0;
             const Clock::time_point t0 = Clock::now();
             const std::string text = strategy.samOfChunkPairedAll(m1, m2, namePtrs, k, prm.orientation, prm.max_frag, prm.min_frag, true, true, mapped);
-            totalMs += msSince(t0);
-            matchMs += strategy.matchMs(mates, namePtrs, k, prm, device, &stats);
+            const double callMs = msSince(t0), callMatchMs = strategy.matchMs(mates, namePtrs, k, prm, device, classes, &stats);
+            totalMs += callMs, matchMs += callMatchMs;
+            if (r >= 0) each += (each.empty() ? "" : ", ") + std::to_string((callMs - callMatchMs) * 1e6 / (double)m1.size());
             bytes = text.size();
             sum = 0;
             for (unsigned char c : text) sum = sum * 1099511628211ull + c;
         }
         const double perM = 1e6 / ((double)m1.size() * reps);
         printf("{\"path\": \"%s\", \"pairs\": %zu, \"repetitions\": %d, \"total_ms_per_1e6_pairs\": %.1f, \"match_ms_per_1e6_pairs\": %.1f, "
-               "\"after_ms_per_1e6_pairs\": %.1f, \"host_pair_share\": %.4f, \"mapped_pairs\": %zu, \"text_bytes\": %zu, \"text_hash\": \"%016llx\"}\n",
-               device ? "device" : "host", m1.size(), reps, totalMs * perM, matchMs * perM, (totalMs - matchMs) * perM,
+               "\"after_ms_per_1e6_pairs\": %.1f, \"after_ms_per_1e6_pairs_each\": [%s], \"classes\": %u, \"one_unmapped\": %llu, \"discordant\": %llu, "
+               "\"over_limit\": %llu, \"host_pair_share\": %.4f, \"mapped_pairs\": %zu, \"text_bytes\": %zu, \"text_hash\": \"%016llx\"}\n",
+               device ? "device" : "host", m1.size(), reps, totalMs * perM, matchMs * perM, (totalMs - matchMs) * perM, each.c_str(), device ? classes : 0u,
+               (unsigned long long)stats.one_unmapped, (unsigned long long)stats.discordant, (unsigned long long)stats.over_limit,
                (double)stats.host_pairs / (double)m1.size(), mapped / (size_t)reps, bytes, (unsigned long long)sum);
     } catch (const std::exception& e) {
         std::cerr << "Fatal error: " << e.what() << "\n";

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Milliseconds per 10^6 read pairs that the SAM text of an ALL-mode chunk costs behind the matching: the host path of the C++ adapter
-(samOfChunkPairedAll: lists copied, cmb_pair_sam per pair) against its device path (CMB_PAIR_DEVICE=1: cmb_pair_sam_device).
+(samOfChunkPairedAll: lists copied, cmb_pair_sam per pair) against its device path (CMB_PAIR_DEVICE=1: cmb_pair_sam_device_classes with every
+class on the device; CMB_PAIR_DEVICE_CLASSES=0 in the environment gives cmb_pair_sam_device's split).
 
 150 bp reads, k = 4, FR, true fragments of 250 - 500 bp with an edit in about half of the mates and a mate from nowhere in --junk of the
 pairs.  The reference is a synthetic text of --mbp: the repeat-rich one of the tests, or with --text human the human-like one of tools/sam_rate.py.  Every GPU step is a process of its own under a time
