@@ -652,10 +652,8 @@ static int batchCreateOne(cmb_index* idx, const cmb_strategy* st, uint32_t max_d
 constexpr uint32_t MAX_SUB_READS = 1u << 23; // reads per sub-batch (keys: kernels.hpp k_pack_keys, packVerifyKey)
 // bits of the group (the read, or read x strand when every strand is filtered by itself) in the filter keys of a
 // sub-batch: 24 in layouts 0 and 1, 22 in the wide layout 2 (dev_search.hpp: keyBits)
-static uint32_t groupBits(const cmb_batch* b) {
-    const uint32_t layout = b->metric == CMB_METRIC_HAMMING ? 1u : b->wideEdit ? 2u : 0u;
-    return 64u - keyBits(layout).group;
-}
+static uint32_t keyLayoutOf(const cmb_batch* b) { return b->metric == CMB_METRIC_HAMMING ? 1u : b->wideEdit ? 2u : 0u; }
+static uint32_t groupBits(const cmb_batch* b) { return 64u - keyBits(keyLayoutOf(b)).group; }
 
 extern "C" int cmb_batch_create(cmb_index* idx, const cmb_strategy* st, uint32_t max_distance, const char* seqs,
                                 const uint64_t* offs, uint32_t n_reads, cmb_batch** out) {
@@ -904,7 +902,7 @@ static void startStagedUpload(cmb_batch* b) {
 // 64-byte lines of the trace rows of one slot: 16 narrow (k <= TBN_MAX_ED) or 8 wide rows to a line (a group is written whole)
 static uint32_t traceLines(bool narrow, uint32_t rows) { return narrow ? (rows + 15u) / 16u + 2u : (rows + 7u) / 8u + 2u; }
 
-// k_traceback over the nTb tasks of tbq (batchRunOne, verifyDirect): the instance of the trace rows and of the text — packed or bytes;
+// k_traceback over the nTb tasks of tbq (runTraceback, verifyDirect): the instance of the trace rows and of the text — packed or bytes;
 // the wide rows read either text through one instance
 static void launchTraceback(hipStream_t s, const DevIndex& d, bool narrow, const uint64_t* offs, MFull mf, const uint4* tbq, uint32_t nTb, VPlanes vp,
                             Queues q, uint32_t rowMin) {
@@ -912,7 +910,7 @@ static void launchTraceback(hipStream_t s, const DevIndex& d, bool narrow, const
     hipLaunchKernelGGL(kTrace, dim3(vp.nSlots / 256), dim3(256), 0, s, d, offs, mf, tbq, nTb, vp, q, rowMin);
 }
 
-// The CIGAR step of batchRunOne, cmb::moveCigarsOnText and cmb_cigar_windows: CIGAR and sequence assignment of nOcc occurrences
+// The CIGAR step of a run (runCigar), cmb::moveCigarsOnText and cmb_cigar_windows: CIGAR and sequence assignment of nOcc occurrences
 // {begin, end, distance, strand} of the reads occRead (device pointers throughout).  wide: k_cigar_wide, the matrix with the wide left margin
 // (k_cigar's match words reach 9 columns right of the diagonal: beyond CIGAR_BLOCK_WORDS_MAX_ED errors), at most 64 k slots of `slab`;
 // otherwise the k_cigar instance of the trace rows (narrow or wide, for `rows` matrix rows per slot of vW) and of the text.  The caller says
@@ -951,7 +949,7 @@ static void launchCigar(cmb_index* ix, hipStream_t s, const CigarJob& j, bool wi
                        j.stride, j.aln, j.flagWord, j.gapless);
 }
 
-// k_prep over nReads reads (batchRunOne, verifyDirect, cmb_cigar_windows): the codes, the bit-strings, the read records (rec, or null) and the
+// k_prep over nReads reads (runPrep, verifyDirect, cmb_cigar_windows): the codes, the bit-strings, the read records (rec, or null) and the
 // match words of the full reads (mfull with nBlk blocks per read x strand, or null) in one launch that leaves no word of them unwritten.
 // A block takes as many reads per pass as give it a (read, chunk) pair per thread; at most 64 k blocks loop over the passes
 static void launchPrep(hipStream_t s, const uint8_t* reads, const uint64_t* offs, uint32_t nReads, uint32_t maxLen, uint32_t gw, uint8_t* seq, uint32_t* G,
@@ -966,37 +964,834 @@ static void launchPrep(hipStream_t s, const uint8_t* reads, const uint64_t* offs
                        G, rec, recW, mfull, nBlk);
 }
 
-// one level of the frontier search, as the pass loop of batchRunOne launches it
+// one level of the frontier search, as the pass loop of runFrontierEdit launches it
 template <class Geo> static void launchBfsPass(cmb_batch* b, const BfsBufs& B, uint32_t pass, const Queues& q) {
     hipLaunchKernelGGL(k_bfs_pass<Geo>, dim3(B.gridX + B.gridEv), dim3(256), 0, b->stream, b->ix->d, stratOf<Geo::MP>(b), B, pass, b->offs.p, b->gw, b->G.p,
                        partsOf<Geo::MP>(b), q);
 }
 
+// ---- one run of a batch: batchRunOne below calls these stages in the order of DESIGN.md §1 ----------------------------------------
+namespace {
+// What the stages of a run share (values only); whatever a single stage needs is a local of that stage
+struct RunCtx {
+    cmb_batch* b;
+    hipStream_t s;
+    Timer& tm;
+    Queues q{};
+    MFull mf{nullptr, 0}; // the match words of the full reads (runPrep)
+    // the last read-back of b->cnt (readCounts): [0] items, [1] in-index occurrences, [2] text occurrences, [3] the FLAG_* bits,
+    // [4] searches with further exact phases, [5] search tasks, [7] traceback tasks
+    uint32_t hcnt[8] = {};
+    // (the environment is read per run, not per process: tests set it between runs)
+    const char* verboseEnv = nullptr;
+    bool verbose = false, smallPools = false;
+    // 11 ... 13 errors: the in-index matrix with 16-row blocks (GeoX, beyond the reference's 64-bit in-index matrix: dev_matrix.hpp, MXN_*),
+    // the in-text matrix with 8-row blocks
+    bool geoX = false;
+    bool preset = false; // no search: the candidates come from the caller (cmb_verify_batch_staged)
+    uint32_t nItems = 0, nFm = 0, nFmUniq = 0, nText = 0;
+    uint64_t naiveSurvivors = 0;
+    std::chrono::steady_clock::time_point t0; // where the last line of lap() ended
+};
+// How a stage of the search ends when it does not fail: the search goes on, or the attempt runs again — the stage has grown what was too
+// small, or changed the geometry; the loop of batchRunOne counts the attempts and holds their limits
+enum class Step { GoOn, AgainNaiveQueue, AgainPools, AgainGeometry };
+} // namespace
+
+static void lap(RunCtx& c, const char* what) {
+    if (!c.verbose) return;
+    auto t1 = std::chrono::steady_clock::now();
+    fprintf(stderr, "[host] %-28s %7.3f ms\n", what, std::chrono::duration<double, std::milli>(t1 - c.t0).count());
+    c.t0 = t1;
+}
+// the queue sizes and flags of the device, once everything on the stream has run
+static void readCounts(RunCtx& c) {
+    HIPCHK(hipMemcpyAsync(c.hcnt, c.b->cnt.p, sizeof(c.hcnt), hipMemcpyDeviceToHost, c.s));
+    HIPCHK(hipStreamSynchronize(c.s));
+}
+// the counters of the run so far as the batch reports them (blocking)
+static void downloadCounters(cmb_batch* b) {
+    unsigned long long hc[CMB_CNT_MAX];
+    HIPCHK(hipMemcpy(hc, b->counters.p, sizeof(hc), hipMemcpyDeviceToHost));
+    for (int i = 0; i < CMB_CNT_MAX; i++) b->cnts[i] = hc[i];
+}
+static uint32_t stratBytesOf(const cmb_batch* b) {
+    return (uint32_t)(((b->wide ? sizeof(DevStrategyKT<MAXP_WIDE>) : sizeof(DevStrategyK)) + 15) / 16 * 16);
+}
+// slots of k_exact: k = 0 one lane per read x strand; otherwise a small grid that loops over the ExactTasks k_parts left
+static uint32_t exactSlots(const cmb_batch* b) {
+    return capSlots(b->k ? 256u * 256u : (uint32_t)std::min<uint64_t>((2ull * b->nReads + 255) / 256 * 256, 256ull * 4096ull));
+}
+
+static int adoptStagedChunk(RunCtx& c) {
+    cmb_batch* b = c.b;
+    if (b->staged) { // the chunk uploaded during the previous run becomes the batch's reads
+        HIPCHK(hipEventSynchronize(b->copyDone));
+        std::swap(b->reads.p, b->readsStage.p);
+        std::swap(b->reads.n, b->readsStage.n);
+        std::swap(b->offs.p, b->offsStage.p);
+        std::swap(b->offs.n, b->offsStage.n);
+        b->hostOffs.swap(b->hostOffsActive);
+        b->staged = false;
+    }
+    if (b->pending) { // the chunk registered since travels to the device while this run's kernels execute
+        startStagedUpload(b);
+        b->hostOffsActive.swap(b->hostOffsStage); // (offsets of the chunk in flight: the batch's from the next run on; the next registration refills hostOffsStage)
+    }
+    return CMB_OK;
+}
+
+static int runPrep(RunCtx& c) {
+    cmb_batch* b = c.b;
+    HIPCHK(hipMemsetAsync(b->counters.p, 0, CMB_CNT_MAX * sizeof(unsigned long long), c.s));
+    c.tm.begin();
+    if (b->metric == CMB_METRIC_EDIT && b->k > 0) { // (the match words of the full reads: k_prep writes them along with the rest)
+        c.mf.nBlk = mfullBlocks(b->maxLen);
+        const uint64_t nW = 2ull * b->nReads * c.mf.nBlk;
+        if (b->mfull.n < 2 * nW) b->mfull.alloc(2 * nW);
+        c.mf.p = b->mfull.p;
+    }
+    launchPrep(c.s, b->reads.p, b->offs.p, b->nReads, b->maxLen, b->gw, b->seq.p, b->G.p, b->rec.p, b->recW, const_cast<uint4*>(c.mf.p), c.mf.nBlk,
+               c.verbose);
+    c.tm.end("k_prep");
+    return CMB_OK;
+}
+
+// the caller's candidates in the place of the search's in-text items
+static int adoptPreset(RunCtx& c) {
+    cmb_batch* b = c.b;
+    if (b->items.n < b->presetItems.size()) b->items.alloc(b->presetItems.size() + 1024);
+    HIPCHK(hipMemsetAsync(b->cnt.p, 0, 8 * sizeof(uint32_t), c.s));
+    HIPCHK(hipMemcpyAsync(b->items.p, b->presetItems.data(), b->presetItems.size() * sizeof(uint4), hipMemcpyHostToDevice, c.s));
+    HIPCHK(hipStreamSynchronize(c.s));
+    memset(c.hcnt, 0, sizeof(c.hcnt));
+    c.hcnt[0] = (uint32_t)b->presetItems.size();
+    c.q.items = b->items.p;
+    c.q.itemCap = cap32(b->items.n);
+    return CMB_OK;
+}
+
+// k_parts + k_exact into the queues at their present sizes, and the first look at what they left
+static int runPrologue(RunCtx& c, int attempt) {
+    cmb_batch* b = c.b;
+    cmb_index* ix = b->ix;
+    hipStream_t s = c.s;
+    Queues& q = c.q;
+    const uint32_t nReads = b->nReads, tasks = 2 * nReads;
+    HIPCHK(hipMemsetAsync(b->cnt.p, 0, 8 * sizeof(uint32_t), s));
+    if (attempt) {
+        HIPCHK(hipMemsetAsync(b->counters.p, 0, CMB_CNT_MAX * sizeof(unsigned long long), s));
+    }
+    q.items = b->items.p;
+    q.itemCap = cap32(b->items.n);
+    q.fm = b->fm.p;
+    q.fmCap = cap32(b->fm.n);
+    q.text = b->text.p;
+    q.textCap = cap32(b->text.n);
+    const uint32_t dfsCap = cap32(b->dfs.n);
+    c.tm.begin();
+    const uint32_t pParts = b->k ? b->sNumParts : 1;
+    const uint32_t stratBytes = stratBytesOf(b);
+    const uint32_t rdWords = 2 * ((b->maxLen + 31) / 32);
+    const bool longReads = b->maxLen > 256;
+    const uint32_t exCap = cap32(b->exq.n);
+    if (b->k) {
+        const uint32_t pCap = capSlots(envSlots("CMB_P_SLOTS", 256u * 32768u)); // (one lane per read x strand
+        // up to 8 M: k_parts 65.7 ms with 512 k lanes looping over the tasks, 65.0 / 62.1 / 62.5 ms with 1 M / 4 M / 8 M)
+        const uint32_t pSlots = std::min<uint32_t>(((tasks + 255) / 256) * 256, pCap);
+        if (b->psel.n < tasks) b->psel.alloc(tasks);
+        const size_t pLds = stratBytes + (5 * pParts + rdWords) * 256 * sizeof(uint32_t);
+        gridLine(c.verbose, "k_parts", tasks, pSlots);
+        withTables(b, [&](auto mp) {
+            withInt<3>((int)b->sPartition, [&](auto part) {
+                withBools(
+                    [&](auto lng) {
+                        constexpr int MP = decltype(mp)::value;
+                        auto kp = k_parts<decltype(part)::value, decltype(lng)::value, MP>;
+                        if (MP != MAXP && pLds > 64 * 1024)
+                            HIPCHK(hipFuncSetAttribute((const void*)kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pLds));
+                        hipLaunchKernelGGL(kp, dim3(pSlots / 256), dim3(256), pLds, s, ix->d, stratOf<MP>(b), nReads, b->k, b->maxLen, b->seq.p,
+                                           (const uint4*)b->rec.p, b->recW / 4, partsOf<MP>(b), b->psel.p, b->dfs.p, dfsCap, b->exq.p, exCap, q);
+                    },
+                    longReads);
+            });
+        });
+    }
+    // k_exact: k = 0 one lane per read x strand; otherwise the ExactTasks k_parts left — their number is on the device, a small
+    // grid loops over them (none in the common case: every search of the multiple_opt schemes has one exact phase)
+    const uint32_t eSlots = exactSlots(b);
+    if (!b->k) gridLine(c.verbose, "k_exact", tasks, eSlots); // (k > 0: the number of its tasks is on the device until the prologue is read back)
+    const size_t eLds = stratBytes + (pParts + rdWords) * 256 * sizeof(uint32_t);
+    withTables(b, [&](auto mp) {
+        constexpr int MP = decltype(mp)::value;
+        auto ke = withBools([](auto lng) { return k_exact<lng(), MP>; }, longReads);
+        hipLaunchKernelGGL(ke, dim3(eSlots / 256), dim3(256), eLds, s, ix->d, stratOf<MP>(b), nReads, b->k, b->maxLen, b->seq.p,
+                           (const uint4*)b->rec.p, b->recW / 4, partsOf<MP>(b), b->exq.p, exCap, b->dfs.p, dfsCap, q);
+    });
+    c.tm.end("k_partition");
+    HIPCHK(hipGetLastError());
+    readCounts(c);
+    return CMB_OK;
+}
+
+// ---- reads not longer than the number of parts (and every read of a one-part strategy): naive backtracking
+// (searchstrategy.cpp:148-152, :442-459 -> dev_bfs_naive.hpp); k_parts marked them in psel
+static int runNaiveSearch(RunCtx& c, Step& step) {
+    cmb_batch* b = c.b;
+    hipStream_t s = c.s;
+    const uint32_t tasks = 2 * b->nReads;
+    c.tm.begin();
+    const uint32_t maxPassN = b->maxLen + 2 * b->k + 4; // (rows of the matrix: len + 2 k + 1 at most)
+    if (!b->nvQCap) b->nvQCap = c.smallPools ? 64 : 16384;
+    for (int j = 0; j < 2; j++)
+        if (b->nvQ[j].n < 3 * b->nvQCap) b->nvQ[j].alloc(3 * b->nvQCap);
+    const size_t cntWords = (size_t)maxPassN + 2;
+    if (b->nvCnt.n < cntWords) b->nvCnt.alloc(cntWords);
+    HIPCHK(hipMemsetAsync(b->nvCnt.p, 0, cntWords * sizeof(uint32_t), s));
+    NaiveBufs N{};
+    N.Q[0] = b->nvQ[0].p;
+    N.Q[1] = b->nvQ[1].p;
+    N.qCap = cap32(b->nvQ[0].n / 3);
+    N.nq = b->nvCnt.p;
+    const bool edit = b->metric == CMB_METRIC_EDIT;
+    hipLaunchKernelGGL(k_naive_start, dim3((tasks + 255) / 256), dim3(256), 0, s, b->ix->d, b->psel.p, b->offs.p, tasks, b->k, edit ? 0u : 1u, N, c.q,
+                       c.geoX ? 1u : 0u);
+    std::vector<uint32_t> hc(cntWords);
+    uint32_t pass = 0, peakQ = 0;
+    bool drained = false;
+    // (the matrix of 11 ... 13 errors is the edit distance's alone)
+    auto kNaive = withBools([](auto e, auto x) { return k_naive_pass<e(), e() && x()>; }, edit, c.geoX);
+    const uint32_t nvGrid = capBlocks(BFS_GRID); // (k_naive_start above takes one lane per read x strand and does not loop: no cap)
+    while (!drained && pass < maxPassN) {
+        const uint32_t upTo = std::min(pass + 16u, maxPassN);
+        for (; pass < upTo; pass++)
+            hipLaunchKernelGGL(kNaive, dim3(nvGrid), dim3(256), 0, s, b->ix->d, N, pass, b->offs.p, b->gw, b->G.p, b->seq.p, b->maxLen, b->k, c.q);
+        HIPCHK(hipMemcpyAsync(hc.data(), b->nvCnt.p, cntWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        readCounts(c);
+        if (c.hcnt[3] & (FLAG_NAIVE_Q | FLAG_ITEM_OVERFLOW | FLAG_FMOCC_OVERFLOW)) break;
+        drained = hc[pass] == 0;
+    }
+    for (uint32_t p2 = 0; p2 <= pass && p2 < cntWords; p2++) peakQ = std::max(peakQ, hc[p2]);
+    if (c.verbose) fprintf(stderr, "[naive] %u roots, %u passes, peak frontier %u\n", hc[0], pass, peakQ);
+    gridLine(c.verbose, "k_naive_pass", peakQ, 256ull * nvGrid); // (the largest frontier of a pass)
+    c.tm.end("k_naive");
+    HIPCHK(hipGetLastError());
+    if (c.hcnt[3] & FLAG_NAIVE_Q) {
+        b->nvQCap = std::max<size_t>(4 * b->nvQCap, (size_t)peakQ + peakQ / 4);
+        step = Step::AgainNaiveQueue;
+        return CMB_OK;
+    }
+    if (!drained && !(c.hcnt[3] & (FLAG_ITEM_OVERFLOW | FLAG_FMOCC_OVERFLOW)))
+        return fail(CMB_ERR_INTERNAL, "the naive search did not finish within its pass bound");
+    return CMB_OK;
+}
+
+// The pools of the edit-distance frontier as the kernels take them (dev_bfs_edit.hpp): grown to the capacities the batch asks for,
+// their cntWords counters (nodes and events per level, four pool sizes) zeroed on the stream, for a search of at most maxPass levels
+static BfsBufs frontierBufs(RunCtx& c, uint32_t maxPass, size_t cntWords) {
+    cmb_batch* b = c.b;
+    // node planes / uint4 per event of the record geometry (dev_bfs_edit.hpp: GeoN, GeoW)
+    const size_t qPlanes = 3 + (b->wide ? GeoW::PK_U4 : GeoN::PK_U4), evU4 = 1 + (b->wide ? GeoW::PK_U4 : GeoN::PK_U4);
+    // (GeoX: blocks of 16 rows — up to 32 of them for 480 + 26 rows, two uint4 of match words each)
+    const uint32_t ctxU4 = c.geoX ? CTX_U4_X : ctxU4For(b->maxLen);
+    BfsBufs B{};
+    for (int j = 0; j < 2; j++) {
+        if (b->bfsQ[j].n < qPlanes * b->bfsQCap) b->bfsQ[j].alloc(qPlanes * b->bfsQCap);
+        if (b->bfsEv[j].n < evU4 * b->bfsEvCap) b->bfsEv[j].alloc(evU4 * b->bfsEvCap);
+        B.Q[j] = b->bfsQ[j].p;
+        B.Ev[j] = b->bfsEv[j].p;
+    }
+    if (b->bfsF.n < F_U4 * b->bfsFCap) b->bfsF.alloc(F_U4 * b->bfsFCap);
+    if (b->bfsC.n < (size_t)ctxU4 * b->bfsCCap) b->bfsC.alloc((size_t)ctxU4 * b->bfsCCap);
+    if (b->bfsA.n < b->bfsACap) b->bfsA.alloc(b->bfsACap);
+    if (b->bfsCnt.n < cntWords) b->bfsCnt.alloc(cntWords);
+    if (b->bfsBlockCnt.n < (size_t)BFS_GRID_CNT * 4) b->bfsBlockCnt.alloc((size_t)BFS_GRID_CNT * 4);
+    HIPCHK(hipMemsetAsync(b->bfsCnt.p, 0, cntWords * sizeof(uint32_t), c.s));
+    HIPCHK(hipMemsetAsync(b->bfsBlockCnt.p, 0, (size_t)BFS_GRID_CNT * 4 * sizeof(unsigned long long), c.s));
+    B.F = b->bfsF.p;
+    B.C = b->bfsC.p;
+    B.A = b->bfsA.p;
+    B.qCap = cap32(b->bfsQ[0].n / qPlanes);
+    B.evCap = cap32(b->bfsEv[0].n / evU4);
+    B.fCap = cap32(b->bfsF.n / F_U4);
+    B.cCap = cap32(b->bfsC.n / ctxU4);
+    B.ctxU4 = ctxU4;
+    B.ctxMblk = c.geoX ? CTX_MBLK_X : ctxMblkFor(b->maxLen);
+    B.aCap = cap32(b->bfsA.n);
+    B.chain = getenv("CMB_BFS_CHAIN") ? (uint32_t)std::max(1, atoi(getenv("CMB_BFS_CHAIN"))) : BFS_CHAIN;
+    B.gridX = capBlocks(std::min<uint32_t>(BFS_GRID_CNT, envBlocks("CMB_BFS_GRID", BFS_GRID_X)));
+    B.gridEv = capBlocks(envBlocks("CMB_BFS_GRID_EV", BFS_GRID_EV));
+    // (CMB_TEST_NARROW_WV: tests lower the bound so that the re-run on the 64-bit geometry is exercised)
+    B.narrowWv = getenv("CMB_TEST_NARROW_WV") ? (uint32_t)std::max(0, atoi(getenv("CMB_TEST_NARROW_WV"))) : 0xFFFFu;
+    B.nq = b->bfsCnt.p;
+    B.ne = b->bfsCnt.p + (maxPass + 2);
+    B.pool = b->bfsCnt.p + 2 * (maxPass + 2);
+    B.blockCnt = b->bfsBlockCnt.p;
+    return B;
+}
+
+// ---- frontier search: start pass, then (expand, events) per level until both queues drain
+static int runFrontierEdit(RunCtx& c, Step& step) {
+    cmb_batch* b = c.b;
+    hipStream_t s = c.s;
+    const uint32_t nReads = b->nReads, nDfs = c.hcnt[5];
+    c.tm.begin();
+    const uint32_t maxPass = 2 * b->maxLen + 8 * (b->wide ? MAXP_WIDE : MAXP) + 64;
+    if (!b->bfsQCap) {
+        // first guess; every pool grows (and the search re-runs) when it turns out too small.
+        // CMB_TEST_SMALL_POOLS starts from almost nothing so that tests exercise that path.
+        const size_t slack = c.smallPools ? 64 : 65536;
+        const size_t per = c.smallPools ? 0 : 1;
+        b->bfsQCap = per * (size_t)nReads * 2 + slack;
+        b->bfsEvCap = per * (size_t)nReads / 2 + slack;
+        b->bfsFCap = per * (size_t)nReads * 16 + slack;
+        b->bfsCCap = per * (size_t)nReads * 2 + slack;
+        b->bfsACap = per * (size_t)nReads * 8 + slack;
+    }
+    b->bfsQCap = std::max<size_t>(b->bfsQCap, (size_t)nDfs + 1024);
+    const size_t cntWords = 2 * ((size_t)maxPass + 2) + 4;
+    const BfsBufs B = frontierBufs(c, maxPass, cntWords);
+    // up to 6 errors the frontier carries the in-index matrix on 32-bit words (GeoN32, dev_matrix.hpp: MXS_*); CMB_MATRIX64=1
+    // keeps the reference's 64-bit words (GeoN), as does a batch one of whose phases did not fit the small matrix
+    const FrontierGeo geo = frontierGeoOf(b);
+    const uint32_t startGrid = capBlocks(std::min<uint32_t>((nDfs + 255) / 256, BFS_GRID));
+    gridLine(c.verbose, "k_bfs_start", nDfs, 256ull * startGrid);
+    withGeo(geo, [&](auto g) {
+        using Geo = typename decltype(g)::type;
+        hipLaunchKernelGGL(k_bfs_start<Geo>, dim3(startGrid), dim3(256), 0, s, b->ix->d, stratOf<Geo::MP>(b), B, b->dfs.p, nDfs, b->offs.p, b->gw, b->G.p,
+                           partsOf<Geo::MP>(b), c.q);
+    });
+    // (the instance of a pass is chosen here, once per attempt: the loop below calls through a pointer)
+    const auto bfsPass = withGeo(geo, [](auto g) { return &launchBfsPass<typename decltype(g)::type>; });
+    std::vector<uint32_t> hc(cntWords);
+    // passes between two looks at the queue sizes (a pass on a drained frontier costs the device ~4 us, a look costs the host a round trip)
+    const uint32_t CHECK = getenv("CMB_BFS_CHECK") ? (uint32_t)std::max(1, atoi(getenv("CMB_BFS_CHECK"))) : 16;
+    uint32_t pass = 0, peakQ = 0, peakEv = 0;
+    bool drained = false;
+    while (!drained && pass < maxPass) {
+        const uint32_t upTo = std::min(pass + CHECK, maxPass);
+        for (; pass < upTo; pass++) bfsPass(b, B, pass, c.q);
+        HIPCHK(hipMemcpyAsync(hc.data(), b->bfsCnt.p, cntWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        readCounts(c);
+        if (c.hcnt[3] & BFS_STOP) break;
+        drained = hc[pass] == 0 && hc[maxPass + 2 + pass] == 0;
+    }
+    for (uint32_t p2 = 0; p2 <= pass && p2 < maxPass + 2; p2++) {
+        peakQ = std::max(peakQ, hc[p2]);
+        peakEv = std::max(peakEv, hc[maxPass + 2 + p2]);
+    }
+    const uint32_t* pool = hc.data() + 2 * (maxPass + 2);
+    if (c.verbose)
+        fprintf(stderr, "[bfs] %u tasks, %u passes, peak frontier %u, peak events %u, F %u, contexts %u, arena %u\n", nDfs, pass, peakQ, peakEv, pool[0],
+                pool[1], pool[2]);
+    gridLine(c.verbose, "k_bfs_pass", peakQ, 256ull * B.gridX); // (the largest frontier and the most events of a pass)
+    gridLine(c.verbose, "k_bfs_pass_events", peakEv, 256ull * B.gridEv);
+    if (c.verbose && atoi(c.verboseEnv) > 1)
+        for (uint32_t p2 = 0; p2 <= pass; p2++) fprintf(stderr, "  pass %u: %u nodes, %u events\n", p2, hc[p2], hc[maxPass + 2 + p2]);
+    hipLaunchKernelGGL(k_bfs_finish, dim3(1), dim3(256), 0, s, B, c.q);
+    int rc = CMB_OK;
+    if (c.hcnt[3] & FLAG_NARROW_MATRIX) { // (a first column wider than the small matrix holds: once more on the reference's words)
+        if (c.verbose) fprintf(stderr, "[bfs] a phase did not fit the 32-bit in-index matrix: re-running on 64-bit words\n");
+        b->noSmallMatrix = true;
+        step = Step::AgainGeometry;
+    } else if (c.hcnt[3] & (FLAG_BFS_Q | FLAG_BFS_EV | FLAG_BFS_F | FLAG_BFS_CTX | FLAG_BFS_ARENA)) {
+        // a pool was too small: grow what was asked for (at least x2) and run the search again
+        // (an attempt only shows the demand up to the pass that overflowed: beyond 7 errors, where the first guesses are far
+        // off — 64 reads at 12 errors on 3 Gbp took eleven attempts at x 2 —, the pools grow x 4)
+        const size_t gf = b->k > 7 ? 4 : 2;
+        const struct {
+            uint32_t flag;
+            size_t* cap;
+            uint32_t demand;
+        } pools[] = {{FLAG_BFS_Q, &b->bfsQCap, peakQ},
+                     {FLAG_BFS_EV, &b->bfsEvCap, peakEv},
+                     {FLAG_BFS_F, &b->bfsFCap, pool[0]},
+                     {FLAG_BFS_CTX, &b->bfsCCap, pool[1]},
+                     {FLAG_BFS_ARENA, &b->bfsACap, pool[2]}};
+        for (const auto& p : pools)
+            if (c.hcnt[3] & p.flag) *p.cap = std::max<size_t>(gf * *p.cap, (size_t)p.demand + p.demand / 4);
+        step = Step::AgainPools;
+    } else if (!drained && !(c.hcnt[3] & BFS_STOP)) {
+        rc = fail(CMB_ERR_INTERNAL, "frontier search did not finish within its pass bound");
+    }
+    if (step != Step::GoOn) HIPCHK(hipStreamSynchronize(s));
+    c.tm.end("k_dfs");
+    return rc;
+}
+
+// ---- Hamming distance: the same frontier idea without a matrix (dev_bfs_hamming.hpp)
+static int runFrontierHamming(RunCtx& c, Step& step) {
+    cmb_batch* b = c.b;
+    hipStream_t s = c.s;
+    const uint32_t nDfs = c.hcnt[5];
+    c.tm.begin();
+    const uint32_t maxPass = b->maxLen + 2 * (b->wide ? MAXP_WIDE : MAXP) + 16;
+    if (!b->bfsQCap) b->bfsQCap = (c.smallPools ? 0 : (size_t)b->nReads * 4) + 1024;
+    b->bfsQCap = std::max<size_t>(b->bfsQCap, (size_t)nDfs + 1024);
+    for (int j = 0; j < 2; j++)
+        if (b->bfsQ[j].n < 2 * b->bfsQCap) b->bfsQ[j].alloc(2 * b->bfsQCap);
+    const size_t cntWords = (size_t)maxPass + 2;
+    if (b->bfsCnt.n < cntWords) b->bfsCnt.alloc(cntWords);
+    if (b->bfsBlockCnt.n < (size_t)BFS_GRID_CNT * 4) b->bfsBlockCnt.alloc((size_t)BFS_GRID_CNT * 4);
+    HIPCHK(hipMemsetAsync(b->bfsCnt.p, 0, cntWords * sizeof(uint32_t), s));
+    HIPCHK(hipMemsetAsync(b->bfsBlockCnt.p, 0, (size_t)BFS_GRID_CNT * 4 * sizeof(unsigned long long), s));
+    HbfsBufs H{};
+    H.Q[0] = b->bfsQ[0].p;
+    H.Q[1] = b->bfsQ[1].p;
+    H.qCap = cap32(b->bfsQ[0].n / 2);
+    H.nq = b->bfsCnt.p;
+    H.blockCnt = b->bfsBlockCnt.p;
+    const uint32_t hLds = stratBytesOf(b);
+    const uint32_t startGrid = capBlocks(std::min<uint32_t>((nDfs + 255) / 256, BFS_GRID)), passGrid = capBlocks(BFS_GRID);
+    gridLine(c.verbose, "k_hbfs_start", nDfs, 256ull * startGrid);
+    withTables(b, [&](auto mp) {
+        constexpr int MP = decltype(mp)::value;
+        hipLaunchKernelGGL((k_hbfs<true, MP>), dim3(startGrid), dim3(256), hLds, s, b->ix->d, stratOf<MP>(b), H, 0u, b->dfs.p, nDfs, b->maxLen, b->seq.p,
+                           partsOf<MP>(b), c.q);
+    });
+    std::vector<uint32_t> hc(cntWords);
+    uint32_t pass = 0, peakQ = 0;
+    bool drained = false;
+    while (!drained && pass < maxPass) {
+        const uint32_t upTo = std::min(pass + 16u, maxPass);
+        for (; pass < upTo; pass++)
+            withTables(b, [&](auto mp) {
+                constexpr int MP = decltype(mp)::value;
+                hipLaunchKernelGGL((k_hbfs<false, MP>), dim3(passGrid), dim3(256), hLds, s, b->ix->d, stratOf<MP>(b), H, pass, (const DfsTask*)nullptr, 0u,
+                                   b->maxLen, b->seq.p, partsOf<MP>(b), c.q);
+            });
+        HIPCHK(hipMemcpyAsync(hc.data(), b->bfsCnt.p, cntWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        readCounts(c);
+        if (c.hcnt[3] & BFS_STOP) break;
+        drained = hc[pass] == 0;
+    }
+    for (uint32_t p2 = 0; p2 <= pass && p2 < cntWords; p2++) peakQ = std::max(peakQ, hc[p2]);
+    if (c.verbose) fprintf(stderr, "[hbfs] %u tasks, %u passes, peak frontier %u\n", nDfs, pass, peakQ);
+    gridLine(c.verbose, "k_hbfs_pass", peakQ, 256ull * passGrid); // (the largest frontier of a pass)
+    BfsBufs Bf{};
+    Bf.blockCnt = b->bfsBlockCnt.p;
+    hipLaunchKernelGGL(k_bfs_finish, dim3(1), dim3(256), 0, s, Bf, c.q);
+    int rc = CMB_OK;
+    if (c.hcnt[3] & FLAG_BFS_Q) {
+        b->bfsQCap = std::max<size_t>(2 * b->bfsQCap, (size_t)peakQ + peakQ / 4);
+        HIPCHK(hipStreamSynchronize(s));
+        step = Step::AgainPools;
+    } else if (!drained && !(c.hcnt[3] & BFS_STOP)) {
+        rc = fail(CMB_ERR_INTERNAL, "frontier search did not finish within its pass bound");
+    }
+    c.tm.end("k_dfs");
+    return rc;
+}
+
+// One attempt of the search with the queues and pools at their present sizes: prologue, naive backtracking, frontier.  Step::GoOn: the
+// attempt ran to its end, and c.hcnt holds what it left — overflowed work queues included, which the caller grows
+static int searchAttempt(RunCtx& c, int attempt, Step& step) {
+    cmb_batch* b = c.b;
+    int rc = runPrologue(c, attempt);
+    if (rc != CMB_OK) return rc;
+    b->hasNaive = (c.hcnt[3] & FLAG_UNSUPPORTED_READ) != 0;
+    if (b->hasNaive && ((rc = runNaiveSearch(c, step)) != CMB_OK || step != Step::GoOn)) return rc;
+    if (c.hcnt[3] & FLAG_SEED_OVERLAP)
+        return fail(CMB_ERR_INVALID,
+                    "dynamic partitioning: the seeds of a read overlap — the k-mer size of the index is too large "
+                    "for the seeding positions of this search strategy at this read length (the reference caps "
+                    "the k-mer size, e.g. at 4 for kuch2 and 01*0: alignparameters.cpp:1070-1114, :1275-1278)");
+    if (c.verbose && b->k) fprintf(stderr, "[prologue] %u items, %u search tasks, %u searches with further exact phases\n", c.hcnt[0], c.hcnt[5], c.hcnt[4]);
+    if (b->k) gridLine(c.verbose, "k_exact", c.hcnt[4], exactSlots(b));
+    if ((c.hcnt[3] & (FLAG_ITEM_OVERFLOW | FLAG_DFS_OVERFLOW | FLAG_EXACT_OVERFLOW)) || !c.hcnt[5]) return CMB_OK;
+    rc = b->metric == CMB_METRIC_EDIT ? runFrontierEdit(c, step) : runFrontierHamming(c, step);
+    if (rc != CMB_OK || step != Step::GoOn) return rc;
+    HIPCHK(hipGetLastError());
+    readCounts(c);
+    return CMB_OK;
+}
+
+// ---- de-duplicate the in-index occurrences (Occurrences::eraseDoublesFM, indexhelpers.h:2135-2146); their number arrives in c.nFmUniq
+// with the next wait for the stream
+static int dedupFmOccurrences(RunCtx& c) {
+    cmb_batch* b = c.b;
+    const uint32_t nFm = c.nFm;
+    if (!nFm) return CMB_OK;
+    if (b->fmKeysA.n < nFm) {
+        b->fmKeysA.alloc((size_t)nFm + nFm / 4 + 256);
+        b->fmKeysB.alloc(b->fmKeysA.n);
+        b->fmIdxA.alloc(b->fmKeysA.n);
+        b->fmIdxB.alloc(b->fmKeysA.n);
+        b->fmUniq.alloc(b->fmKeysA.n);
+    }
+    if (b->fmN.n < 1) b->fmN.alloc(1);
+    HIPCHK(hipMemsetAsync(b->fmN.p, 0, sizeof(uint32_t), c.s));
+    hipLaunchKernelGGL(k_fm_keys, dim3((nFm + 255) / 256), dim3(256), 0, c.s, b->fm.p, nFm, b->fmKeysA.p, b->fmIdxA.p);
+    sortPairs(b->sortTmp, b->fmKeysA.p, b->fmKeysB.p, b->fmIdxA.p, b->fmIdxB.p, nFm, 0, 64, c.s);
+    hipLaunchKernelGGL(k_fm_unique, dim3((nFm + 255) / 256), dim3(256), 0, c.s, b->fm.p, b->fmKeysB.p, b->fmIdxB.p, nFm, b->fmUniq.p, b->fmN.p, c.q);
+    HIPCHK(hipMemcpyAsync(&c.nFmUniq, b->fmN.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c.s));
+    return CMB_OK;
+}
+
+// k_verify over the items, then — edit distance — the key sort and the matrix kernels over the distinct keys; c.hcnt[7] traceback tasks
+static int verifyCandidates(RunCtx& c) {
+    cmb_batch* b = c.b;
+    cmb_index* ix = b->ix;
+    hipStream_t s = c.s;
+    const Queues& q = c.q;
+    const MFull mf = c.mf;
+    const uint32_t nReads = b->nReads, nItems = c.nItems;
+    const bool verbose = c.verbose;
+    // (lanes of k_verify: 128 k / 256 k / 512 k -> 34.8 / 32.0 / 35.9 ms of the locate group on the headline workload, round 4)
+    const uint32_t vCap = capSlots(envSlots("CMB_V_SLOTS", 256u * 1024u, 256u * 2048u));
+    const uint32_t vSlots = std::min<uint32_t>(((nItems + 255) / 256) * 256, vCap);
+    gridLine(verbose, "k_verify", nItems, vSlots);
+    // Edit distance: identical verifications (same read x strand, text window and bounds — the parts of
+    // one read seeding the same alignment) are performed once: k_verify only locates and emits a key per
+    // candidate, the keys are sorted and run-length encoded, k_verify_edit verifies the distinct ones and
+    // scales the counters by the multiplicities.
+    // (25 key bits for read x strand; 23 in the key layout of batches at 8 ... 13 errors — 64 - VKW_RS — whose sub-batches
+    // hold at most 2^20 reads: the sorted bits below end at VKW_RS + rsBits <= 64)
+    const bool dedup = b->metric == CMB_METRIC_EDIT && b->k > 0 && 2ull * nReads < (b->wideEdit ? (1ull << (64u - VKW_RS)) : (1ull << 25));
+    if (b->wideEdit && !dedup) return fail(CMB_ERR_INTERNAL, "a sub-batch beyond 7 errors holds more reads than its verification keys number");
+    const uint32_t tbCap = cap32(b->tbq.n);
+    c.tm.begin();
+    if (dedup) growTo(b->vkeysA, nItems), growTo(b->vkeysB, nItems), growTo(b->vcounts, nItems), growTo(b->vruns, 4);
+    auto kv = withBools([](auto keys) { return k_verify<keys()>; }, dedup);
+    hipLaunchKernelGGL(kv, dim3(vSlots / 256), dim3(256), 0, s, ix->d, b->offs.p, b->maxLen, b->gw, b->seq.p, mf, b->items.p, nItems, b->tbq.p, tbCap,
+                       dedup ? b->vkeysA.p : (unsigned long long*)nullptr, q, b->wideEdit ? 1u : 0u); // (1: the wide key layout)
+    if (!dedup) {
+        c.tm.end("k_verify");
+        readCounts(c);
+        return CMB_OK;
+    }
+    uint32_t nRuns = 0;
+    // sorted bits: low VK_LOW bits of the start, the bounds, read x strand (2 nReads < 2^rsBits, so
+    // that the all-ones key of the other items sorts behind every real key) — see packVerifyKey
+    uint32_t rsBits = 1;
+    while ((1ull << rsBits) <= 2ull * nReads) rsBits++;
+    const uint32_t bit0 = 32u - VK_LOW, bit1 = (b->wideEdit ? VKW_RS : 39u) + rsBits;
+    sortKeys(b->sortTmp, b->vkeysA.p, b->vkeysB.p, nItems, bit0, bit1, s);
+    runLengthEncode(b->scanTmp, b->vkeysB.p, nItems, b->vkeysA.p, b->vcounts.p, b->vruns.p, s);
+    HIPCHK(hipMemcpyAsync(&nRuns, b->vruns.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    c.tm.end("k_verify"); // locate + key sort + run-length encode; the matrix stages are timed apart
+    c.tm.begin();
+    if (verbose) fprintf(stderr, "[verify] %u items, %u distinct keys\n", nItems, nRuns);
+    if (nRuns && b->wideEdit) {
+        // 8 ... 13 errors: the band (up to 53 columns) needs the wide left margins of the 64-bit in-text matrix (dev_matrix.hpp:
+        // MXX_*, MXY_*): k_wide_filter sorts out the candidates that never reach their final column, k_verify_wide<true> verifies the rest
+        const uint32_t fGrid = capBlocks(std::min<uint32_t>((nRuns + 255) / 256, 2048u));
+        gridLine(verbose, "k_wide_filter", nRuns, 256ull * fGrid);
+        // (every key, the slots a wavefront leaves unused when it retires a chunk — fewer than 64 of 256 —, a chunk per wavefront)
+        const size_t listNeed = (size_t)nRuns + nRuns / 3 + (size_t)fGrid * 4 * 256 + 512;
+        if (b->dpList.n < listNeed) b->dpList.alloc(listNeed + listNeed / 8);
+        if (b->dpWork.n < 4) b->dpWork.alloc(4);
+        HIPCHK(hipMemsetAsync(b->dpWork.p, 0, 4 * sizeof(uint32_t), s));
+        auto kFilter = k_wide_filter<WxTen>;
+        auto kWide = k_verify_wide<true, WxTen>;
+        if (c.geoX) kFilter = k_wide_filter<WxThirteen>, kWide = k_verify_wide<true, WxThirteen>;
+        hipLaunchKernelGGL(kFilter, dim3(fGrid), dim3(256), 0, s, ix->d, b->offs.p, b->G.p, b->gw, b->vkeysA.p, b->vcounts.p, nRuns, b->dpWork.p,
+                           b->dpList.p, cap32(b->dpList.n), q);
+        const uint32_t slotBytes = (vwRows(b->maxLen) + 1u) * VW_ROW_BYTES;
+        // (six wavefronts per SIMD: 1024 SIMDs x 6 x 64 lanes — forward pass and traceback wait for memory; a slot is 3 - 8 KB)
+        const uint32_t dSlots = std::min<uint32_t>(((nRuns + 255) / 256) * 256, capSlots(envSlots("CMB_VW_SLOTS", 256u * 1536u)));
+        if (b->dpSlab.n < (size_t)slotBytes * dSlots) b->dpSlab.alloc((size_t)slotBytes * dSlots);
+        hipLaunchKernelGGL(kWide, dim3(dSlots / 256), dim3(256), 0, s, ix->d, b->offs.p, b->maxLen, b->seq.p, b->G.p, b->gw, (const uint4*)nullptr,
+                           cap32(b->dpList.n), b->vkeysA.p, b->vcounts.p, b->dpList.p, b->dpWork.p + 1, b->dpSlab.p, slotBytes, q);
+        if (verbose) {
+            uint32_t hw[2];
+            HIPCHK(hipMemcpyAsync(hw, b->dpWork.p, sizeof(hw), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            fprintf(stderr, "[verify] %u list slots (survivors and holes) for %u distinct candidates\n", hw[1], nRuns);
+            gridLine(verbose, "k_verify_wide", hw[1], dSlots); // (it loops over the list the filter left)
+        }
+    } else if (nRuns) {
+        // staged verification (kernels.hpp: k_verify_stage): one launch per nb 32-row matrix blocks,
+        // survivor lists ping-pong, list sizes stay on the device
+        // nb 32-row blocks per stage: fewer stages re-fetch fewer text lines and move fewer survivor
+        // records, more blocks leave more lanes idle behind candidates that ended (CMB_STAGE_BLOCKS)
+        const char* nbEnv = getenv("CMB_STAGE_BLOCKS");
+        // (round 4, 150 bp reads at 4 errors: 1 / 2 / 3 / 4 / 6 blocks per stage -> 53.1 / 31.4 / 29.4 / 32.0 / 38.0 ms of k_verify_edit)
+        const uint32_t nb = nbEnv ? std::min(8u, std::max(1u, (uint32_t)atoi(nbEnv))) : 3u;
+        const uint32_t nStages = (vRows(b->maxLen) + 32u * nb - 1u) / (32u * nb) + 1u;
+        for (int j = 0; j < 2; j++)
+            if (b->vsC[j].n < nRuns) {
+                b->vsA[j].alloc((size_t)nRuns + nRuns / 8 + 256);
+                b->vsB[j].alloc(b->vsA[j].n);
+                b->vsC[j].alloc(b->vsA[j].n);
+            }
+        if (b->vsN.n < nStages + 2) b->vsN.alloc(nStages + 2);
+        HIPCHK(hipMemsetAsync(b->vsN.p, 0, (nStages + 2) * sizeof(uint32_t), s));
+        const uint32_t listCap = cap32(b->vsC[0].n);
+        const uint32_t gridCap = capBlocks(envBlocks("CMB_STAGE_GRID", 8192u));
+        const uint32_t grid = std::min<uint32_t>((nRuns + 255) / 256, gridCap);
+        gridLine(verbose, "k_verify_stage", nRuns, 256ull * grid); // (the first stage: the later ones take its survivors)
+        VStageList L0{b->vsA[0].p, b->vsB[0].p, b->vsC[0].p}, L1{b->vsA[1].p, b->vsB[1].p, b->vsC[1].p};
+        // k <= 4: the matrix on 32-bit words (dev_matrix.hpp); CMB_MATRIX_WIDE=1 keeps the 64-bit words
+        const bool w32 = b->k <= MX32_MAX_ED && !getenv("CMB_MATRIX_WIDE");
+        const bool packed = ix->d.text2 != nullptr; // 2-bit text (cmb_index_create)
+        // stages no read of the batch can reach its final-column rows in (row >= len - maxED - 1,
+        // maxED <= 7) run the instance without final-column code
+        auto needsFinal = [&](uint32_t st) { return 32u * nb * (st + 1u) - 1u + 8u >= b->minLen; };
+        auto stageKernel = [&](bool first, bool fin) {
+            return withBools([](auto f, auto w, auto p, auto c2) { return k_verify_stage<f(), w(), p(), c2()>; }, first, w32, packed, fin);
+        };
+        hipLaunchKernelGGL(stageKernel(true, needsFinal(0)), dim3(grid), dim3(256), 0, s, ix->d, b->offs.p, mf, b->vkeysA.p, b->vcounts.p, nRuns, L0, L1,
+                           b->vsN.p, listCap, 0u, nb, b->tbq.p, tbCap, q);
+        for (uint32_t st = 1; st < nStages; st++)
+            hipLaunchKernelGGL(stageKernel(false, needsFinal(st)), dim3(grid), dim3(256), 0, s, ix->d, b->offs.p, mf, (const unsigned long long*)nullptr,
+                               (const uint32_t*)nullptr, 0u, (st & 1u) ? L1 : L0, (st & 1u) ? L0 : L1, b->vsN.p, listCap, st, nb, b->tbq.p, tbCap, q);
+        if (verbose) {
+            std::vector<uint32_t> hn(nStages + 2);
+            HIPCHK(hipMemcpyAsync(hn.data(), b->vsN.p, hn.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            fprintf(stderr, "[verify] survivors per stage:");
+            for (uint32_t st = 1; st <= nStages; st++) fprintf(stderr, " %u", hn[st]);
+            fprintf(stderr, "\n");
+        }
+    }
+    c.tm.end("k_verify_edit");
+    readCounts(c);
+    return CMB_OK;
+}
+
+// k_traceback over the c.hcnt[7] tasks the verification left
+static int runTraceback(RunCtx& c) {
+    cmb_batch* b = c.b;
+    const uint32_t nTb = c.hcnt[7];
+    if (!nTb) return CMB_OK;
+    const uint32_t slotCap = capSlots(envSlots("CMB_TB_SLOTS", 512u * 1024u)); // (measured 64 k … 2 M slots: 84 / 49 / 34.4 / 32.8 / 31 / 29 ms alone; 512 k best beside other sub-batches)
+    const uint32_t tSlots = std::min<uint32_t>(((nTb + 255) / 256) * 256, slotCap);
+    gridLine(c.verbose, "k_traceback", nTb, tSlots);
+    // 64-byte lines of 16 narrow (k <= 4) or 8 wide trace rows (a group is written whole)
+    const bool narrow = b->k <= TBN_MAX_ED && !getenv("CMB_TRACE_WIDE");
+    const uint32_t tLines = traceLines(narrow, vRows(b->maxLen));
+    if (b->vW.n < (size_t)tLines * 8 * tSlots) b->vW.alloc((size_t)tLines * 8 * tSlots);
+    VPlanes vp{b->vW.p, tSlots, tLines};
+    c.tm.begin();
+    // no final-column row (> len - maxED - 1, maxED <= 7) at or before this row, for any read of the batch
+    const uint32_t rowMin = b->minLen > 8u ? b->minLen - 8u : 0u;
+    launchTraceback(c.s, b->ix->d, narrow, b->offs.p, c.mf, b->tbq.p, nTb, vp, c.q, rowMin);
+    c.tm.end("k_traceback");
+    return CMB_OK;
+}
+
+// ---- locate + verify: the items and the distinct in-index occurrences become text occurrences (c.nText of them).  The text queue is
+// retried on overflow: a retry starts from the counters as the search left them, with the overflow flag cleared
+static int locateAndVerify(RunCtx& c) {
+    cmb_batch* b = c.b;
+    hipStream_t s = c.s;
+    // traceback task queue: at most one task per item + the chunk slack of every k_verify wavefront
+    // (a chunk of 256 is retired when the wavefront's next group does not fit: at most 63 holes per chunk)
+    const size_t tbNeed = (size_t)c.nItems + (size_t)c.nItems / 2 + (size_t)(256u * 2048u / 64u + 1) * 256u;
+    if (b->tbq.n < tbNeed) b->tbq.alloc(tbNeed + c.nItems / 8);
+    for (int attempt = 0;; attempt++) {
+        c.q.text = b->text.p;
+        c.q.textCap = cap32(b->text.n);
+        uint32_t zero[2] = {0, 0};
+        HIPCHK(hipMemcpyAsync(b->cnt.p + 2, zero, sizeof(zero), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(b->cnt.p + 7, zero, sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        unsigned long long keep[CMB_CNT_MAX];
+        HIPCHK(hipMemcpyAsync(keep, b->counters.p, sizeof(keep), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (c.nItems) {
+            int rc = verifyCandidates(c);
+            if (rc == CMB_OK) rc = runTraceback(c);
+            if (rc != CMB_OK) return rc;
+        }
+        readCounts(c);
+        if (c.nFmUniq) {
+            c.tm.begin();
+            const uint32_t nb = (uint32_t)std::min<size_t>(((size_t)c.nFmUniq + 255) / 256, 4096);
+            hipLaunchKernelGGL(k_fmocc, dim3(nb), dim3(256), 0, s, b->ix->d, b->fmUniq.p, c.nFmUniq, c.q);
+            c.tm.end("k_fmocc");
+        }
+        HIPCHK(hipGetLastError());
+        readCounts(c);
+        if (!(c.hcnt[3] & FLAG_TEXT_OVERFLOW)) break;
+        if (attempt >= 3) return fail(CMB_ERR_INTERNAL, "text occurrence queue keeps overflowing");
+        b->text.alloc((size_t)c.hcnt[2] + c.hcnt[2] / 8 + 1024);
+        HIPCHK(hipMemcpy(b->counters.p, keep, sizeof(keep), hipMemcpyHostToDevice));
+        uint32_t fl = c.hcnt[3] & ~(uint32_t)FLAG_TEXT_OVERFLOW; // clear the overflow flag for the retry
+        HIPCHK(hipMemcpy(b->cnt.p + 3, &fl, sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    c.nText = c.hcnt[2];
+    return CMB_OK;
+}
+
+// candidates given by the caller: the raw text occurrences and the counters are the result
+static int finishPreset(RunCtx& c) {
+    cmb_batch* b = c.b;
+    if (c.hcnt[3] & (FLAG_CAPACITY | FLAG_TRACE_RULE)) return fail(CMB_ERR_INTERNAL, "a traceback left the band");
+    b->presetOut.resize(c.nText);
+    if (c.nText) HIPCHK(hipMemcpy(b->presetOut.data(), b->text.p, (size_t)c.nText * sizeof(TextOccRec), hipMemcpyDeviceToHost));
+    downloadCounters(b);
+    b->done = true;
+    return CMB_OK;
+}
+
+// The filter of getUniqueTextOccurrences / getTextOccHamming (indexinterface.cpp:1331-1491) up to the ranks: the nText text occurrences
+// packed into keys (k_pack_keys: per read, or per read x strand; psel: only those of the reads it marks) -> one 64-bit radix sort ->
+// per-group scan.  Leaves the sorted keys in keysB, the rank of every survivor within its group in frank, the survivors per group in
+// fcounts and their exclusive scan in foffs, whose last element (foffs[nGroups], the total) the caller reads
+static void rankSurvivors(RunCtx& c, uint32_t nText, uint32_t nGroups, uint32_t perStrandKeys, const uint8_t* psel, int mode, uint32_t keyLayout) {
+    cmb_batch* b = c.b;
+    hipStream_t s = c.s;
+    growTo(b->keysA, nText), growTo(b->keysB, nText), growTo(b->frank, nText);
+    if (b->fcounts.n < (size_t)nGroups + 1) {
+        b->fcounts.alloc((size_t)nGroups + 1);
+        b->foffs.alloc((size_t)nGroups + 1);
+        b->fsegB.alloc((size_t)nGroups + 1);
+        b->fsegE.alloc((size_t)nGroups + 1);
+    }
+    if (nText) {
+        hipLaunchKernelGGL(k_pack_keys, dim3((nText + 255) / 256), dim3(256), 0, s, b->text.p, nText, b->offs.p, b->k, b->keysA.p, b->cnt.p, perStrandKeys,
+                           psel, keyLayout);
+        sortKeys(b->sortTmp, b->keysA.p, b->keysB.p, nText, 0, 64, s);
+    }
+    HIPCHK(hipMemsetAsync(b->fcounts.p, 0, ((size_t)nGroups + 1) * sizeof(uint32_t), s));
+    HIPCHK(hipMemsetAsync(b->fsegB.p, 0xFF, ((size_t)nGroups + 1) * sizeof(uint32_t), s));
+    if (nText) {
+        HIPCHK(hipMemsetAsync(b->frank.p, 0xFF, (size_t)nText * sizeof(uint32_t), s));
+        hipLaunchKernelGGL(k_filter_segments, dim3((nText + 255) / 256), dim3(256), 0, s, b->keysB.p, nText, b->fsegB.p, b->fsegE.p, keyBits(keyLayout).group);
+    }
+    hipLaunchKernelGGL(k_filter_mark, dim3((nGroups + 255) / 256), dim3(256), 0, s, b->keysB.p, nGroups, b->k, mode, b->fcounts.p, b->frank.p, b->fsegB.p,
+                       b->fsegE.p, keyLayout);
+    scanExclusive(b->scanTmp, b->fcounts.p, b->foffs.p, (size_t)nGroups + 1, s);
+}
+
+// ---- naive backtracking: the filter pass of approxMatchesNaive[Hamming] itself, per read x strand (dev_bfs_naive.hpp): the occurrences
+// of the naive reads are dropped from the text queue and their survivors appended to it
+static int filterNaive(RunCtx& c) {
+    cmb_batch* b = c.b;
+    hipStream_t s = c.s;
+    const uint32_t nText = c.nText;
+    if (!b->hasNaive || !nText) return CMB_OK;
+    const uint32_t keyLayout = keyLayoutOf(b);
+    const uint32_t nG = 2u * b->nReads;
+    if (nG >= (1u << groupBits(b))) return fail(CMB_ERR_UNSUPPORTED, "more than 2^23 reads in a sub-batch with reads matched by naive backtracking");
+    c.tm.begin();
+    rankSurvivors(c, nText, nG, 1u, (const uint8_t*)b->psel.p, b->metric == CMB_METRIC_HAMMING ? 1 : 2, keyLayout);
+    HIPCHK(hipMemcpyAsync(&c.naiveSurvivors, b->foffs.p + nG, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    readCounts(c);
+    int rc = CMB_OK;
+    if (c.hcnt[3] & FLAG_CAPACITY) {
+        rc = fail(CMB_ERR_INTERNAL, "occurrence does not fit the filter key (width / distance range) or a traceback left the band");
+    } else if ((uint64_t)nText + c.naiveSurvivors >= 0xFFFFFFF0ull) {
+        rc = fail(CMB_ERR_UNSUPPORTED, "too many occurrences in one sub-batch");
+    } else {
+        if (b->text.n < (size_t)nText + c.naiveSurvivors) { // grow, keeping the records
+            DevBuf<TextOccRec> bigger;
+            bigger.alloc((size_t)nText + c.naiveSurvivors + 1024);
+            HIPCHK(hipMemcpyAsync(bigger.p, b->text.p, (size_t)nText * sizeof(TextOccRec), hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipStreamSynchronize(s));
+            std::swap(bigger.p, b->text.p);
+            std::swap(bigger.n, b->text.n);
+        }
+        hipLaunchKernelGGL(k_naive_drop, dim3((nText + 255) / 256), dim3(256), 0, s, b->text.p, nText, (const uint8_t*)b->psel.p);
+        if (c.naiveSurvivors)
+            hipLaunchKernelGGL(k_naive_keep, dim3((nText + 255) / 256), dim3(256), 0, s, b->keysB.p, nText, b->offs.p, b->k, b->frank.p, b->foffs.p,
+                               b->text.p + nText, keyLayout);
+        HIPCHK(hipGetLastError());
+        c.nText += (uint32_t)c.naiveSurvivors;
+    }
+    c.tm.end("k_naive_filter");
+    return rc;
+}
+
+// groups of the final filter: reads, or read x strand when every strand is filtered by itself
+static uint32_t filterGroups(const cmb_batch* b) { return b->perStrand ? 2u * b->nReads : b->nReads; }
+
+// ---- sort + filter on the device (getUniqueTextOccurrences / getTextOccHamming, indexinterface.cpp:1331-1491): the `total` final
+// occurrences in fout, group by group (foffs)
+static int filterFinal(RunCtx& c, uint64_t& total) {
+    cmb_batch* b = c.b;
+    hipStream_t s = c.s;
+    const uint32_t nText = c.nText, nGroups = filterGroups(b), keyLayout = keyLayoutOf(b);
+    // (group numbers 0 ... nGroups - 1: 2^24 groups fit the 24 bits of layouts 0 and 1 — a BEST sub-batch of 2^23 reads)
+    if (nGroups > (1u << groupBits(b))) return fail(CMB_ERR_UNSUPPORTED, "more filter groups in one sub-batch than the keys number");
+    c.tm.begin();
+    rankSurvivors(c, nText, nGroups, b->perStrand ? 1u : 0u, (const uint8_t*)nullptr, b->k == 0 ? 0 : (b->metric == CMB_METRIC_HAMMING ? 1 : 2), keyLayout);
+    HIPCHK(hipMemcpyAsync(&total, b->foffs.p + nGroups, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    readCounts(c);
+    int rc = CMB_OK;
+    if (c.hcnt[3] & FLAG_TRACE_RULE) {
+        rc = fail(CMB_ERR_INTERNAL, "a traceback read a band-edge bit the narrow trace rows take as implied");
+    } else if (c.hcnt[3] & FLAG_CAPACITY) {
+        rc = fail(CMB_ERR_INTERNAL, "occurrence does not fit the filter key (width / distance range) or a traceback left the band");
+    } else {
+        growTo(b->fout, total);
+        if (b->wantAln) growTo(b->foutRead, total);
+        if (total)
+            hipLaunchKernelGGL(k_filter_write, dim3((nText + 255) / 256), dim3(256), 0, s, b->keysB.p, nText, b->offs.p, b->k, b->frank.p, b->foffs.p,
+                               b->fout.p, b->wantAln ? b->foutRead.p : (uint32_t*)nullptr, b->perStrand ? 1u : 0u, keyLayout);
+        HIPCHK(hipGetLastError());
+    }
+    c.tm.end("k_filter");
+    return rc;
+}
+
+// CIGAR + sequence of every final occurrence (k_cigar), on request
+static int runCigar(RunCtx& c, uint64_t total) {
+    cmb_batch* b = c.b;
+    if (!b->wantAln) return CMB_OK;
+    c.tm.begin();
+    b->alnStride = 2u * b->k + 3u;
+    if (b->alnRec.n < total) {
+        b->alnRec.alloc((size_t)total + total / 8 + 256);
+        b->alnOps.alloc(b->alnRec.n * std::max<size_t>(b->alnStride, 2u * 7u + 3u));
+    }
+    if (total) {
+        const uint32_t cSlots = capSlots((uint32_t)std::min<uint64_t>(((total + 255) / 256) * 256, 512u * 1024u));
+        MFull mfc = c.mf;
+        if (!mfc.p) mfc.nBlk = 0; // (Hamming / exact batches have no match words: every CIGAR is len x M, nothing is traced)
+        const CigarJob job{b->offs.p, b->G.p, b->gw, b->maxLen, mfc, b->fout.p, b->foutRead.p, (uint64_t)total, b->alnOps.p, b->alnStride,
+                           b->alnRec.p, b->cnt.p + 3, (b->metric != CMB_METRIC_EDIT || b->k == 0) ? 1u : 0u};
+        launchCigar(b->ix, c.s, job, b->metric == CMB_METRIC_EDIT && b->k > CIGAR_BLOCK_WORDS_MAX_ED, b->k <= TBN_MAX_ED && !getenv("CMB_TRACE_WIDE"),
+                    vRows(b->maxLen), cSlots, b->vW, b->dpSlab, c.verbose);
+    }
+    c.tm.end("k_cigar");
+    HIPCHK(hipGetLastError());
+    return CMB_OK;
+}
+
+// the final occurrences, their offsets per group and (on request) their alignments in the page-locked buffers of the batch
+static int downloadResults(RunCtx& c, uint64_t total) {
+    cmb_batch* b = c.b;
+    hipStream_t s = c.s;
+    const uint32_t nGroups = filterGroups(b);
+    b->occs.resize(total);
+    b->occOffs.resize((size_t)nGroups + 1);
+    if (total) HIPCHK(hipMemcpyAsync(b->occs.data(), b->fout.p, (size_t)total * sizeof(cmb_occ), hipMemcpyDeviceToHost, s));
+    if (b->wantAln) {
+        b->hAlnRec.resize(total);
+        b->hAlnOps.resize((size_t)total * b->alnStride);
+        if (total) {
+            HIPCHK(hipMemcpyAsync(b->hAlnRec.data(), b->alnRec.p, (size_t)total * sizeof(AlnRec), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(b->hAlnOps.data(), b->alnOps.p, (size_t)total * b->alnStride * sizeof(uint16_t), hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(hipMemcpyAsync(c.hcnt, b->cnt.p, sizeof(c.hcnt), hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipMemcpyAsync(b->occOffs.data(), b->foffs.p, ((size_t)nGroups + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (b->wantAln && (c.hcnt[3] & FLAG_CAPACITY))
+        return fail(CMB_ERR_INTERNAL, "a CIGAR traceback left the band or an occurrence is not an alignment within its distance");
+    lap(c, "results to the host");
+    if (c.verbose) {
+        size_t fr = 0, tot = 0;
+        (void)hipMemGetInfo(&fr, &tot);
+        fprintf(stderr, "[mem] device memory in use: %.1f GB of %.1f GB\n", (tot - fr) / 1e9, tot / 1e9);
+    }
+    return CMB_OK;
+}
+
 static int batchRunOne(cmb_batch* b) {
     try {
-        cmb_index* ix = b->ix;
-        useDevice(ix->device);
-        hipStream_t s = b->stream;
-        if (b->staged) { // the chunk uploaded during the previous run becomes the batch's reads
-            HIPCHK(hipEventSynchronize(b->copyDone));
-            std::swap(b->reads.p, b->readsStage.p);
-            std::swap(b->reads.n, b->readsStage.n);
-            std::swap(b->offs.p, b->offsStage.p);
-            std::swap(b->offs.n, b->offsStage.n);
-            b->hostOffs.swap(b->hostOffsActive);
-            b->staged = false;
-        }
-        if (b->pending) { // the chunk registered since travels to the device while this run's kernels execute
-            startStagedUpload(b);
-            b->hostOffsActive.swap(b->hostOffsStage); // (offsets of the chunk in flight: the batch's from the next run on; the next registration refills hostOffsStage)
-        }
+        useDevice(b->ix->device);
+        Timer tm(b->stream, b->times);
+        RunCtx c{b, b->stream, tm};
+        int rc = adoptStagedChunk(c);
+        if (rc != CMB_OK) return rc;
         b->times.clear();
         b->done = false;
         b->hasNaive = false;
-        Timer tm(s, b->times);
-        const uint32_t nReads = b->nReads;
-        const uint32_t tasks = 2 * nReads;
-        if (nReads == 0) {
+        if (b->nReads == 0) {
             b->occs.resize(0);
             b->occOffs.resize(1);
             b->occOffs.p[0] = 0;
@@ -1004,719 +1799,61 @@ static int batchRunOne(cmb_batch* b) {
             b->done = true;
             return CMB_OK;
         }
-        uint32_t hcnt[8];
-        // (both read per run, not per process: tests set them between runs)
-        const char* verboseEnv = getenv("CMB_VERBOSE");
-        const bool verbose = verboseEnv != nullptr, smallPools = getenv("CMB_TEST_SMALL_POOLS") != nullptr;
-        // 11 ... 13 errors: the in-index matrix with 16-row blocks (GeoX, beyond the reference's 64-bit in-index matrix: dev_matrix.hpp, MXN_*),
-        // the in-text matrix with 8-row blocks
-        const bool geoX = b->wideEdit && frontierGeoOf(b) == FrontierGeo::X;
-        auto t0 = std::chrono::steady_clock::now();
-        auto lap = [&](const char* what) {
-            if (!verbose) return;
-            auto t1 = std::chrono::steady_clock::now();
-            fprintf(stderr, "[host] %-28s %7.3f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count());
-            t0 = t1;
-        };
-        Queues q{};
-        q.cnt = b->cnt.p;
-        q.counters = b->counters.p;
+        c.verboseEnv = getenv("CMB_VERBOSE");
+        c.verbose = c.verboseEnv != nullptr, c.smallPools = getenv("CMB_TEST_SMALL_POOLS") != nullptr;
+        c.geoX = b->wideEdit && frontierGeoOf(b) == FrontierGeo::X;
+        c.preset = !b->presetItems.empty();
+        c.t0 = std::chrono::steady_clock::now();
+        c.q.cnt = b->cnt.p;
+        c.q.counters = b->counters.p;
 
-        HIPCHK(hipMemsetAsync(b->counters.p, 0, CMB_CNT_MAX * sizeof(unsigned long long), s));
-        tm.begin();
-        MFull mf{nullptr, 0};
-        if (b->metric == CMB_METRIC_EDIT && b->k > 0) { // (the match words of the full reads: k_prep writes them along with the rest)
-            mf.nBlk = mfullBlocks(b->maxLen);
-            const uint64_t nW = (uint64_t)tasks * mf.nBlk;
-            if (b->mfull.n < 2 * nW) b->mfull.alloc(2 * nW);
-            mf.p = b->mfull.p;
+        if ((rc = runPrep(c)) != CMB_OK) return rc;
+        if (c.preset && (rc = adoptPreset(c)) != CMB_OK) return rc;
+        // ---- prologue + search (re-run with larger queues and pools if they overflow: nothing is truncated)
+        // (a stage that asks for another attempt has already grown its pool when the limit is tested here: the sizes of a batch
+        // whose run fails on a limit are one step larger than they would be had the test come first)
+        const bool edit = b->metric == CMB_METRIC_EDIT;
+        int poolAttempts = 0;
+        for (int attempt = 0; !c.preset; attempt++) {
+            Step step = Step::GoOn;
+            if ((rc = searchAttempt(c, attempt, step)) != CMB_OK) return rc;
+            if (step == Step::AgainNaiveQueue && attempt >= 60) return fail(CMB_ERR_INTERNAL, "the naive search's frontier keeps overflowing");
+            if (step == Step::AgainPools && ++poolAttempts >= (edit ? 48 : 24))
+                return fail(CMB_ERR_INTERNAL, edit ? "frontier pools keep overflowing" : "frontier keeps overflowing");
+            if (step != Step::GoOn) continue;
+            if (c.hcnt[3] & FLAG_CAPACITY) return fail(CMB_ERR_INTERNAL, "device search capacity exceeded (band width / descendants / stack)");
+            if (!(c.hcnt[3] & (FLAG_ITEM_OVERFLOW | FLAG_FMOCC_OVERFLOW | FLAG_DFS_OVERFLOW | FLAG_EXACT_OVERFLOW))) break;
+            if (attempt >= 60) return fail(CMB_ERR_INTERNAL, "work queues keep overflowing");
+            const uint32_t dfsCap = cap32(b->dfs.n), exCap = cap32(b->exq.n);
+            if (c.verbose)
+                fprintf(stderr, "[retry] queues too small:%s%s%s%s\n", c.hcnt[0] > c.q.itemCap ? " items" : "", c.hcnt[1] > c.q.fmCap ? " occurrences" : "",
+                        c.hcnt[5] > dfsCap ? " tasks" : "", c.hcnt[4] > exCap ? " exact" : "");
+            // (a search that stopped at the overflow has only counted what it needed up to there: the naive search of very
+            // short reads, which match all over the text, asks for orders of magnitude more than the first guess)
+            const size_t grow = b->hasNaive ? 8 : 2;
+            if (c.hcnt[0] > c.q.itemCap) b->items.alloc((size_t)c.hcnt[0] * grow + 1024);
+            if (c.hcnt[1] > c.q.fmCap) b->fm.alloc((size_t)c.hcnt[1] * grow + 1024);
+            if (c.hcnt[5] > dfsCap) b->dfs.alloc((size_t)c.hcnt[5] + c.hcnt[5] / 8 + 1024);
+            if (c.hcnt[4] > exCap) b->exq.alloc((size_t)c.hcnt[4] + c.hcnt[4] / 8 + 1024);
         }
-        launchPrep(s, b->reads.p, b->offs.p, nReads, b->maxLen, b->gw, b->seq.p, b->G.p, b->rec.p, b->recW, const_cast<uint4*>(mf.p),
-                   mf.nBlk, verbose);
-        tm.end("k_prep");
+        c.nItems = c.hcnt[0], c.nFm = c.hcnt[1];
+        lap(c, "prep + search");
+        if ((rc = dedupFmOccurrences(c)) != CMB_OK) return rc;
+        lap(c, "fm occurrences");
+        if ((rc = locateAndVerify(c)) != CMB_OK) return rc;
+        lap(c, "verify + traceback + fmocc");
+        if (c.preset) return finishPreset(c);
 
-        // ---- prologue + DFS (re-run with larger queues if they overflow: nothing is truncated)
-        const uint32_t pCap = capSlots(envSlots("CMB_P_SLOTS", 256u * 32768u)); // (one lane per read x strand
-        // up to 8 M: k_parts 65.7 ms with 512 k lanes looping over the tasks, 65.0 / 62.1 / 62.5 ms with 1 M / 4 M / 8 M)
-        const uint32_t pSlots = std::min<uint32_t>(((tasks + 255) / 256) * 256, pCap);
-        const bool preset = !b->presetItems.empty();
-        if (preset) { // (no search: the candidates come from the caller)
-            if (b->items.n < b->presetItems.size()) b->items.alloc(b->presetItems.size() + 1024);
-            HIPCHK(hipMemsetAsync(b->cnt.p, 0, 8 * sizeof(uint32_t), s));
-            HIPCHK(hipMemcpyAsync(b->items.p, b->presetItems.data(), b->presetItems.size() * sizeof(uint4), hipMemcpyHostToDevice, s));
-            HIPCHK(hipStreamSynchronize(s));
-            memset(hcnt, 0, sizeof(hcnt));
-            hcnt[0] = (uint32_t)b->presetItems.size();
-            q.items = b->items.p;
-            q.itemCap = cap32(b->items.n);
-        }
-        int bfsAttempts = 0;
-        for (int attempt = 0; !preset; attempt++) {
-            HIPCHK(hipMemsetAsync(b->cnt.p, 0, 8 * sizeof(uint32_t), s));
-            if (attempt) {
-                HIPCHK(hipMemsetAsync(b->counters.p, 0, CMB_CNT_MAX * sizeof(unsigned long long), s));
-            }
-            q.items = b->items.p;
-            q.itemCap = cap32(b->items.n);
-            q.fm = b->fm.p;
-            q.fmCap = cap32(b->fm.n);
-            q.text = b->text.p;
-            q.textCap = cap32(b->text.n);
-            const uint32_t dfsCap = cap32(b->dfs.n);
-            tm.begin();
-            const uint32_t pParts = b->k ? b->sNumParts : 1;
-            const uint32_t stratBytes = (uint32_t)(((b->wide ? sizeof(DevStrategyKT<MAXP_WIDE>) : sizeof(DevStrategyK)) + 15) / 16 * 16);
-            const uint32_t rdWords = 2 * ((b->maxLen + 31) / 32);
-            const bool longReads = b->maxLen > 256;
-            const uint32_t exCap = cap32(b->exq.n);
-            if (b->k) {
-                if (b->psel.n < tasks) b->psel.alloc(tasks);
-                const size_t pLds = stratBytes + (5 * pParts + rdWords) * 256 * sizeof(uint32_t);
-                gridLine(verbose, "k_parts", tasks, pSlots);
-                withTables(b, [&](auto mp) {
-                    withInt<3>((int)b->sPartition, [&](auto part) {
-                        withBools(
-                            [&](auto lng) {
-                                constexpr int MP = decltype(mp)::value;
-                                auto kp = k_parts<decltype(part)::value, decltype(lng)::value, MP>;
-                                if (MP != MAXP && pLds > 64 * 1024)
-                                    HIPCHK(hipFuncSetAttribute((const void*)kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pLds));
-                                hipLaunchKernelGGL(kp, dim3(pSlots / 256), dim3(256), pLds, s, ix->d, stratOf<MP>(b), nReads, b->k, b->maxLen, b->seq.p,
-                                                   (const uint4*)b->rec.p, b->recW / 4, partsOf<MP>(b), b->psel.p, b->dfs.p, dfsCap, b->exq.p, exCap, q);
-                            },
-                            longReads);
-                    });
-                });
-            }
-            // k_exact: k = 0 one lane per read x strand; otherwise the ExactTasks k_parts left — their number is on the device, a small
-            // grid loops over them (none in the common case: every search of the multiple_opt schemes has one exact phase)
-            const uint32_t eSlots = capSlots(b->k ? 256u * 256u : (uint32_t)std::min<uint64_t>((((uint64_t)tasks + 255) / 256) * 256, 256ull * 4096ull));
-            if (!b->k) gridLine(verbose, "k_exact", tasks, eSlots); // (k > 0: the number of its tasks is on the device until the prologue is read back)
-            const size_t eLds = stratBytes + (pParts + rdWords) * 256 * sizeof(uint32_t);
-            withTables(b, [&](auto mp) {
-                constexpr int MP = decltype(mp)::value;
-                auto ke = withBools([](auto lng) { return k_exact<lng(), MP>; }, longReads);
-                hipLaunchKernelGGL(ke, dim3(eSlots / 256), dim3(256), eLds, s, ix->d, stratOf<MP>(b), nReads, b->k, b->maxLen, b->seq.p,
-                                   (const uint4*)b->rec.p, b->recW / 4, partsOf<MP>(b), b->exq.p, exCap, b->dfs.p, dfsCap, q);
-            });
-            tm.end("k_partition");
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            uint32_t flags = hcnt[3];
-            // ---- reads not longer than the number of parts (and every read of a one-part strategy): naive backtracking
-            // (searchstrategy.cpp:148-152, :442-459 -> dev_bfs_naive.hpp); k_parts marked them in psel
-            b->hasNaive = (flags & FLAG_UNSUPPORTED_READ) != 0;
-            if (b->hasNaive) {
-                tm.begin();
-                const uint32_t maxPassN = b->maxLen + 2 * b->k + 4; // (rows of the matrix: len + 2 k + 1 at most)
-                if (!b->nvQCap) b->nvQCap = smallPools ? 64 : 16384;
-                for (int j = 0; j < 2; j++)
-                    if (b->nvQ[j].n < 3 * b->nvQCap) b->nvQ[j].alloc(3 * b->nvQCap);
-                const size_t cntWords = (size_t)maxPassN + 2;
-                if (b->nvCnt.n < cntWords) b->nvCnt.alloc(cntWords);
-                HIPCHK(hipMemsetAsync(b->nvCnt.p, 0, cntWords * sizeof(uint32_t), s));
-                NaiveBufs N{};
-                N.Q[0] = b->nvQ[0].p;
-                N.Q[1] = b->nvQ[1].p;
-                N.qCap = cap32(b->nvQ[0].n / 3);
-                N.nq = b->nvCnt.p;
-                const bool edit = b->metric == CMB_METRIC_EDIT;
-                hipLaunchKernelGGL(k_naive_start, dim3((tasks + 255) / 256), dim3(256), 0, s, ix->d, b->psel.p, b->offs.p, tasks,
-                                   b->k, edit ? 0u : 1u, N, q, geoX ? 1u : 0u);
-                std::vector<uint32_t> hc(cntWords);
-                uint32_t pass = 0, peakQ = 0;
-                bool drained = false;
-                // (the matrix of 11 ... 13 errors is the edit distance's alone)
-                auto kNaive = withBools([](auto e, auto x) { return k_naive_pass<e(), e() && x()>; }, edit, geoX);
-                const uint32_t nvGrid = capBlocks(BFS_GRID); // (k_naive_start above takes one lane per read x strand and does not loop: no cap)
-                while (!drained && pass < maxPassN) {
-                    const uint32_t upTo = std::min(pass + 16u, maxPassN);
-                    for (; pass < upTo; pass++)
-                        hipLaunchKernelGGL(kNaive, dim3(nvGrid), dim3(256), 0, s, ix->d, N,
-                                           pass, b->offs.p, b->gw, b->G.p, b->seq.p, b->maxLen, b->k, q);
-                    HIPCHK(hipMemcpyAsync(hc.data(), b->nvCnt.p, cntWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                    HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
-                    HIPCHK(hipStreamSynchronize(s));
-                    if (hcnt[3] & (FLAG_NAIVE_Q | FLAG_ITEM_OVERFLOW | FLAG_FMOCC_OVERFLOW)) break;
-                    drained = hc[pass] == 0;
-                }
-                for (uint32_t p2 = 0; p2 <= pass && p2 < cntWords; p2++) peakQ = std::max(peakQ, hc[p2]);
-                if (verbose) fprintf(stderr, "[naive] %u roots, %u passes, peak frontier %u\n", hc[0], pass, peakQ);
-                gridLine(verbose, "k_naive_pass", peakQ, 256ull * nvGrid); // (the largest frontier of a pass)
-                tm.end("k_naive");
-                HIPCHK(hipGetLastError());
-                flags = hcnt[3];
-                if (flags & FLAG_NAIVE_Q) {
-                    if (attempt >= 60) return fail(CMB_ERR_INTERNAL, "the naive search's frontier keeps overflowing");
-                    b->nvQCap = std::max<size_t>(4 * b->nvQCap, (size_t)peakQ + peakQ / 4);
-                    continue;
-                }
-                if (!drained && !(flags & (FLAG_ITEM_OVERFLOW | FLAG_FMOCC_OVERFLOW)))
-                    return fail(CMB_ERR_INTERNAL, "the naive search did not finish within its pass bound");
-            }
-            if (flags & FLAG_SEED_OVERLAP)
-                return fail(CMB_ERR_INVALID,
-                            "dynamic partitioning: the seeds of a read overlap — the k-mer size of the index is too large "
-                            "for the seeding positions of this search strategy at this read length (the reference caps "
-                            "the k-mer size, e.g. at 4 for kuch2 and 01*0: alignparameters.cpp:1070-1114, :1275-1278)");
-            const uint32_t nDfs = hcnt[5];
-            if (verbose && b->k) fprintf(stderr, "[prologue] %u items, %u search tasks, %u searches with further exact phases\n", hcnt[0], nDfs, hcnt[4]);
-            if (b->k) gridLine(verbose, "k_exact", hcnt[4], eSlots);
-            if (!(flags & (FLAG_ITEM_OVERFLOW | FLAG_DFS_OVERFLOW | FLAG_EXACT_OVERFLOW)) && nDfs) {
-                tm.begin();
-                if (b->metric == CMB_METRIC_EDIT) {
-                    // ---- frontier search: start pass, then (expand, events) per level until both queues drain
-                    const uint32_t maxPass = 2 * b->maxLen + 8 * (b->wide ? MAXP_WIDE : MAXP) + 64;
-                    // node planes / uint4 per event of the record geometry (dev_bfs_edit.hpp: GeoN, GeoW)
-                    const size_t qPlanes = 3 + (b->wide ? GeoW::PK_U4 : GeoN::PK_U4), evU4 = 1 + (b->wide ? GeoW::PK_U4 : GeoN::PK_U4);
-                    if (!b->bfsQCap) {
-                        // first guess; every pool grows (and the search re-runs) when it turns out too small.
-                        // CMB_TEST_SMALL_POOLS starts from almost nothing so that tests exercise that path.
-                        const size_t slack = smallPools ? 64 : 65536;
-                        const size_t per = smallPools ? 0 : 1;
-                        b->bfsQCap = per * (size_t)nReads * 2 + slack;
-                        b->bfsEvCap = per * (size_t)nReads / 2 + slack;
-                        b->bfsFCap = per * (size_t)nReads * 16 + slack;
-                        b->bfsCCap = per * (size_t)nReads * 2 + slack;
-                        b->bfsACap = per * (size_t)nReads * 8 + slack;
-                    }
-                    b->bfsQCap = std::max<size_t>(b->bfsQCap, (size_t)nDfs + 1024);
-                    for (int j = 0; j < 2; j++) {
-                        if (b->bfsQ[j].n < qPlanes * b->bfsQCap) b->bfsQ[j].alloc(qPlanes * b->bfsQCap);
-                        if (b->bfsEv[j].n < evU4 * b->bfsEvCap) b->bfsEv[j].alloc(evU4 * b->bfsEvCap);
-                    }
-                    if (b->bfsF.n < F_U4 * b->bfsFCap) b->bfsF.alloc(F_U4 * b->bfsFCap);
-                    // (GeoX: blocks of 16 rows — up to 32 of them for 480 + 26 rows, two uint4 of match words each)
-                    const uint32_t ctxU4 = geoX ? CTX_U4_X : ctxU4For(b->maxLen);
-                    if (b->bfsC.n < (size_t)ctxU4 * b->bfsCCap) b->bfsC.alloc((size_t)ctxU4 * b->bfsCCap);
-                    if (b->bfsA.n < b->bfsACap) b->bfsA.alloc(b->bfsACap);
-                    const size_t cntWords = 2 * ((size_t)maxPass + 2) + 4;
-                    if (b->bfsCnt.n < cntWords) b->bfsCnt.alloc(cntWords);
-                    if (b->bfsBlockCnt.n < (size_t)BFS_GRID_CNT * 4) b->bfsBlockCnt.alloc((size_t)BFS_GRID_CNT * 4);
-                    HIPCHK(hipMemsetAsync(b->bfsCnt.p, 0, cntWords * sizeof(uint32_t), s));
-                    HIPCHK(hipMemsetAsync(b->bfsBlockCnt.p, 0, (size_t)BFS_GRID_CNT * 4 * sizeof(unsigned long long), s));
-                    BfsBufs B{};
-                    for (int j = 0; j < 2; j++) {
-                        B.Q[j] = b->bfsQ[j].p;
-                        B.Ev[j] = b->bfsEv[j].p;
-                    }
-                    B.F = b->bfsF.p;
-                    B.C = b->bfsC.p;
-                    B.A = b->bfsA.p;
-                    B.qCap = cap32(b->bfsQ[0].n / qPlanes);
-                    B.evCap = cap32(b->bfsEv[0].n / evU4);
-                    B.fCap = cap32(b->bfsF.n / F_U4);
-                    B.cCap = cap32(b->bfsC.n / ctxU4);
-                    B.ctxU4 = ctxU4;
-                    B.ctxMblk = geoX ? CTX_MBLK_X : ctxMblkFor(b->maxLen);
-                    B.aCap = cap32(b->bfsA.n);
-                    B.chain = getenv("CMB_BFS_CHAIN") ? (uint32_t)std::max(1, atoi(getenv("CMB_BFS_CHAIN"))) : BFS_CHAIN;
-                    B.gridX = capBlocks(std::min<uint32_t>(BFS_GRID_CNT, envBlocks("CMB_BFS_GRID", BFS_GRID_X)));
-                    B.gridEv = capBlocks(envBlocks("CMB_BFS_GRID_EV", BFS_GRID_EV));
-                    // (CMB_TEST_NARROW_WV: tests lower the bound so that the re-run on the 64-bit geometry is exercised)
-                    B.narrowWv = getenv("CMB_TEST_NARROW_WV") ? (uint32_t)std::max(0, atoi(getenv("CMB_TEST_NARROW_WV"))) : 0xFFFFu;
-                    B.nq = b->bfsCnt.p;
-                    B.ne = b->bfsCnt.p + (maxPass + 2);
-                    B.pool = b->bfsCnt.p + 2 * (maxPass + 2);
-                    B.blockCnt = b->bfsBlockCnt.p;
-                    // up to 6 errors the frontier carries the in-index matrix on 32-bit words (GeoN32, dev_matrix.hpp: MXS_*); CMB_MATRIX64=1
-                    // keeps the reference's 64-bit words (GeoN), as does a batch one of whose phases did not fit the small matrix
-                    const FrontierGeo geo = frontierGeoOf(b);
-                    const uint32_t startGrid = capBlocks(std::min<uint32_t>((nDfs + 255) / 256, BFS_GRID));
-                    gridLine(verbose, "k_bfs_start", nDfs, 256ull * startGrid);
-                    withGeo(geo, [&](auto g) {
-                        using Geo = typename decltype(g)::type;
-                        hipLaunchKernelGGL(k_bfs_start<Geo>, dim3(startGrid), dim3(256), 0, s, ix->d, stratOf<Geo::MP>(b), B, b->dfs.p, nDfs, b->offs.p,
-                                           b->gw, b->G.p, partsOf<Geo::MP>(b), q);
-                    });
-                    // (the instance of a pass is chosen here, once per attempt: the loop below calls through a pointer)
-                    const auto bfsPass = withGeo(geo, [](auto g) { return &launchBfsPass<typename decltype(g)::type>; });
-                    std::vector<uint32_t> hc(cntWords);
-                    // passes between two looks at the queue sizes (a pass on a drained frontier costs the device ~4 us, a look costs the host a round trip)
-                    const uint32_t CHECK = getenv("CMB_BFS_CHECK") ? (uint32_t)std::max(1, atoi(getenv("CMB_BFS_CHECK"))) : 16;
-                    uint32_t pass = 0, peakQ = 0, peakEv = 0;
-                    bool drained = false;
-                    while (!drained && pass < maxPass) {
-                        const uint32_t upTo = std::min(pass + CHECK, maxPass);
-                        for (; pass < upTo; pass++) bfsPass(b, B, pass, q);
-                        HIPCHK(hipMemcpyAsync(hc.data(), b->bfsCnt.p, cntWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                        HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
-                        HIPCHK(hipStreamSynchronize(s));
-                        if (hcnt[3] & BFS_STOP) break;
-                        drained = hc[pass] == 0 && hc[maxPass + 2 + pass] == 0;
-                    }
-                    for (uint32_t p2 = 0; p2 <= pass && p2 < maxPass + 2; p2++) {
-                        peakQ = std::max(peakQ, hc[p2]);
-                        peakEv = std::max(peakEv, hc[maxPass + 2 + p2]);
-                    }
-                    const uint32_t* pool = hc.data() + 2 * (maxPass + 2);
-                    if (verbose)
-                        fprintf(stderr, "[bfs] %u tasks, %u passes, peak frontier %u, peak events %u, F %u, contexts %u, arena %u\n",
-                                nDfs, pass, peakQ, peakEv, pool[0], pool[1], pool[2]);
-                    gridLine(verbose, "k_bfs_pass", peakQ, 256ull * B.gridX); // (the largest frontier and the most events of a pass)
-                    gridLine(verbose, "k_bfs_pass_events", peakEv, 256ull * B.gridEv);
-                    if (verbose && atoi(verboseEnv) > 1)
-                        for (uint32_t p2 = 0; p2 <= pass; p2++)
-                            fprintf(stderr, "  pass %u: %u nodes, %u events\n", p2, hc[p2], hc[maxPass + 2 + p2]);
-                    hipLaunchKernelGGL(k_bfs_finish, dim3(1), dim3(256), 0, s, B, q);
-                    if (hcnt[3] & FLAG_NARROW_MATRIX) { // (a first column wider than the small matrix holds: once more on the reference's words)
-                        if (verbose) fprintf(stderr, "[bfs] a phase did not fit the 32-bit in-index matrix: re-running on 64-bit words\n");
-                        b->noSmallMatrix = true;
-                        HIPCHK(hipStreamSynchronize(s));
-                        tm.end("k_dfs");
-                        continue;
-                    }
-                    if (hcnt[3] & (FLAG_BFS_Q | FLAG_BFS_EV | FLAG_BFS_F | FLAG_BFS_CTX | FLAG_BFS_ARENA)) {
-                        // a pool was too small: grow what was asked for (at least x2) and run the search again
-                        // (an attempt only shows the demand up to the pass that overflowed: beyond 7 errors, where the first guesses are far
-                        // off — 64 reads at 12 errors on 3 Gbp took eleven attempts at x 2 —, the pools grow x 4)
-                        if (++bfsAttempts >= 48) return fail(CMB_ERR_INTERNAL, "frontier pools keep overflowing");
-                        const size_t gf = b->k > 7 ? 4 : 2;
-                        if (hcnt[3] & FLAG_BFS_Q) b->bfsQCap = std::max<size_t>(gf * b->bfsQCap, (size_t)peakQ + peakQ / 4);
-                        if (hcnt[3] & FLAG_BFS_EV) b->bfsEvCap = std::max<size_t>(gf * b->bfsEvCap, (size_t)peakEv + peakEv / 4);
-                        if (hcnt[3] & FLAG_BFS_F) b->bfsFCap = std::max<size_t>(gf * b->bfsFCap, (size_t)pool[0] + pool[0] / 4);
-                        if (hcnt[3] & FLAG_BFS_CTX) b->bfsCCap = std::max<size_t>(gf * b->bfsCCap, (size_t)pool[1] + pool[1] / 4);
-                        if (hcnt[3] & FLAG_BFS_ARENA) b->bfsACap = std::max<size_t>(gf * b->bfsACap, (size_t)pool[2] + pool[2] / 4);
-                        HIPCHK(hipStreamSynchronize(s));
-                        tm.end("k_dfs");
-                        continue;
-                    }
-                    if (!drained && !(hcnt[3] & BFS_STOP))
-                        return fail(CMB_ERR_INTERNAL, "frontier search did not finish within its pass bound");
-                } else {
-                    // ---- Hamming distance: the same frontier idea without a matrix (dev_bfs_hamming.hpp)
-                    const uint32_t maxPass = b->maxLen + 2 * (b->wide ? MAXP_WIDE : MAXP) + 16;
-                    if (!b->bfsQCap) b->bfsQCap = (smallPools ? 0 : (size_t)nReads * 4) + 1024;
-                    b->bfsQCap = std::max<size_t>(b->bfsQCap, (size_t)nDfs + 1024);
-                    for (int j = 0; j < 2; j++)
-                        if (b->bfsQ[j].n < 2 * b->bfsQCap) b->bfsQ[j].alloc(2 * b->bfsQCap);
-                    const size_t cntWords = (size_t)maxPass + 2;
-                    if (b->bfsCnt.n < cntWords) b->bfsCnt.alloc(cntWords);
-                    if (b->bfsBlockCnt.n < (size_t)BFS_GRID_CNT * 4) b->bfsBlockCnt.alloc((size_t)BFS_GRID_CNT * 4);
-                    HIPCHK(hipMemsetAsync(b->bfsCnt.p, 0, cntWords * sizeof(uint32_t), s));
-                    HIPCHK(hipMemsetAsync(b->bfsBlockCnt.p, 0, (size_t)BFS_GRID_CNT * 4 * sizeof(unsigned long long), s));
-                    HbfsBufs H{};
-                    H.Q[0] = b->bfsQ[0].p;
-                    H.Q[1] = b->bfsQ[1].p;
-                    H.qCap = cap32(b->bfsQ[0].n / 2);
-                    H.nq = b->bfsCnt.p;
-                    H.blockCnt = b->bfsBlockCnt.p;
-                    const uint32_t hLds = stratBytes;
-                    const uint32_t startGrid = capBlocks(std::min<uint32_t>((nDfs + 255) / 256, BFS_GRID)), passGrid = capBlocks(BFS_GRID);
-                    gridLine(verbose, "k_hbfs_start", nDfs, 256ull * startGrid);
-                    withTables(b, [&](auto mp) {
-                        constexpr int MP = decltype(mp)::value;
-                        hipLaunchKernelGGL((k_hbfs<true, MP>), dim3(startGrid), dim3(256), hLds, s, ix->d, stratOf<MP>(b), H, 0u, b->dfs.p, nDfs, b->maxLen,
-                                           b->seq.p, partsOf<MP>(b), q);
-                    });
-                    std::vector<uint32_t> hc(cntWords);
-                    uint32_t pass = 0, peakQ = 0;
-                    bool drained = false;
-                    while (!drained && pass < maxPass) {
-                        const uint32_t upTo = std::min(pass + 16u, maxPass);
-                        for (; pass < upTo; pass++)
-                            withTables(b, [&](auto mp) {
-                                constexpr int MP = decltype(mp)::value;
-                                hipLaunchKernelGGL((k_hbfs<false, MP>), dim3(passGrid), dim3(256), hLds, s, ix->d, stratOf<MP>(b), H, pass,
-                                                   (const DfsTask*)nullptr, 0u, b->maxLen, b->seq.p, partsOf<MP>(b), q);
-                            });
-                        HIPCHK(hipMemcpyAsync(hc.data(), b->bfsCnt.p, cntWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                        HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
-                        HIPCHK(hipStreamSynchronize(s));
-                        if (hcnt[3] & BFS_STOP) break;
-                        drained = hc[pass] == 0;
-                    }
-                    for (uint32_t p2 = 0; p2 <= pass && p2 < cntWords; p2++) peakQ = std::max(peakQ, hc[p2]);
-                    if (verbose) fprintf(stderr, "[hbfs] %u tasks, %u passes, peak frontier %u\n", nDfs, pass, peakQ);
-                    gridLine(verbose, "k_hbfs_pass", peakQ, 256ull * passGrid); // (the largest frontier of a pass)
-                    BfsBufs Bf{};
-                    Bf.blockCnt = b->bfsBlockCnt.p;
-                    hipLaunchKernelGGL(k_bfs_finish, dim3(1), dim3(256), 0, s, Bf, q);
-                    if (hcnt[3] & FLAG_BFS_Q) {
-                        if (++bfsAttempts >= 24) return fail(CMB_ERR_INTERNAL, "frontier keeps overflowing");
-                        b->bfsQCap = std::max<size_t>(2 * b->bfsQCap, (size_t)peakQ + peakQ / 4);
-                        HIPCHK(hipStreamSynchronize(s));
-                        tm.end("k_dfs");
-                        continue;
-                    }
-                    if (!drained && !(hcnt[3] & BFS_STOP))
-                        return fail(CMB_ERR_INTERNAL, "frontier search did not finish within its pass bound");
-                }
-                tm.end("k_dfs");
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
-                HIPCHK(hipStreamSynchronize(s));
-                flags = hcnt[3];
-            }
-            if (flags & FLAG_CAPACITY)
-                return fail(CMB_ERR_INTERNAL, "device search capacity exceeded (band width / descendants / stack)");
-            if (flags & (FLAG_ITEM_OVERFLOW | FLAG_FMOCC_OVERFLOW | FLAG_DFS_OVERFLOW | FLAG_EXACT_OVERFLOW)) {
-                if (attempt >= 60) return fail(CMB_ERR_INTERNAL, "work queues keep overflowing");
-                if (verbose)
-                    fprintf(stderr, "[retry] queues too small:%s%s%s%s\n", hcnt[0] > q.itemCap ? " items" : "", hcnt[1] > q.fmCap ? " occurrences" : "",
-                            hcnt[5] > dfsCap ? " tasks" : "", hcnt[4] > exCap ? " exact" : "");
-                // (a search that stopped at the overflow has only counted what it needed up to there: the naive search of very
-                // short reads, which match all over the text, asks for orders of magnitude more than the first guess)
-                const size_t grow = b->hasNaive ? 8 : 2;
-                if (hcnt[0] > q.itemCap) b->items.alloc((size_t)hcnt[0] * grow + 1024);
-                if (hcnt[1] > q.fmCap) b->fm.alloc((size_t)hcnt[1] * grow + 1024);
-                if (hcnt[5] > dfsCap) b->dfs.alloc((size_t)hcnt[5] + hcnt[5] / 8 + 1024);
-                if (hcnt[4] > exCap) b->exq.alloc((size_t)hcnt[4] + hcnt[4] / 8 + 1024);
-                continue;
-            }
-            break;
-        }
-        const uint32_t nItems = hcnt[0], nFm = hcnt[1];
-        lap("prep + search");
-
-        // ---- de-duplicate the in-index occurrences (Occurrences::eraseDoublesFM, indexhelpers.h:2135-2146)
-        uint32_t nFmUniq = 0;
-        if (nFm) {
-            if (b->fmKeysA.n < nFm) {
-                b->fmKeysA.alloc((size_t)nFm + nFm / 4 + 256);
-                b->fmKeysB.alloc(b->fmKeysA.n);
-                b->fmIdxA.alloc(b->fmKeysA.n);
-                b->fmIdxB.alloc(b->fmKeysA.n);
-                b->fmUniq.alloc(b->fmKeysA.n);
-            }
-            if (b->fmN.n < 1) b->fmN.alloc(1);
-            HIPCHK(hipMemsetAsync(b->fmN.p, 0, sizeof(uint32_t), s));
-            hipLaunchKernelGGL(k_fm_keys, dim3((nFm + 255) / 256), dim3(256), 0, s, b->fm.p, nFm, b->fmKeysA.p, b->fmIdxA.p);
-            sortPairs(b->sortTmp, b->fmKeysA.p, b->fmKeysB.p, b->fmIdxA.p, b->fmIdxB.p, nFm, 0, 64, s);
-            hipLaunchKernelGGL(k_fm_unique, dim3((nFm + 255) / 256), dim3(256), 0, s, b->fm.p, b->fmKeysB.p, b->fmIdxB.p, nFm,
-                               b->fmUniq.p, b->fmN.p, q);
-            HIPCHK(hipMemcpyAsync(&nFmUniq, b->fmN.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        }
-        lap("fm occurrences");
-
-        // ---- locate + verify; text queue retried on overflow
-        // traceback task queue: at most one task per item + the chunk slack of every k_verify wavefront
-        // (a chunk of 256 is retired when the wavefront's next group does not fit: at most 63 holes per chunk)
-        const size_t tbNeed = (size_t)nItems + (size_t)nItems / 2 + (size_t)(256u * 2048u / 64u + 1) * 256u;
-        if (b->tbq.n < tbNeed) b->tbq.alloc(tbNeed + nItems / 8);
-        for (int attempt = 0;; attempt++) {
-            q.text = b->text.p;
-            q.textCap = cap32(b->text.n);
-            uint32_t zero[2] = {0, 0};
-            HIPCHK(hipMemcpyAsync(b->cnt.p + 2, zero, sizeof(zero), hipMemcpyHostToDevice, s));
-            HIPCHK(hipMemcpyAsync(b->cnt.p + 7, zero, sizeof(uint32_t), hipMemcpyHostToDevice, s));
-            unsigned long long keep[CMB_CNT_MAX];
-            HIPCHK(hipMemcpyAsync(keep, b->counters.p, sizeof(keep), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            if (nItems) {
-                // (lanes of k_verify: 128 k / 256 k / 512 k -> 34.8 / 32.0 / 35.9 ms of the locate group on the headline workload, round 4)
-                const uint32_t vCap = capSlots(envSlots("CMB_V_SLOTS", 256u * 1024u, 256u * 2048u));
-                const uint32_t vSlots = std::min<uint32_t>(((nItems + 255) / 256) * 256, vCap);
-                gridLine(verbose, "k_verify", nItems, vSlots);
-                // Edit distance: identical verifications (same read x strand, text window and bounds — the parts of
-                // one read seeding the same alignment) are performed once: k_verify only locates and emits a key per
-                // candidate, the keys are sorted and run-length encoded, k_verify_edit verifies the distinct ones and
-                // scales the counters by the multiplicities.
-                // (25 key bits for read x strand; 23 in the key layout of batches at 8 ... 13 errors — 64 - VKW_RS — whose sub-batches
-                // hold at most 2^20 reads: the sorted bits below end at VKW_RS + rsBits <= 64)
-                const bool dedup = b->metric == CMB_METRIC_EDIT && b->k > 0 && 2ull * nReads < (b->wideEdit ? (1ull << (64u - VKW_RS)) : (1ull << 25));
-                if (b->wideEdit && !dedup) return fail(CMB_ERR_INTERNAL, "a sub-batch beyond 7 errors holds more reads than its verification keys number");
-                const uint32_t tbCap = cap32(b->tbq.n);
-                const char* vGroup = "k_verify";
-                tm.begin();
-                if (dedup) growTo(b->vkeysA, nItems), growTo(b->vkeysB, nItems), growTo(b->vcounts, nItems), growTo(b->vruns, 4);
-                auto kv = withBools([](auto keys) { return k_verify<keys()>; }, dedup);
-                hipLaunchKernelGGL(kv, dim3(vSlots / 256), dim3(256), 0, s, ix->d, b->offs.p, b->maxLen, b->gw,
-                                   b->seq.p, mf, b->items.p, nItems, b->tbq.p, tbCap,
-                                   dedup ? b->vkeysA.p : (unsigned long long*)nullptr, q, b->wideEdit ? 1u : 0u); // (1: the wide key layout)
-                if (dedup) {
-                    uint32_t nRuns = 0;
-                    // sorted bits: low VK_LOW bits of the start, the bounds, read x strand (2 nReads < 2^rsBits, so
-                    // that the all-ones key of the other items sorts behind every real key) — see packVerifyKey
-                    uint32_t rsBits = 1;
-                    while ((1ull << rsBits) <= 2ull * nReads) rsBits++;
-                    const uint32_t bit0 = 32u - VK_LOW, bit1 = (b->wideEdit ? VKW_RS : 39u) + rsBits;
-                    sortKeys(b->sortTmp, b->vkeysA.p, b->vkeysB.p, nItems, bit0, bit1, s);
-                    runLengthEncode(b->scanTmp, b->vkeysB.p, nItems, b->vkeysA.p, b->vcounts.p, b->vruns.p, s);
-                    HIPCHK(hipMemcpyAsync(&nRuns, b->vruns.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                    HIPCHK(hipStreamSynchronize(s));
-                    tm.end("k_verify"); // locate + key sort + run-length encode; the matrix stages are timed apart
-                    vGroup = "k_verify_edit";
-                    tm.begin();
-                    if (verbose) fprintf(stderr, "[verify] %u items, %u distinct keys\n", nItems, nRuns);
-                    if (nRuns && b->wideEdit) {
-                        // 8 ... 13 errors: the band (up to 53 columns) needs the wide left margins of the 64-bit in-text matrix (dev_matrix.hpp:
-                        // MXX_*, MXY_*): k_wide_filter sorts out the candidates that never reach their final column, k_verify_wide<true> verifies the rest
-                        const uint32_t fGrid = capBlocks(std::min<uint32_t>((nRuns + 255) / 256, 2048u));
-                        gridLine(verbose, "k_wide_filter", nRuns, 256ull * fGrid);
-                        // (every key, the slots a wavefront leaves unused when it retires a chunk — fewer than 64 of 256 —, a chunk per wavefront)
-                        const size_t listNeed = (size_t)nRuns + nRuns / 3 + (size_t)fGrid * 4 * 256 + 512;
-                        if (b->dpList.n < listNeed) b->dpList.alloc(listNeed + listNeed / 8);
-                        if (b->dpWork.n < 4) b->dpWork.alloc(4);
-                        HIPCHK(hipMemsetAsync(b->dpWork.p, 0, 4 * sizeof(uint32_t), s));
-                        auto kFilter = k_wide_filter<WxTen>;
-                        auto kWide = k_verify_wide<true, WxTen>;
-                        if (geoX) kFilter = k_wide_filter<WxThirteen>, kWide = k_verify_wide<true, WxThirteen>;
-                        hipLaunchKernelGGL(kFilter, dim3(fGrid), dim3(256), 0, s, ix->d, b->offs.p, b->G.p, b->gw, b->vkeysA.p, b->vcounts.p, nRuns,
-                                           b->dpWork.p, b->dpList.p, cap32(b->dpList.n), q);
-                        const uint32_t slotBytes = (vwRows(b->maxLen) + 1u) * VW_ROW_BYTES;
-                        // (six wavefronts per SIMD: 1024 SIMDs x 6 x 64 lanes — forward pass and traceback wait for memory; a slot is 3 - 8 KB)
-                        const uint32_t dSlots = std::min<uint32_t>(((nRuns + 255) / 256) * 256, capSlots(envSlots("CMB_VW_SLOTS", 256u * 1536u)));
-                        if (b->dpSlab.n < (size_t)slotBytes * dSlots) b->dpSlab.alloc((size_t)slotBytes * dSlots);
-                        hipLaunchKernelGGL(kWide, dim3(dSlots / 256), dim3(256), 0, s, ix->d, b->offs.p, b->maxLen, b->seq.p, b->G.p, b->gw,
-                                           (const uint4*)nullptr, cap32(b->dpList.n), b->vkeysA.p, b->vcounts.p, b->dpList.p, b->dpWork.p + 1, b->dpSlab.p, slotBytes, q);
-                        if (verbose) {
-                            uint32_t hw[2];
-                            HIPCHK(hipMemcpyAsync(hw, b->dpWork.p, sizeof(hw), hipMemcpyDeviceToHost, s));
-                            HIPCHK(hipStreamSynchronize(s));
-                            fprintf(stderr, "[verify] %u list slots (survivors and holes) for %u distinct candidates\n", hw[1], nRuns);
-                            gridLine(verbose, "k_verify_wide", hw[1], dSlots); // (it loops over the list the filter left)
-                        }
-                    } else if (nRuns) {
-                        // staged verification (kernels.hpp: k_verify_stage): one launch per nb 32-row matrix blocks,
-                        // survivor lists ping-pong, list sizes stay on the device
-                        // nb 32-row blocks per stage: fewer stages re-fetch fewer text lines and move fewer survivor
-                        // records, more blocks leave more lanes idle behind candidates that ended (CMB_STAGE_BLOCKS)
-                        const char* nbEnv = getenv("CMB_STAGE_BLOCKS");
-                        // (round 4, 150 bp reads at 4 errors: 1 / 2 / 3 / 4 / 6 blocks per stage -> 53.1 / 31.4 / 29.4 / 32.0 / 38.0 ms of k_verify_edit)
-                        const uint32_t nb = nbEnv ? std::min(8u, std::max(1u, (uint32_t)atoi(nbEnv))) : 3u;
-                        const uint32_t nStages = (vRows(b->maxLen) + 32u * nb - 1u) / (32u * nb) + 1u;
-                        for (int j = 0; j < 2; j++)
-                            if (b->vsC[j].n < nRuns) {
-                                b->vsA[j].alloc((size_t)nRuns + nRuns / 8 + 256);
-                                b->vsB[j].alloc(b->vsA[j].n);
-                                b->vsC[j].alloc(b->vsA[j].n);
-                            }
-                        if (b->vsN.n < nStages + 2) b->vsN.alloc(nStages + 2);
-                        HIPCHK(hipMemsetAsync(b->vsN.p, 0, (nStages + 2) * sizeof(uint32_t), s));
-                        const uint32_t listCap = cap32(b->vsC[0].n);
-                        const uint32_t gridCap = capBlocks(envBlocks("CMB_STAGE_GRID", 8192u));
-                        const uint32_t grid = std::min<uint32_t>((nRuns + 255) / 256, gridCap);
-                        gridLine(verbose, "k_verify_stage", nRuns, 256ull * grid); // (the first stage: the later ones take its survivors)
-                        VStageList L0{b->vsA[0].p, b->vsB[0].p, b->vsC[0].p}, L1{b->vsA[1].p, b->vsB[1].p, b->vsC[1].p};
-                        // k <= 4: the matrix on 32-bit words (dev_matrix.hpp); CMB_MATRIX_WIDE=1 keeps the 64-bit words
-                        const bool w32 = b->k <= MX32_MAX_ED && !getenv("CMB_MATRIX_WIDE");
-                        const bool packed = ix->d.text2 != nullptr; // 2-bit text (cmb_index_create)
-                        // stages no read of the batch can reach its final-column rows in (row >= len - maxED - 1,
-                        // maxED <= 7) run the instance without final-column code
-                        auto needsFinal = [&](uint32_t st) { return 32u * nb * (st + 1u) - 1u + 8u >= b->minLen; };
-                        auto stageKernel = [&](bool first, bool fin) {
-                            return withBools([](auto f, auto w, auto p, auto c) { return k_verify_stage<f(), w(), p(), c()>; }, first, w32, packed, fin);
-                        };
-                        hipLaunchKernelGGL(stageKernel(true, needsFinal(0)), dim3(grid), dim3(256), 0, s, ix->d, b->offs.p, mf,
-                                           b->vkeysA.p, b->vcounts.p, nRuns, L0, L1, b->vsN.p, listCap, 0u, nb, b->tbq.p, tbCap, q);
-                        for (uint32_t st = 1; st < nStages; st++)
-                            hipLaunchKernelGGL(stageKernel(false, needsFinal(st)), dim3(grid), dim3(256), 0, s, ix->d, b->offs.p, mf,
-                                               (const unsigned long long*)nullptr, (const uint32_t*)nullptr, 0u,
-                                               (st & 1u) ? L1 : L0, (st & 1u) ? L0 : L1, b->vsN.p, listCap, st, nb, b->tbq.p, tbCap,
-                                               q);
-                        if (verbose) {
-                            std::vector<uint32_t> hn(nStages + 2);
-                            HIPCHK(hipMemcpyAsync(hn.data(), b->vsN.p, hn.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                            HIPCHK(hipStreamSynchronize(s));
-                            fprintf(stderr, "[verify] survivors per stage:");
-                            for (uint32_t st = 1; st <= nStages; st++) fprintf(stderr, " %u", hn[st]);
-                            fprintf(stderr, "\n");
-                        }
-                    }
-                }
-                tm.end(vGroup);
-                HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
-                HIPCHK(hipStreamSynchronize(s));
-                const uint32_t nTb = hcnt[7];
-                if (nTb) {
-                    const uint32_t slotCap = capSlots(envSlots("CMB_TB_SLOTS", 512u * 1024u)); // (measured 64 k … 2 M slots: 84 / 49 / 34.4 / 32.8 / 31 / 29 ms alone; 512 k best beside other sub-batches)
-                    const uint32_t tSlots = std::min<uint32_t>(((nTb + 255) / 256) * 256, slotCap);
-                    gridLine(verbose, "k_traceback", nTb, tSlots);
-                    // 64-byte lines of 16 narrow (k <= 4) or 8 wide trace rows (a group is written whole)
-                    const bool narrow = b->k <= TBN_MAX_ED && !getenv("CMB_TRACE_WIDE");
-                    const uint32_t tLines = traceLines(narrow, vRows(b->maxLen));
-                    if (b->vW.n < (size_t)tLines * 8 * tSlots) b->vW.alloc((size_t)tLines * 8 * tSlots);
-                    VPlanes vp{b->vW.p, tSlots, tLines};
-                    tm.begin();
-                    // no final-column row (> len - maxED - 1, maxED <= 7) at or before this row, for any read of the batch
-                    const uint32_t rowMin = b->minLen > 8u ? b->minLen - 8u : 0u;
-                    launchTraceback(s, ix->d, narrow, b->offs.p, mf, b->tbq.p, nTb, vp, q, rowMin);
-                    tm.end("k_traceback");
-                }
-            }
-            HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            if (nFmUniq) {
-                tm.begin();
-                const uint32_t nb = (uint32_t)std::min<size_t>(((size_t)nFmUniq + 255) / 256, 4096);
-                hipLaunchKernelGGL(k_fmocc, dim3(nb), dim3(256), 0, s, ix->d, b->fmUniq.p, nFmUniq, q);
-                tm.end("k_fmocc");
-            }
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            if (hcnt[3] & FLAG_TEXT_OVERFLOW) {
-                if (attempt >= 3) return fail(CMB_ERR_INTERNAL, "text occurrence queue keeps overflowing");
-                b->text.alloc((size_t)hcnt[2] + hcnt[2] / 8 + 1024);
-                HIPCHK(hipMemcpy(b->counters.p, keep, sizeof(keep), hipMemcpyHostToDevice));
-                uint32_t fl = hcnt[3] & ~(uint32_t)FLAG_TEXT_OVERFLOW; // clear the overflow flag for the retry
-                HIPCHK(hipMemcpy(b->cnt.p + 3, &fl, sizeof(uint32_t), hipMemcpyHostToDevice));
-                continue;
-            }
-            break;
-        }
-        uint32_t nText = hcnt[2];
-        lap("verify + traceback + fmocc");
-        if (preset) { // the raw text occurrences and the counters are the result
-            if (hcnt[3] & (FLAG_CAPACITY | FLAG_TRACE_RULE)) return fail(CMB_ERR_INTERNAL, "a traceback left the band");
-            b->presetOut.resize(nText);
-            if (nText) HIPCHK(hipMemcpy(b->presetOut.data(), b->text.p, (size_t)nText * sizeof(TextOccRec), hipMemcpyDeviceToHost));
-            unsigned long long hc2[CMB_CNT_MAX];
-            HIPCHK(hipMemcpy(hc2, b->counters.p, sizeof(hc2), hipMemcpyDeviceToHost));
-            for (int i = 0; i < CMB_CNT_MAX; i++) b->cnts[i] = hc2[i];
-            b->done = true;
-            return CMB_OK;
-        }
-
-        const uint32_t keyLayout = b->metric == CMB_METRIC_HAMMING ? 1u : b->wideEdit ? 2u : 0u; // (kernels.hpp: keyBits)
-        const uint32_t groupShift = keyBits(keyLayout).group;
-        // ---- naive backtracking: the filter pass of approxMatchesNaive[Hamming] itself, per read x strand (dev_bfs_naive.hpp)
-        uint64_t naiveSurvivors = 0;
-        if (b->hasNaive && nText) {
-            tm.begin();
-            const uint32_t nG = 2u * nReads;
-            if (nG >= (1u << (64u - groupShift))) return fail(CMB_ERR_UNSUPPORTED, "more than 2^23 reads in a sub-batch with reads matched by naive backtracking");
-            growTo(b->keysA, nText), growTo(b->keysB, nText);
-            if (b->fcounts.n < (size_t)nG + 1) {
-                b->fcounts.alloc((size_t)nG + 1);
-                b->foffs.alloc((size_t)nG + 1);
-                b->fsegB.alloc((size_t)nG + 1);
-                b->fsegE.alloc((size_t)nG + 1);
-            }
-            growTo(b->frank, nText);
-            hipLaunchKernelGGL(k_pack_keys, dim3((nText + 255) / 256), dim3(256), 0, s, b->text.p, nText, b->offs.p, b->k, b->keysA.p,
-                               b->cnt.p, 1u, (const uint8_t*)b->psel.p, keyLayout);
-            sortKeys(b->sortTmp, b->keysA.p, b->keysB.p, nText, 0, 64, s);
-            const int mode = b->metric == CMB_METRIC_HAMMING ? 1 : 2;
-            HIPCHK(hipMemsetAsync(b->fcounts.p, 0, ((size_t)nG + 1) * sizeof(uint32_t), s));
-            HIPCHK(hipMemsetAsync(b->fsegB.p, 0xFF, ((size_t)nG + 1) * sizeof(uint32_t), s));
-            HIPCHK(hipMemsetAsync(b->frank.p, 0xFF, (size_t)nText * sizeof(uint32_t), s));
-            hipLaunchKernelGGL(k_filter_segments, dim3((nText + 255) / 256), dim3(256), 0, s, b->keysB.p, nText, b->fsegB.p, b->fsegE.p, groupShift);
-            hipLaunchKernelGGL(k_filter_mark, dim3((nG + 255) / 256), dim3(256), 0, s, b->keysB.p, nG, b->k, mode, b->fcounts.p,
-                               b->frank.p, b->fsegB.p, b->fsegE.p, keyLayout);
-            scanExclusive(b->scanTmp, b->fcounts.p, b->foffs.p, (size_t)nG + 1, s);
-            HIPCHK(hipMemcpyAsync(&naiveSurvivors, b->foffs.p + nG, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            if (hcnt[3] & FLAG_CAPACITY)
-                return fail(CMB_ERR_INTERNAL, "occurrence does not fit the filter key (width / distance range) or a traceback left the band");
-            if ((uint64_t)nText + naiveSurvivors >= 0xFFFFFFF0ull) return fail(CMB_ERR_UNSUPPORTED, "too many occurrences in one sub-batch");
-            if (b->text.n < (size_t)nText + naiveSurvivors) { // grow, keeping the records
-                DevBuf<TextOccRec> bigger;
-                bigger.alloc((size_t)nText + naiveSurvivors + 1024);
-                HIPCHK(hipMemcpyAsync(bigger.p, b->text.p, (size_t)nText * sizeof(TextOccRec), hipMemcpyDeviceToDevice, s));
-                HIPCHK(hipStreamSynchronize(s));
-                std::swap(bigger.p, b->text.p);
-                std::swap(bigger.n, b->text.n);
-            }
-            hipLaunchKernelGGL(k_naive_drop, dim3((nText + 255) / 256), dim3(256), 0, s, b->text.p, nText, (const uint8_t*)b->psel.p);
-            if (naiveSurvivors)
-                hipLaunchKernelGGL(k_naive_keep, dim3((nText + 255) / 256), dim3(256), 0, s, b->keysB.p, nText, b->offs.p, b->k,
-                                   b->frank.p, b->foffs.p, b->text.p + nText, keyLayout);
-            HIPCHK(hipGetLastError());
-            nText += (uint32_t)naiveSurvivors;
-            tm.end("k_naive_filter");
-        }
-
-        // ---- sort + filter on the device (getUniqueTextOccurrences / getTextOccHamming,
-        // indexinterface.cpp:1331-1491): pack -> one 64-bit radix sort -> per-read scan
-        unsigned long long hc[CMB_CNT_MAX];
-        HIPCHK(hipMemcpy(hc, b->counters.p, sizeof(hc), hipMemcpyDeviceToHost));
-        for (int i = 0; i < CMB_CNT_MAX; i++) b->cnts[i] = hc[i];
-        b->cnts[1] += naiveSurvivors; // reported once more, as text occurrences of the read (indexinterface.cpp:1333, :1378)
-        // groups of the filter: reads, or read x strand when every strand is filtered by itself
-        const uint32_t nGroups = b->perStrand ? 2u * nReads : nReads;
-        // (group numbers 0 ... nGroups - 1: 2^24 groups fit the 24 bits of layouts 0 and 1 — a BEST sub-batch of 2^23 reads)
-        if (nGroups > (1u << (64u - groupShift))) return fail(CMB_ERR_UNSUPPORTED, "more filter groups in one sub-batch than the keys number");
-        {
-            tm.begin();
-            growTo(b->keysA, nText), growTo(b->keysB, nText);
-            if (b->fcounts.n < (size_t)nGroups + 1) {
-                b->fcounts.alloc((size_t)nGroups + 1);
-                b->foffs.alloc((size_t)nGroups + 1);
-                b->fsegB.alloc((size_t)nGroups + 1);
-                b->fsegE.alloc((size_t)nGroups + 1);
-            }
-            if (nText) {
-                hipLaunchKernelGGL(k_pack_keys, dim3((nText + 255) / 256), dim3(256), 0, s, b->text.p, nText, b->offs.p,
-                                   b->k, b->keysA.p, b->cnt.p, b->perStrand ? 1u : 0u, (const uint8_t*)nullptr,
-                                   keyLayout);
-                sortKeys(b->sortTmp, b->keysA.p, b->keysB.p, nText, 0, 64, s);
-            }
-            const int mode = b->k == 0 ? 0 : (b->metric == CMB_METRIC_HAMMING ? 1 : 2);
-            HIPCHK(hipMemsetAsync(b->fcounts.p, 0, ((size_t)nGroups + 1) * sizeof(uint32_t), s));
-            HIPCHK(hipMemsetAsync(b->fsegB.p, 0xFF, ((size_t)nGroups + 1) * sizeof(uint32_t), s));
-            if (nText)
-                hipLaunchKernelGGL(k_filter_segments, dim3((nText + 255) / 256), dim3(256), 0, s, b->keysB.p, nText, b->fsegB.p,
-                                   b->fsegE.p, groupShift);
-            growTo(b->frank, nText);
-            if (nText) HIPCHK(hipMemsetAsync(b->frank.p, 0xFF, (size_t)nText * sizeof(uint32_t), s));
-            hipLaunchKernelGGL(k_filter_mark, dim3((nGroups + 255) / 256), dim3(256), 0, s, b->keysB.p, nGroups, b->k, mode,
-                               b->fcounts.p, b->frank.p, b->fsegB.p, b->fsegE.p, keyLayout);
-            scanExclusive(b->scanTmp, b->fcounts.p, b->foffs.p, (size_t)nGroups + 1, s);
-            uint64_t total = 0;
-            HIPCHK(hipMemcpyAsync(&total, b->foffs.p + nGroups, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            if (hcnt[3] & FLAG_TRACE_RULE)
-                return fail(CMB_ERR_INTERNAL, "a traceback read a band-edge bit the narrow trace rows take as implied");
-            if (hcnt[3] & FLAG_CAPACITY)
-                return fail(CMB_ERR_INTERNAL, "occurrence does not fit the filter key (width / distance range) or a traceback left the band");
-            growTo(b->fout, total);
-            if (b->wantAln) growTo(b->foutRead, total);
-            if (total)
-                hipLaunchKernelGGL(k_filter_write, dim3((nText + 255) / 256), dim3(256), 0, s, b->keysB.p, nText, b->offs.p,
-                                   b->k, b->frank.p, b->foffs.p, b->fout.p, b->wantAln ? b->foutRead.p : (uint32_t*)nullptr,
-                                   b->perStrand ? 1u : 0u, keyLayout);
-            HIPCHK(hipGetLastError());
-            tm.end("k_filter");
-            lap("filter");
-            if (b->wantAln) { // CIGAR + sequence of every final occurrence (k_cigar)
-                tm.begin();
-                b->alnStride = 2u * b->k + 3u;
-                if (b->alnRec.n < total) {
-                    b->alnRec.alloc((size_t)total + total / 8 + 256);
-                    b->alnOps.alloc(b->alnRec.n * std::max<size_t>(b->alnStride, 2u * 7u + 3u));
-                }
-                if (total) {
-                    const uint32_t cSlots = capSlots((uint32_t)std::min<uint64_t>(((total + 255) / 256) * 256, 512u * 1024u));
-                    MFull mfc = mf;
-                    if (!mfc.p) mfc.nBlk = 0; // (Hamming / exact batches have no match words: every CIGAR is len x M, nothing is traced)
-                    const CigarJob job{b->offs.p, b->G.p, b->gw, b->maxLen, mfc, b->fout.p, b->foutRead.p, (uint64_t)total, b->alnOps.p, b->alnStride,
-                                       b->alnRec.p, b->cnt.p + 3, (b->metric != CMB_METRIC_EDIT || b->k == 0) ? 1u : 0u};
-                    launchCigar(ix, s, job, b->metric == CMB_METRIC_EDIT && b->k > CIGAR_BLOCK_WORDS_MAX_ED, b->k <= TBN_MAX_ED && !getenv("CMB_TRACE_WIDE"),
-                                vRows(b->maxLen), cSlots, b->vW, b->dpSlab, verbose);
-                }
-                tm.end("k_cigar");
-                HIPCHK(hipGetLastError());
-            }
-            b->occs.resize(total);
-            b->occOffs.resize((size_t)nGroups + 1);
-            if (total) HIPCHK(hipMemcpyAsync(b->occs.data(), b->fout.p, (size_t)total * sizeof(cmb_occ), hipMemcpyDeviceToHost, s));
-            if (b->wantAln) {
-                b->hAlnRec.resize(total);
-                b->hAlnOps.resize((size_t)total * b->alnStride);
-                if (total) {
-                    HIPCHK(hipMemcpyAsync(b->hAlnRec.data(), b->alnRec.p, (size_t)total * sizeof(AlnRec), hipMemcpyDeviceToHost, s));
-                    HIPCHK(hipMemcpyAsync(b->hAlnOps.data(), b->alnOps.p, (size_t)total * b->alnStride * sizeof(uint16_t), hipMemcpyDeviceToHost, s));
-                }
-                HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
-            }
-            HIPCHK(hipMemcpyAsync(b->occOffs.data(), b->foffs.p, ((size_t)nGroups + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            if (b->wantAln && (hcnt[3] & FLAG_CAPACITY))
-                return fail(CMB_ERR_INTERNAL, "a CIGAR traceback left the band or an occurrence is not an alignment within its distance");
-            lap("results to the host");
-            if (verbose) {
-                size_t fr = 0, tot = 0;
-                (void)hipMemGetInfo(&fr, &tot);
-                fprintf(stderr, "[mem] device memory in use: %.1f GB of %.1f GB\n", (tot - fr) / 1e9, tot / 1e9);
-            }
-        }
+        if ((rc = filterNaive(c)) != CMB_OK) return rc;
         // TOTAL_REPORTED_POSITIONS (indexinterface.cpp:1378,1390 / :1333,1352)
         // (the device counter holds the records k_verify / k_traceback wrote; queue holes are not records)
+        downloadCounters(b);
+        b->cnts[1] += c.naiveSurvivors; // reported once more, as text occurrences of the read (indexinterface.cpp:1333, :1378)
+        uint64_t total = 0;
+        if ((rc = filterFinal(c, total)) != CMB_OK) return rc;
+        lap(c, "filter");
+        if ((rc = runCigar(c, total)) != CMB_OK) return rc;
+        if ((rc = downloadResults(c, total)) != CMB_OK) return rc;
         b->done = true;
         return CMB_OK;
     } catch (const std::exception& e) {
@@ -1759,7 +1896,7 @@ int batchListViews(cmb_batch* b, bool perStrand, std::vector<ListView>& out) {
     }
     return CMB_OK;
 }
-// (declared in units.hpp; the k_cigar launch of batchRunOne)
+// (declared in units.hpp; the k_cigar launch of runCigar)
 int moveCigarsOnText(cmb_index* textIndex, hipStream_t s, const uint64_t* offs, const uint32_t* G, uint32_t gw, uint32_t nReads, uint32_t maxLen,
                      uint32_t k, int gapless, const uint4* occs, const uint32_t* occRead, uint64_t nOcc, AlnRec* aln, uint16_t* ops, uint32_t stride,
                      uint32_t* flagWord) {
