@@ -58,6 +58,8 @@ EXPORTS = [
     "cmb_move_batch_alignments", "cmb_move_batch_filter_per_strand", "cmb_move_match_best",
     "cmb_move_batch_keep_device_lists", "cmb_move_batch_sam_device", "cmb_move_match_best_device",
     "cmb_pair_sam_device_classes", "cmb_move_pair_sam_device",
+    "cmb_build_create", "cmb_build_destroy", "cmb_build_sizes_of", "cmb_build_bwt_arrays", "cmb_build_sparse_sa_sizes", "cmb_build_sparse_sa",
+    "cmb_build_suffix_array", "cmb_build_index", "cmb_build_timings",
     "cmb_last_error", "cmb_version",
 ]
 
@@ -165,6 +167,19 @@ class IndexLayout(C.Structure):
         ("kmer_size", C.c_uint32), ("in_text_switch", C.c_uint32), ("n_seqs", C.c_uint32),
         ("bytes", C.c_uint64 * DEV_ARRAYS),
     ]
+
+
+class BuildSizes(C.Structure):
+    """cmb_build_sizes"""
+    _fields_ = [("text_length", C.c_uint64), ("bv_words", C.c_uint64), ("cnt_words", C.c_uint64), ("bwt_words", C.c_uint64)]
+
+
+class _BuildArrays(C.Structure):
+    """cmb_build_arrays"""
+    _fields_ = [("counts", C.c_uint64 * 5), ("dollar_pos_fwd", C.c_uint64), ("dollar_pos_rev", C.c_uint64),
+                ("bv_fwd", C.c_void_p), ("cnt_fwd", C.c_void_p), ("bv_rev", C.c_void_p), ("cnt_rev", C.c_void_p),
+                ("bv_cap", C.c_uint64), ("cnt_cap", C.c_uint64), ("bwt_words", C.c_void_p), ("bwt_cap", C.c_uint64),
+                ("char_counts", C.c_uint32 * 256)]
 
 
 class _DevArray:
@@ -374,6 +389,16 @@ def lib():
         L.cmb_move_create_empty.argtypes = [C.POINTER(MoveLayout), i32, C.POINTER(vp)]
         L.cmb_move_device_arrays.argtypes = [vp, C.POINTER(vp * MOVE_DEV_ARRAYS), C.POINTER(u64 * MOVE_DEV_ARRAYS)]
         L.cmb_move_validate.argtypes = [vp]
+        L.cmb_build_create.argtypes = [vp, u64, i32, C.POINTER(vp)]
+        L.cmb_build_destroy.argtypes = [vp]
+        L.cmb_build_destroy.restype = None
+        L.cmb_build_sizes_of.argtypes = [vp, C.POINTER(BuildSizes)]
+        L.cmb_build_bwt_arrays.argtypes = [vp, C.POINTER(_BuildArrays), vp]
+        L.cmb_build_sparse_sa_sizes.argtypes = [vp, u32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+        L.cmb_build_sparse_sa.argtypes = [vp, u32, vp, u64, vp, u64, vp, u64, C.POINTER(u64)]
+        L.cmb_build_suffix_array.argtypes = [vp, i32, vp, u64]
+        L.cmb_build_index.argtypes = [vp, u32, u32, u32, vp, u32, C.POINTER(vp)]
+        L.cmb_build_timings.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), u32]
         _lib = L
     return _lib
 
@@ -517,6 +542,84 @@ class Index:
         _chk(fn(self.h, pattern, len(pattern), _p(starts), starts.shape[0], max_ed, min_ed,
                                     int(fixed), _p(out), cap, C.byref(n), _p(cnt)))
         return out[:n.value], dict(zip(COUNTER_NAMES, cnt.tolist()))
+
+
+class DeviceBuild:
+    """The index of a preprocessed text (upper-case ACGT and a final '$'), built on the device (handle of ``cmb_build_create``):
+    both suffix arrays and every array derived from the BWTs stay in HBM; ``arrays`` / ``sparse_sa`` download them in the reference's
+    layouts, ``index`` makes a resident ``Index`` of them without a host round trip."""
+
+    def __init__(self, text, device: int = 0):
+        t = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, dtype=np.uint8)
+        self.text = np.array(t, dtype=np.uint8, copy=True)
+        self.n, self.device = int(self.text.shape[0]), device
+        h = C.c_void_p()
+        _chk(lib().cmb_build_create(_p(self.text), self.n, device, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.cmb_build_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def sizes(self) -> BuildSizes:
+        z = BuildSizes()
+        _chk(lib().cmb_build_sizes_of(self.h, C.byref(z)))
+        return z
+
+    def sparse_sa(self, sparseness: int):
+        """(sampled-row bitvector, its counts, samples in row order) of the sparse suffix array"""
+        nb, nc, ns = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _chk(lib().cmb_build_sparse_sa_sizes(self.h, sparseness, C.byref(nb), C.byref(nc), C.byref(ns)))
+        bv, cnt, smp = np.zeros(nb.value, np.uint64), np.zeros(nc.value, np.uint64), np.zeros(ns.value, np.uint32)
+        _chk(lib().cmb_build_sparse_sa(self.h, sparseness, _p(bv), nb.value, _p(cnt), nc.value, _p(smp), ns.value, C.byref(ns)))
+        return bv, cnt, smp
+
+    def suffix_array(self, reverse: bool = False) -> np.ndarray:
+        out = np.zeros(self.n, np.uint32)
+        _chk(lib().cmb_build_suffix_array(self.h, int(reverse), _p(out), self.n))
+        return out
+
+    def bwt_arrays(self):
+        """cmb_build_bwt_arrays: the filled structure and the numpy arrays its pointers refer to"""
+        z = self.sizes()
+        bufs = {k: np.zeros(int(w), np.uint64) for k, w in (("bv_fwd", z.bv_words), ("cnt_fwd", z.cnt_words), ("bv_rev", z.bv_words),
+                                                             ("cnt_rev", z.cnt_words), ("bwt_words", z.bwt_words))}
+        a = _BuildArrays()
+        for k, v in bufs.items():
+            setattr(a, k, _p(v))
+        a.bv_cap, a.cnt_cap, a.bwt_cap = z.bv_words, z.cnt_words, z.bwt_words
+        _chk(lib().cmb_build_bwt_arrays(self.h, C.byref(a), None))
+        return a, bufs
+
+    def arrays(self, sparseness: int = 4, seq_starts=None, seq_names=None):
+        """the index as ``indexbuild.IndexArrays`` (``indexbuild.save_index`` writes it unchanged)"""
+        from .indexbuild import IndexArrays
+        a, bufs = self.bwt_arrays()
+        sa_bv, sa_cnt, samples = self.sparse_sa(sparseness)
+        if seq_starts is None:
+            seq_starts = np.array([0, self.n - 1], dtype=np.uint32)
+        if seq_names is None:
+            seq_names = [f"seq{i}" for i in range(len(seq_starts) - 1)]
+        return IndexArrays(text=self.text, counts=np.array(list(a.counts), dtype=np.uint64), dollar_pos_fwd=int(a.dollar_pos_fwd),
+                           bv_fwd=bufs["bv_fwd"], cnt_fwd=bufs["cnt_fwd"], dollar_pos_rev=int(a.dollar_pos_rev), bv_rev=bufs["bv_rev"],
+                           cnt_rev=bufs["cnt_rev"], bwt_words=bufs["bwt_words"], sa_bv=sa_bv, sa_bv_counts=sa_cnt, sa_samples=samples,
+                           sparseness=sparseness, seq_starts=np.asarray(seq_starts, dtype=np.uint32), seq_names=list(seq_names))
+
+    def index(self, sparseness: int = 4, kmer_size: int = 10, in_text_switch: int = 4, seq_starts=None) -> "Index":
+        starts = np.ascontiguousarray(seq_starts if seq_starts is not None else [0, self.n - 1], np.uint32)
+        h = C.c_void_p()
+        _chk(lib().cmb_build_index(self.h, sparseness, kmer_size, in_text_switch, _p(starts), starts.shape[0], C.byref(h)))
+        return Index(self.n, kmer_size=kmer_size, device=self.device, _handle=h)
+
+    def timings(self) -> Dict[str, float]:
+        """host time per phase of the build in ms, every doubling round by itself (cmb_build_timings)"""
+        names = (C.c_char_p * 256)()
+        ms = (C.c_float * 256)()
+        n = lib().cmb_build_timings(self.h, names, ms, 256)
+        return {names[i].decode(): float(ms[i]) for i in range(n)}
 
 
 class SearchStrategy:

@@ -152,37 +152,56 @@ extern "C" int cmb_index_create(const cmb_index_desc* desc, int device, cmb_inde
         if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
             return fail(CMB_ERR_DEVICE, "no HIP device available (the product path has no CPU fallback)");
         useDevice(device);
+        // the upload boundary: the description's host arrays into HBM as they are, the rest is indexFromDeviceArrays
+        const uint64_t n = desc->text_length, N = n + 1, saW = (n + 63) / 64;
+        DevBuf<uint64_t> bvF, cntF, bvR, cntR, saBv, saCnt;
+        DevBuf<uint32_t> samples;
+        DevBuf<uint8_t> text;
+        bvF.upload(desc->bv_fwd, 4 * ((N + 63) / 64)), cntF.upload(desc->cnt_fwd, 8 * ((N + 511) / 512));
+        bvR.upload(desc->bv_rev, 4 * ((N + 63) / 64)), cntR.upload(desc->cnt_rev, 8 * ((N + 511) / 512));
+        saBv.upload(desc->sa_bv, saW), saCnt.upload(desc->sa_bv_counts, (saW + 7) / 4);
+        samples.upload(desc->sa_samples, desc->n_samples);
+        text.upload(desc->text, n);
+        IndexDeviceArrays a{};
+        a.n = n, a.text = text.p;
+        for (int i = 0; i < 5; i++) a.counts[i] = desc->counts[i];
+        a.dollarFwd = desc->dollar_pos_fwd, a.dollarRev = desc->dollar_pos_rev;
+        a.bvFwd = bvF.p, a.cntFwd = cntF.p, a.bvRev = bvR.p, a.cntRev = cntR.p;
+        a.saBv = saBv.p, a.saBvCounts = saCnt.p, a.saSamples = samples.p, a.nSamples = desc->n_samples;
+        a.saSparseness = desc->sa_sparseness, a.seqStarts = desc->seq_starts, a.nSeqs = desc->seq_starts ? desc->n_seqs : 0;
+        a.kmerSize = desc->kmer_size, a.inTextSwitch = desc->in_text_switch;
+        return indexFromDeviceArrays(a, device, out);
+    } catch (const std::exception& e) {
+        return fail(CMB_ERR_DEVICE, e.what());
+    }
+}
+int cmb::indexFromDeviceArrays(const IndexDeviceArrays& a, int device, cmb_index** out) {
+    try {
+        useDevice(device);
         std::unique_ptr<cmb_index> ix(new cmb_index());
         ix->device = device;
-        ix->saSparseness = desc->sa_sparseness;
-        const uint64_t n = desc->text_length, N = n + 1;
-        const uint64_t bvW = 4 * ((N + 63) / 64), cW = 8 * ((N + 511) / 512);
+        ix->saSparseness = a.saSparseness;
+        const uint64_t n = a.n, N = n + 1;
         const uint64_t nBlocks = N / RANK_BLOCK + 1; // rank(N) must be answerable
         for (int dir = 0; dir < 2; dir++) {        // re-pack the reference arrays, one direction at a time
-            DevBuf<uint64_t> bv, cnt;
-            bv.upload(dir ? desc->bv_rev : desc->bv_fwd, bvW);
-            cnt.upload(dir ? desc->cnt_rev : desc->cnt_fwd, cW);
             DevBuf<uint4>& blk = dir ? ix->blkR : ix->blkF;
             blk.alloc(nBlocks * 2);
-            hipLaunchKernelGGL(k_relayout, dim3((unsigned)((nBlocks + 255) / 256)), dim3(256), 0, 0, bv.p, cnt.p, N,
-                               nBlocks, blk.p);
+            hipLaunchKernelGGL(k_relayout, dim3((unsigned)((nBlocks + 255) / 256)), dim3(256), 0, 0, dir ? a.bvRev : a.bvFwd,
+                               dir ? a.cntRev : a.cntFwd, N, nBlocks, blk.p);
             HIPCHK(hipGetLastError());
             HIPCHK(hipDeviceSynchronize());
         }
         const uint64_t saW = (n + 63) / 64;
         { // the sparse suffix array's bitvector + rank9 counts ride in slot 3 of the forward blocks (k_relayout_sa)
-            DevBuf<uint64_t> bv, cnt;
-            bv.upload(desc->sa_bv, saW);
-            cnt.upload(desc->sa_bv_counts, (saW + 7) / 4);
-            hipLaunchKernelGGL(k_relayout_sa, dim3((unsigned)((nBlocks + 255) / 256)), dim3(256), 0, 0, bv.p, cnt.p, saW,
+            hipLaunchKernelGGL(k_relayout_sa, dim3((unsigned)((nBlocks + 255) / 256)), dim3(256), 0, 0, a.saBv, a.saBvCounts, saW,
                                nBlocks, ix->blkF.p);
             HIPCHK(hipGetLastError());
             HIPCHK(hipDeviceSynchronize());
         }
         // (a description without samples has always left ONE element here: saSamples.n is the sample count of the probe and of
         // cmb_index_layout_of, and counts into cmb_index_device_bytes)
-        ix->saSamples.alloc(std::max<size_t>(desc->n_samples, 1));
-        if (desc->n_samples) HIPCHK(hipMemcpy(ix->saSamples.p, desc->sa_samples, desc->n_samples * sizeof(uint32_t), hipMemcpyHostToDevice));
+        ix->saSamples.alloc(std::max<size_t>(a.nSamples, 1));
+        if (a.nSamples) HIPCHK(hipMemcpy(ix->saSamples.p, a.saSamples, a.nSamples * sizeof(uint32_t), hipMemcpyDeviceToDevice));
         // padded: the verification kernels read (unaligned) 16-byte chunks up to two chunks ahead, and lanes whose
         // candidate has ended keep prefetching while their wavefront runs (at most MAX_READ + 3 k rows + 48 bytes)
         constexpr uint64_t TEXT_PAD = 640;
@@ -192,7 +211,7 @@ extern "C" int cmb_index_create(const cmb_index_desc* desc, int device, cmb_inde
         static_assert(TEXT_PAD >= (uint64_t)MAX_READ + 13 + 64, "text padding must cover an occurrence that begins on the last character");
         ix->text.alloc(n + TEXT_PAD);
         HIPCHK(hipMemset(ix->text.p, 0, n + TEXT_PAD));
-        HIPCHK(hipMemcpy(ix->text.p, desc->text, n, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(ix->text.p, a.text, n, hipMemcpyDeviceToDevice));
         hipLaunchKernelGGL(k_encode_text, dim3(4096), dim3(256), 0, 0, ix->text.p, n, n + TEXT_PAD); // ASCII -> codes 0..4
         HIPCHK(hipGetLastError());
         bool packedOk = false;
@@ -210,21 +229,21 @@ extern "C" int cmb_index_create(const cmb_index_desc* desc, int device, cmb_inde
             packedOk = hb == 0 && !getenv("CMB_TEXT_BYTES");
             if (!packedOk) ix->text2.release();
         }
-        ix->kmer.alloc(1ull << (2 * desc->kmer_size));
-        if (desc->seq_starts) ix->seqStarts.assign(desc->seq_starts, desc->seq_starts + desc->n_seqs);
+        ix->kmer.alloc(1ull << (2 * a.kmerSize));
+        if (a.seqStarts) ix->seqStarts.assign(a.seqStarts, a.seqStarts + a.nSeqs);
         DevIndex& d = ix->d;
         d.n = (uint32_t)n;
-        for (int i = 0; i < 5; i++) d.counts[i] = (uint32_t)desc->counts[i];
-        d.fwd = DevBWT{ix->blkF.p, (uint32_t)desc->dollar_pos_fwd};
-        d.rev = DevBWT{ix->blkR.p, (uint32_t)desc->dollar_pos_rev};
+        for (int i = 0; i < 5; i++) d.counts[i] = (uint32_t)a.counts[i];
+        d.fwd = DevBWT{ix->blkF.p, (uint32_t)a.dollarFwd};
+        d.rev = DevBWT{ix->blkR.p, (uint32_t)a.dollarRev};
         d.saSamples = ix->saSamples.p;
         d.saSparseness = ix->saSparseness;
         d.text = ix->text.p;
         d.text2 = packedOk ? ix->text2.p : nullptr;
         d.kmer = ix->kmer.p;
-        d.kmerSize = desc->kmer_size;
-        d.switchPoint = desc->in_text_switch;
-        const uint32_t total = 1u << (2 * desc->kmer_size);
+        d.kmerSize = a.kmerSize;
+        d.switchPoint = a.inTextSwitch;
+        const uint32_t total = 1u << (2 * a.kmerSize);
         hipLaunchKernelGGL(k_kmer_table, dim3((total + 255) / 256), dim3(256), 0, 0, d, ix->kmer.p);
         HIPCHK(hipGetLastError());
         HIPCHK(hipDeviceSynchronize());

@@ -20,6 +20,22 @@ int batchListViews(cmb_batch* b, bool perStrand, std::vector<ListView>& out);
 int moveCigarsOnText(cmb_index* textIndex, hipStream_t s, const uint64_t* offs, const uint32_t* G, uint32_t gw, uint32_t nReads, uint32_t maxLen,
                      uint32_t k, int gapless, const uint4* occs, const uint32_t* occRead, uint64_t nOcc, AlnRec* aln, uint16_t* ops, uint32_t stride,
                      uint32_t* flagWord);
+// The arrays of cmb_index_desc in the reference's layouts, already in HBM on the index's device (seqStarts alone is a host array).
+// cmb_index_create uploads a description into this form; cmb_build_index (build.hip) hands over the arrays the device builder made.
+struct IndexDeviceArrays {
+    uint64_t n;          // text length with the final '$'
+    const uint8_t* text; // ASCII
+    uint64_t counts[5], dollarFwd, dollarRev;
+    const uint64_t *bvFwd, *cntFwd, *bvRev, *cntRev, *saBv, *saBvCounts;
+    const uint32_t* saSamples;
+    uint64_t nSamples;
+    uint32_t saSparseness;
+    const uint32_t* seqStarts;
+    uint32_t nSeqs, kmerSize, inTextSwitch;
+};
+// everything cmb_index_create does behind its upload: the re-laid-out rank blocks, text codes and 2-bit text, the k-mer table, the
+// consistency probe, the dense suffix array and the sequence starts.  The arguments have been checked; the arrays stay the caller's.
+int indexFromDeviceArrays(const IndexDeviceArrays& a, int device, cmb_index** out);
 // ---- move_backend.hip
 // one view per part of a batch that has run with its lists kept (cmb_move_batch_keep_device_lists)
 int moveBatchListViews(cmb_move_batch* b, std::vector<ListView>& out);

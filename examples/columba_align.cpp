@@ -1,6 +1,6 @@
 // A Columba-style aligner (single-end and paired-end reads, ALL and BEST mode) over the C-ABI (the counterpart of `columba` for the hot path this library
 // accelerates: reference src/parallel.cpp main / threadEntrySingleEnd / processChunk):
-//   columba_align -r <index base> -f <reads.fq|fa> -o <out.sam> [-e <max distance>] [-a all|best] [-x <strata>]
+//   columba_align (-r <index base> | -G <fasta> [<fasta> ...]) -f <reads.fq|fa> -o <out.sam> [-e <max distance>] [-a all|best] [-x <strata>]
 //                 [-I <min identity>] [-S <strategy>] [-m edit|hamming] [-p uniform|static|dynamic]
 //                 [-s <SA sparseness>] [-K <k-mer size>] [-i <in-text switch>] [-b <reads per chunk>] [-XA] [-nU]
 //                 [-F <mates.fq> -O fr|rf|ff -X <max insert> -N <min insert> -nD -nI]  (read pairs)
@@ -8,7 +8,11 @@
 // the files as the reference does (parallel.cpp:468-655, :862-935: up to 10 000 reads matched single-end, the pairs whose mates both map
 // unambiguously are the sample) and that first chunk is paired from its single-end results.
 // FASTQ / FASTA in, SAM out (header of <base>.headerSN.bin, records in input order).
+// -G <fasta> [<fasta> ...] instead of -r <index base>: no index files — the reference sequences are preprocessed as columba_build does
+// (seed length 0) and their index is built on the GPU, where it stays (include/columba_amd_build_device.hpp: fmIndexFromFasta).  The
+// records are those of a run with -r on the files columba_build writes for the same FASTA files.
 #include "columba_amd.hpp"
+#include "columba_amd_build_device.hpp"
 #include "columba_amd_io.hpp"
 
 #include <cstring>
@@ -21,6 +25,7 @@ int main(int argc, char** argv) {
     std::string base, readsFile, matesFile, orientation = "fr", outFile, strategyName = "columba", mode = "best", metric = "edit", part = "dynamic", cmdline;
     int k = 0, x = 0, identity = 95, sparse = 4, kmer = 10, inTextSwitch = 4;
     size_t chunkReads = 1000000;
+    std::vector<std::string> fastaFiles; // -G
     bool xa = false, unmapped = true, discordant = true, noInfer = false, pairParamsGiven = false;
     unsigned maxInsert = 500, minInsert = 0;
     for (int i = 0; i < argc; i++) cmdline += std::string(i ? " " : "") + argv[i];
@@ -33,6 +38,10 @@ int main(int argc, char** argv) {
         try {
             if (a == "-r") base = val();
             else if (a == "-f") readsFile = val();
+            else if (a == "-G") {
+                while (i + 1 < argc && argv[i + 1][0] != '-') fastaFiles.push_back(argv[++i]);
+                if (fastaFiles.empty()) throw std::runtime_error("missing value for -G");
+            }
             else if (a == "-o") outFile = val();
             else if (a == "-e") k = std::stoi(val());
             else if (a == "-a") mode = val();
@@ -59,24 +68,30 @@ int main(int argc, char** argv) {
             return 2;
         }
     }
-    if (base.empty() || readsFile.empty() || outFile.empty()) {
-        std::cerr << "usage: " << argv[0] << " -r <index base> -f <reads> -o <out.sam> [-e k] [-a all|best] [-x strata] [-I identity] "
+    if (base.empty() == fastaFiles.empty() || readsFile.empty() || outFile.empty()) {
+        std::cerr << "usage: " << argv[0] << " (-r <index base> | -G <fasta> [<fasta> ...]) -f <reads> -o <out.sam> [-e k] [-a all|best] [-x strata] [-I identity] "
                      "[-S strategy] [-m edit|hamming] [-p uniform|static|dynamic] [-s sparseness] [-K kmer] [-i in-text switch] [-b chunk] [-XA] [-nU] "
                      "[-F mates -O fr|rf|ff -X max insert -N min insert -nD -nI]\n";
         return 2;
     }
     try {
-        FMIndex index(base, (length_t)inTextSwitch, false, sparse, false, (length_t)kmer);
+        build::Text refText; // -G: names, positions and first sequences per file of the reference, as the index files hold them
+        std::unique_ptr<FMIndex> indexPtr(fastaFiles.empty() ? new FMIndex(base, (length_t)inTextSwitch, false, sparse, false, (length_t)kmer)
+                                                             : build::fmIndexFromFasta(fastaFiles, refText, (length_t)inTextSwitch, sparse, (length_t)kmer).release());
+        FMIndex& index = *indexPtr;
         const PartitionStrategy ps = part == "uniform" ? UNIFORM : part == "static" ? STATIC : DYNAMIC;
         const DistanceMetric dm = metric == "hamming" ? HAMMING : EDIT;
         NamedStrategy strategy(index, strategyName.c_str(), ps, dm);
-        const std::vector<std::string> seqNames = readSequenceNames(base);
+        const std::vector<std::string> seqNames = fastaFiles.empty() ? readSequenceNames(base) : refText.seqNames;
+        std::string headerLines; // (-G: what columba_build writes to .headerSN.bin)
+        for (size_t i = 0; i < refText.seqNames.size(); i++)
+            headerLines += "@SQ\tSN:" + refText.seqNames[i] + "\tLN:" + std::to_string(refText.positions[i + 1] - refText.positions[i]) + "\n";
         std::vector<const char*> seqNamePtrs;
         for (const auto& s : seqNames) seqNamePtrs.push_back(s.c_str());
         uint32_t ori = orientation == "rf" ? CMB_ORIENTATION_RF : orientation == "ff" ? CMB_ORIENTATION_FF : CMB_ORIENTATION_FR;
         Reader reader(readsFile);
         std::unique_ptr<Reader> mateReader(matesFile.empty() ? nullptr : new Reader(matesFile));
-        OutputWriter writer(outFile, base + ".headerSN.bin", cmdline);
+        OutputWriter writer(outFile, fastaFiles.empty() ? base + ".headerSN.bin" : headerLines, cmdline, !fastaFiles.empty());
         std::vector<SequenceRecord> chunk;
         size_t chunkID = 0, nReads = 0, nMapped = 0;
         if (mateReader && !noInfer && !pairParamsGiven) {
@@ -86,7 +101,9 @@ int main(int argc, char** argv) {
             if (reader.getNextChunk(chunk, want)) {
                 mateReader->getNextChunk(mates, want);
                 uint32_t seqsInFirstFile = (uint32_t)seqNames.size();
-                {
+                if (!fastaFiles.empty()) {
+                    if (refText.firstSeqIDPerFile.size() > 1) seqsInFirstFile = refText.firstSeqIDPerFile[1];
+                } else {
                     std::ifstream fs(base + ".fsid", std::ios::binary);
                     uint32_t v[2] = {0, 0};
                     if (fs.read(reinterpret_cast<char*>(v), sizeof(v))) seqsInFirstFile = v[1]; // (a second file starts at sequence v[1])

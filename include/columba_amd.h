@@ -109,6 +109,57 @@ int cmb_index_validate(cmb_index* idx);
  * IndexInterface::populateTable (indexinterface.cpp:294-335) */
 int cmb_index_kmer_table(const cmb_index* idx, uint32_t* out /* 4 * 4^kmer_size */);
 
+/* --- index construction on the device ---------------------------------------------------
+ * From the preprocessed text (buildindex.cpp: preprocessFastaFiles — n bytes, upper-case A, C, G, T and exactly one '$', the last
+ * byte; 1 <= n < 2^32 - 1) to the arrays of cmb_index_desc in the reference's layouts, bit for bit what include/columba_amd_build.hpp
+ * computes on the host, and to a resident cmb_index without a round trip through host arrays or files.
+ * cmb_build_create sorts the suffixes of the text and of the reversed text with one algorithm (a radix sort on 20 symbols, then prefix
+ * doubling over the groups that are still open; columba_amd/csrc/dev_build.hpp), one pass after the other, and keeps the text, both
+ * suffix arrays, both sets of bitvectors with their counts and the 3-bit BWT in HBM: about 11 bytes per character while the handle
+ * lives, 43 bytes per character at the peak of the second sort.  The free memory is checked first (CMB_ERR_DEVICE names the bytes
+ * needed).  Any other byte in the text, or a '$' that is not the last byte, is CMB_ERR_INVALID (found by a kernel, before any sort);
+ * n = 0 is CMB_ERR_INVALID, n >= 2^32 - 1 CMB_ERR_UNSUPPORTED.  Lengths of 2^31 and more need no split: rocPRIM's sorts, scans and
+ * selections take 64-bit sizes. */
+typedef struct cmb_build cmb_build;
+int cmb_build_create(const char* text, uint64_t n, int device, cmb_build** out);
+void cmb_build_destroy(cmb_build* b);
+typedef struct {
+    uint64_t text_length;
+    uint64_t bv_words;  /* 4 * ceil((n + 1) / 64): bv_fwd, bv_rev */
+    uint64_t cnt_words; /* 8 * ceil((n + 1) / 512): cnt_fwd, cnt_rev */
+    uint64_t bwt_words; /* 3 n / 64 + 1: the 3-bit BWT (.bwt, EncodedText<5>, most significant bit first) */
+} cmb_build_sizes;
+int cmb_build_sizes_of(const cmb_build* b, cmb_build_sizes* out);
+/* the arrays that depend on the BWTs alone, to caller-allocated buffers (capacities in 64-bit words); the scalars are written by the
+ * call.  CMB_ERR_OVERFLOW if a buffer is too small: nothing is written but needed[0 .. 2] = {bv_words, cnt_words, bwt_words}
+ * (needed may be NULL). */
+typedef struct {
+    uint64_t counts[5];         /* cumulative, as cmb_index_desc.counts */
+    uint64_t dollar_pos_fwd, dollar_pos_rev;
+    uint64_t *bv_fwd, *cnt_fwd, *bv_rev, *cnt_rev;
+    uint64_t bv_cap, cnt_cap;
+    uint64_t* bwt_words;
+    uint64_t bwt_cap;
+    uint32_t char_counts[256];  /* .cct */
+} cmb_build_arrays;
+int cmb_build_bwt_arrays(cmb_build* b, cmb_build_arrays* io, uint64_t* needed /* [3] or NULL */);
+/* the sparse suffix array of a power-of-two sparseness (.sa.bv.<s>, .sa.<s>): sampled-row bitvector, its rank9 counts, the samples in
+ * row order.  May be called any number of times on one handle (columba_build -a: the factors 1 ... 128 from one build).
+ * CMB_ERR_OVERFLOW if a buffer is too small (*n_samples is set either way; cmb_build_sparse_sa_sizes gives all three sizes). */
+int cmb_build_sparse_sa_sizes(const cmb_build* b, uint32_t sparseness, uint64_t* bv_words, uint64_t* count_words, uint64_t* n_samples);
+int cmb_build_sparse_sa(cmb_build* b, uint32_t sparseness, uint64_t* bv, uint64_t bv_cap, uint64_t* counts, uint64_t count_cap,
+                        uint32_t* samples, uint64_t sample_cap, uint64_t* n_samples);
+/* test hook, as cmb_index_kmer_table: the suffix array of the text (reverse != 0: of the reversed text), text_length entries */
+int cmb_build_suffix_array(cmb_build* b, int reverse, uint32_t* out, uint64_t cap);
+/* a cmb_index on the build's device from the arrays in HBM — what cmb_index_create makes of the same arrays uploaded from the host
+ * (the dense suffix array is derived by the same rule).  seq_starts / n_seqs as in cmb_index_desc.  The index does not depend on the
+ * handle afterwards. */
+int cmb_build_index(cmb_build* b, uint32_t sparseness, uint32_t kmer_size, uint32_t in_text_switch, const uint32_t* seq_starts,
+                    uint32_t n_seqs, cmb_index** out);
+/* host time per phase of cmb_build_create in ms, every doubling round of either pass by itself (as cmb_best_timings: names[i] / ms[i],
+ * returns how many) */
+int cmb_build_timings(const cmb_build* b, const char** names, float* ms, uint32_t cap);
+
 /* --- strategy ----------------------------------------------------------------------
  * Replaces Parameters::createStrategy (src/parameters/alignparameters.cpp:1313-1376). */
 #define CMB_METRIC_HAMMING 0

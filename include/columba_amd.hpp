@@ -208,6 +208,19 @@ class FMIndex {
         d.in_text_switch = inTextSwitch;
         check(cmb_index_create(&d, device, &h));
     }
+    // Without index files: the index of a preprocessed text (upper-case ACGT and a final '$', as columba_build's preprocessing leaves
+    // it; positions = the start of every sequence and the end of the last, the contents of .pos) is built on the device and stays
+    // there (cmb_build_create, cmb_build_index).  include/columba_amd_build_device.hpp: fmIndexFromFasta starts from FASTA files.
+    struct FromText {};
+    FMIndex(FromText, const std::string& text, const std::vector<length_t>& positions, length_t inTextSwitch, int sa_sparse = 4,
+            length_t wordSize = 10, int device = 0)
+        : textLength((length_t)text.size()), switchPoint(inTextSwitch), startPos(positions) {
+        cmb_build* b = nullptr;
+        check(cmb_build_create(text.data(), text.size(), device, &b));
+        const int rc = cmb_build_index(b, (uint32_t)sa_sparse, wordSize, inTextSwitch, startPos.data(), (uint32_t)startPos.size(), &h);
+        cmb_build_destroy(b);
+        check(rc);
+    }
     FMIndex(const FMIndex&) = delete;
     FMIndex& operator=(const FMIndex&) = delete;
     ~FMIndex() { cmb_index_destroy(h); }

@@ -309,12 +309,59 @@ inline std::ofstream openOut(const std::string& name) {
     return f;
 }
 
-// FASTA files -> <base>.{meta, cct, txt.bin, bwt, brt, rev.brt, sa.<s>, sa.bv.<s>, pos, sna, fsid, headerSN.bin}
-// allSparsenessFactors: the sparse suffix array for every factor 1, 2, 4 ... 128 (`-a`, buildindex.cpp:1914-1918) instead of the one given
-inline void buildIndex(const std::vector<std::string>& fastaFiles, const std::string& base, uint32_t sparseness = 4, uint32_t seedLength = 0,
-                       bool allSparsenessFactors = false) {
-    if (sparseness == 0 || (sparseness & (sparseness - 1)) != 0) throw std::runtime_error("the sparseness factor must be a power of two");
-    const Text tx = preprocessFastaFiles(fastaFiles, seedLength);
+// The arrays of an index as the writer below asks for them, computed on the host: character counts, the sparse suffix array of a
+// factor, the 3-bit BWT and the bitvectors of either direction.  The writer asks in file order — forward first, the reversed text
+// last —, so the forward suffix array is gone before the reverse one is built.  A second producer with the same five members
+// (include/columba_amd_build_device.hpp: the device builder) hands its arrays to the same writer.
+class HostArrays {
+  public:
+    explicit HostArrays(const std::string& text) : T(text) {}
+    std::vector<uint32_t> charCounts() const {
+        std::vector<uint32_t> cct(256, 0);
+        for (char c : T) cct[(unsigned char)c]++;
+        return cct;
+    }
+    SparseSA sparse(uint32_t sf) {
+        forward();
+        return sparseSuffixArray(SA, sf);
+    }
+    std::vector<uint64_t> bwtWords() {
+        forward();
+        return encodeBwt(bwt);
+    }
+    BwtBitvectors bitvectors(bool reversed) {
+        if (!reversed) {
+            forward();
+            return bwtBitvectors(bwt);
+        }
+        // the reversed text (the '$' in front: createRevSAWithSanityCheck reverses the whole string)
+        std::vector<uint32_t>().swap(SA);
+        std::string().swap(bwt);
+        const size_t n = T.size();
+        std::string revT(T.rbegin(), T.rend());
+        const std::vector<uint32_t> revSA = suffixArray(revT);
+        revT.clear();
+        std::string rbwt(n, '$');
+        for (size_t i = 0; i < n; i++) rbwt[i] = revSA[i] > 0 ? T[n - revSA[i]] : T.front();
+        return bwtBitvectors(rbwt);
+    }
+
+  private:
+    void forward() { // the text's own suffix array and BWT, once
+        if (!SA.empty()) return;
+        const size_t n = T.size();
+        SA = suffixArray(T);
+        bwt.assign(n, '$');
+        for (size_t i = 0; i < n; i++) bwt[i] = SA[i] > 0 ? T[SA[i] - 1] : T.back();
+    }
+    const std::string& T;
+    std::vector<uint32_t> SA;
+    std::string bwt;
+};
+
+// the preprocessed text and the arrays of a producer -> <base>.{meta, cct, txt.bin, bwt, brt, rev.brt, sa.<s>, sa.bv.<s>, pos, sna, fsid, headerSN.bin}
+template <typename Arrays>
+inline void writeIndexFiles(const Text& tx, const std::string& base, uint32_t sparseness, bool allSparsenessFactors, Arrays& arrays) {
     const std::string& T = tx.T;
     const size_t n = T.size();
     { // text, sequences, header lines
@@ -335,17 +382,12 @@ inline void buildIndex(const std::vector<std::string>& fastaFiles, const std::st
         putAll(fs, tx.firstSeqIDPerFile);
     }
     { // character counts
-        std::vector<uint32_t> cct(256, 0);
-        for (char c : T) cct[(unsigned char)c]++;
         std::ofstream f = openOut(base + ".cct");
-        putAll(f, cct);
+        putAll(f, arrays.charCounts());
     }
-    { // the text's own BWT: 3-bit BWT, bitvectors, sparse suffix array
-        const std::vector<uint32_t> SA = suffixArray(T);
-        std::string bwt(n, '$');
-        for (size_t i = 0; i < n; i++) bwt[i] = SA[i] > 0 ? T[SA[i] - 1] : T.back();
+    { // the text's own BWT: sparse suffix array, 3-bit BWT, bitvectors
         for (uint32_t sf = allSparsenessFactors ? 1u : sparseness; sf <= (allSparsenessFactors ? 128u : sparseness); sf *= 2) {
-            const SparseSA ssa = sparseSuffixArray(SA, sf);
+            const SparseSA ssa = arrays.sparse(sf);
             std::ofstream f = openOut(base + ".sa.bv." + std::to_string(sf));
             put<uint64_t>(f, (uint64_t)n);
             putAll(f, ssa.bv);
@@ -353,25 +395,20 @@ inline void buildIndex(const std::vector<std::string>& fastaFiles, const std::st
             std::ofstream g = openOut(base + ".sa." + std::to_string(sf));
             putAll(g, ssa.samples);
         }
-        const std::vector<uint64_t> words = encodeBwt(bwt);
+        const std::vector<uint64_t> words = arrays.bwtWords();
         std::ofstream f = openOut(base + ".bwt");
         put<uint64_t>(f, (uint64_t)n);
         put<uint64_t>(f, (uint64_t)words.size());
         putAll(f, words);
-        const BwtBitvectors b = bwtBitvectors(bwt);
+        const BwtBitvectors b = arrays.bitvectors(false);
         std::ofstream g = openOut(base + ".brt");
         put<uint64_t>(g, b.dollarPos);
         put<uint64_t>(g, b.N);
         putAll(g, b.bv);
         putAll(g, b.counts);
     }
-    { // the reversed text (the '$' in front: createRevSAWithSanityCheck reverses the whole string)
-        std::string revT(T.rbegin(), T.rend());
-        const std::vector<uint32_t> revSA = suffixArray(revT);
-        revT.clear();
-        std::string rbwt(n, '$');
-        for (size_t i = 0; i < n; i++) rbwt[i] = revSA[i] > 0 ? T[n - revSA[i]] : T.front();
-        const BwtBitvectors b = bwtBitvectors(rbwt);
+    { // the reversed text
+        const BwtBitvectors b = arrays.bitvectors(true);
         std::ofstream g = openOut(base + ".rev.brt");
         put<uint64_t>(g, b.dollarPos);
         put<uint64_t>(g, b.N);
@@ -380,6 +417,16 @@ inline void buildIndex(const std::vector<std::string>& fastaFiles, const std::st
     }
     std::ofstream m = openOut(base + ".meta");
     m << 21 << "\n" << 4 << "\n" << "VANILLA" << "\n";
+}
+
+// FASTA files -> the index files, every array computed on the host
+// allSparsenessFactors: the sparse suffix array for every factor 1, 2, 4 ... 128 (`-a`, buildindex.cpp:1914-1918) instead of the one given
+inline void buildIndex(const std::vector<std::string>& fastaFiles, const std::string& base, uint32_t sparseness = 4, uint32_t seedLength = 0,
+                       bool allSparsenessFactors = false) {
+    if (sparseness == 0 || (sparseness & (sparseness - 1)) != 0) throw std::runtime_error("the sparseness factor must be a power of two");
+    const Text tx = preprocessFastaFiles(fastaFiles, seedLength);
+    HostArrays arrays(tx.T);
+    writeIndexFiles(tx, base, sparseness, allSparsenessFactors, arrays);
 }
 
 // ---------------------------------------------------------------- the run-length compressed flavour (b-move)

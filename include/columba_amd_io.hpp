@@ -190,7 +190,8 @@ class OutputWriter { // fastq.h OutputWriter: SAM header, then the chunks in the
     }
 
   public:
-    OutputWriter(const std::string& file, const std::string& headerFile, const std::string& commandLine) {
+    // headerIsText: `headerFile` holds the @SQ lines themselves instead of the name of the file with them (an index without files)
+    OutputWriter(const std::string& file, const std::string& headerFile, const std::string& commandLine, bool headerIsText = false) {
         std::string ext = file.size() >= 7 ? file.substr(file.size() - 7) : std::string();
         for (auto& c : ext) c = (char)toupper((unsigned char)c);
         if (ext == ".SAM.GZ") {
@@ -206,6 +207,10 @@ class OutputWriter { // fastq.h OutputWriter: SAM header, then the chunks in the
         }
         put("@HD\tVN:1.6\tSO:queryname\n"); // fastq.cpp:579-583
         put("@PG\tID:Columba-amd\tPN:Columba\tCL:" + commandLine + "\n");
+        if (headerIsText) {
+            put(headerFile);
+            return;
+        }
         std::ifstream hs(headerFile, std::ios::binary);
         std::string line;
         while (hs && std::getline(hs, line)) put(line + "\n");
