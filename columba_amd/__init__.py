@@ -60,6 +60,7 @@ EXPORTS = [
     "cmb_pair_sam_device_classes", "cmb_move_pair_sam_device",
     "cmb_build_create", "cmb_build_destroy", "cmb_build_sizes_of", "cmb_build_bwt_arrays", "cmb_build_sparse_sa_sizes", "cmb_build_sparse_sa",
     "cmb_build_suffix_array", "cmb_build_index", "cmb_build_timings",
+    "cmb_build_move_sizes_of", "cmb_build_move_arrays", "cmb_build_move_index", "cmb_build_pack_lfbp",
     "cmb_last_error", "cmb_version",
 ]
 
@@ -180,6 +181,21 @@ class _BuildArrays(C.Structure):
                 ("bv_fwd", C.c_void_p), ("cnt_fwd", C.c_void_p), ("bv_rev", C.c_void_p), ("cnt_rev", C.c_void_p),
                 ("bv_cap", C.c_uint64), ("cnt_cap", C.c_uint64), ("bwt_words", C.c_void_p), ("bwt_cap", C.c_uint64),
                 ("char_counts", C.c_uint32 * 256)]
+
+
+class BuildMoveSizes(C.Structure):
+    """cmb_build_move_sizes"""
+    _fields_ = [("text_length", C.c_uint64), ("runs", C.c_uint64), ("rev_runs", C.c_uint64), ("lfbp_bytes", C.c_uint64),
+                ("rev_lfbp_bytes", C.c_uint64), ("n_plcp", C.c_uint64)]
+
+
+class _BuildMoveArrays(C.Structure):
+    """cmb_build_move_arrays_io"""
+    _fields_ = [("length_bits", C.c_uint32), ("lfbp", C.c_void_p), ("rev_lfbp", C.c_void_p), ("lfbp_cap", C.c_uint64), ("rev_lfbp_cap", C.c_uint64),
+                ("samples_first", C.c_void_p), ("samples_last", C.c_void_p), ("pred_first", C.c_void_p), ("first_to_run", C.c_void_p),
+                ("pred_last", C.c_void_p), ("last_to_run", C.c_void_p), ("runs_cap", C.c_uint64),
+                ("rev_samples_first", C.c_void_p), ("rev_samples_last", C.c_void_p), ("rev_runs_cap", C.c_uint64),
+                ("plcp_pos", C.c_void_p), ("plcp_sum", C.c_void_p), ("plcp_cap", C.c_uint64)]
 
 
 class _DevArray:
@@ -399,6 +415,10 @@ def lib():
         L.cmb_build_suffix_array.argtypes = [vp, i32, vp, u64]
         L.cmb_build_index.argtypes = [vp, u32, u32, u32, vp, u32, C.POINTER(vp)]
         L.cmb_build_timings.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), u32]
+        L.cmb_build_move_sizes_of.argtypes = [vp, u32, C.POINTER(BuildMoveSizes)]
+        L.cmb_build_move_arrays.argtypes = [vp, C.POINTER(_BuildMoveArrays), vp]
+        L.cmb_build_move_index.argtypes = [vp, i32, i32, vp, u32, C.POINTER(vp)]
+        L.cmb_build_pack_lfbp.argtypes = [u64, u64, u64, vp, u32, vp, u64, C.POINTER(u64)]
         _lib = L
     return _lib
 
@@ -614,12 +634,60 @@ class DeviceBuild:
         _chk(lib().cmb_build_index(self.h, sparseness, kmer_size, in_text_switch, _p(starts), starts.shape[0], C.byref(h)))
         return Index(self.n, kmer_size=kmer_size, device=self.device, _handle=h)
 
+    def move_sizes(self, length_bits: int = 64) -> BuildMoveSizes:
+        z = BuildMoveSizes()
+        _chk(lib().cmb_build_move_sizes_of(self.h, length_bits, C.byref(z)))
+        return z
+
+    def move_arrays(self, length_bits: int = 64):
+        """the b-move index of the text as ``movebuild.MoveArrays`` (``movebuild.save_move`` writes it unchanged): the two .LFBP images,
+        samples, predecessors and the PLCP in its run form; ``sa``, ``rev_sa`` and ``plcp`` stay None"""
+        from .movebuild import MoveArrays
+        z = self.move_sizes(length_bits)
+        per_run = ("samples_first", "samples_last", "pred_first", "first_to_run", "pred_last", "last_to_run")
+        bufs = {"lfbp": np.zeros(int(z.lfbp_bytes), np.uint8), "rev_lfbp": np.zeros(int(z.rev_lfbp_bytes), np.uint8)}
+        bufs.update({k: np.zeros(int(z.runs), np.uint64) for k in per_run})
+        bufs.update({k: np.zeros(int(z.rev_runs), np.uint64) for k in ("rev_samples_first", "rev_samples_last")})
+        bufs.update({k: np.zeros(int(z.n_plcp), np.uint64) for k in ("plcp_pos", "plcp_sum")})
+        a = _BuildMoveArrays()
+        for k, v in bufs.items():
+            setattr(a, k, _p(v))
+        a.length_bits = length_bits
+        a.lfbp_cap, a.rev_lfbp_cap, a.runs_cap, a.rev_runs_cap, a.plcp_cap = z.lfbp_bytes, z.rev_lfbp_bytes, z.runs, z.rev_runs, z.n_plcp
+        _chk(lib().cmb_build_move_arrays(self.h, C.byref(a), None))
+        return MoveArrays(n=self.n, lfbp_fwd=bufs["lfbp"], lfbp_rev=bufs["rev_lfbp"], smpf=bufs["samples_first"], smpl=bufs["samples_last"],
+                          rev_smpf=bufs["rev_samples_first"], rev_smpl=bufs["rev_samples_last"], pred_first=bufs["pred_first"],
+                          first_to_run=bufs["first_to_run"], pred_last=bufs["pred_last"], last_to_run=bufs["last_to_run"], plcp=None, sa=None,
+                          rev_sa=None, text=self.text, plcp_pos=bufs["plcp_pos"], plcp_sum=bufs["plcp_sum"])
+
+    def move_index(self, with_locate: bool = True, attach_text: bool = False, seq_starts=None) -> "MoveIndex":
+        """a resident ``MoveIndex`` from the arrays in HBM (cmb_build_move_index); attach_text: with the handle's text beside it"""
+        st = None if seq_starts is None else np.ascontiguousarray(seq_starts, np.uint32)
+        h = C.c_void_p()
+        _chk(lib().cmb_build_move_index(self.h, int(with_locate), int(attach_text), None if st is None else _p(st),
+                                        0 if st is None else st.shape[0], C.byref(h)))
+        return MoveIndex(None, device=self.device, _handle=h)
+
     def timings(self) -> Dict[str, float]:
         """host time per phase of the build in ms, every doubling round by itself (cmb_build_timings)"""
         names = (C.c_char_p * 256)()
         ms = (C.c_float * 256)()
         n = lib().cmb_build_timings(self.h, names, ms, 256)
         return {names[i].decode(): float(ms[i]) for i in range(n)}
+
+
+def device_pack_lfbp(n: int, rows: np.ndarray, zero_pos: int, length_bits: int = 64) -> np.ndarray:
+    """cmb_build_pack_lfbp: the bytes of a .LFBP file from r rows {head, start row, LF of the start row, its run} of a text of n
+    characters, packed by the device builder's kernel"""
+    rows = np.ascontiguousarray(rows, np.uint64).reshape(-1, 4)
+    size = C.c_uint64()
+    out = np.zeros(1, np.uint8)
+    rc = lib().cmb_build_pack_lfbp(n, rows.shape[0], zero_pos, _p(rows), length_bits, _p(out), 0, C.byref(size))
+    if rc != CMB_ERR_OVERFLOW:
+        _chk(rc)
+    out = np.zeros(int(size.value), np.uint8)
+    _chk(lib().cmb_build_pack_lfbp(n, rows.shape[0], zero_pos, _p(rows), length_bits, _p(out), out.shape[0], C.byref(size)))
+    return out
 
 
 class SearchStrategy:

@@ -11,7 +11,16 @@
 // radix sort (device_radix_sort.hpp, radix_sort_onesweep_iteration) works through batches of 2^30 items with 64-bit offsets, the scan
 // and the selection through chunks of their size_limit, so lengths of 2^31 and beyond need no split here.  That was verified by
 // reading the headers of rocPRIM 7.2; tools/build_bench.py compares a build at 3.0 * 10^9 characters with the harness builder.
-#include "dev_build.hpp"
+//
+// THE B-MOVE INDEX (cmb_build_move_*; kernels and algorithm: dev_move_build.hpp).  The first call derives, one direction after the other,
+// the run table, the samples and, for the text, the predecessors and the PLCP's run form, and keeps them in the handle: 56 bytes per
+// run (88 for the text's direction) and 16 per PLCP run.  While it works it holds 2 bytes per character (the BWT bytes and the
+// run-start flags, gone once the runs are known) and at most 256 bytes per run (starts, run lengths and their sums, sort keys and values
+// in and out, the open pairs, rocPRIM's scratch); both needs are compared with hipMemGetInfo before the allocation, and so are the packed
+// rows of a download (at most 16 bytes per run, allocated per call).  Host
+// synchronisations per direction: the number of runs, and for the text the number of pairs the wavefront pass takes and the number of
+// PLCP runs.
+#include "dev_move_build.hpp"
 #include "units.hpp"
 
 #include <chrono>
@@ -35,6 +44,14 @@ struct cmb_build {
     uint64_t hist[5] = {0, 0, 0, 0, 0}; // how often every code occurs
     DevBuf<uint8_t> tmp;                // rocPRIM's scratch
     std::vector<std::pair<std::string, double>> times;
+    // cmb_build_move_*: the O(runs) arrays of the b-move index, derived on first use
+    struct MoveSide {
+        uint64_t runs = 0, zeroPos = 0;
+        DevBuf<uint64_t> run; // {head, start row, LF of the start row, the run that holds it} per run
+        DevBuf<uint64_t> smpF, smpL;
+    } mv[2]; // the text, the reversed text
+    DevBuf<uint64_t> predFirst, firstToRun, predLast, lastToRun, plcpPos, plcpSum;
+    bool moveDone = false;
 };
 
 namespace {
@@ -204,6 +221,145 @@ int noDevice() {
 template <typename T> void download(T* host, const DevBuf<T>& d, uint64_t count) {
     if (count) HIPCHK(hipMemcpy(host, d.p, count * sizeof(T), hipMemcpyDeviceToHost));
 }
+
+// ---- the b-move index
+uint32_t ceilLog2(uint64_t v) { // moverepr.h:44-46 (build::bitsFor)
+    uint32_t b = 0;
+    while (b < 64 && (1ull << b) < v) b++;
+    return b;
+}
+bool isPowerOfTwo(uint64_t n) { return (n & (n - 1)) == 0; }
+const char* const MOVE_POWER_OF_TWO =
+    "a text size that is a power of two cannot be packed into a move table (the terminating row's start position n does not fit "
+    "ceil(log2 n) bits, moverepr.cpp:75-77)";
+void needFree(uint64_t need, const std::string& what) {
+    size_t freeB = 0, totalB = 0;
+    HIPCHK(hipMemGetInfo(&freeB, &totalB));
+    if (freeB < need)
+        throw std::runtime_error("the move tables on the device need " + std::to_string(need) + " bytes for " + what + ", " + std::to_string(freeB) +
+                                 " are free");
+}
+template <typename T> void copyBuf(const DevBuf<T>& from, DevBuf<T>& to, uint64_t count) {
+    to.alloc(count);
+    if (count) HIPCHK(hipMemcpy(to.p, from.p, count * sizeof(T), hipMemcpyDeviceToDevice));
+}
+constexpr uint64_t MVB_BYTES_PER_CHAR = 2, MVB_BYTES_PER_RUN = 256; // (above)
+
+// the O(runs) arrays of one direction into the handle
+void deriveMoveSide(cmb_build* b, bool rev) {
+    const uint64_t n = b->n;
+    const std::string tag = rev ? "move rev: " : "move fwd: ";
+    const hipStream_t s0 = nullptr;
+    cmb_build::MoveSide& m = b->mv[rev ? 1 : 0];
+    const uint32_t* sa = rev ? b->saR.p : b->saF.p;
+    Clock clk;
+    needFree(n * MVB_BYTES_PER_CHAR + (64ull << 20), std::to_string(n) + " characters (" + std::to_string(MVB_BYTES_PER_CHAR) + " per character)");
+    DevBuf<uint8_t> bwt, flag;
+    DevBuf<uint64_t> word, starts;
+    bwt.alloc(n), flag.alloc(n), word.alloc(2);
+    HIPCHK(hipMemset(word.p, 0, 2 * sizeof(uint64_t)));
+    rowLaunch(k_bld_bwt, "k_bld_bwt", n, (const uint8_t*)b->text.p, n, sa, rev, bwt.p, (unsigned long long*)(word.p + 1));
+    rowLaunch(k_mvb_flags, "k_mvb_flags", n, (const uint8_t*)bwt.p, n, flag.p, (unsigned long long*)word.p);
+    const uint64_t r = readWord(word.p);
+    needFree(r * MVB_BYTES_PER_RUN + (64ull << 20), std::to_string(r) + " runs (" + std::to_string(MVB_BYTES_PER_RUN) + " per run)");
+    starts.alloc(r), m.run.alloc(4 * r), m.smpF.alloc(r), m.smpL.alloc(r);
+    withScratch(b->tmp, [&](void* p, size_t& bytes) {
+        return rocprim::select(p, bytes, rocprim::counting_iterator<uint64_t>(0), flag.p, starts.p, word.p + 1, (size_t)n, s0);
+    });
+    rowLaunch(k_mvb_heads, "k_mvb_heads", r, (const uint8_t*)bwt.p, sa, (const uint64_t*)starts.p, r, n, m.run.p, m.smpF.p, m.smpL.p);
+    HIPCHK(hipDeviceSynchronize());
+    bwt.release(), flag.release();
+    b->times.push_back({tag + "run starts, heads and samples of " + std::to_string(r) + " runs", clk.lap()});
+    {
+        DevBuf<uint32_t> len, before;
+        len.alloc(r), before.alloc(r);
+        uint64_t cum = b->hist[0];
+        for (uint32_t c = 1; c <= 4; c++) {
+            rowLaunch(k_mvb_lens, "k_mvb_lens", r, (const uint64_t*)m.run.p, (const uint64_t*)starts.p, r, n, c, len.p);
+            scanExclusive(b->tmp, (const uint32_t*)len.p, before.p, (size_t)r, s0);
+            rowLaunch(k_mvb_lf, "k_mvb_lf", r, (const uint32_t*)before.p, r, c, cum, m.run.p);
+            cum += b->hist[c];
+        }
+        rowLaunch(k_mvb_out_run, "k_mvb_out_run", r, (const uint64_t*)starts.p, r, m.run.p);
+        HIPCHK(hipDeviceSynchronize());
+    }
+    m.runs = r, m.zeroPos = rev ? b->dollarR : b->dollarF;
+    b->times.push_back({tag + "LF of the run starts and their runs", clk.lap()});
+    if (rev) return;
+    const uint32_t keyBits = bitsOf(n - 1);
+    auto predecessors = [&](const DevBuf<uint64_t>& smp, DevBuf<uint64_t>& marked, DevBuf<uint64_t>& toRun) {
+        DevBuf<uint64_t> key, val;
+        key.alloc(r), val.alloc(r), marked.alloc(r), toRun.alloc(r);
+        rowLaunch(k_mvb_pred_keys, "k_mvb_pred_keys", r, (const uint64_t*)smp.p, r, n, key.p, val.p);
+        withScratch(b->tmp, [&](void* p, size_t& bytes) {
+            return rocprim::radix_sort_pairs(p, bytes, key.p, marked.p, val.p, toRun.p, (size_t)r, 0u, keyBits, s0);
+        });
+        HIPCHK(hipDeviceSynchronize());
+    };
+    predecessors(m.smpF, b->predFirst, b->firstToRun);
+    predecessors(m.smpL, b->predLast, b->lastToRun);
+    b->times.push_back({tag + "predecessors", clk.lap()});
+    DevBuf<uint64_t> sum, posSorted, sumSorted;
+    DevBuf<uint32_t> open, nOpen;
+    sum.alloc(r), open.alloc(r), nOpen.alloc(1);
+    HIPCHK(hipMemset(nOpen.p, 0, sizeof(uint32_t)));
+    rowLaunch(k_mvb_lcp_prefix, "k_mvb_lcp_prefix", r, (const uint8_t*)b->text.p, n, sa, (const uint64_t*)starts.p, r, sum.p, open.p, nOpen.p);
+    uint32_t mOpen = 0;
+    HIPCHK(hipMemcpy(&mOpen, nOpen.p, sizeof(mOpen), hipMemcpyDeviceToHost));
+    rowLaunch(k_mvb_lcp_wave, "k_mvb_lcp_wave", (uint64_t)mOpen * 64, (const uint8_t*)b->text.p, n, sa, (const uint64_t*)starts.p,
+              (const uint32_t*)open.p, (uint64_t)mOpen, sum.p);
+    b->times.push_back({tag + "PLCP at " + std::to_string(r) + " run starts, " + std::to_string(mOpen) + " by a wavefront each", clk.lap()});
+    open.release();
+    posSorted.alloc(r), sumSorted.alloc(r);
+    withScratch(b->tmp, [&](void* p, size_t& bytes) {
+        return rocprim::radix_sort_pairs(p, bytes, m.smpF.p, posSorted.p, sum.p, sumSorted.p, (size_t)r, 0u, keyBits, s0);
+    });
+    DevBuf<uint8_t> keep;
+    keep.alloc(r);
+    rowLaunch(k_mvb_plcp_keep, "k_mvb_plcp_keep", r, (const uint64_t*)sumSorted.p, r, keep.p);
+    withScratch(b->tmp, [&](void* p, size_t& bytes) { return rocprim::select(p, bytes, posSorted.p, keep.p, sum.p, word.p, (size_t)r, s0); });
+    const uint64_t nPlcp = readWord(word.p);
+    copyBuf(sum, b->plcpPos, nPlcp);
+    withScratch(b->tmp, [&](void* p, size_t& bytes) { return rocprim::select(p, bytes, sumSorted.p, keep.p, sum.p, word.p, (size_t)r, s0); });
+    HIPCHK(hipDeviceSynchronize());
+    copyBuf(sum, b->plcpSum, nPlcp);
+    b->times.push_back({tag + "PLCP run form, " + std::to_string(nPlcp) + " runs", clk.lap()});
+}
+// selects the handle's device (every cmb_build_move_* call works on it, the later ones too) and derives on first use
+void deriveMove(cmb_build* b) {
+    HIPCHK(hipSetDevice(b->device));
+    if (b->moveDone) return;
+    const size_t phases = b->times.size();
+    try {
+        deriveMoveSide(b, false);
+        deriveMoveSide(b, true);
+    } catch (...) { // a later call derives again: its phases must not stand beside those of the attempt that failed
+        b->times.resize(phases);
+        throw;
+    }
+    b->tmp.release();
+    b->moveDone = true;
+}
+uint64_t lfbpBytes(uint64_t n, uint64_t r, uint32_t lengthBits) {
+    return 3 * (uint64_t)(lengthBits / 8) + (uint64_t)((3 + 2 * ceilLog2(n) + ceilLog2(r) + 7) / 8) * (r + 1);
+}
+// the image of a .LFBP file from a run table in HBM: the header from the host, the rows packed by k_mvb_pack
+void packLfbp(const uint64_t* run, uint64_t n, uint64_t r, uint64_t zeroPos, uint32_t lengthBits, uint8_t* out) {
+    const uint32_t bitsN = ceilLog2(n), bitsR = ceilLog2(r), rowBytes = (3 + 2 * bitsN + bitsR + 7) / 8;
+    const size_t W = lengthBits / 8;
+    needFree((uint64_t)rowBytes * (r + 1) + (64ull << 20), std::to_string(r + 1) + " packed rows (" + std::to_string(rowBytes) + " bytes each)");
+    DevBuf<uint8_t> body;
+    body.alloc((size_t)rowBytes * (r + 1));
+    rowLaunch(k_mvb_pack, "k_mvb_pack", r + 1, run, r, n, bitsN, bitsR, rowBytes, body.p);
+    const uint64_t hdr[3] = {n, r, zeroPos};
+    for (int i = 0; i < 3; i++) memcpy(out + i * W, &hdr[i], W); // (little-endian, as MoveLFReprBP::write leaves them)
+    HIPCHK(hipMemcpy(out + 3 * W, body.p, (size_t)rowBytes * (r + 1), hipMemcpyDeviceToHost));
+}
+void moveSizes(const cmb_build* b, uint32_t lengthBits, cmb_build_move_sizes* z) {
+    z->text_length = b->n, z->runs = b->mv[0].runs, z->rev_runs = b->mv[1].runs;
+    z->lfbp_bytes = lfbpBytes(b->n, z->runs, lengthBits), z->rev_lfbp_bytes = lfbpBytes(b->n, z->rev_runs, lengthBits);
+    z->n_plcp = b->plcpPos.n;
+}
 } // namespace
 
 extern "C" int cmb_build_create(const char* text, uint64_t n, int device, cmb_build** out) {
@@ -359,4 +515,109 @@ extern "C" int cmb_build_timings(const cmb_build* b, const char** names, float* 
         n++;
     }
     return (int)n;
+}
+
+extern "C" int cmb_build_move_sizes_of(cmb_build* b, uint32_t length_bits, cmb_build_move_sizes* out) {
+    if (!b || !out) return fail(CMB_ERR_INVALID, "null argument");
+    if (length_bits != 64 && length_bits != 32) return fail(CMB_ERR_INVALID, "length_bits must be 64 or 32");
+    if (isPowerOfTwo(b->n)) return fail(CMB_ERR_UNSUPPORTED, MOVE_POWER_OF_TWO);
+    try {
+        deriveMove(b);
+        moveSizes(b, length_bits, out);
+        return CMB_OK;
+    } catch (const std::exception& e) {
+        return fail(CMB_ERR_DEVICE, e.what());
+    }
+}
+extern "C" int cmb_build_move_arrays(cmb_build* b, cmb_build_move_arrays_io* io, uint64_t* needed) {
+    if (!b || !io || !io->lfbp || !io->rev_lfbp || !io->samples_first || !io->samples_last || !io->pred_first || !io->first_to_run ||
+        !io->pred_last || !io->last_to_run || !io->rev_samples_first || !io->rev_samples_last || !io->plcp_pos || !io->plcp_sum)
+        return fail(CMB_ERR_INVALID, "null argument");
+    if (io->length_bits != 64 && io->length_bits != 32) return fail(CMB_ERR_INVALID, "length_bits must be 64 or 32");
+    if (isPowerOfTwo(b->n)) return fail(CMB_ERR_UNSUPPORTED, MOVE_POWER_OF_TWO);
+    try {
+        deriveMove(b);
+        cmb_build_move_sizes z;
+        moveSizes(b, io->length_bits, &z);
+        if (io->lfbp_cap < z.lfbp_bytes || io->rev_lfbp_cap < z.rev_lfbp_bytes || io->runs_cap < z.runs || io->rev_runs_cap < z.rev_runs ||
+            io->plcp_cap < z.n_plcp) {
+            if (needed) needed[0] = z.lfbp_bytes, needed[1] = z.rev_lfbp_bytes, needed[2] = z.runs, needed[3] = z.rev_runs, needed[4] = z.n_plcp;
+            return fail(CMB_ERR_OVERFLOW, "output buffers too small: " + std::to_string(z.lfbp_bytes) + " and " + std::to_string(z.rev_lfbp_bytes) +
+                                              " bytes of move tables, " + std::to_string(z.runs) + " and " + std::to_string(z.rev_runs) +
+                                              " values per run and " + std::to_string(z.n_plcp) + " PLCP runs are needed");
+        }
+        packLfbp(b->mv[0].run.p, b->n, z.runs, b->mv[0].zeroPos, io->length_bits, io->lfbp);
+        packLfbp(b->mv[1].run.p, b->n, z.rev_runs, b->mv[1].zeroPos, io->length_bits, io->rev_lfbp);
+        download(io->samples_first, b->mv[0].smpF, z.runs), download(io->samples_last, b->mv[0].smpL, z.runs);
+        download(io->rev_samples_first, b->mv[1].smpF, z.rev_runs), download(io->rev_samples_last, b->mv[1].smpL, z.rev_runs);
+        download(io->pred_first, b->predFirst, z.runs), download(io->first_to_run, b->firstToRun, z.runs);
+        download(io->pred_last, b->predLast, z.runs), download(io->last_to_run, b->lastToRun, z.runs);
+        download(io->plcp_pos, b->plcpPos, z.n_plcp), download(io->plcp_sum, b->plcpSum, z.n_plcp);
+        return CMB_OK;
+    } catch (const std::exception& e) {
+        return fail(CMB_ERR_DEVICE, e.what());
+    }
+}
+extern "C" int cmb_build_move_index(cmb_build* b, int with_locate, int attach_text, const uint32_t* seq_starts, uint32_t n_seqs,
+                                    cmb_move_index** out) {
+    if (!b || !out) return fail(CMB_ERR_INVALID, "null argument");
+    if (isPowerOfTwo(b->n)) return fail(CMB_ERR_UNSUPPORTED, MOVE_POWER_OF_TWO);
+    if (attach_text && b->n >= 0xFFFFFF00ull)
+        return fail(CMB_ERR_UNSUPPORTED, "alignments on texts of 2^32 characters and more are not implemented");
+    *out = nullptr;
+    try {
+        deriveMove(b);
+        MoveDeviceArrays a;
+        a.n = b->n;
+        for (int s = 0; s < 2; s++) { // the rows go straight into the buffer the index keeps; the O(runs) arrays of the handle are copied
+            const cmb_build::MoveSide& m = b->mv[s];
+            a.side[s].runs = m.runs, a.side[s].zeroCharPos = m.zeroPos;
+            a.side[s].rows.alloc(m.runs + 2);
+            rowLaunch(k_mvb_rows, "k_mvb_rows", m.runs + 1, (const uint64_t*)m.run.p, m.runs, b->n, a.side[s].rows.p);
+            copyBuf(m.smpF, a.side[s].smpF, m.runs), copyBuf(m.smpL, a.side[s].smpL, m.runs);
+        }
+        if (with_locate) {
+            const uint64_t r = b->mv[0].runs;
+            copyBuf(b->predFirst, a.predFirst, r), copyBuf(b->firstToRun, a.firstToRun, r);
+            copyBuf(b->predLast, a.predLast, r), copyBuf(b->lastToRun, a.lastToRun, r);
+            copyBuf(b->plcpPos, a.plcpPos, b->plcpPos.n), copyBuf(b->plcpSum, a.plcpSum, b->plcpSum.n);
+            a.hasLocate = true;
+        }
+        if (int rc = moveIndexFromDeviceArrays(a, b->device, out)) return rc;
+        if (attach_text) { // through a host copy: cmb_move_attach_text takes the text from the host
+            std::vector<char> text(b->n);
+            HIPCHK(hipMemcpy(text.data(), b->text.p, b->n, hipMemcpyDeviceToHost));
+            if (int rc = cmb_move_attach_text(*out, text.data(), b->n, seq_starts, seq_starts ? n_seqs : 0)) {
+                cmb_move_destroy(*out);
+                *out = nullptr;
+                return rc;
+            }
+        }
+        return CMB_OK;
+    } catch (const std::exception& e) {
+        if (*out) cmb_move_destroy(*out);
+        *out = nullptr;
+        return fail(CMB_ERR_DEVICE, e.what());
+    }
+}
+extern "C" int cmb_build_pack_lfbp(uint64_t n, uint64_t r, uint64_t zero_pos, const uint64_t* rows, uint32_t length_bits, uint8_t* out,
+                                   uint64_t cap, uint64_t* bytes) {
+    if (!rows || !out || !bytes) return fail(CMB_ERR_INVALID, "null argument");
+    if (length_bits != 64 && length_bits != 32) return fail(CMB_ERR_INVALID, "length_bits must be 64 or 32");
+    if (n < 3 || r < 2 || r > n || zero_pos >= n) return fail(CMB_ERR_INVALID, "implausible text size, number of runs or position of the sentinel");
+    if (length_bits == 32 && n > 0xFFFFFFFFull) return fail(CMB_ERR_INVALID, "the text size does not fit a 32-bit length_t");
+    if (isPowerOfTwo(n)) return fail(CMB_ERR_UNSUPPORTED, MOVE_POWER_OF_TWO);
+    if (ceilLog2(n) > 40) return fail(CMB_ERR_UNSUPPORTED, "texts of 2^40 characters and more are not supported");
+    *bytes = lfbpBytes(n, r, length_bits);
+    if (cap < *bytes) return fail(CMB_ERR_OVERFLOW, "output buffer too small: " + std::to_string(*bytes) + " bytes are needed");
+    if (int rc = noDevice()) return rc;
+    try {
+        HIPCHK(hipSetDevice(0));
+        DevBuf<uint64_t> run;
+        run.upload(rows, 4 * r);
+        packLfbp(run.p, n, r, zero_pos, length_bits, out);
+        return CMB_OK;
+    } catch (const std::exception& e) {
+        return fail(CMB_ERR_DEVICE, e.what());
+    }
 }

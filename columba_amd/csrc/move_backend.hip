@@ -73,10 +73,12 @@ struct PosSetHost {
     uint32_t shift = 0;
     uint64_t count = 0;
     PosSet dev() const { return PosSet{pos.p, count, dir.p, shift}; }
-    // elements below `limit`, strictly increasing; about eight elements per directory bucket
-    void build(const uint64_t* h, uint64_t cnt, uint64_t limit, uint32_t* dFlags) {
+    // elements below `limit`, strictly increasing, in HBM already (the set takes the buffer over); about eight elements per directory bucket
+    void build(DevBuf<uint64_t>& d, uint64_t cnt, uint64_t limit, uint32_t* dFlags) {
         count = cnt;
-        pos.upload(h, cnt);
+        pos.release();
+        std::swap(pos.p, d.p), std::swap(pos.n, d.n);
+        pos.n = cnt;
         hipLaunchKernelGGL(k_posset_check, dim3(gridFor(cnt)), dim3(256), 0, 0, pos.p, cnt, limit, dFlags);
         shift = 0;
         while (shift < 40 && (limit >> shift) > std::max<uint64_t>(cnt / 8, 1)) shift++;
@@ -134,9 +136,9 @@ static void bindMoveDev(cmb_move_index* ix) { // MoveDev pointers from the ownin
     }
 }
 
-// one .LFBP file (moverepr.cpp:103-168) -> 16-byte rows in HBM, checked
-static void loadTable(TableHost& t, const uint8_t* file, uint64_t fileBytes, uint32_t lengthBits, const uint64_t* smpF,
-                      const uint64_t* smpL, uint64_t& nOut, uint32_t* dFlags, const char* what) {
+// one .LFBP file (moverepr.cpp:103-168) -> 16-byte rows in HBM (the gap fields and the checks: moveIndexFromDeviceArrays)
+static void loadTable(MoveDeviceArrays::Side& t, const uint8_t* file, uint64_t fileBytes, uint32_t lengthBits, const uint64_t* smpF,
+                      const uint64_t* smpL, uint64_t& nOut, const char* what) {
     const size_t W = lengthBits / 8;
     if (fileBytes < 3 * W) throw std::invalid_argument(std::string(what) + ": shorter than its header");
     uint64_t hdr[3] = {0, 0, 0};
@@ -152,17 +154,76 @@ static void loadTable(TableHost& t, const uint8_t* file, uint64_t fileBytes, uin
     DevBuf<uint8_t> packed;
     packed.upload(file + 3 * W, body);
     t.rows.alloc(runs + 2);
-    HIPCHK(hipMemset(t.rows.p + runs + 1, 0xFF, sizeof(uint4)));
     hipLaunchKernelGGL(k_move_unpack, dim3(gridFor(runs + 1)), dim3(256), 0, 0, packed.p, runs + 1, rowBytes, bitsN, bitsR, t.rows.p);
-    hipLaunchKernelGGL(k_move_gaps, dim3(gridFor(runs)), dim3(256), 0, 0, t.rows.p, runs);
-    hipLaunchKernelGGL(k_move_check, dim3(gridFor(runs + 1)), dim3(256), 0, 0, t.rows.p, runs, n, dFlags);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipDeviceSynchronize()); // (`packed` goes)
     t.runs = runs;
     t.zeroCharPos = hdr[2];
     t.smpF.upload(smpF, runs);
     t.smpL.upload(smpL, runs);
     nOut = n;
+}
+
+template <typename T> static void takeBuf(DevBuf<T>& from, DevBuf<T>& to) {
+    to.release();
+    std::swap(from.p, to.p);
+    std::swap(from.n, to.n);
+}
+
+int cmb::moveIndexFromDeviceArrays(MoveDeviceArrays& a, int device, cmb_move_index** out) {
+    *out = nullptr;
+    try {
+        HIPCHK(hipSetDevice(device));
+        std::unique_ptr<cmb_move_index> ix(new cmb_move_index());
+        ix->device = device;
+        ix->n = a.n;
+        DevBuf<uint32_t> flags;
+        flags.alloc(4);
+        HIPCHK(hipMemset(flags.p, 0, 4 * sizeof(uint32_t)));
+        for (int s = 0; s < 2; s++) {
+            TableHost& t = ix->tab[s];
+            const uint64_t runs = a.side[s].runs;
+            if (a.side[s].rows.n < runs + 2 || a.side[s].smpF.n < runs || a.side[s].smpL.n < runs)
+                return failWith(CMB_ERR_INVALID, "the arrays of a move table are shorter than its number of runs");
+            takeBuf(a.side[s].rows, t.rows), takeBuf(a.side[s].smpF, t.smpF), takeBuf(a.side[s].smpL, t.smpL);
+            t.runs = runs, t.zeroCharPos = a.side[s].zeroCharPos;
+            HIPCHK(hipMemset(t.rows.p + runs + 1, 0xFF, sizeof(uint4)));
+            hipLaunchKernelGGL(k_move_gaps, dim3(gridFor(runs)), dim3(256), 0, 0, t.rows.p, runs);
+            hipLaunchKernelGGL(k_move_check, dim3(gridFor(runs + 1)), dim3(256), 0, 0, t.rows.p, runs, a.n, flags.p + s);
+            HIPCHK(hipGetLastError());
+        }
+        if (a.hasLocate) {
+            const uint64_t r = ix->tab[0].runs, nPlcp = a.plcpPos.n;
+            if (a.predFirst.n < r || a.firstToRun.n < r || a.predLast.n < r || a.lastToRun.n < r || !nPlcp || a.plcpSum.n < nPlcp)
+                return failWith(CMB_ERR_INVALID, "the locate arrays are shorter than the number of runs");
+            ix->predFirst.build(a.predFirst, r, ix->n, flags.p + 2);
+            ix->predLast.build(a.predLast, r, ix->n, flags.p + 2);
+            ix->plcpPos.build(a.plcpPos, nPlcp, ix->n, flags.p + 2);
+            takeBuf(a.firstToRun, ix->firstToRun), takeBuf(a.lastToRun, ix->lastToRun), takeBuf(a.plcpSum, ix->plcpSum);
+            hipLaunchKernelGGL(k_run_map_check, dim3(gridFor(r)), dim3(256), 0, 0, ix->firstToRun.p, r, r, flags.p + 2);
+            hipLaunchKernelGGL(k_run_map_check, dim3(gridFor(r)), dim3(256), 0, 0, ix->lastToRun.p, r, r, flags.p + 2);
+            uint64_t first = 0;
+            HIPCHK(hipMemcpy(&first, ix->plcpPos.pos.p, sizeof(first), hipMemcpyDeviceToHost));
+            if (first != 0) return failWith(CMB_ERR_INVALID, "the PLCP samples must start at position 0");
+            ix->hasLocate = true;
+        }
+        HIPCHK(hipGetLastError());
+        uint32_t h[4];
+        HIPCHK(hipMemcpy(h, flags.p, sizeof(h), hipMemcpyDeviceToHost));
+        if (h[0] || h[1])
+            return failWith(CMB_ERR_INVALID, "inconsistent move table (" + std::to_string(h[0]) + " rows of .LFBP, " + std::to_string(h[1]) +
+                                                 " rows of .rev.LFBP break the order of the runs, the LF targets or the terminating row)");
+        if (h[2]) return failWith(CMB_ERR_INVALID, "inconsistent locate arrays (positions not increasing / outside the text, or run numbers outside the table)");
+        bindMoveDev(ix.get());
+        *out = ix.release();
+        return CMB_OK;
+    } catch (const std::invalid_argument& e) {
+        return failWith(CMB_ERR_INVALID, e.what());
+    } catch (const std::length_error& e) {
+        return failWith(CMB_ERR_UNSUPPORTED, e.what());
+    } catch (const std::exception& e) {
+        return failWith(CMB_ERR_DEVICE, e.what());
+    }
 }
 
 extern "C" int cmb_move_create(const cmb_move_desc* desc, int device, cmb_move_index** out) {
@@ -179,40 +240,23 @@ extern "C" int cmb_move_create(const cmb_move_desc* desc, int device, cmb_move_i
         if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count)
             return failWith(CMB_ERR_DEVICE, "no such GPU (the move tables live in HBM; there is no CPU path)");
         HIPCHK(hipSetDevice(device));
-        std::unique_ptr<cmb_move_index> ix(new cmb_move_index());
-        ix->device = device;
-        DevBuf<uint32_t> flags;
-        flags.alloc(4);
-        HIPCHK(hipMemset(flags.p, 0, 4 * sizeof(uint32_t)));
+        // the upload boundary: the two files unpacked into 16-byte rows, the other arrays into HBM as they are; the rest is
+        // moveIndexFromDeviceArrays
+        MoveDeviceArrays a;
         uint64_t nF = 0, nR = 0;
-        loadTable(ix->tab[0], desc->lfbp, desc->lfbp_bytes, desc->length_bits, desc->samples_first, desc->samples_last, nF, flags.p, ".LFBP");
-        loadTable(ix->tab[1], desc->rev_lfbp, desc->rev_lfbp_bytes, desc->length_bits, desc->rev_samples_first, desc->rev_samples_last, nR,
-                  flags.p + 1, ".rev.LFBP");
+        loadTable(a.side[0], desc->lfbp, desc->lfbp_bytes, desc->length_bits, desc->samples_first, desc->samples_last, nF, ".LFBP");
+        loadTable(a.side[1], desc->rev_lfbp, desc->rev_lfbp_bytes, desc->length_bits, desc->rev_samples_first, desc->rev_samples_last, nR,
+                  ".rev.LFBP");
         if (nF != nR) return failWith(CMB_ERR_INVALID, "the two move tables are of different texts");
-        ix->n = nF;
+        a.n = nF;
         if (loc) {
-            const uint64_t r = ix->tab[0].runs;
-            ix->predFirst.build(desc->pred_first, r, ix->n, flags.p + 2);
-            ix->predLast.build(desc->pred_last, r, ix->n, flags.p + 2);
-            ix->plcpPos.build(desc->plcp_pos, desc->n_plcp, ix->n, flags.p + 2);
-            ix->firstToRun.upload(desc->first_to_run, r);
-            ix->lastToRun.upload(desc->last_to_run, r);
-            ix->plcpSum.upload(desc->plcp_sum, desc->n_plcp);
-            hipLaunchKernelGGL(k_run_map_check, dim3(gridFor(r)), dim3(256), 0, 0, ix->firstToRun.p, r, r, flags.p + 2);
-            hipLaunchKernelGGL(k_run_map_check, dim3(gridFor(r)), dim3(256), 0, 0, ix->lastToRun.p, r, r, flags.p + 2);
-            if (desc->plcp_pos[0] != 0) return failWith(CMB_ERR_INVALID, "the PLCP samples must start at position 0");
-            ix->hasLocate = true;
+            const uint64_t r = a.side[0].runs;
+            a.predFirst.upload(desc->pred_first, r), a.firstToRun.upload(desc->first_to_run, r);
+            a.predLast.upload(desc->pred_last, r), a.lastToRun.upload(desc->last_to_run, r);
+            a.plcpPos.upload(desc->plcp_pos, desc->n_plcp), a.plcpSum.upload(desc->plcp_sum, desc->n_plcp);
+            a.hasLocate = true;
         }
-        HIPCHK(hipGetLastError());
-        uint32_t h[4];
-        HIPCHK(hipMemcpy(h, flags.p, sizeof(h), hipMemcpyDeviceToHost));
-        if (h[0] || h[1])
-            return failWith(CMB_ERR_INVALID, "inconsistent move table (" + std::to_string(h[0]) + " rows of .LFBP, " + std::to_string(h[1]) +
-                                                 " rows of .rev.LFBP break the order of the runs, the LF targets or the terminating row)");
-        if (h[2]) return failWith(CMB_ERR_INVALID, "inconsistent locate arrays (positions not increasing / outside the text, or run numbers outside the table)");
-        bindMoveDev(ix.get());
-        *out = ix.release();
-        return CMB_OK;
+        return moveIndexFromDeviceArrays(a, device, out);
     } catch (const std::invalid_argument& e) {
         return failWith(CMB_ERR_INVALID, e.what());
     } catch (const std::length_error& e) {

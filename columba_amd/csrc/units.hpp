@@ -37,6 +37,23 @@ struct IndexDeviceArrays {
 // consistency probe, the dense suffix array and the sequence starts.  The arguments have been checked; the arrays stay the caller's.
 int indexFromDeviceArrays(const IndexDeviceArrays& a, int device, cmb_index** out);
 // ---- move_backend.hip
+// The arrays of a b-move index in the DEVICE layout, already in HBM on the index's device: per direction the 16-byte rows 0 .. runs (the
+// terminating row among them; room for runs + 2 rows, the gap fields not yet filled) and the samples; the locate arrays as
+// cmb_move_desc names them.  cmb_move_create uploads and unpacks a description into this form; cmb_build_move_index (build.hip) hands
+// over what the device builder made.
+struct MoveDeviceArrays {
+    uint64_t n = 0; // text length with the final '$'
+    struct Side {
+        DevBuf<uint4> rows;
+        DevBuf<uint64_t> smpF, smpL;
+        uint64_t runs = 0, zeroCharPos = 0;
+    } side[2]; // the text, the reversed text
+    bool hasLocate = false;
+    DevBuf<uint64_t> predFirst, firstToRun, predLast, lastToRun, plcpPos, plcpSum; // (plcpPos.n: the number of PLCP runs)
+};
+// everything cmb_move_create does behind its upload: the gap fields, the directories of the position sets and every consistency check
+// (CMB_ERR_INVALID for arrays that are not a consistent index).  The index takes the buffers over: `a` is left empty.
+int moveIndexFromDeviceArrays(MoveDeviceArrays& a, int device, cmb_move_index** out);
 // one view per part of a batch that has run with its lists kept (cmb_move_batch_keep_device_lists)
 int moveBatchListViews(cmb_move_batch* b, std::vector<ListView>& out);
 

@@ -8,8 +8,8 @@
 // (.LFBP, .rev.LFBP in the reference's format), samples, predecessors and PLCP as the .u64 files include/columba_amd_bmove.hpp (BMove)
 // loads; seed length 100 unless -l is given (definitions.h:41); --keep-text also writes <base>.txt.bin for alignments (BMove::attachText).
 //   g++ -std=c++17 -O2 -I include examples/columba_build.cpp -o columba_build -lz
-// --device [id]: the Vanilla index's arrays are built on GPU <id> (default 0) by the library (cmb_build_*, include/columba_amd_build_device.hpp)
-// instead of the host's SA-IS; the files are the same bytes.  Compiled in only with the define, which makes the tool need the library:
+// --device [id]: the arrays of either flavour are built on GPU <id> (default 0) by the library (cmb_build_*, include/columba_amd_build_device.hpp)
+// instead of the host's SA-IS and scalar loops; the files are the same bytes.  Compiled in only with the define, which makes the tool need the library:
 //   g++ -std=c++17 -O2 -DCOLUMBA_AMD_DEVICE_BUILD -I include examples/columba_build.cpp -o columba_build -L columba_amd -lcolumba_amd -lz
 #ifdef COLUMBA_AMD_DEVICE_BUILD
 #include "columba_amd_build_device.hpp"
@@ -55,11 +55,12 @@ int main(int argc, char** argv) {
         return 1;
     }
 #endif
-    if (device >= 0 && rlc) {
-        std::fprintf(stderr, "columba_build: --device builds the Vanilla index only, not --rlc\n");
-        return 1;
-    }
     try {
+#ifdef COLUMBA_AMD_DEVICE_BUILD
+        if (rlc && device >= 0)
+            columba_amd::build::buildMoveIndexDevice(fasta, base, seedGiven ? seedLength : 100u, keepText, device);
+        else
+#endif
         if (rlc)
             columba_amd::build::buildMoveIndex(fasta, base, seedGiven ? seedLength : 100u, keepText);
 #ifdef COLUMBA_AMD_DEVICE_BUILD

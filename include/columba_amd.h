@@ -156,8 +156,8 @@ int cmb_build_suffix_array(cmb_build* b, int reverse, uint32_t* out, uint64_t ca
  * handle afterwards. */
 int cmb_build_index(cmb_build* b, uint32_t sparseness, uint32_t kmer_size, uint32_t in_text_switch, const uint32_t* seq_starts,
                     uint32_t n_seqs, cmb_index** out);
-/* host time per phase of cmb_build_create in ms, every doubling round of either pass by itself (as cmb_best_timings: names[i] / ms[i],
- * returns how many) */
+/* host time per phase of cmb_build_create in ms, every doubling round of either pass by itself, and of the first cmb_build_move_*
+ * call (section "b-move"; "move fwd: ..." / "move rev: ..."; as cmb_best_timings: names[i] / ms[i], returns how many) */
 int cmb_build_timings(const cmb_build* b, const char** names, float* ms, uint32_t cap);
 
 /* --- strategy ----------------------------------------------------------------------
@@ -736,6 +736,49 @@ int cmb_move_layout_of(const cmb_move_index* idx, cmb_move_layout* out);
 int cmb_move_create_empty(const cmb_move_layout* layout, int device, cmb_move_index** out);
 int cmb_move_device_arrays(cmb_move_index* idx, void** ptrs /* [CMB_MOVE_DEV_ARRAYS] */, uint64_t* bytes /* [CMB_MOVE_DEV_ARRAYS] */);
 int cmb_move_validate(cmb_move_index* idx);
+
+/* The index from a cmb_build handle (index construction on the device, above): the move tables of the text and of the reversed text, the suffix array
+ * samples at the run boundaries, the phi predecessors and the PLCP in its run form — every array of cmb_move_desc, value for value what
+ * include/columba_amd_build.hpp (buildMoveIndex) computes on the host, the .LFBP images byte for byte — and a resident cmb_move_index
+ * without a round trip through host arrays (columba_amd/csrc/dev_move_build.hpp).  The first of these calls derives the O(runs) arrays
+ * from the text and the suffix arrays in HBM and keeps them in the handle; it needs 2 bytes per character (the BWT and the run-start
+ * flags of one direction) and up to 256 bytes per run on top of the live handle, released but for 56 bytes per run (88 for the text's
+ * direction) and 16 per PLCP run before it returns.  The free memory is checked first (CMB_ERR_DEVICE names the bytes).
+ * A text whose length is a power of two is CMB_ERR_UNSUPPORTED: the terminating row (n, n) does not fit ceil(log2 n) bits
+ * (moverepr.cpp:75-77).  That leaves n >= 3, and every such text has two runs or more. */
+typedef struct {
+    uint64_t text_length;
+    uint64_t runs, rev_runs;             /* BWT runs of the text, of the reversed text */
+    uint64_t lfbp_bytes, rev_lfbp_bytes; /* <base>.LFBP, <base>.rev.LFBP: 3 header words of length_bits, then runs + 1 packed rows */
+    uint64_t n_plcp;                     /* runs of the PLCP's run form */
+} cmb_build_move_sizes;
+int cmb_build_move_sizes_of(cmb_build* b, uint32_t length_bits /* 64 or 32 */, cmb_build_move_sizes* out);
+/* everything cmb_move_desc names, to caller-allocated buffers (capacities in bytes for the two images, in 64-bit values for the rest).
+ * CMB_ERR_OVERFLOW if a buffer is too small: nothing is written but needed[0 .. 4] = {lfbp_bytes, rev_lfbp_bytes, runs, rev_runs,
+ * n_plcp} (needed may be NULL). */
+typedef struct {
+    uint32_t length_bits; /* width of length_t in the two images: 64 or 32 */
+    uint8_t *lfbp, *rev_lfbp;
+    uint64_t lfbp_cap, rev_lfbp_cap;
+    uint64_t *samples_first, *samples_last, *pred_first, *first_to_run, *pred_last, *last_to_run; /* runs values each */
+    uint64_t runs_cap;
+    uint64_t *rev_samples_first, *rev_samples_last; /* rev_runs values each */
+    uint64_t rev_runs_cap;
+    uint64_t *plcp_pos, *plcp_sum; /* n_plcp values each */
+    uint64_t plcp_cap;
+} cmb_build_move_arrays_io;
+int cmb_build_move_arrays(cmb_build* b, cmb_build_move_arrays_io* io, uint64_t* needed /* [5] or NULL */);
+/* a cmb_move_index on the build's device from the arrays in HBM — what cmb_move_create makes of the same arrays uploaded from the host,
+ * with the same consistency checks (with_locate == 0: an index for extension only).  attach_text != 0: the handle's own text becomes the
+ * text beside the index as after cmb_move_attach_text (seq_starts / n_seqs as there; CMB_ERR_UNSUPPORTED from 2^32 - 256 characters
+ * on); the text travels through a host copy, as cmb_move_attach_text takes it.  The index does not depend on the handle afterwards. */
+int cmb_build_move_index(cmb_build* b, int with_locate, int attach_text, const uint32_t* seq_starts, uint32_t n_seqs, cmb_move_index** out);
+/* test hook, as cmb_build_suffix_array: the device kernel that packs the rows of a .LFBP file, on rows given by the caller — r rows of
+ * {head, inputStartPos, outputStartPos, outputStartRun} of a text of n characters (n < 2^40, no power of two; 2 <= r <= n) —, so that
+ * field offsets of 64 bits and more are reached without a text of 2^31 characters.  out: the file image, header included; *bytes is
+ * its size (set with CMB_ERR_OVERFLOW too).  Needs a GPU (device 0). */
+int cmb_build_pack_lfbp(uint64_t n, uint64_t r, uint64_t zero_pos, const uint64_t* rows /* 4 * r */, uint32_t length_bits, uint8_t* out,
+                        uint64_t cap, uint64_t* bytes);
 
 /* k = 0 on the b-move index, end to end: SearchStrategy::matchApproxAllMap with maxED = 0 (searchstrategy.cpp:499-510) =
  * IndexInterface::exactMatchesOutput (indexinterface.cpp:947-1014, RLC branch) of every read and of its reverse complement.

@@ -140,6 +140,20 @@ class BMove {
             throw std::runtime_error("sample arrays do not have one entry per run");
         }
     }
+    // Without index files: the index of a preprocessed text (upper-case ACGT and a final '$', its length no power of two) is built on
+    // the device and stays there (cmb_build_create, cmb_build_move_index).  attachTextToo: the text becomes the text beside the index
+    // as after attachText(text, seqStarts).  include/columba_amd_build_device.hpp: bmoveFromFasta starts from FASTA files.
+    struct FromText {};
+    BMove(FromText, const std::string& text, int device = 0, bool withLocate = true, bool attachTextToo = false,
+          const std::vector<uint32_t>& seqStarts = {}) {
+        cmb_build* b = nullptr;
+        check(cmb_build_create(text.data(), text.size(), device, &b));
+        const int rc = cmb_build_move_index(b, withLocate, attachTextToo, seqStarts.empty() ? nullptr : seqStarts.data(),
+                                            (uint32_t)seqStarts.size(), &h);
+        cmb_build_destroy(b);
+        check(rc);
+        check(cmb_move_info(h, &textLength, &nRuns, &nRunsRev));
+    }
     ~BMove() { cmb_move_destroy(h); }
     BMove(const BMove&) = delete;
     BMove& operator=(const BMove&) = delete;

@@ -546,19 +546,49 @@ inline void put64(const std::string& name, const std::vector<uint64_t>& v) {
     putAll(f, v);
 }
 
-// FASTA files -> <base>.{meta, cct, pos, sna, fsid, headerSN.bin, LFBP, rev.LFBP, *.u64} (64-bit length_t as the reference's RLC build);
-// keepText: also <base>.txt.bin — the reference's RLC flavour does not keep the text, this framework computes alignments of b-move
-// occurrences on it (BMove::attachText)
-inline void buildMoveIndex(const std::vector<std::string>& fastaFiles, const std::string& base, uint32_t seedLength = 100, bool keepText = false) {
-    const Text tx = preprocessFastaFiles(fastaFiles, seedLength);
+// everything of the index that is computed from the text: the two .LFBP images and the contents of the .u64 files
+struct MoveParts {
+    std::vector<uint8_t> lfbp, revLfbp;
+    std::vector<uint64_t> smpf, smpl, revSmpf, revSmpl, prdf, ftr, prdl, ltr, plcpPos, plcpSum;
+};
+// ... on the host: SA-IS, the scalar loops above (include/columba_amd_build_device.hpp has the producer that asks the device)
+inline MoveParts hostMoveParts(const std::string& T) {
+    const size_t n = T.size();
+    MoveParts p;
+    {
+        const std::vector<uint32_t> SA = suffixArray(T);
+        std::string bwt(n, '$');
+        for (size_t i = 0; i < n; i++) bwt[i] = SA[i] > 0 ? T[SA[i] - 1] : T.back();
+        plcpRuns(T, SA, p.plcpPos, p.plcpSum);
+        runSamples(SA, bwt, p.smpf, p.smpl);
+        predecessors(p.smpf, n, p.prdf, p.ftr);
+        predecessors(p.smpl, n, p.prdl, p.ltr);
+        p.lfbp = packLFBP(bwt);
+    }
+    {
+        std::string revT(T.rbegin(), T.rend());
+        const std::vector<uint32_t> revSA = suffixArray(revT);
+        revT.clear();
+        std::string rbwt(n, '$');
+        for (size_t i = 0; i < n; i++) rbwt[i] = revSA[i] > 0 ? T[n - revSA[i]] : T.front();
+        runSamples(revSA, rbwt, p.revSmpf, p.revSmpl);
+        p.revLfbp = packLFBP(rbwt);
+    }
+    return p;
+}
+
+// <base>.{meta, cct, pos, sna, fsid, headerSN.bin, LFBP, rev.LFBP, *.u64} (64-bit length_t as the reference's RLC build) from the
+// preprocessed text and the parts a producer made of it; keepText: also <base>.txt.bin — the reference's RLC flavour does not keep the
+// text, this framework computes alignments of b-move occurrences on it (BMove::attachText)
+inline void writeMoveIndexFiles(const Text& tx, const std::string& base, bool keepText, const MoveParts& p) {
     const std::string& T = tx.T;
     const size_t n = T.size();
+    if (keepText) {
+        std::ofstream f = openOut(base + ".txt.bin");
+        put<uint64_t>(f, (uint64_t)n);
+        f.write(T.data(), (std::streamsize)n);
+    }
     {
-        if (keepText) {
-            std::ofstream f = openOut(base + ".txt.bin");
-            put<uint64_t>(f, (uint64_t)n);
-            f.write(T.data(), (std::streamsize)n);
-        }
         std::ofstream h = openOut(base + ".headerSN.bin");
         for (size_t i = 0; i < tx.seqNames.size(); i++)
             h << "@SQ\tSN:" << tx.seqNames[i] << "\tLN:" << tx.positions[i + 1] - tx.positions[i] << "\n";
@@ -577,34 +607,21 @@ inline void buildMoveIndex(const std::vector<std::string>& fastaFiles, const std
         std::ofstream f = openOut(name);
         putAll(f, b);
     };
-    {
-        const std::vector<uint32_t> SA = suffixArray(T);
-        std::string bwt(n, '$');
-        for (size_t i = 0; i < n; i++) bwt[i] = SA[i] > 0 ? T[SA[i] - 1] : T.back();
-        std::vector<uint64_t> a, b, c, d;
-        plcpRuns(T, SA, a, b);
-        put64(base + ".plcp.pos.u64", a), put64(base + ".plcp.sum.u64", b);
-        runSamples(SA, bwt, a, b);
-        put64(base + ".smpf.u64", a), put64(base + ".smpl.u64", b);
-        predecessors(a, n, c, d);
-        put64(base + ".prdf.u64", c), put64(base + ".ftr.u64", d);
-        predecessors(b, n, c, d);
-        put64(base + ".prdl.u64", c), put64(base + ".ltr.u64", d);
-        writeBytes(base + ".LFBP", packLFBP(bwt));
-    }
-    {
-        std::string revT(T.rbegin(), T.rend());
-        const std::vector<uint32_t> revSA = suffixArray(revT);
-        revT.clear();
-        std::string rbwt(n, '$');
-        for (size_t i = 0; i < n; i++) rbwt[i] = revSA[i] > 0 ? T[n - revSA[i]] : T.front();
-        std::vector<uint64_t> a, b;
-        runSamples(revSA, rbwt, a, b);
-        put64(base + ".rev.smpf.u64", a), put64(base + ".rev.smpl.u64", b);
-        writeBytes(base + ".rev.LFBP", packLFBP(rbwt));
-    }
+    put64(base + ".plcp.pos.u64", p.plcpPos), put64(base + ".plcp.sum.u64", p.plcpSum);
+    put64(base + ".smpf.u64", p.smpf), put64(base + ".smpl.u64", p.smpl);
+    put64(base + ".prdf.u64", p.prdf), put64(base + ".ftr.u64", p.ftr);
+    put64(base + ".prdl.u64", p.prdl), put64(base + ".ltr.u64", p.ltr);
+    writeBytes(base + ".LFBP", p.lfbp);
+    put64(base + ".rev.smpf.u64", p.revSmpf), put64(base + ".rev.smpl.u64", p.revSmpl);
+    writeBytes(base + ".rev.LFBP", p.revLfbp);
     std::ofstream m = openOut(base + ".meta");
     m << 21 << "\n" << 8 << "\n" << "RLC" << "\n";
+}
+
+// FASTA files -> the index files of the RLC flavour, every array computed on the host
+inline void buildMoveIndex(const std::vector<std::string>& fastaFiles, const std::string& base, uint32_t seedLength = 100, bool keepText = false) {
+    const Text tx = preprocessFastaFiles(fastaFiles, seedLength);
+    writeMoveIndexFiles(tx, base, keepText, hostMoveParts(tx.T));
 }
 
 } // namespace build
