@@ -61,6 +61,7 @@ EXPORTS = [
     "cmb_build_create", "cmb_build_destroy", "cmb_build_sizes_of", "cmb_build_bwt_arrays", "cmb_build_sparse_sa_sizes", "cmb_build_sparse_sa",
     "cmb_build_suffix_array", "cmb_build_index", "cmb_build_timings",
     "cmb_build_move_sizes_of", "cmb_build_move_arrays", "cmb_build_move_index", "cmb_build_pack_lfbp",
+    "cmb_reads_create", "cmb_reads_destroy", "cmb_reads_parse_fastq", "cmb_reads_arrays", "cmb_reads_device_arrays",
     "cmb_last_error", "cmb_version",
 ]
 
@@ -260,6 +261,22 @@ class SamInputs(C.Structure):
                 ("seq_names", C.c_void_p), ("seq_name_offs", C.c_void_p), ("n_seqs", C.c_uint32)]
 
 
+READS_DEV_ARRAYS = 6           # CMB_READS_DEV_ARRAYS: seqs, offs, ids, id_offs, quals, qual_offs
+READS_MAX_WINDOW = 1 << 30     # CMB_READS_MAX_WINDOW
+READS_STOP_MAX_RECORDS, READS_STOP_WINDOW, READS_STOP_EMPTY_READ = 0, 1, 2
+
+
+class ReadsInfo(C.Structure):
+    """cmb_reads_info"""
+    _fields_ = [("n_records", C.c_uint32), ("stop", C.c_uint32), ("consumed", C.c_uint64)]
+
+
+class ReadsView(C.Structure):
+    """cmb_reads_view"""
+    _fields_ = [("seqs", C.c_void_p), ("offs", C.c_void_p), ("ids", C.c_void_p), ("id_offs", C.c_void_p), ("quals", C.c_void_p),
+                ("qual_offs", C.c_void_p), ("n_records", C.c_uint32)]
+
+
 class SamHit(C.Structure):
     """cmb_sam_hit"""
     _fields_ = [("seq_name", C.c_char_p), ("pos0", C.c_uint32), ("distance", C.c_uint32), ("revcomp", C.c_uint32),
@@ -419,6 +436,12 @@ def lib():
         L.cmb_build_move_arrays.argtypes = [vp, C.POINTER(_BuildMoveArrays), vp]
         L.cmb_build_move_index.argtypes = [vp, i32, i32, vp, u32, C.POINTER(vp)]
         L.cmb_build_pack_lfbp.argtypes = [u64, u64, u64, vp, u32, vp, u64, C.POINTER(u64)]
+        L.cmb_reads_create.argtypes = [i32, C.POINTER(vp)]
+        L.cmb_reads_destroy.argtypes = [vp]
+        L.cmb_reads_destroy.restype = None
+        L.cmb_reads_parse_fastq.argtypes = [vp, vp, u64, u32, i32, C.POINTER(ReadsInfo)]
+        L.cmb_reads_arrays.argtypes = [vp, C.POINTER(ReadsView)]
+        L.cmb_reads_device_arrays.argtypes = [vp, C.POINTER(vp * READS_DEV_ARRAYS), C.POINTER(u64 * READS_DEV_ARRAYS)]
         _lib = L
     return _lib
 
@@ -991,6 +1014,80 @@ def unpack_fields(buf: np.ndarray, offs: np.ndarray):
     return [b[int(offs[i]):int(offs[i + 1])] for i in range(offs.shape[0] - 1)]
 
 
+class ParsedReads:
+    """A FASTQ chunk as ``ReadParser.parse`` leaves it: ``n_records``, ``consumed`` (bytes of the window the chunk and a dropped empty-read
+    record took; the next window begins there), ``stop`` (READS_STOP_*), and the packed arrays ``seqs`` / ``offs``, ``ids`` /
+    ``id_offs`` (raw identifier lines with their '@'), ``quals`` / ``qual_offs``.  The arrays are numpy views of the parser's
+    page-locked buffers: they hold this chunk until the parser's next ``parse`` or ``close``."""
+
+    def __init__(self, parser: "ReadParser", info: ReadsInfo, view: ReadsView):
+        self._parser = parser  # (the buffers are the parser's)
+        self.n_records, self.consumed, self.stop = int(info.n_records), int(info.consumed), int(info.stop)
+        n = self.n_records
+
+        def offsets(ptr):
+            return np.ctypeslib.as_array((C.c_uint64 * (n + 1)).from_address(ptr))
+
+        def chars(ptr, offs):
+            return np.ctypeslib.as_array((C.c_uint8 * max(int(offs[n]), 1)).from_address(ptr))  # (one byte at least, as pack_reads)
+
+        self.offs, self.id_offs, self.qual_offs = offsets(view.offs), offsets(view.id_offs), offsets(view.qual_offs)
+        self.seqs, self.ids, self.quals = chars(view.seqs, self.offs), chars(view.ids, self.id_offs), chars(view.quals, self.qual_offs)
+
+    @property
+    def packed(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(seqs, offs) for ``Batch(..., packed=...)``, ``Batch.stage`` and ``BestDevice(..., packed=...)``"""
+        return self.seqs, self.offs
+
+    @property
+    def packed_ids(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(ids, id_offs) as the ``sam_device_bytes`` methods take identifiers"""
+        return self.ids, self.id_offs
+
+    @property
+    def packed_quals(self) -> Tuple[np.ndarray, np.ndarray]:
+        return self.quals, self.qual_offs
+
+    def records(self):
+        """[(identifier line, read, quality)] as bytes: what ``Reader`` of include/columba_amd_io.hpp holds per record"""
+        s, i, q = self.seqs.tobytes(), self.ids.tobytes(), self.quals.tobytes()
+        return [(i[int(self.id_offs[r]):int(self.id_offs[r + 1])], s[int(self.offs[r]):int(self.offs[r + 1])],
+                 q[int(self.qual_offs[r]):int(self.qual_offs[r + 1])]) for r in range(self.n_records)]
+
+
+class ReadParser:
+    """The device FASTQ parser of one read file (handle of ``cmb_reads_create``): ``parse`` turns a window of raw file bytes into the
+    packed arrays the batches and the SAM writers take (cmb_reads_parse_fastq)."""
+
+    def __init__(self, device: int = 0):
+        self.h, self.device = C.c_void_p(), device
+        _chk(lib().cmb_reads_create(device, C.byref(self.h)))
+
+    def parse(self, data, max_records: int, final: bool) -> ParsedReads:
+        """The first ``max_records`` records of ``data`` (bytes, or a contiguous uint8 array) at most; ``final``: the window ends the file."""
+        buf = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, np.uint8)
+        info, view = ReadsInfo(), ReadsView()
+        _chk(lib().cmb_reads_parse_fastq(self.h, _p(buf) if buf.size else None, buf.size, max_records, int(bool(final)), C.byref(info)))
+        _chk(lib().cmb_reads_arrays(self.h, C.byref(view)))
+        return ParsedReads(self, info, view)
+
+    def device_tensors(self):
+        """the resident copies of the last parse as flat uint8 torch tensors sharing the library's memory (cmb_reads_device_arrays):
+        seqs, offs, ids, id_offs, quals, qual_offs; None for an array without bytes.  Valid until the next ``parse``."""
+        import torch
+        ptrs, sizes = (C.c_void_p * READS_DEV_ARRAYS)(), (C.c_uint64 * READS_DEV_ARRAYS)()
+        _chk(lib().cmb_reads_device_arrays(self.h, C.byref(ptrs), C.byref(sizes)))
+        return [torch.as_tensor(_DevArray(int(ptrs[i]), int(sizes[i]), self), device=torch.device("cuda", self.device)) if sizes[i] else None
+                for i in range(READS_DEV_ARRAYS)]
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.cmb_reads_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+
 def sam_device_mapq(n: int) -> np.ndarray:
     """test hook: the MAPQ the device path prints for 1 ... n occurrences of minimal distance"""
     out = np.zeros(max(n, 1), np.uint32)
@@ -1108,6 +1205,10 @@ class Batch:
         packed with pack_fields; quals=None: no qualities."""
         return _sam_device_bytes(lib().cmb_batch_sam_device, self, ids, quals, seq_names, unmapped, xa)
 
+    def sam_device_bytes_packed(self, parsed: "ParsedReads", seq_names, unmapped: bool = True, xa: bool = False):
+        """``sam_device_bytes`` with the identifiers and qualities of a ``ParsedReads`` chunk, handed over packed as they are"""
+        return _sam_device_bytes(lib().cmb_batch_sam_device, self, parsed.packed_ids, parsed.packed_quals, seq_names, unmapped, xa)
+
     def sam_device(self, ids, quals, seq_names, unmapped: bool = True, xa: bool = False):
         """(SAM text, number of host-formatted reads): sam_device_bytes, decoded"""
         t, host = self.sam_device_bytes(ids, quals, seq_names, unmapped, xa)
@@ -1174,9 +1275,10 @@ class BestDevice:
     writes the chunk's SAM text from them on the device (cmb_best_sam_device).  Single-end reads; ``index``: an ``Index``, or a
     ``MoveIndex`` with its text attached (cmb_move_match_best_device; ``kmer_size``: the k-mer table of that flavour's search)."""
 
-    def __init__(self, index, strategy: SearchStrategy, reads: Sequence[bytes], x: int = 0, min_identity: int = 95, kmer_size: int = 10):
-        self._packed = pack_reads(reads)
-        self.n_reads = len(reads)
+    def __init__(self, index, strategy: SearchStrategy, reads: Optional[Sequence[bytes]] = None, x: int = 0, min_identity: int = 95,
+                 kmer_size: int = 10, packed=None):
+        self._packed = packed if packed is not None else pack_reads(reads)  # (packed: (characters, offsets), as ``Batch`` takes them)
+        self.n_reads = self._packed[1].shape[0] - 1
         self.index = index
         self.h = C.c_void_p()
         args = (_p(self._packed[0]), _p(self._packed[1]), self.n_reads, C.byref(self.h))
@@ -1207,6 +1309,10 @@ class BestDevice:
     def sam_device_bytes(self, ids, quals, seq_names, unmapped: bool = True, xa: bool = False):
         """(the SAM text of the chunk as bytes, number of reads the host formatted); inputs as ``Batch.sam_device_bytes``"""
         return _sam_device_bytes(lib().cmb_best_sam_device, self, ids, quals, seq_names, unmapped, xa)
+
+    def sam_device_bytes_packed(self, parsed: "ParsedReads", seq_names, unmapped: bool = True, xa: bool = False):
+        """``sam_device_bytes`` with the identifiers and qualities of a ``ParsedReads`` chunk, handed over packed as they are"""
+        return _sam_device_bytes(lib().cmb_best_sam_device, self, parsed.packed_ids, parsed.packed_quals, seq_names, unmapped, xa)
 
     def sam_device(self, ids, quals, seq_names, unmapped: bool = True, xa: bool = False):
         t, host = self.sam_device_bytes(ids, quals, seq_names, unmapped, xa)
@@ -1485,6 +1591,10 @@ class MoveBatch:
         """the text of sam() written on the device from the kept lists (cmb_move_batch_sam_device; needs keep_device_lists() before
         run()): (bytes, number of reads the host formatted); inputs as ``Batch.sam_device_bytes``"""
         return _sam_device_bytes(lib().cmb_move_batch_sam_device, self, ids, quals, seq_names, unmapped, xa)
+
+    def sam_device_bytes_packed(self, parsed: "ParsedReads", seq_names, unmapped: bool = True, xa: bool = False):
+        """``sam_device_bytes`` with the identifiers and qualities of a ``ParsedReads`` chunk, handed over packed as they are"""
+        return _sam_device_bytes(lib().cmb_move_batch_sam_device, self, parsed.packed_ids, parsed.packed_quals, seq_names, unmapped, xa)
 
     def sam_device(self, ids, quals, seq_names, unmapped: bool = True, xa: bool = False):
         """(SAM text, number of host-formatted reads): sam_device_bytes, decoded"""

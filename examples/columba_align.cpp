@@ -21,6 +21,32 @@
 
 using namespace columba_amd;
 
+// The chunks of a read file: the packed chunks of DeviceReader (the records of a FASTQ file found on the device; FASTA files fall back
+// to Reader inside it) with their records made only where a path wants them, or with CMB_READER_HOST=1 Reader's records.
+struct ChunkSource {
+    std::unique_ptr<Reader> host;
+    std::unique_ptr<DeviceReader> device;
+    ParsedChunk packed;
+    std::vector<SequenceRecord> records;
+    static constexpr bool READER_DEVICE_DEFAULT = true; // 30 against 208 ms per 10^6 reads of 150 bp
+    static bool onDevice() { // CMB_READER_HOST=1 keeps the host reader, CMB_READER_DEVICE=1 asks for the device reader
+        if (const char* e = getenv("CMB_READER_HOST"); e && atoi(e) != 0) return false;
+        if (const char* e = getenv("CMB_READER_DEVICE"); e && atoi(e) != 0) return true;
+        return READER_DEVICE_DEFAULT;
+    }
+    explicit ChunkSource(const std::string& file) {
+        if (onDevice()) device.reset(new DeviceReader(file));
+        else host.reset(new Reader(file));
+    }
+    bool next(size_t n, bool wantRecords) {
+        if (host) return host->getNextChunk(records, n);
+        const bool any = device->getNextChunk(packed, n);
+        if (wantRecords) records = packed.records();
+        return any;
+    }
+    size_t size() const { return host ? records.size() : packed.size(); }
+};
+
 int main(int argc, char** argv) {
     std::string base, readsFile, matesFile, orientation = "fr", outFile, strategyName = "columba", mode = "best", metric = "edit", part = "dynamic", cmdline;
     int k = 0, x = 0, identity = 95, sparse = 4, kmer = 10, inTextSwitch = 4;
@@ -89,17 +115,17 @@ int main(int argc, char** argv) {
         std::vector<const char*> seqNamePtrs;
         for (const auto& s : seqNames) seqNamePtrs.push_back(s.c_str());
         uint32_t ori = orientation == "rf" ? CMB_ORIENTATION_RF : orientation == "ff" ? CMB_ORIENTATION_FF : CMB_ORIENTATION_FR;
-        Reader reader(readsFile);
-        std::unique_ptr<Reader> mateReader(matesFile.empty() ? nullptr : new Reader(matesFile));
+        ChunkSource reader(readsFile);
+        std::unique_ptr<ChunkSource> mateReader(matesFile.empty() ? nullptr : new ChunkSource(matesFile));
         OutputWriter writer(outFile, fastaFiles.empty() ? base + ".headerSN.bin" : headerLines, cmdline, !fastaFiles.empty());
-        std::vector<SequenceRecord> chunk;
+        const std::vector<SequenceRecord>& chunk = reader.records;
         size_t chunkID = 0, nReads = 0, nMapped = 0;
         if (mateReader && !noInfer && !pairParamsGiven) {
             // PE_MAX_READS_FOR_INFERENCE = 10 000 reads (definitions.h:58): the first 5 000 pairs at most
-            std::vector<SequenceRecord> mates;
             const size_t want = std::min<size_t>(chunkReads, 5000);
-            if (reader.getNextChunk(chunk, want)) {
-                mateReader->getNextChunk(mates, want);
+            if (reader.next(want, true)) {
+                mateReader->next(want, true);
+                const std::vector<SequenceRecord>& mates = mateReader->records;
                 uint32_t seqsInFirstFile = (uint32_t)seqNames.size();
                 if (!fastaFiles.empty()) {
                     if (refText.firstSeqIDPerFile.size() > 1) seqsInFirstFile = refText.firstSeqIDPerFile[1];
@@ -133,7 +159,14 @@ int main(int argc, char** argv) {
                 writer.commitChunk(chunkID++, std::move(text));
             }
         }
-        while (reader.getNextChunk(chunk, chunkReads)) {
+        while (reader.next(chunkReads, mateReader != nullptr)) {
+            if (reader.device && !mateReader) { // the chunk is packed already
+                std::string text = mode == "all" ? strategy.samOfChunkAll(reader.packed, seqNamePtrs, (length_t)k, unmapped, xa)
+                                                 : strategy.samOfChunkBest(reader.packed, seqNames, (uint32_t)x, (uint32_t)identity, unmapped, xa, nMapped);
+                nReads += reader.size();
+                writer.commitChunk(chunkID++, std::move(text));
+                continue;
+            }
             std::string seqs;
             std::vector<uint64_t> offs(chunk.size() + 1, 0);
             std::vector<const char*> ids, quals;
@@ -145,8 +178,8 @@ int main(int argc, char** argv) {
             }
             std::string text;
             if (mateReader) {
-                std::vector<SequenceRecord> mates;
-                mateReader->getNextChunk(mates, chunkReads);
+                mateReader->next(chunkReads, true);
+                const std::vector<SequenceRecord>& mates = mateReader->records;
                 if (mode == "all")
                     text = strategy.samOfChunkPairedAll(chunk, mates, seqNamePtrs, (length_t)k, ori, maxInsert, minInsert, discordant, unmapped, nMapped);
                 else

@@ -878,6 +878,56 @@ int cmb_move_match_best_device(cmb_move_index* idx, const cmb_strategy* st, uint
  * [1] the prefix sum of the widths, [2] locate + occurrence records */
 int cmb_move_last_timings(float* ms, uint32_t n);
 
+/* ---- FASTQ chunks parsed on the device (csrc/reads.hip, csrc/dev_reads.hpp)
+ * A window of raw FASTQ bytes becomes the packed arrays cmb_batch_create / cmb_batch_stage_reads, cmb_match_best_device and
+ * cmb_sam_inputs take: the read characters with offs[n + 1], the raw identifier lines (with their '@', as cmb_sam_inputs wants them)
+ * with id_offs[n + 1], the qualities with qual_offs[n + 1]; all offsets count bytes and are 64-bit.  Record for record and chunk for
+ * chunk the result is what Reader of include/columba_amd_io.hpp (the reference's src/fastq.cpp:43-99, :395) returns for the same bytes:
+ * a line ends at '\n' (the last line of a final window may lack it); where a record would begin, lines that are empty or begin with '\r'
+ * are skipped; the next four lines are identifier, read, separator and quality as they stand (the separator is not looked at, a quality
+ * may begin with '@' or '+', an empty line inside a record is a field); trailing '\r' are removed from each field.
+ * One handle per read file: its device and page-locked buffers are reused from window to window and grow on demand.
+ * cmb_reads_parse_fastq selects the handle's device, uploads bytes[0, n_bytes) (host memory) and takes the first
+ * min(max_records, records in the window, index of the first record with an empty read) records:
+ *   final != 0: the window ends the file; a last record of fewer than four lines is taken with its missing fields empty.
+ *   final == 0: a record counts only if the newline of its fourth line lies in the window; the rest is left to the next window.
+ *   info->stop: CMB_READS_STOP_MAX_RECORDS, CMB_READS_STOP_WINDOW (no further record in the window) or CMB_READS_STOP_EMPTY_READ
+ *   (a record with an empty read ends the chunk as it ends Reader's: its lines are consumed, it is not part of the chunk).
+ *   info->consumed: the offset behind the last line of the last record taken, a dropped empty-read record included; 0 if there is
+ *   none.  The next window begins there.
+ * CMB_ERR_INVALID: NULL arguments, n_bytes != 0 with bytes == NULL, max_records == 0 (all before any device work); a record among
+ * those the call reaches whose first line does not begin with '@' (the message names its index in the window; a bad record behind
+ * the end of the chunk is not an error of this call).  CMB_ERR_UNSUPPORTED, before any work: n_bytes > CMB_READS_MAX_WINDOW; a window
+ * whose first record begins with '>' (FASTA read files keep the host reader).  CMB_ERR_DEVICE: no GPU (cmb_reads_create).
+ * After an error the handle holds an empty chunk. */
+#define CMB_READS_MAX_WINDOW (1ull << 30)
+#define CMB_READS_STOP_MAX_RECORDS 0
+#define CMB_READS_STOP_WINDOW 1
+#define CMB_READS_STOP_EMPTY_READ 2
+typedef struct cmb_reads cmb_reads;
+typedef struct {
+    uint32_t n_records;
+    uint32_t stop;
+    uint64_t consumed;
+} cmb_reads_info;
+typedef struct {
+    const char* seqs;
+    const uint64_t* offs; /* [n_records + 1] */
+    const char* ids;
+    const uint64_t* id_offs;
+    const char* quals;
+    const uint64_t* qual_offs;
+    uint32_t n_records;
+} cmb_reads_view;
+int cmb_reads_create(int device, cmb_reads** out);
+void cmb_reads_destroy(cmb_reads* r);
+int cmb_reads_parse_fastq(cmb_reads* r, const char* bytes, uint64_t n_bytes, uint32_t max_records, int final, cmb_reads_info* info);
+/* the page-locked host copies of the last parse; valid until the next cmb_reads_parse_fastq or cmb_reads_destroy on the handle */
+int cmb_reads_arrays(const cmb_reads* r, cmb_reads_view* out);
+/* the copies in HBM (as cmb_index_device_arrays): seqs, offs, ids, id_offs, quals, qual_offs and their sizes in bytes */
+#define CMB_READS_DEV_ARRAYS 6
+int cmb_reads_device_arrays(const cmb_reads* r, void** ptrs /* [CMB_READS_DEV_ARRAYS] */, uint64_t* bytes /* [CMB_READS_DEV_ARRAYS] */);
+
 const char* cmb_last_error(void);
 const char* cmb_version(void);
 

@@ -333,6 +333,36 @@ class SearchStrategy {
         text.resize((size_t)n);
         return text;
     }
+    // ... of a chunk that is packed already (ParsedChunk of columba_amd_io.hpp: the arrays of DeviceReader's parser): they go to
+    // cmb_batch_create and cmb_sam_inputs as they are.  CMB_SAM_HOST=1 keeps the host formatter, through the chunk's records.
+    template <class Chunk>
+    std::string samOfChunkAll(const Chunk& c, const std::vector<const char*>& seqNames, length_t maxED, bool unmappedRecords, bool xaTag) {
+        if (const char* e = getenv("CMB_SAM_HOST"); e && atoi(e) != 0) {
+            const auto recs = c.records();
+            std::string seqs;
+            std::vector<uint64_t> offs(recs.size() + 1, 0);
+            std::vector<const char*> ids, quals;
+            for (size_t i = 0; i < recs.size(); i++) {
+                seqs += recs[i].read, offs[i + 1] = seqs.size();
+                ids.push_back(recs[i].seqID.c_str()), quals.push_back(recs[i].qual.c_str());
+            }
+            return samOfChunkAll(seqs, offs, ids, quals, seqNames, maxED, unmappedRecords, xaTag);
+        }
+        cmb_batch* b = nullptr;
+        check(cmb_batch_create(index.handle(), h, maxED, c.seqs, c.offs, (uint32_t)c.n, &b));
+        struct Guard {
+            cmb_batch* b;
+            ~Guard() { cmb_batch_destroy(b); }
+        } guard{b};
+        check(cmb_batch_want_alignments(b, 1));
+        check(cmb_batch_run(b));
+        const SamPacked names(0, seqNames, [](size_t) { return ""; }, true, [](size_t) { return ""; });
+        const cmb_sam_inputs in{c.seqs, c.ids, c.idOffs, c.quals, c.qualOffs, names.nameBuf.data(), names.nameOffs.data(), (uint32_t)seqNames.size()};
+        const char* text = nullptr;
+        uint64_t length = 0;
+        check(cmb_batch_sam_device(b, &in, unmappedRecords, xaTag, &text, &length, nullptr));
+        return std::string(text, (size_t)length);
+    }
     // ---- read pairs in ALL mode
     // the occurrences of one read as cmb_pair_sam takes them: sequence assigned (trimmed where they ran over its end, findSeqName,
     // indexinterface.cpp:833-899; those for which that fails are dropped), with their CIGAR operations
@@ -753,6 +783,32 @@ class SearchStrategy {
         }
         check(cmb_match_best(index.handle(), h, x, minIdentity, seqs.data(), offs.data(), nReads, &r));
         return samOfBest(r, seqs, offs, recs, seqNames, unmappedRecords, xaTag, nMapped);
+    }
+    // ... of a chunk that is packed already (as samOfChunkAll above); the host path (CMB_BEST_HOST=1) goes through the chunk's records
+    template <class Chunk>
+    std::string samOfChunkBest(const Chunk& c, const std::vector<std::string>& seqNames, uint32_t x, uint32_t minIdentity, bool unmappedRecords,
+                               bool xaTag, size_t& nMapped) {
+        const uint32_t nReads = (uint32_t)c.n;
+        if (!bestOnDevice()) {
+            const auto recs = c.records();
+            return samOfChunkBest(std::string(c.seqs, (size_t)c.offs[nReads]), std::vector<uint64_t>(c.offs, c.offs + nReads + 1), recs, seqNames, x,
+                                  minIdentity, unmappedRecords, xaTag, nMapped);
+        }
+        cmb_best* r = nullptr;
+        check(cmb_match_best_device(index.handle(), h, x, minIdentity, c.seqs, c.offs, nReads, &r));
+        struct Guard {
+            cmb_best* r;
+            ~Guard() { cmb_best_destroy(r); }
+        } guard{r};
+        const SamPacked names(0, seqNames, [](size_t) { return ""; }, true, [](size_t) { return ""; });
+        const cmb_sam_inputs in{c.seqs, c.ids, c.idOffs, c.quals, c.qualOffs, names.nameBuf.data(), names.nameOffs.data(), (uint32_t)seqNames.size()};
+        const char* text = nullptr;
+        uint64_t length = 0;
+        check(cmb_best_sam_device(r, &in, unmappedRecords, xaTag, &text, &length, nullptr));
+        std::vector<uint64_t> oo(nReads + 1, 0);
+        check(cmb_best_results(r, nullptr, nullptr, 0, nullptr, 0, oo.data(), nullptr, nullptr, nullptr)); // (the offsets: nothing is downloaded)
+        for (uint32_t i = 0; i < nReads; i++) nMapped += oo[i + 1] != oo[i];
+        return std::string(text, (size_t)length);
     }
     // SearchStrategy::matchApprox (searchstrategy.h:2021-2024), ALL mode, one read
     void matchApprox(ReadBundle& bundle, length_t maxED, Counters& counters, std::vector<TextOcc>& result) {

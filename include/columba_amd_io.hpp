@@ -1,5 +1,6 @@
 // Host-side I/O around the C-ABI: a FASTA / FASTQ chunk reader, an ordered SAM writer and the chunk loop of a
-// Columba-style aligner.  Host C++ only; all matching happens behind include/columba_amd.h.
+// Columba-style aligner.  Host C++ only; all matching happens behind include/columba_amd.h, and so does the
+// record splitting of DeviceReader (cmb_reads_*), which hands FASTQ chunks over packed.
 //
 // Mirrors (reference, src/):
 //   SequenceRecord::readFromFileFASTQ / readFromFileFASTA   fastq.cpp:43-146 (records; multi-line FASTA; "*" quality)
@@ -9,8 +10,11 @@
 #pragma once
 #include "columba_amd.h"
 
+#include <algorithm>
+#include <cstring>
 #include <fstream>
 #include <map>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -165,6 +169,162 @@ class Reader { // fastq.h Reader (single-end; plain text or .gz)
         SequenceRecord r;
         while (chunk.size() < n && next(r)) chunk.push_back(r);
         return !chunk.empty();
+    }
+};
+
+// A chunk of records in the packed form cmb_batch_create, cmb_match_best_device and cmb_sam_inputs take: read i is
+// seqs[offs[i], offs[i + 1]), its raw identifier line ids[idOffs[i], idOffs[i + 1]), its quality quals[qualOffs[i], qualOffs[i + 1]).
+// From DeviceReader the arrays are those of the reader's parser (page-locked, valid until its next chunk); from a FASTA file the
+// chunk owns them.
+struct ParsedChunk {
+    const char *seqs = "", *ids = "", *quals = "";
+    const uint64_t *offs = nullptr, *idOffs = nullptr, *qualOffs = nullptr;
+    size_t n = 0;
+    size_t size() const { return n; }
+    bool empty() const { return n == 0; }
+    std::vector<SequenceRecord> records() const {
+        std::vector<SequenceRecord> out(n);
+        for (size_t i = 0; i < n; i++) {
+            out[i].seqID.assign(ids + idOffs[i], (size_t)(idOffs[i + 1] - idOffs[i]));
+            out[i].read.assign(seqs + offs[i], (size_t)(offs[i + 1] - offs[i]));
+            out[i].qual.assign(quals + qualOffs[i], (size_t)(qualOffs[i + 1] - qualOffs[i]));
+        }
+        return out;
+    }
+    void view(const cmb_reads_view& v) {
+        seqs = v.seqs, ids = v.ids, quals = v.quals, offs = v.offs, idOffs = v.id_offs, qualOffs = v.qual_offs, n = v.n_records;
+    }
+    void pack(const std::vector<SequenceRecord>& recs) { // (the host reader's records: a FASTA file)
+        own[0].clear(), own[1].clear(), own[2].clear();
+        for (auto& o : ownOffs) o.assign(1, 0);
+        for (const auto& r : recs) {
+            own[0] += r.read, own[1] += r.seqID, own[2] += r.qual;
+            for (int f = 0; f < 3; f++) ownOffs[f].push_back(own[f].size());
+        }
+        seqs = own[0].data(), ids = own[1].data(), quals = own[2].data();
+        offs = ownOffs[0].data(), idOffs = ownOffs[1].data(), qualOffs = ownOffs[2].data(), n = recs.size();
+    }
+
+  private:
+    std::string own[3];
+    std::vector<uint64_t> ownOffs[3];
+};
+
+// Reader for FASTQ files with the records found on the device: the file is read in windows of raw bytes (plain, or inflated with zlib
+// for ".gz"), cmb_reads_parse_fastq splits a window into records and returns the chunk packed.  Chunk for chunk and record for record
+// what Reader returns (its behaviour is the parser's specification), the return value and the exception for a file that is not FASTQ
+// included.  A file whose first record does not begin with '@' (FASTA among them) is read by Reader.  One limit Reader does not have:
+// a chunk is cut where CMB_READS_MAX_WINDOW bytes of the file end, and a single record longer than that is an error.
+class DeviceReader {
+    std::string fileName;
+    std::ifstream in;
+#ifdef COLUMBA_AMD_HAVE_ZLIB
+    gzFile gz = nullptr;
+#endif
+    bool compressed = false, eof = false;
+    std::unique_ptr<Reader> host; // FASTA, or whatever Reader is to complain about
+    cmb_reads* parser = nullptr;
+    std::unique_ptr<char[]> win; // the window is win[begin, end)
+    size_t cap = 0, begin = 0, end = 0;
+    double bytesPerRecord = 512; // the estimate the window is sized from; the first chunk corrects it
+
+    size_t readRaw(char* dst, size_t n) {
+        if (compressed) {
+#ifdef COLUMBA_AMD_HAVE_ZLIB
+            size_t got = 0;
+            while (got < n) { // (gzread takes an unsigned count)
+                const int k = gzread(gz, dst + got, (unsigned)std::min<size_t>(n - got, 1u << 30));
+                if (k < 0) throw std::ios::failure("error while reading a gz-compressed file");
+                if (k == 0) break;
+                got += (size_t)k;
+            }
+            return got;
+#else
+            return 0;
+#endif
+        }
+        in.read(dst, (std::streamsize)n);
+        return (size_t)in.gcount();
+    }
+    // the window holds `want` bytes, or everything up to the end of the file
+    void fill(size_t want) {
+        if (eof || end - begin >= want) return;
+        if (want > cap || begin) { // the unconsumed tail moves to the front (of a larger buffer if need be)
+            const size_t newCap = std::max(cap, want);
+            std::unique_ptr<char[]> grown(newCap > cap ? new char[newCap] : nullptr);
+            char* to = grown ? grown.get() : win.get();
+            if (end > begin) memmove(to, win.get() + begin, end - begin);
+            if (grown) win = std::move(grown), cap = newCap;
+            end -= begin, begin = 0;
+        }
+        const size_t got = readRaw(win.get() + end, want - end);
+        end += got;
+        if (end < want) eof = true;
+    }
+
+  public:
+    explicit DeviceReader(const std::string& file, int device = 0) : fileName(file) {
+        int first;
+        { // what the first record begins with (blank lines skipped, as Reader does)
+            LineSource peek(file);
+            std::string dummy;
+            while ((first = peek.peek()) == '\n' || first == '\r') peek.getline(dummy);
+        }
+        if (first != '@' && first != EOF) {
+            host.reset(new Reader(file));
+            return;
+        }
+        compressed = file.size() > 3 && file.compare(file.size() - 3, 3, ".gz") == 0;
+        if (compressed) {
+#ifdef COLUMBA_AMD_HAVE_ZLIB
+            gz = gzopen(file.c_str(), "rb");
+            if (!gz) throw std::runtime_error("Cannot open file: " + file);
+#endif
+        } else {
+            in.open(file, std::ios::binary);
+            if (!in) throw std::runtime_error("Cannot open file: " + file);
+        }
+        if (cmb_reads_create(device, &parser) != CMB_OK) throw std::runtime_error(cmb_last_error());
+    }
+    DeviceReader(const DeviceReader&) = delete;
+    ~DeviceReader() {
+        cmb_reads_destroy(parser);
+#ifdef COLUMBA_AMD_HAVE_ZLIB
+        if (gz) gzclose(gz);
+#endif
+    }
+    bool onDevice() const { return !host; }
+    // up to n records; false when Reader::getNextChunk would return false
+    bool getNextChunk(ParsedChunk& chunk, size_t n) {
+        if (host) {
+            std::vector<SequenceRecord> recs;
+            const bool any = host->getNextChunk(recs, n);
+            chunk.pack(recs);
+            return any;
+        }
+        const uint32_t maxRecords = (uint32_t)std::min<size_t>(std::max<size_t>(n, 1), 0xFFFFFFFFu);
+        size_t want = (size_t)std::min<double>((double)CMB_READS_MAX_WINDOW, std::max(65536.0, bytesPerRecord * (double)maxRecords));
+        for (;;) {
+            fill(want);
+            cmb_reads_info info;
+            const int rc = cmb_reads_parse_fastq(parser, win.get() + begin, end - begin, maxRecords, eof, &info);
+            // (CMB_ERR_UNSUPPORTED: a window that begins with '>' — in a file that began with '@' that is a bad record as well)
+            if (rc == CMB_ERR_INVALID || rc == CMB_ERR_UNSUPPORTED) throw std::ios::failure("File " + fileName + " doesn't appear to be in FastQ format");
+            if (rc != CMB_OK) throw std::runtime_error(cmb_last_error());
+            if (info.stop == CMB_READS_STOP_WINDOW && !eof) { // the window ended before the chunk did
+                if (want < CMB_READS_MAX_WINDOW) {
+                    want = (size_t)std::min<uint64_t>(CMB_READS_MAX_WINDOW, 2 * (uint64_t)want);
+                    continue;
+                }
+                if (!info.n_records) throw std::runtime_error("File " + fileName + ": a record is longer than the largest window of the device parser");
+            }
+            begin += (size_t)info.consumed;
+            cmb_reads_view v;
+            if (cmb_reads_arrays(parser, &v) != CMB_OK) throw std::runtime_error(cmb_last_error());
+            chunk.view(v);
+            if (info.n_records) bytesPerRecord = 1.05 * (double)info.consumed / (double)info.n_records + 64.0 / (double)info.n_records;
+            return info.n_records != 0;
+        }
     }
 };
 
