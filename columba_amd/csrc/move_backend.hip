@@ -832,9 +832,9 @@ extern "C" int cmb_move_batch_create(cmb_move_index* idx, const cmb_strategy* st
     return CMB_OK;
 }
 
+// (the arguments have passed the null test of cmb_move_batch_create)
 static int moveBatchCreateOne(cmb_move_index* idx, const cmb_strategy* st, uint32_t max_distance, uint32_t kmer_size, const char* seqs,
                               const uint64_t* offs, uint32_t n_reads, cmb_move_batch** out) {
-    if (!idx || !st || !offs || !out || (!seqs && n_reads)) return failWith(CMB_ERR_INVALID, "null argument");
     if (!idx->hasLocate) return failWith(CMB_ERR_INVALID, "this index was created without the locate arrays");
     if (n_reads >= (1u << 23)) return failWith(CMB_ERR_UNSUPPORTED, "2^23 reads and more per b-move batch (24-bit read numbers in the filter keys)");
     if (idx->n >> 40) return failWith(CMB_ERR_UNSUPPORTED, "texts of 2^40 characters and more");
@@ -971,532 +971,704 @@ static int moveBatchRunOne(cmb_move_batch* b) {
     return CMB_OK;
 }
 
-// one level of the frontier search, as the pass loop of runSlice launches it (SMALL: 32-bit positions, on the narrow tables alone)
+// one level of the frontier search, as the pass loop of runFrontierEdit launches it (SMALL: 32-bit positions, on the narrow tables alone)
 template <class Geo, bool SMALL>
 static void launchMvsPass(cmb_move_batch* b, const MvBufs& B, uint32_t pass, const uint64_t* dOffs, const Queues& q) {
     hipLaunchKernelGGL((k_mvs_pass<Geo, SMALL && Geo::MP == MAXP>), dim3(B.gridX + B.gridEv), dim3(256), 0, b->stream, b->ix->d, stratOf<Geo::MP>(b), B, pass,
                        dOffs, b->gw, b->G.p, partsOf<Geo::MP>(b), q);
 }
 
+// ---- one slice of a batch: runSlice below calls these stages in the order of DESIGN.md §4.9 ----------------------------------------
+namespace {
+// What the stages of a slice share (values only); whatever a single stage needs is a local of that stage
+struct SliceCtx {
+    cmb_move_batch* b;
+    hipStream_t s;
+    Timer& tm;
+    uint32_t lo, nReads; // the slice: reads lo ... lo + nReads - 1 of the batch
+    const uint64_t* dOffs; // (the kernels number the slice's reads from 0; offsets stay absolute)
+    Queues q{};
+    MvSearchIndex sx{};
+    // the last read-back of b->cnt: [1] in-index occurrences, [3] the FLAG_* bits, [5] search tasks
+    uint32_t hcnt[8] = {};
+    // (the environment is read per slice, not per process: tests set it between runs)
+    bool verbose = false, smallPools = false;
+    bool edit = false, geoX = false; // (geoX, 11 ... 13 errors: the in-index matrix with 16-row blocks)
+    bool hasNaive = false;           // reads of the slice are matched by naive backtracking (k_mvs_parts marked them in psel)
+    uint32_t nFm = 0, nUniq = 0;     // in-index occurrences of the search, the distinct ones among them
+    uint64_t totalPos = 0, nNaiveKept = 0, nOut = 0; // text positions located, survivors of the naive filter, final occurrences
+};
+} // namespace
+
+static int failTooManyPositions() { return failWith(CMB_ERR_UNSUPPORTED, "2^31 and more text positions in one b-move batch"); }
+// the queue sizes and flags of the device, once everything on the stream has run
+static void readCounts(SliceCtx& c) {
+    HIPCHK(hipMemcpyAsync(c.hcnt, c.b->cnt.p, sizeof(c.hcnt), hipMemcpyDeviceToHost, c.s));
+    HIPCHK(hipStreamSynchronize(c.s));
+}
+// ... behind the per-pass counters of a search (what its loop looks at after each block of 16 passes)
+static void readPassCounts(SliceCtx& c, std::vector<uint32_t>& hc, const uint32_t* dCnt) {
+    HIPCHK(hipMemcpyAsync(hc.data(), dCnt, hc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c.s));
+    readCounts(c);
+}
+// FLAG_FMOCC_OVERFLOW: the list of in-index occurrences grows to what the attempt counted (a search that stopped there has only
+// counted what it needed up to there), by the factor of the stage at least
+static void growFmList(SliceCtx& c, size_t factor) {
+    c.b->fm.alloc(std::max<size_t>(factor * c.b->fm.n, (size_t)c.hcnt[1] + c.hcnt[1] / 4 + 1024));
+}
+
+// the records of the k = 0 path into the kept lists (the consumers read a read's first and last group offset only)
+static void fillKeptListsExact(cmb_move_batch* b, uint32_t nReads, uint64_t nOcc) {
+    hipStream_t s = b->stream;
+    b->keepReserve(nOcc, s);
+    std::vector<uint4> o32(nOcc);
+    for (uint64_t i = 0; i < nOcc; i++) o32[i] = make_uint4((uint32_t)b->occs[i].begin, (uint32_t)b->occs[i].end, b->occs[i].distance, b->occs[i].strand);
+    const uint32_t gs = b->keepStride;
+    std::vector<uint64_t> go((size_t)gs * nReads + 1);
+    for (uint32_t r = 0; r < nReads; r++)
+        for (uint32_t g = 0; g < gs; g++) go[(size_t)gs * r + g] = b->occOffs[r];
+    go[(size_t)gs * nReads] = b->occOffs[nReads];
+    if (nOcc) {
+        HIPCHK(hipMemcpyAsync(b->keepOcc.p, o32.data(), nOcc * sizeof(uint4), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(b->keepAln.p, b->hAlnRec.data(), nOcc * sizeof(AlnRec), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(b->keepOps.p, b->hAlnOps.data(), nOcc * b->alnStride * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+    }
+    HIPCHK(hipMemcpyAsync(b->keepOff.p, go.data(), go.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s)); // (the host vectors go out of scope)
+    b->keepN = nOcc;
+}
+
+// ---- k = 0: exactMatchesOutput of both strands (searchstrategy.cpp:499-510), the whole chunk as one slice through cmb_move_match_exact
+static int runExactSlice(cmb_move_batch* b, uint32_t nReads) {
+    cmb_move_index* ix = b->ix;
+    uint64_t nOcc = 0, c2[2] = {0, 0};
+    std::vector<cmb_move_occ> tmp((size_t)nReads * 8 + 1024);
+    int rc = cmb_move_match_exact(ix, (const char*)b->hostReads.data(), b->hostOffs.data(), nReads, tmp.data(), tmp.size(), b->occOffs.data(), &nOcc, c2);
+    if (rc == CMB_ERR_OVERFLOW) { // (nOcc: the number needed; nothing of that size has been allocated yet)
+        if (nOcc >= (1ull << 31)) return failTooManyPositions();
+        tmp.resize(nOcc);
+        rc = cmb_move_match_exact(ix, (const char*)b->hostReads.data(), b->hostOffs.data(), nReads, tmp.data(), tmp.size(), b->occOffs.data(), &nOcc, c2);
+    }
+    if (rc != CMB_OK) return rc;
+    tmp.resize(nOcc);
+    b->occs.assign(tmp);
+    if (b->wantAln) { // an exact match aligns as <length>M; its sequence by position (findSeqName, indexinterface.cpp:799-832)
+        const std::vector<uint32_t>& sp = cmb::seqStartsOfIndex(ix->textIndex);
+        b->hAlnRec.resize(nOcc);
+        b->hAlnOps.assign((size_t)nOcc * b->alnStride, 0);
+        for (uint64_t i = 0; i < nOcc; i++) {
+            const cmb_move_occ& o = b->occs[i];
+            if (sp.size() < 2) { // one sequence
+                b->hAlnRec[i] = AlnRec{0u, (uint32_t)o.begin, 1u, 0u};
+            } else {
+                const uint32_t id = (uint32_t)(std::upper_bound(sp.begin(), sp.end() - 1, (uint32_t)o.begin) - sp.begin()) - 1;
+                b->hAlnRec[i] = AlnRec{id, (uint32_t)o.begin - sp[id], 1u, o.end > sp[id + 1] ? 1u : 0u};
+            }
+            b->hAlnOps[i * b->alnStride] = (uint16_t)(((o.end - o.begin) << 2) | 0u);
+        }
+        if (b->keepLists) fillKeptListsExact(b, nReads, nOcc);
+    }
+    b->cnts[CMB_CNT_NODE] = c2[0];
+    b->cnts[CMB_CNT_EXPANSIONS] = g_exactExpansions;
+    b->cnts[CMB_CNT_TOTAL_REPORTED] = c2[1];
+    b->cnts[CMB_CNT_LOCATED_ROWS] = c2[1];
+    float ms[3];
+    (void)cmb_move_last_timings(ms, 3);
+    b->times.push_back({"k_move_exact", ms[0]});
+    b->times.push_back({"locate", ms[1] + ms[2]});
+    return CMB_OK;
+}
+
+// the per-read scratch of a slice (slices of a run have one size, the last may be shorter)
+static void sizeSliceScratch(SliceCtx& c) {
+    cmb_move_batch* b = c.b;
+    const uint32_t nReads = c.nReads;
+    if ((b->wide ? b->partsW.n : b->parts.n) < (size_t)2 * nReads) {
+        b->seq.alloc((size_t)2 * nReads * b->maxLen);
+        b->G.alloc((size_t)nReads * 8 * b->gw);
+        if (b->wide) b->partsW.alloc((size_t)2 * nReads);
+        else b->parts.alloc((size_t)2 * nReads);
+        b->psel.alloc((size_t)2 * nReads);
+        b->exr.alloc((size_t)2 * nReads * b->sNumParts);
+        b->tasks.alloc((size_t)2 * nReads * b->sMaxSearches + 64);
+    }
+}
+
+// ---- read preparation: both strands of every read and their match words
+static void runPrep(SliceCtx& c) {
+    cmb_move_batch* b = c.b;
+    hipStream_t s = c.s;
+    const uint32_t nReads = c.nReads;
+    c.tm.begin();
+    HIPCHK(hipMemsetAsync(b->G.p, 0, (size_t)nReads * 8 * b->gw * sizeof(uint32_t), s));
+    hipLaunchKernelGGL(k_mvs_prep, dim3(gridFor((uint64_t)nReads * b->gw)), dim3(256), 0, s, b->reads.p, c.dOffs, nReads, b->maxLen, b->gw, b->seq.p, b->G.p);
+    c.tm.end("k_prep");
+}
+
+// ---- prologue: k_mvs_parts + k_mvs_exact into the queues at their present sizes, and the first look at what they left
+static int runPrologue(SliceCtx& c) {
+    cmb_move_batch* b = c.b;
+    hipStream_t s = c.s;
+    Queues& q = c.q;
+    const uint32_t nReads = c.nReads, tasksRS = 2 * nReads;
+    const uint32_t P = b->sNumParts, maxSearches = b->sMaxSearches;
+    HIPCHK(hipMemsetAsync(b->cnt.p, 0, 8 * sizeof(uint32_t), s));
+    HIPCHK(hipMemsetAsync(b->counters.p, 0, CMB_CNT_MAX * sizeof(unsigned long long), s));
+    if (!b->fm.n) b->fm.alloc((size_t)nReads * 16 + 4096);
+    q.fmCap = cap32(b->fm.n);
+    c.tm.begin();
+    const unsigned grid = capBlocks((unsigned)std::min<uint64_t>(((uint64_t)tasksRS + 63) / 64, 256 * 64));
+    const uint64_t nWork = (uint64_t)tasksRS * maxSearches;
+    const unsigned gridE = capBlocks((unsigned)std::min<uint64_t>((nWork + 63) / 64, 256 * 64));
+    gridLine(c.verbose, "k_mvs_parts", tasksRS, 64ull * grid);
+    gridLine(c.verbose, "k_mvs_exact", nWork, 64ull * gridE);
+    const size_t exLdsBytes = (size_t)P * 3 * 64 * sizeof(uint4);
+    withTables(b, [&](auto mp) {
+        constexpr int MP = decltype(mp)::value;
+        auto kp = withInt<3>((int)b->sPartition, [](auto part) { return k_mvs_parts<part(), MP>; });
+        hipLaunchKernelGGL(kp, dim3(grid), dim3(64), exLdsBytes, s, c.sx, stratOf<MP>(b), nReads, b->maxLen, b->seq.p, c.dOffs, partsOf<MP>(b), b->exr.p,
+                           b->psel.p, q);
+        hipLaunchKernelGGL(k_mvs_exact<MP>, dim3(gridE), dim3(64), 0, s, c.sx, stratOf<MP>(b), nReads, b->maxLen, maxSearches, b->seq.p, partsOf<MP>(b),
+                           b->exr.p, b->psel.p, b->tasks.p, cap32(b->tasks.n), q);
+    });
+    c.tm.end("k_partition");
+    HIPCHK(hipGetLastError());
+    readCounts(c);
+    c.hasNaive = (c.hcnt[3] & FLAG_UNSUPPORTED_READ) != 0;
+    if (c.hcnt[3] & FLAG_SEED_OVERLAP)
+        return failWith(CMB_ERR_INVALID, "dynamic partitioning: the seeds of a read overlap — the k-mer size is too large for the seeding "
+                                         "positions of this search strategy at this read length");
+    if (c.hcnt[3] & FLAG_DFS_OVERFLOW) return failWith(CMB_ERR_INTERNAL, "task queue too small");
+    return CMB_OK;
+}
+
+// ---- reads not longer than the number of parts / one-part strategies: naive backtracking (k_mvs_naive); k_mvs_parts marked them in psel
+static int runNaiveSearch(SliceCtx& c, bool& again) {
+    cmb_move_batch* b = c.b;
+    hipStream_t s = c.s;
+    const Queues& q = c.q;
+    const uint32_t tasksRS = 2 * c.nReads;
+    c.tm.begin();
+    const uint32_t maxPassN = b->maxLen + 2 * b->k + 4;
+    constexpr uint32_t PU = MvTraits::PAIR_U4;
+    if (!b->nvQCap) b->nvQCap = c.smallPools ? 64 : 16384;
+    for (int j = 0; j < 2; j++)
+        if (b->nvQ[j].n < (PU + 2) * b->nvQCap) b->nvQ[j].alloc((PU + 2) * b->nvQCap);
+    const size_t cntWords = (size_t)maxPassN + 2;
+    if (b->nvCnt.n < cntWords) b->nvCnt.alloc(cntWords);
+    HIPCHK(hipMemsetAsync(b->nvCnt.p, 0, cntWords * sizeof(uint32_t), s));
+    MvHbfsBufs N{};
+    N.Q[0] = b->nvQ[0].p;
+    N.Q[1] = b->nvQ[1].p;
+    N.qCap = cap32(b->nvQ[0].n / (PU + 2));
+    N.nq = b->nvCnt.p;
+    N.blockCnt = nullptr;
+    N.fmX = b->fm.p;
+    // (the matrix of 11 ... 13 errors is the edit distance's alone)
+    auto naiveKernel = [&](bool start) {
+        return withBools([](auto e, auto st, auto x) { return k_mvs_naive<e(), st(), e() && x()>; }, c.edit, start, c.geoX);
+    };
+    auto kNaiveStart = naiveKernel(true), kNaivePass = naiveKernel(false);
+    const uint32_t nvStart = capBlocks((tasksRS + 255) / 256), nvGrid = capBlocks(BFS_GRID);
+    gridLine(c.verbose, "k_mvs_naive_start", tasksRS, 256ull * nvStart);
+    hipLaunchKernelGGL(kNaiveStart, dim3(nvStart), dim3(256), 0, s, b->ix->d, N, 0u,
+                       (const uint8_t*)b->psel.p, tasksRS, c.dOffs, b->gw, b->G.p, b->seq.p, b->maxLen, b->k, q);
+    std::vector<uint32_t> hc(cntWords);
+    uint32_t pass = 0, peakQ = 0;
+    bool drained = false;
+    while (!drained && pass < maxPassN) {
+        const uint32_t upTo = std::min(pass + 16u, maxPassN);
+        for (; pass < upTo; pass++)
+            hipLaunchKernelGGL(kNaivePass, dim3(nvGrid), dim3(256), 0, s, b->ix->d, N, pass,
+                               (const uint8_t*)b->psel.p, tasksRS, c.dOffs, b->gw, b->G.p, b->seq.p, b->maxLen, b->k, q);
+        readPassCounts(c, hc, b->nvCnt.p);
+        if (c.hcnt[3] & MVS_NAIVE_STOP) break;
+        drained = hc[pass] == 0;
+    }
+    for (uint32_t p2 = 0; p2 <= pass && p2 < cntWords; p2++) peakQ = std::max(peakQ, hc[p2]);
+    gridLine(c.verbose, "k_mvs_naive_pass", peakQ, 256ull * nvGrid); // (the largest frontier of a pass)
+    c.tm.end("k_naive");
+    HIPCHK(hipGetLastError());
+    if (c.hcnt[3] & MVS_NAIVE_STOP) {
+        // (the search stopped at the overflow: it has only counted what it needed up to there)
+        if (c.hcnt[3] & FLAG_NAIVE_Q) b->nvQCap = std::max<size_t>(4 * b->nvQCap, (size_t)peakQ + peakQ / 4);
+        if (c.hcnt[3] & FLAG_FMOCC_OVERFLOW) growFmList(c, 8);
+        again = true;
+        return CMB_OK;
+    }
+    if (!drained) return failWith(CMB_ERR_INTERNAL, "the naive search did not finish within its pass bound");
+    return CMB_OK;
+}
+
+// ---- Hamming distance: the frontier without a matrix (k_mvs_hbfs), one row per pass
+static int runFrontierHamming(SliceCtx& c, bool& again) {
+    cmb_move_batch* b = c.b;
+    hipStream_t s = c.s;
+    const Queues& q = c.q;
+    const uint32_t nReads = c.nReads, nTasks = c.hcnt[5];
+    c.tm.begin();
+    const uint32_t maxPass = b->maxLen + 2 * (b->wide ? MAXP_WIDE : MAXP) + 16;
+    constexpr uint32_t PU = MvTraits::PAIR_U4;
+    if (!b->qCap) b->qCap = (c.smallPools ? 0 : (size_t)nReads * 8) + 1024;
+    b->qCap = std::max<size_t>(b->qCap, (size_t)nTasks + 1024);
+    for (int j = 0; j < 2; j++)
+        if (b->Q[j].n < (PU + 1) * b->qCap) b->Q[j].alloc((PU + 1) * b->qCap);
+    const size_t cntWords = (size_t)maxPass + 2;
+    if (b->bfsCnt.n < cntWords) b->bfsCnt.alloc(cntWords);
+    if (b->blockCnt.n < (size_t)BFS_GRID * 4) b->blockCnt.alloc((size_t)BFS_GRID * 4);
+    HIPCHK(hipMemsetAsync(b->bfsCnt.p, 0, cntWords * sizeof(uint32_t), s));
+    HIPCHK(hipMemsetAsync(b->blockCnt.p, 0, (size_t)BFS_GRID * 4 * sizeof(unsigned long long), s));
+    MvHbfsBufs H{};
+    H.Q[0] = b->Q[0].p;
+    H.Q[1] = b->Q[1].p;
+    H.qCap = cap32(b->Q[0].n / (PU + 1));
+    H.nq = b->bfsCnt.p;
+    H.blockCnt = b->blockCnt.p;
+    H.fmX = b->fm.p;
+    const uint32_t startGrid = capBlocks(std::min<uint32_t>((nTasks + 255) / 256, BFS_GRID)), passGrid = capBlocks(BFS_GRID);
+    gridLine(c.verbose, "k_mvs_hbfs_start", nTasks, 256ull * startGrid);
+    withTables(b, [&](auto mp) {
+        constexpr int MP = decltype(mp)::value;
+        hipLaunchKernelGGL((k_mvs_hbfs<true, MP>), dim3(startGrid), dim3(256), 0, s, b->ix->d, stratOf<MP>(b), H, 0u, b->tasks.p, nTasks, b->maxLen,
+                           b->seq.p, partsOf<MP>(b), q);
+    });
+    std::vector<uint32_t> hc(cntWords);
+    uint32_t pass = 0, peakQ = 0;
+    bool drained = false;
+    while (!drained && pass < maxPass) {
+        const uint32_t upTo = std::min(pass + 16u, maxPass);
+        for (; pass < upTo; pass++)
+            withTables(b, [&](auto mp) {
+                constexpr int MP = decltype(mp)::value;
+                hipLaunchKernelGGL((k_mvs_hbfs<false, MP>), dim3(passGrid), dim3(256), 0, s, b->ix->d, stratOf<MP>(b), H, pass, (const MvTask*)nullptr,
+                                   0u, b->maxLen, b->seq.p, partsOf<MP>(b), q);
+            });
+        readPassCounts(c, hc, b->bfsCnt.p);
+        if (c.hcnt[3] & BFS_STOP) break;
+        drained = hc[pass] == 0;
+    }
+    for (uint32_t p2 = 0; p2 <= pass && p2 < cntWords; p2++) peakQ = std::max(peakQ, hc[p2]);
+    gridLine(c.verbose, "k_mvs_hbfs_pass", peakQ, 256ull * passGrid); // (the largest frontier of a pass)
+    MvBufs Bf{};
+    Bf.blockCnt = b->blockCnt.p;
+    hipLaunchKernelGGL(k_mvs_finish, dim3(1), dim3(256), 0, s, Bf, q);
+    c.tm.end("k_dfs");
+    HIPCHK(hipGetLastError());
+    if (c.hcnt[3] & (FLAG_BFS_Q | FLAG_FMOCC_OVERFLOW)) {
+        if (c.hcnt[3] & FLAG_BFS_Q) b->qCap = std::max<size_t>(2 * b->qCap, (size_t)peakQ + peakQ / 4);
+        if (c.hcnt[3] & FLAG_FMOCC_OVERFLOW) growFmList(c, 2);
+        again = true;
+        return CMB_OK;
+    }
+    if (!drained) return failWith(CMB_ERR_INTERNAL, "frontier search did not finish within its pass bound");
+    return CMB_OK;
+}
+
+// The pools of the edit-distance frontier as the kernels take them (move_search.hpp): grown to the capacities the batch asks for, their
+// cntWords counters (nodes and events per level, the pool sizes) zeroed on the stream, for a search of at most maxPass levels.
+// smallPos: text and run counts below 2^32 (the reference's default build of length_t) — the expanding blocks work on 32-bit positions
+// with the children in slots (mvExpandSlots; CMB_MOVE_POS64=1: the general 40-bit path)
+static MvBufs frontierBufs(SliceCtx& c, uint32_t maxPass, size_t cntWords, bool smallPos) {
+    cmb_move_batch* b = c.b;
+    hipStream_t s = c.s;
+    const uint32_t pkU4 = b->wide ? GeoW::PK_U4 : GeoN::PK_U4; // planes of a node's final-column pack / uint4 of an event's
+    constexpr uint32_t PU = MvTraits::PAIR_U4;
+    for (int j = 0; j < 2; j++) {
+        if (b->Q[j].n < (PU + 2 + pkU4) * b->qCap) b->Q[j].alloc((PU + 2 + pkU4) * b->qCap);
+        if (b->Ev[j].n < (1 + pkU4) * b->evCap) b->Ev[j].alloc((1 + pkU4) * b->evCap);
+    }
+    if (b->F.n < (PU + 1) * b->fCap) b->F.alloc((PU + 1) * b->fCap);
+    const uint32_t ctxU4 = c.geoX ? CTX_U4_X : ctxU4For(b->maxLen);
+    if (b->C.n < (size_t)ctxU4 * b->cCap) b->C.alloc((size_t)ctxU4 * b->cCap);
+    if (b->A.n < b->aCap) b->A.alloc(b->aCap);
+    if (b->bfsCnt.n < cntWords) b->bfsCnt.alloc(cntWords);
+    if (b->blockCnt.n < (size_t)BFS_GRID * 4) b->blockCnt.alloc((size_t)BFS_GRID * 4);
+    HIPCHK(hipMemsetAsync(b->bfsCnt.p, 0, cntWords * sizeof(uint32_t), s));
+    HIPCHK(hipMemsetAsync(b->blockCnt.p, 0, (size_t)BFS_GRID * 4 * sizeof(unsigned long long), s));
+    MvBufs B{};
+    for (int j = 0; j < 2; j++) {
+        B.Q[j] = b->Q[j].p;
+        B.Ev[j] = b->Ev[j].p;
+    }
+    B.F = b->F.p;
+    B.C = b->C.p;
+    B.A = b->A.p;
+    B.qCap = cap32(b->Q[0].n / (PU + 2 + pkU4));
+    B.evCap = cap32(b->Ev[0].n / (1 + pkU4));
+    B.fCap = cap32(b->F.n / (PU + 1));
+    B.cCap = cap32(b->C.n / ctxU4);
+    B.ctxU4 = ctxU4;
+    B.ctxMblk = c.geoX ? CTX_MBLK_X : ctxMblkFor(b->maxLen);
+    B.aCap = cap32(b->A.n);
+    B.chain = getenv("CMB_MVS_CHAIN") ? (uint32_t)std::max(1, atoi(getenv("CMB_MVS_CHAIN"))) : (smallPos ? MVS_CHAIN_SMALL : MVS_CHAIN);
+    B.gridX = capBlocks(std::min<uint32_t>(BFS_GRID, envBlocks("CMB_MVS_GRID", b->wide ? MVS_GRID_X_WIDE : smallPos ? MVS_GRID_X_SMALL : MVS_GRID_X)));
+    B.gridEv = capBlocks(BFS_GRID_EV);
+    B.nq = b->bfsCnt.p;
+    B.ne = b->bfsCnt.p + (maxPass + 2);
+    B.pool = b->bfsCnt.p + 2 * (maxPass + 2);
+    B.blockCnt = b->blockCnt.p;
+    B.fmX = b->fm.p;
+    B.rowSteps = nullptr;
+    B.narrowWv = getenv("CMB_TEST_NARROW_WV") ? (uint32_t)std::max(0, atoi(getenv("CMB_TEST_NARROW_WV"))) : 0xFFFFu;
+    return B;
+}
+
+// ---- edit distance: the frontier with the in-index matrix — start pass, then (expand, events) per level until both queues drain
+static int runFrontierEdit(SliceCtx& c, bool& again) {
+    cmb_move_batch* b = c.b;
+    hipStream_t s = c.s;
+    const Queues& q = c.q;
+    const uint32_t nReads = c.nReads, nTasks = c.hcnt[5];
+    c.tm.begin();
+    const uint32_t maxPass = 2 * b->maxLen + 8 * (b->wide ? MAXP_WIDE : MAXP) + 64;
+    if (!b->qCap) {
+        const size_t slack = c.smallPools ? 64 : 65536;
+        const size_t per = c.smallPools ? 0 : 1;
+        b->qCap = per * (size_t)nReads * 4 + slack;
+        b->evCap = per * (size_t)nReads + slack;
+        b->fCap = per * (size_t)nReads * 16 + slack;
+        b->cCap = per * (size_t)nReads * 4 + slack;
+        b->aCap = per * (size_t)nReads * 32 + slack;
+    }
+    b->qCap = std::max<size_t>(b->qCap, (size_t)nTasks + 1024);
+    const size_t cntWords = 2 * ((size_t)maxPass + 2) + 4;
+    const cmb_move_index* ix = b->ix;
+    const bool smallPos = !b->wide && ix->d.n < 0xFFFFFFF0ull && ix->d.fwd.runs < 0xFFFFFFF0ull && ix->d.rev.runs < 0xFFFFFFF0ull && !getenv("CMB_MOVE_POS64");
+    const MvBufs B = frontierBufs(c, maxPass, cntWords, smallPos);
+    const FrontierGeo geo = frontierGeoOf(b);
+    const dim3 gStart(capBlocks(std::min<uint32_t>((nTasks + 255) / 256, BFS_GRID)));
+    gridLine(c.verbose, "k_mvs_start", nTasks, 256ull * gStart.x);
+    withGeo(geo, [&](auto g) {
+        using Geo = typename decltype(g)::type;
+        hipLaunchKernelGGL(k_mvs_start<Geo>, gStart, dim3(256), 0, s, stratOf<Geo::MP>(b), B, b->tasks.p, nTasks, c.dOffs, b->gw, b->G.p,
+                           partsOf<Geo::MP>(b), q);
+    });
+    // (the instance of a pass is chosen here, once per attempt: the loop below calls through a pointer)
+    const auto mvsPass = withGeo(geo, [&](auto g) {
+        return withBools([](auto small) { return &launchMvsPass<typename decltype(g)::type, decltype(small)::value>; }, smallPos);
+    });
+    std::vector<uint32_t> hc(cntWords);
+    uint32_t pass = 0, peakQ = 0, peakEv = 0;
+    bool drained = false;
+    while (!drained && pass < maxPass) {
+        const uint32_t upTo = std::min(pass + 16u, maxPass);
+        for (; pass < upTo; pass++) mvsPass(b, B, pass, c.dOffs, q);
+        readPassCounts(c, hc, b->bfsCnt.p);
+        if (c.hcnt[3] & BFS_STOP) break;
+        drained = hc[pass] == 0 && hc[maxPass + 2 + pass] == 0;
+    }
+    for (uint32_t p2 = 0; p2 <= pass && p2 < maxPass + 2; p2++) {
+        peakQ = std::max(peakQ, hc[p2]);
+        peakEv = std::max(peakEv, hc[maxPass + 2 + p2]);
+    }
+    const uint32_t* pool = hc.data() + 2 * (maxPass + 2);
+    gridLine(c.verbose, "k_mvs_pass", peakQ, 256ull * B.gridX); // (the largest frontier and the most events of a pass)
+    gridLine(c.verbose, "k_mvs_pass_events", peakEv, 256ull * B.gridEv);
+    if (c.verbose)
+        fprintf(stderr, "[mvs] %u tasks, %u passes, peak frontier %u, peak events %u, F %u, contexts %u, arena %u\n", nTasks, pass, peakQ, peakEv,
+                pool[0], pool[1], pool[2]);
+    hipLaunchKernelGGL(k_mvs_finish, dim3(1), dim3(256), 0, s, B, q);
+    c.tm.end("k_dfs");
+    HIPCHK(hipGetLastError());
+    if (c.hcnt[3] & FLAG_NARROW_MATRIX) { // (a first column wider than the small matrix holds: once more on the reference's words)
+        b->noSmallMatrix = true;
+        again = true;
+        return CMB_OK;
+    }
+    if (c.hcnt[3] & FLAG_CAPACITY) return failWith(CMB_ERR_INTERNAL, "device search capacity exceeded (band width / descendants)");
+    if (c.hcnt[3] & (FLAG_BFS_Q | FLAG_BFS_EV | FLAG_BFS_F | FLAG_BFS_CTX | FLAG_BFS_ARENA | FLAG_FMOCC_OVERFLOW)) {
+        if (c.hcnt[3] & FLAG_BFS_Q) b->qCap = std::max<size_t>(2 * b->qCap, (size_t)peakQ + peakQ / 4);
+        if (c.hcnt[3] & FLAG_BFS_EV) b->evCap = std::max<size_t>(2 * b->evCap, (size_t)peakEv + peakEv / 4);
+        if (c.hcnt[3] & FLAG_BFS_F) b->fCap = std::max<size_t>(2 * b->fCap, (size_t)pool[0] + pool[0] / 4);
+        if (c.hcnt[3] & FLAG_BFS_CTX) b->cCap = std::max<size_t>(2 * b->cCap, (size_t)pool[1] + pool[1] / 4);
+        if (c.hcnt[3] & FLAG_BFS_ARENA) b->aCap = std::max<size_t>(2 * b->aCap, (size_t)pool[2] + pool[2] / 4);
+        if (c.hcnt[3] & FLAG_FMOCC_OVERFLOW) growFmList(c, 2);
+        again = true;
+        return CMB_OK;
+    }
+    if (!drained) return failWith(CMB_ERR_INTERNAL, "frontier search did not finish within its pass bound");
+    return CMB_OK;
+}
+
+// One attempt of the search with the pools at their present sizes: prologue, naive backtracking, frontier.  again: a stage has grown
+// what was too small (or changed the geometry) and the attempt runs once more; otherwise c.hcnt holds what the search left
+static int searchAttempt(SliceCtx& c, bool& again) {
+    int rc = runPrologue(c);
+    if (rc != CMB_OK) return rc;
+    if (c.hasNaive && ((rc = runNaiveSearch(c, again)) != CMB_OK || again)) return rc;
+    if (!c.hcnt[5]) return CMB_OK; // (no search tasks)
+    return c.edit ? runFrontierEdit(c, again) : runFrontierHamming(c, again);
+}
+
+// ---- in-index occurrences: de-duplicate the c.nFm of the search into c.nUniq ranges (locRanges, locMeta) and scan their widths
+// (locOff): c.totalPos text positions to locate
+static int dedupFmOccurrences(SliceCtx& c) {
+    cmb_move_batch* b = c.b;
+    hipStream_t s = c.s;
+    const uint32_t nFm = c.nFm;
+    uint32_t& nUniq = c.nUniq;
+    c.tm.begin();
+    if (nFm) {
+        if (b->keysA.n < nFm) {
+            const size_t cap = (size_t)nFm + nFm / 4 + 256;
+            b->keysA.alloc(cap), b->keysB.alloc(cap), b->fmIdxA.alloc(cap), b->fmIdxB.alloc(cap), b->keep.alloc(cap + 1), b->slot.alloc(cap + 1),
+                b->widths.alloc(cap + 1);
+        }
+        hipLaunchKernelGGL(k_mvs_fm_keys, dim3(gridFor(nFm)), dim3(256), 0, s, b->fm.p, nFm, b->keysA.p, b->fmIdxA.p);
+        MV_COUNT_LIMIT((uint64_t)nFm + 1, "in-index occurrences of one slice"); // (2^31 records of 96 bytes would not fit the HBM)
+        sortPairs(b->sortTmp, b->keysA.p, b->keysB.p, b->fmIdxA.p, b->fmIdxB.p, nFm, 0, 64, s);
+        hipLaunchKernelGGL(k_mvs_fm_unique, dim3(gridFor(nFm)), dim3(256), 0, s, b->fm.p, b->fmIdxB.p, nFm, b->keep.p, b->widths.p);
+        HIPCHK(hipMemsetAsync(b->keep.p + nFm, 0, sizeof(uint32_t), s));
+        scanExclusive(b->sortTmp, b->keep.p, b->slot.p, (size_t)nFm + 1, s);
+        HIPCHK(hipMemcpyAsync(&nUniq, b->slot.p + nFm, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (nUniq) {
+            if (b->locRanges.n < nUniq) {
+                const size_t cap = (size_t)nUniq + nUniq / 4 + 256;
+                b->locRanges.alloc(cap), b->locMeta.alloc(cap), b->locWidths.alloc(cap + 1), b->locOff.alloc(cap + 1);
+            }
+            hipLaunchKernelGGL(k_mvs_fm_compact, dim3(gridFor(nFm)), dim3(256), 0, s, b->fm.p, b->fmIdxB.p, b->keep.p, b->slot.p, nFm, b->locRanges.p,
+                               b->locMeta.p, b->locWidths.p);
+            HIPCHK(hipMemsetAsync(b->locWidths.p + nUniq, 0, sizeof(uint64_t), s));
+            MV_COUNT_LIMIT((uint64_t)nUniq + 1, "distinct in-index occurrences of one slice"); // (nUniq <= nFm)
+            scanExclusive(b->sortTmp, b->locWidths.p, b->locOff.p, (size_t)nUniq + 1, s);
+            HIPCHK(hipMemcpyAsync(&c.totalPos, b->locOff.p + nUniq, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+        }
+    }
+    c.tm.end("fm_unique");
+    if (c.totalPos >= (1ull << 31)) return failTooManyPositions();
+    return CMB_OK;
+}
+
+// ---- locate: the text positions of every distinct in-index occurrence (k_move_locate), range by range at locOff
+static void locatePositions(SliceCtx& c) {
+    cmb_move_batch* b = c.b;
+    hipStream_t s = c.s;
+    const uint64_t totalPos = c.totalPos;
+    c.tm.begin();
+    if (totalPos) {
+        if (b->positions.n < totalPos) {
+            const size_t cap = totalPos + totalPos / 4 + 256;
+            b->positions.alloc(cap), b->keysA.alloc(std::max(cap, b->keysA.n)), b->keysB.alloc(std::max(cap, b->keysB.n)), b->vals.alloc(cap),
+                b->valsB.alloc(cap);
+        }
+        if (b->keysA.n < totalPos) b->keysA.alloc(totalPos + 256), b->keysB.alloc(totalPos + 256);
+        HIPCHK(hipMemsetAsync(b->bad.p, 0, sizeof(uint32_t), s));
+        hipLaunchKernelGGL(k_move_locate, dim3(gridFor(c.nUniq)), dim3(256), 0, s, b->ix->d, b->locRanges.p, (uint64_t)c.nUniq, b->locOff.p, (uint64_t)0,
+                           b->positions.p, b->bad.p, true);
+    }
+    c.tm.end("locate");
+}
+
+// The filter of getUniqueTextOccurrences / getTextOccHamming on the nKeys keys in keysA / vals: one 64-bit radix sort -> survivors per
+// group (k_mvs_filter) -> scan -> the `kept` survivors into dst, group by group at readOff
+static int filterGroups(SliceCtx& c, uint64_t nKeys, uint32_t nGroups, DevBuf<MoveOccOut>& dst, uint64_t& kept) {
+    cmb_move_batch* b = c.b;
+    hipStream_t s = c.s;
+    const uint32_t window = c.edit ? b->k : 0u;
+    const uint32_t uniqueOnly = c.edit ? 0u : 1u; // (getTextOccHamming, indexinterface.cpp:1331-1371: no redundancy filter)
+    // (nKeys < 2^31: the refusals of 2^31 text positions per slice; nGroups <= 2^24: 2^23 reads per batch)
+    MV_COUNT_LIMIT(nKeys, "text occurrences of one slice");
+    MV_COUNT_LIMIT((uint64_t)nGroups + 1, "filter groups of one slice");
+    sortPairs(b->sortTmp, b->keysA.p, b->keysB.p, b->vals.p, b->valsB.p, (uint32_t)nKeys, 0, 64, s);
+    HIPCHK(hipMemsetAsync(b->readCnt.p, 0, ((size_t)nGroups + 1) * sizeof(uint64_t), s));
+    hipLaunchKernelGGL(k_mvs_filter<false>, dim3(gridFor(nGroups)), dim3(256), 0, s, b->keysB.p, b->valsB.p, nKeys, nGroups, window, b->readCnt.p,
+                       (const uint64_t*)nullptr, (MoveOccOut*)nullptr, uniqueOnly);
+    scanExclusive(b->sortTmp, b->readCnt.p, b->readOff.p, (size_t)nGroups + 1, s);
+    HIPCHK(hipMemcpyAsync(&kept, b->readOff.p + nGroups, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (dst.n < kept) dst.alloc(kept + kept / 4 + 256);
+    if (kept)
+        hipLaunchKernelGGL(k_mvs_filter<true>, dim3(gridFor(nGroups)), dim3(256), 0, s, b->keysB.p, b->valsB.p, nKeys, nGroups, window, b->readCnt.p,
+                           b->readOff.p, dst.p, uniqueOnly);
+    return CMB_OK;
+}
+
+// the naive path's own filter pass, per read x strand (indexinterface.cpp:1137, :1205): its c.nNaiveKept survivors in naiveOut / naiveOff
+static int filterNaive(SliceCtx& c) {
+    cmb_move_batch* b = c.b;
+    hipStream_t s = c.s;
+    const uint32_t nReads = c.nReads;
+    const uint64_t totalPos = c.totalPos;
+    hipLaunchKernelGGL(k_mvs_text_keys, dim3(gridFor(totalPos)), dim3(256), 0, s, b->positions.p, b->locOff.p, c.nUniq, totalPos, b->locMeta.p, b->keysA.p,
+                       b->vals.p, b->bad.p, (const uint8_t*)b->psel.p, 1);
+    if (const int rc = filterGroups(c, totalPos, 2 * nReads, b->naiveOut, c.nNaiveKept); rc != CMB_OK) return rc;
+    if (b->naiveOff.n < (size_t)2 * nReads + 1) b->naiveOff.alloc((size_t)2 * nReads + 1);
+    HIPCHK(hipMemcpyAsync(b->naiveOff.p, b->readOff.p, ((size_t)2 * nReads + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+    const uint64_t need = totalPos + c.nNaiveKept;
+    if (need >= (1ull << 31)) return failTooManyPositions();
+    if (b->keysA.n < need || b->vals.n < need) {
+        HIPCHK(hipStreamSynchronize(s));
+        b->keysA.alloc(need + 256), b->keysB.alloc(need + 256), b->vals.alloc(need + 256), b->valsB.alloc(need + 256);
+    }
+    return CMB_OK;
+}
+
+// the final filter per read (or per read x strand) over the located positions and the naive path's survivors: c.nOut occurrences in
+// b->out, read by read at readOff (rsOff: group by group, when every strand is filtered by itself)
+static int filterFinal(SliceCtx& c) {
+    cmb_move_batch* b = c.b;
+    hipStream_t s = c.s;
+    const uint32_t nReads = c.nReads;
+    const uint64_t totalPos = c.totalPos;
+    const int perStrand = b->perStrand ? 1 : 0;
+    hipLaunchKernelGGL(k_mvs_text_keys, dim3(gridFor(totalPos)), dim3(256), 0, s, b->positions.p, b->locOff.p, c.nUniq, totalPos, b->locMeta.p, b->keysA.p,
+                       b->vals.p, b->bad.p, (const uint8_t*)b->psel.p, c.hasNaive ? 2 : 0, perStrand);
+    if (c.nNaiveKept)
+        hipLaunchKernelGGL(k_mvs_occ_keys, dim3(gridFor(2 * nReads)), dim3(256), 0, s, b->naiveOut.p, b->naiveOff.p, 2 * nReads, b->keysA.p + totalPos,
+                           b->vals.p + totalPos, perStrand);
+    // (the previous slice's records may still be on their way out of b->out: this stream waits for them before the buffer is
+    // written or enlarged — filterGroups synchronises the stream before it allocates)
+    if (b->copyPending) HIPCHK(hipStreamWaitEvent(s, b->copyDone, 0));
+    if (const int rc = filterGroups(c, totalPos + c.nNaiveKept, perStrand ? 2 * nReads : nReads, b->out, c.nOut); rc != CMB_OK) return rc;
+    if (perStrand) { // per read again: the two strands of a read are neighbouring groups
+        if (b->rsOff.n < (size_t)2 * nReads + 1) b->rsOff.alloc((size_t)2 * nReads + 1);
+        HIPCHK(hipMemcpyAsync(b->rsOff.p, b->readOff.p, ((size_t)2 * nReads + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+        hipLaunchKernelGGL(k_mvs_read_offsets, dim3(gridFor(nReads + 1)), dim3(256), 0, s, b->rsOff.p, nReads, b->readOff.p);
+    }
+    return CMB_OK;
+}
+
+// ---- sort + filter of the located positions: the naive path's own pass first, where the slice has such reads
+static int filterOccurrences(SliceCtx& c) {
+    cmb_move_batch* b = c.b;
+    c.tm.begin();
+    if (b->readCnt.n < (size_t)2 * c.nReads + 1) b->readCnt.alloc((size_t)2 * c.nReads + 1), b->readOff.alloc((size_t)2 * c.nReads + 1);
+    if (c.totalPos) {
+        int rc = c.hasNaive ? filterNaive(c) : CMB_OK;
+        if (rc != CMB_OK || (rc = filterFinal(c)) != CMB_OK) return rc;
+    }
+    c.tm.end("filter");
+    HIPCHK(hipGetLastError());
+    return CMB_OK;
+}
+
+// ---- CIGAR and sequence of every final occurrence: findCIGAR on text[begin, end) (k_cigar), on request; with the lists kept, in
+// place behind the records of the slices before this one
+static int runCigar(SliceCtx& c) {
+    cmb_move_batch* b = c.b;
+    hipStream_t s = c.s;
+    const uint32_t nReads = c.nReads;
+    const uint64_t nOut = c.nOut;
+    if (!b->wantAln || !nOut) return CMB_OK;
+    c.tm.begin();
+    uint4* dOcc = nullptr;
+    AlnRec* dAln = nullptr;
+    uint16_t* dOps = nullptr;
+    if (b->keepLists) { // in place, behind the records of the slices before this one
+        b->keepReserve(b->keepN + nOut, s);
+        if (b->occRead.n < nOut) b->occRead.alloc(nOut + nOut / 4 + 256);
+        dOcc = b->keepOcc.p + b->keepN, dAln = b->keepAln.p + b->keepN, dOps = b->keepOps.p + b->keepN * b->alnStride;
+    } else {
+        if (b->occ32.n < nOut) {
+            const size_t cap = nOut + nOut / 4 + 256;
+            b->occ32.alloc(cap), b->alnRec.alloc(cap), b->occRead.alloc(cap), b->alnOps.alloc(cap * b->alnStride);
+        }
+        dOcc = b->occ32.p, dAln = b->alnRec.p, dOps = b->alnOps.p;
+    }
+    hipLaunchKernelGGL(k_mvs_occ32, dim3(gridFor(nReads)), dim3(256), 0, s, b->out.p, b->readOff.p, nReads, dOcc, b->occRead.p);
+    uint32_t flagBefore = 0;
+    HIPCHK(hipMemcpyAsync(&flagBefore, b->cnt.p + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    const int rc = cmb::moveCigarsOnText(b->ix->textIndex, s, c.dOffs, b->G.p, b->gw, nReads, b->maxLen, b->k, b->metric == CMB_METRIC_EDIT ? 0 : 1,
+                                         dOcc, b->occRead.p, nOut, dAln, dOps, b->alnStride, b->cnt.p + 3);
+    if (rc != CMB_OK) return rc;
+    const size_t base = b->hAlnRec.size();
+    b->hAlnRec.resize(base + nOut);
+    b->hAlnOps.resize((base + nOut) * b->alnStride);
+    HIPCHK(hipMemcpyAsync(b->hAlnRec.data() + base, dAln, nOut * sizeof(AlnRec), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(b->hAlnOps.data() + base * b->alnStride, dOps, nOut * b->alnStride * sizeof(uint16_t), hipMemcpyDeviceToHost, s));
+    uint32_t flagAfter = 0;
+    HIPCHK(hipMemcpyAsync(&flagAfter, b->cnt.p + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    c.tm.end("k_cigar");
+    if ((flagAfter & ~flagBefore) & FLAG_CAPACITY)
+        return failWith(CMB_ERR_INTERNAL, "a CIGAR traceback left the band or an occurrence is not an alignment within its distance");
+    return CMB_OK;
+}
+
+// with the lists kept: the slice's group offsets behind those of the slices before it, rebased to the chunk
+static void appendKeptOffsets(SliceCtx& c) {
+    cmb_move_batch* b = c.b;
+    if (!b->keepLists) return;
+    const uint32_t gs = b->keepStride;
+    const uint64_t* src = !c.totalPos ? nullptr : gs == 2 ? b->rsOff.p : b->readOff.p;
+    hipLaunchKernelGGL(k_mvs_keep_offsets, dim3(gridFor((uint64_t)gs * c.nReads + 1)), dim3(256), 0, c.s, src, (uint64_t)gs * c.nReads, b->keepN,
+                       b->keepOff.p + (size_t)gs * c.lo);
+    HIPCHK(hipGetLastError());
+    b->keepN += c.nOut;
+}
+
+// ---- the slice's results: its records travel to the host on the copy stream while the next slice is matched; the offsets per read
+// rebased to the chunk, the bad-chain check, and the slice's counters added to the batch's
+static int downloadSlice(SliceCtx& c) {
+    cmb_move_batch* b = c.b;
+    hipStream_t s = c.s;
+    const uint32_t lo = c.lo, nReads = c.nReads;
+    const uint64_t totalPos = c.totalPos, nOut = c.nOut;
+    uint32_t hb = 0;
+    HIPCHK(hipMemcpyAsync(&hb, b->bad.p, sizeof(hb), hipMemcpyDeviceToHost, s));
+    unsigned long long hc64[CMB_CNT_MAX];
+    HIPCHK(hipMemcpyAsync(hc64, b->counters.p, sizeof(hc64), hipMemcpyDeviceToHost, s));
+    static_assert(sizeof(cmb_move_occ) == sizeof(MoveOccOut), "cmb_move_occ layout");
+    const size_t occBase = b->occs.size();
+    if (occBase + nOut > b->occs.cap) b->waitForCopies(); // (the page-locked vector moves when it grows)
+    b->occs.resize(occBase + nOut);
+    std::vector<uint64_t> sliceOffs((size_t)nReads + 1, 0);
+    if (nOut) { // on the copy stream, behind everything this slice has queued: the next slice starts while the records travel
+        HIPCHK(hipEventRecord(b->outReady, s));
+        HIPCHK(hipStreamWaitEvent(b->copyStream, b->outReady, 0));
+        HIPCHK(hipMemcpyAsync(b->occs.data() + occBase, b->out.p, nOut * sizeof(MoveOccOut), hipMemcpyDeviceToHost, b->copyStream));
+        HIPCHK(hipEventRecord(b->copyDone, b->copyStream));
+        b->copyPending = true;
+    }
+    if (totalPos) HIPCHK(hipMemcpyAsync(sliceOffs.data(), b->readOff.p, ((size_t)nReads + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (uint32_t i = 0; i <= nReads; i++) b->occOffs[(size_t)lo + i] = occBase + sliceOffs[i];
+    if (totalPos && hb)
+        return failWith(CMB_ERR_INTERNAL, std::to_string(hb) + " occurrences whose phi chains do not have the width of their range, or whose "
+                                                               "fields do not fit the filter keys");
+    for (int i = 0; i < CMB_CNT_MAX; i++) b->cnts[i] += hc64[i];
+    b->cnts[CMB_CNT_TOTAL_REPORTED] += totalPos + c.nNaiveKept; // (the naive path's survivors are reported again as text occurrences of the read)
+    b->cnts[CMB_CNT_LOCATED_ROWS] += totalPos;
+    return CMB_OK;
+}
+
 static int runSlice(cmb_move_batch* b, uint32_t lo, uint32_t hi) {
     try {
         cmb_move_index* ix = b->ix;
         HIPCHK(hipSetDevice(ix->device));
-        hipStream_t s = b->stream;
-        const uint32_t nReads = hi - lo, tasksRS = 2 * nReads;
-        const uint64_t* dOffs = b->offs.p + lo; // (the kernels number the slice's reads from 0; offsets stay absolute)
-        if (b->k == 0) { // exactMatchesOutput of both strands (searchstrategy.cpp:499-510): the k = 0 path of this backend
-            uint64_t nOcc = 0, c2[2] = {0, 0};
-            std::vector<cmb_move_occ> tmp((size_t)nReads * 8 + 1024);
-            int rc = cmb_move_match_exact(ix, (const char*)b->hostReads.data(), b->hostOffs.data(), nReads, tmp.data(), tmp.size(), b->occOffs.data(), &nOcc, c2);
-            if (rc == CMB_ERR_OVERFLOW) { // (nOcc: the number needed; nothing of that size has been allocated yet)
-                if (nOcc >= (1ull << 31)) return failWith(CMB_ERR_UNSUPPORTED, "2^31 and more text positions in one b-move batch");
-                tmp.resize(nOcc);
-                rc = cmb_move_match_exact(ix, (const char*)b->hostReads.data(), b->hostOffs.data(), nReads, tmp.data(), tmp.size(), b->occOffs.data(), &nOcc, c2);
-            }
-            if (rc != CMB_OK) return rc;
-            tmp.resize(nOcc);
-            b->occs.assign(tmp);
-            if (b->wantAln) { // an exact match aligns as <length>M; its sequence by position (findSeqName, indexinterface.cpp:799-832)
-                const std::vector<uint32_t>& sp = cmb::seqStartsOfIndex(ix->textIndex);
-                b->hAlnRec.resize(nOcc);
-                b->hAlnOps.assign((size_t)nOcc * b->alnStride, 0);
-                for (uint64_t i = 0; i < nOcc; i++) {
-                    const cmb_move_occ& o = b->occs[i];
-                    if (sp.size() < 2) { // one sequence
-                        b->hAlnRec[i] = AlnRec{0u, (uint32_t)o.begin, 1u, 0u};
-                    } else {
-                        const uint32_t id = (uint32_t)(std::upper_bound(sp.begin(), sp.end() - 1, (uint32_t)o.begin) - sp.begin()) - 1;
-                        b->hAlnRec[i] = AlnRec{id, (uint32_t)o.begin - sp[id], 1u, o.end > sp[id + 1] ? 1u : 0u};
-                    }
-                    b->hAlnOps[i * b->alnStride] = (uint16_t)(((o.end - o.begin) << 2) | 0u);
-                }
-                if (b->keepLists) { // the same records into the kept lists (the consumers read a read's first and last group offset only)
-                    b->keepReserve(nOcc, s);
-                    std::vector<uint4> o32(nOcc);
-                    for (uint64_t i = 0; i < nOcc; i++) o32[i] = make_uint4((uint32_t)b->occs[i].begin, (uint32_t)b->occs[i].end, b->occs[i].distance, b->occs[i].strand);
-                    const uint32_t gs = b->keepStride;
-                    std::vector<uint64_t> go((size_t)gs * nReads + 1);
-                    for (uint32_t r = 0; r < nReads; r++)
-                        for (uint32_t g = 0; g < gs; g++) go[(size_t)gs * r + g] = b->occOffs[r];
-                    go[(size_t)gs * nReads] = b->occOffs[nReads];
-                    if (nOcc) {
-                        HIPCHK(hipMemcpyAsync(b->keepOcc.p, o32.data(), nOcc * sizeof(uint4), hipMemcpyHostToDevice, s));
-                        HIPCHK(hipMemcpyAsync(b->keepAln.p, b->hAlnRec.data(), nOcc * sizeof(AlnRec), hipMemcpyHostToDevice, s));
-                        HIPCHK(hipMemcpyAsync(b->keepOps.p, b->hAlnOps.data(), nOcc * b->alnStride * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-                    }
-                    HIPCHK(hipMemcpyAsync(b->keepOff.p, go.data(), go.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-                    HIPCHK(hipStreamSynchronize(s)); // (the host vectors go out of scope)
-                    b->keepN = nOcc;
-                }
-            }
-            b->cnts[CMB_CNT_NODE] = c2[0];
-            b->cnts[CMB_CNT_EXPANSIONS] = g_exactExpansions;
-            b->cnts[CMB_CNT_TOTAL_REPORTED] = c2[1];
-            b->cnts[CMB_CNT_LOCATED_ROWS] = c2[1];
-            float ms[3];
-            (void)cmb_move_last_timings(ms, 3);
-            b->times.push_back({"k_move_exact", ms[0]});
-            b->times.push_back({"locate", ms[1] + ms[2]});
-            return CMB_OK;
-        }
-        Timer tm(s, b->times);
-        Queues q{};
-        q.cnt = b->cnt.p;
-        q.counters = b->counters.p;
-        MvSearchIndex sx{ix->d, ix->kmer.p, ix->kmerSize};
+        if (b->k == 0) return runExactSlice(b, hi - lo);
+        Timer tm(b->stream, b->times);
+        SliceCtx c{b, b->stream, tm, lo, hi - lo, b->offs.p + lo};
+        c.q.cnt = b->cnt.p;
+        c.q.counters = b->counters.p;
         if (ix->kmerSize != b->kmerSize) {
             const int rc = ensureKmerTable(ix, b->kmerSize);
             if (rc != CMB_OK) return rc;
-            sx.kmer = ix->kmer.p;
-            sx.kmerSize = ix->kmerSize;
         }
-        uint32_t hcnt[8];
-        // (both read per run, not per process: tests set them between runs)
-        const bool verbose = getenv("CMB_VERBOSE") != nullptr, smallPools = getenv("CMB_TEST_SMALL_POOLS") != nullptr;
-        const bool edit = b->metric == CMB_METRIC_EDIT;
-        const bool geoX = edit && frontierGeoOf(b) == FrontierGeo::X; // (11 ... 13 errors: the in-index matrix with 16-row blocks)
-        if ((b->wide ? b->partsW.n : b->parts.n) < (size_t)2 * nReads) { // per-read scratch of a slice
-            b->seq.alloc((size_t)2 * nReads * b->maxLen);
-            b->G.alloc((size_t)nReads * 8 * b->gw);
-            if (b->wide) b->partsW.alloc((size_t)2 * nReads);
-            else b->parts.alloc((size_t)2 * nReads);
-            b->psel.alloc((size_t)2 * nReads);
-            b->exr.alloc((size_t)2 * nReads * b->sNumParts);
-            b->tasks.alloc((size_t)2 * nReads * b->sMaxSearches + 64);
-        }
-        // ---- read preparation
-        tm.begin();
-        HIPCHK(hipMemsetAsync(b->G.p, 0, (size_t)nReads * 8 * b->gw * sizeof(uint32_t), s));
-        hipLaunchKernelGGL(k_mvs_prep, dim3(gridFor((uint64_t)nReads * b->gw)), dim3(256), 0, s, b->reads.p, dOffs, nReads, b->maxLen, b->gw, b->seq.p, b->G.p);
-        tm.end("k_prep");
-        const uint32_t P = b->sNumParts, maxSearches = b->sMaxSearches;
-        uint32_t nFm = 0;
-        bool hasNaive = false; // reads of the slice are matched by naive backtracking (k_mvs_parts marked them in psel)
+        c.sx = MvSearchIndex{ix->d, ix->kmer.p, ix->kmerSize};
+        c.verbose = getenv("CMB_VERBOSE") != nullptr, c.smallPools = getenv("CMB_TEST_SMALL_POOLS") != nullptr;
+        c.edit = b->metric == CMB_METRIC_EDIT;
+        c.geoX = c.edit && frontierGeoOf(b) == FrontierGeo::X;
+
+        sizeSliceScratch(c);
+        runPrep(c);
+        // ---- prologue + search (run again with larger pools where they overflow: nothing is truncated)
+        int rc = CMB_OK;
         for (int attempt = 0;; attempt++) {
             if (attempt >= 60) return failWith(CMB_ERR_INTERNAL, "work queues keep overflowing");
-            HIPCHK(hipMemsetAsync(b->cnt.p, 0, 8 * sizeof(uint32_t), s));
-            HIPCHK(hipMemsetAsync(b->counters.p, 0, CMB_CNT_MAX * sizeof(unsigned long long), s));
-            if (!b->fm.n) b->fm.alloc((size_t)nReads * 16 + 4096);
-            q.fmCap = cap32(b->fm.n);
-            // ---- prologue
-            tm.begin();
-            {
-                const unsigned grid = capBlocks((unsigned)std::min<uint64_t>(((uint64_t)tasksRS + 63) / 64, 256 * 64));
-                const uint64_t nWork = (uint64_t)tasksRS * maxSearches;
-                const unsigned gridE = capBlocks((unsigned)std::min<uint64_t>((nWork + 63) / 64, 256 * 64));
-                gridLine(verbose, "k_mvs_parts", tasksRS, 64ull * grid);
-                gridLine(verbose, "k_mvs_exact", nWork, 64ull * gridE);
-                const size_t exLdsBytes = (size_t)P * 3 * 64 * sizeof(uint4);
-                withTables(b, [&](auto mp) {
-                    constexpr int MP = decltype(mp)::value;
-                    auto kp = withInt<3>((int)b->sPartition, [](auto part) { return k_mvs_parts<part(), MP>; });
-                    hipLaunchKernelGGL(kp, dim3(grid), dim3(64), exLdsBytes, s, sx, stratOf<MP>(b), nReads, b->maxLen, b->seq.p, dOffs, partsOf<MP>(b), b->exr.p,
-                                       b->psel.p, q);
-                    hipLaunchKernelGGL(k_mvs_exact<MP>, dim3(gridE), dim3(64), 0, s, sx, stratOf<MP>(b), nReads, b->maxLen, maxSearches, b->seq.p, partsOf<MP>(b),
-                                       b->exr.p, b->psel.p, b->tasks.p, cap32(b->tasks.n), q);
-                });
-            }
-            tm.end("k_partition");
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            hasNaive = (hcnt[3] & FLAG_UNSUPPORTED_READ) != 0;
-            if (hcnt[3] & FLAG_SEED_OVERLAP)
-                return failWith(CMB_ERR_INVALID, "dynamic partitioning: the seeds of a read overlap — the k-mer size is too large for the seeding "
-                                                 "positions of this search strategy at this read length");
-            if (hcnt[3] & FLAG_DFS_OVERFLOW) return failWith(CMB_ERR_INTERNAL, "task queue too small");
-            if (hasNaive) {
-                // ---- reads not longer than the number of parts / one-part strategies: naive backtracking (k_mvs_naive)
-                tm.begin();
-                const uint32_t maxPassN = b->maxLen + 2 * b->k + 4;
-                constexpr uint32_t PU = MvTraits::PAIR_U4;
-                if (!b->nvQCap) b->nvQCap = smallPools ? 64 : 16384;
-                for (int j = 0; j < 2; j++)
-                    if (b->nvQ[j].n < (PU + 2) * b->nvQCap) b->nvQ[j].alloc((PU + 2) * b->nvQCap);
-                const size_t cntWords = (size_t)maxPassN + 2;
-                if (b->nvCnt.n < cntWords) b->nvCnt.alloc(cntWords);
-                HIPCHK(hipMemsetAsync(b->nvCnt.p, 0, cntWords * sizeof(uint32_t), s));
-                MvHbfsBufs N{};
-                N.Q[0] = b->nvQ[0].p;
-                N.Q[1] = b->nvQ[1].p;
-                N.qCap = cap32(b->nvQ[0].n / (PU + 2));
-                N.nq = b->nvCnt.p;
-                N.blockCnt = nullptr;
-                N.fmX = b->fm.p;
-                // (the matrix of 11 ... 13 errors is the edit distance's alone)
-                auto naiveKernel = [&](bool start) {
-                    return withBools([](auto e, auto st, auto x) { return k_mvs_naive<e(), st(), e() && x()>; }, edit, start, geoX);
-                };
-                auto kNaiveStart = naiveKernel(true), kNaivePass = naiveKernel(false);
-                const uint32_t nvStart = capBlocks((tasksRS + 255) / 256), nvGrid = capBlocks(BFS_GRID);
-                gridLine(verbose, "k_mvs_naive_start", tasksRS, 256ull * nvStart);
-                hipLaunchKernelGGL(kNaiveStart, dim3(nvStart), dim3(256), 0, s, ix->d, N, 0u,
-                                   (const uint8_t*)b->psel.p, tasksRS, dOffs, b->gw, b->G.p, b->seq.p, b->maxLen, b->k, q);
-                std::vector<uint32_t> hc(cntWords);
-                uint32_t pass = 0, peakQ = 0;
-                bool drained = false;
-                while (!drained && pass < maxPassN) {
-                    const uint32_t upTo = std::min(pass + 16u, maxPassN);
-                    for (; pass < upTo; pass++)
-                        hipLaunchKernelGGL(kNaivePass, dim3(nvGrid), dim3(256), 0, s, ix->d, N, pass,
-                                           (const uint8_t*)b->psel.p, tasksRS, dOffs, b->gw, b->G.p, b->seq.p, b->maxLen, b->k, q);
-                    HIPCHK(hipMemcpyAsync(hc.data(), b->nvCnt.p, cntWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                    HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
-                    HIPCHK(hipStreamSynchronize(s));
-                    if (hcnt[3] & MVS_NAIVE_STOP) break;
-                    drained = hc[pass] == 0;
-                }
-                for (uint32_t p2 = 0; p2 <= pass && p2 < cntWords; p2++) peakQ = std::max(peakQ, hc[p2]);
-                gridLine(verbose, "k_mvs_naive_pass", peakQ, 256ull * nvGrid); // (the largest frontier of a pass)
-                tm.end("k_naive");
-                HIPCHK(hipGetLastError());
-                if (hcnt[3] & MVS_NAIVE_STOP) {
-                    // (the search stopped at the overflow: it has only counted what it needed up to there)
-                    if (hcnt[3] & FLAG_NAIVE_Q) b->nvQCap = std::max<size_t>(4 * b->nvQCap, (size_t)peakQ + peakQ / 4);
-                    if (hcnt[3] & FLAG_FMOCC_OVERFLOW) b->fm.alloc(std::max<size_t>(8 * b->fm.n, (size_t)hcnt[1] + hcnt[1] / 4 + 1024));
-                    continue;
-                }
-                if (!drained) return failWith(CMB_ERR_INTERNAL, "the naive search did not finish within its pass bound");
-            }
-            const uint32_t nTasks = hcnt[5];
-            if (nTasks && b->metric != CMB_METRIC_EDIT) {
-                // ---- Hamming distance: the frontier without a matrix (k_mvs_hbfs), one row per pass
-                tm.begin();
-                const uint32_t maxPass = b->maxLen + 2 * (b->wide ? MAXP_WIDE : MAXP) + 16;
-                constexpr uint32_t PU = MvTraits::PAIR_U4;
-                if (!b->qCap) b->qCap = (smallPools ? 0 : (size_t)nReads * 8) + 1024;
-                b->qCap = std::max<size_t>(b->qCap, (size_t)nTasks + 1024);
-                for (int j = 0; j < 2; j++)
-                    if (b->Q[j].n < (PU + 1) * b->qCap) b->Q[j].alloc((PU + 1) * b->qCap);
-                const size_t cntWords = (size_t)maxPass + 2;
-                if (b->bfsCnt.n < cntWords) b->bfsCnt.alloc(cntWords);
-                if (b->blockCnt.n < (size_t)BFS_GRID * 4) b->blockCnt.alloc((size_t)BFS_GRID * 4);
-                HIPCHK(hipMemsetAsync(b->bfsCnt.p, 0, cntWords * sizeof(uint32_t), s));
-                HIPCHK(hipMemsetAsync(b->blockCnt.p, 0, (size_t)BFS_GRID * 4 * sizeof(unsigned long long), s));
-                MvHbfsBufs H{};
-                H.Q[0] = b->Q[0].p;
-                H.Q[1] = b->Q[1].p;
-                H.qCap = cap32(b->Q[0].n / (PU + 1));
-                H.nq = b->bfsCnt.p;
-                H.blockCnt = b->blockCnt.p;
-                H.fmX = b->fm.p;
-                const uint32_t startGrid = capBlocks(std::min<uint32_t>((nTasks + 255) / 256, BFS_GRID)), passGrid = capBlocks(BFS_GRID);
-                gridLine(verbose, "k_mvs_hbfs_start", nTasks, 256ull * startGrid);
-                withTables(b, [&](auto mp) {
-                    constexpr int MP = decltype(mp)::value;
-                    hipLaunchKernelGGL((k_mvs_hbfs<true, MP>), dim3(startGrid), dim3(256), 0, s, ix->d, stratOf<MP>(b), H, 0u, b->tasks.p, nTasks, b->maxLen,
-                                       b->seq.p, partsOf<MP>(b), q);
-                });
-                std::vector<uint32_t> hc(cntWords);
-                uint32_t pass = 0, peakQ = 0;
-                bool drained = false;
-                while (!drained && pass < maxPass) {
-                    const uint32_t upTo = std::min(pass + 16u, maxPass);
-                    for (; pass < upTo; pass++)
-                        withTables(b, [&](auto mp) {
-                            constexpr int MP = decltype(mp)::value;
-                            hipLaunchKernelGGL((k_mvs_hbfs<false, MP>), dim3(passGrid), dim3(256), 0, s, ix->d, stratOf<MP>(b), H, pass, (const MvTask*)nullptr,
-                                               0u, b->maxLen, b->seq.p, partsOf<MP>(b), q);
-                        });
-                    HIPCHK(hipMemcpyAsync(hc.data(), b->bfsCnt.p, cntWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                    HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
-                    HIPCHK(hipStreamSynchronize(s));
-                    if (hcnt[3] & BFS_STOP) break;
-                    drained = hc[pass] == 0;
-                }
-                for (uint32_t p2 = 0; p2 <= pass && p2 < cntWords; p2++) peakQ = std::max(peakQ, hc[p2]);
-                gridLine(verbose, "k_mvs_hbfs_pass", peakQ, 256ull * passGrid); // (the largest frontier of a pass)
-                MvBufs Bf{};
-                Bf.blockCnt = b->blockCnt.p;
-                hipLaunchKernelGGL(k_mvs_finish, dim3(1), dim3(256), 0, s, Bf, q);
-                tm.end("k_dfs");
-                HIPCHK(hipGetLastError());
-                if (hcnt[3] & (FLAG_BFS_Q | FLAG_FMOCC_OVERFLOW)) {
-                    if (hcnt[3] & FLAG_BFS_Q) b->qCap = std::max<size_t>(2 * b->qCap, (size_t)peakQ + peakQ / 4);
-                    if (hcnt[3] & FLAG_FMOCC_OVERFLOW) b->fm.alloc(std::max<size_t>(2 * b->fm.n, (size_t)hcnt[1] + hcnt[1] / 4 + 1024));
-                    continue;
-                }
-                if (!drained) return failWith(CMB_ERR_INTERNAL, "frontier search did not finish within its pass bound");
-            } else if (nTasks) {
-                tm.begin();
-                const uint32_t maxPass = 2 * b->maxLen + 8 * (b->wide ? MAXP_WIDE : MAXP) + 64;
-                const uint32_t pkU4 = b->wide ? GeoW::PK_U4 : GeoN::PK_U4; // planes of a node's final-column pack / uint4 of an event's
-                if (!b->qCap) {
-                    const size_t slack = smallPools ? 64 : 65536;
-                    const size_t per = smallPools ? 0 : 1;
-                    b->qCap = per * (size_t)nReads * 4 + slack;
-                    b->evCap = per * (size_t)nReads + slack;
-                    b->fCap = per * (size_t)nReads * 16 + slack;
-                    b->cCap = per * (size_t)nReads * 4 + slack;
-                    b->aCap = per * (size_t)nReads * 32 + slack;
-                }
-                b->qCap = std::max<size_t>(b->qCap, (size_t)nTasks + 1024);
-                constexpr uint32_t PU = MvTraits::PAIR_U4;
-                for (int j = 0; j < 2; j++) {
-                    if (b->Q[j].n < (PU + 2 + pkU4) * b->qCap) b->Q[j].alloc((PU + 2 + pkU4) * b->qCap);
-                    if (b->Ev[j].n < (1 + pkU4) * b->evCap) b->Ev[j].alloc((1 + pkU4) * b->evCap);
-                }
-                if (b->F.n < (PU + 1) * b->fCap) b->F.alloc((PU + 1) * b->fCap);
-                const uint32_t ctxU4 = geoX ? CTX_U4_X : ctxU4For(b->maxLen);
-                if (b->C.n < (size_t)ctxU4 * b->cCap) b->C.alloc((size_t)ctxU4 * b->cCap);
-                if (b->A.n < b->aCap) b->A.alloc(b->aCap);
-                const size_t cntWords = 2 * ((size_t)maxPass + 2) + 4;
-                if (b->bfsCnt.n < cntWords) b->bfsCnt.alloc(cntWords);
-                if (b->blockCnt.n < (size_t)BFS_GRID * 4) b->blockCnt.alloc((size_t)BFS_GRID * 4);
-                HIPCHK(hipMemsetAsync(b->bfsCnt.p, 0, cntWords * sizeof(uint32_t), s));
-                HIPCHK(hipMemsetAsync(b->blockCnt.p, 0, (size_t)BFS_GRID * 4 * sizeof(unsigned long long), s));
-                MvBufs B{};
-                for (int j = 0; j < 2; j++) {
-                    B.Q[j] = b->Q[j].p;
-                    B.Ev[j] = b->Ev[j].p;
-                }
-                B.F = b->F.p;
-                B.C = b->C.p;
-                B.A = b->A.p;
-                B.qCap = cap32(b->Q[0].n / (PU + 2 + pkU4));
-                B.evCap = cap32(b->Ev[0].n / (1 + pkU4));
-                B.fCap = cap32(b->F.n / (PU + 1));
-                B.cCap = cap32(b->C.n / ctxU4);
-                B.ctxU4 = ctxU4;
-                B.ctxMblk = geoX ? CTX_MBLK_X : ctxMblkFor(b->maxLen);
-                B.aCap = cap32(b->A.n);
-                // text and run counts below 2^32 (the reference's default build of length_t): the expanding blocks work on 32-bit positions with
-                // the children in slots (mvExpandSlots; CMB_MOVE_POS64=1: the general 40-bit path)
-                const bool smallPos = !b->wide && ix->d.n < 0xFFFFFFF0ull && ix->d.fwd.runs < 0xFFFFFFF0ull && ix->d.rev.runs < 0xFFFFFFF0ull && !getenv("CMB_MOVE_POS64");
-                B.chain = getenv("CMB_MVS_CHAIN") ? (uint32_t)std::max(1, atoi(getenv("CMB_MVS_CHAIN"))) : (smallPos ? MVS_CHAIN_SMALL : MVS_CHAIN);
-                B.gridX = capBlocks(std::min<uint32_t>(BFS_GRID, envBlocks("CMB_MVS_GRID", b->wide ? MVS_GRID_X_WIDE : smallPos ? MVS_GRID_X_SMALL : MVS_GRID_X)));
-                B.gridEv = capBlocks(BFS_GRID_EV);
-                B.nq = b->bfsCnt.p;
-                B.ne = b->bfsCnt.p + (maxPass + 2);
-                B.pool = b->bfsCnt.p + 2 * (maxPass + 2);
-                B.blockCnt = b->blockCnt.p;
-                B.fmX = b->fm.p;
-                B.rowSteps = nullptr;
-                B.narrowWv = getenv("CMB_TEST_NARROW_WV") ? (uint32_t)std::max(0, atoi(getenv("CMB_TEST_NARROW_WV"))) : 0xFFFFu;
-                const FrontierGeo geo = frontierGeoOf(b);
-                const dim3 gStart(capBlocks(std::min<uint32_t>((nTasks + 255) / 256, BFS_GRID)));
-                gridLine(verbose, "k_mvs_start", nTasks, 256ull * gStart.x);
-                withGeo(geo, [&](auto g) {
-                    using Geo = typename decltype(g)::type;
-                    hipLaunchKernelGGL(k_mvs_start<Geo>, gStart, dim3(256), 0, s, stratOf<Geo::MP>(b), B, b->tasks.p, nTasks, dOffs, b->gw, b->G.p,
-                                       partsOf<Geo::MP>(b), q);
-                });
-                // (the instance of a pass is chosen here, once per attempt: the loop below calls through a pointer)
-                const auto mvsPass = withGeo(geo, [&](auto g) {
-                    return withBools([](auto small) { return &launchMvsPass<typename decltype(g)::type, decltype(small)::value>; }, smallPos);
-                });
-                std::vector<uint32_t> hc(cntWords);
-                uint32_t pass = 0, peakQ = 0, peakEv = 0;
-                bool drained = false;
-                while (!drained && pass < maxPass) {
-                    const uint32_t upTo = std::min(pass + 16u, maxPass);
-                    for (; pass < upTo; pass++) mvsPass(b, B, pass, dOffs, q);
-                    HIPCHK(hipMemcpyAsync(hc.data(), b->bfsCnt.p, cntWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                    HIPCHK(hipMemcpyAsync(hcnt, b->cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, s));
-                    HIPCHK(hipStreamSynchronize(s));
-                    if (hcnt[3] & BFS_STOP) break;
-                    drained = hc[pass] == 0 && hc[maxPass + 2 + pass] == 0;
-                }
-                for (uint32_t p2 = 0; p2 <= pass && p2 < maxPass + 2; p2++) {
-                    peakQ = std::max(peakQ, hc[p2]);
-                    peakEv = std::max(peakEv, hc[maxPass + 2 + p2]);
-                }
-                const uint32_t* pool = hc.data() + 2 * (maxPass + 2);
-                gridLine(verbose, "k_mvs_pass", peakQ, 256ull * B.gridX); // (the largest frontier and the most events of a pass)
-                gridLine(verbose, "k_mvs_pass_events", peakEv, 256ull * B.gridEv);
-                if (verbose)
-                    fprintf(stderr, "[mvs] %u tasks, %u passes, peak frontier %u, peak events %u, F %u, contexts %u, arena %u\n", nTasks, pass, peakQ, peakEv,
-                            pool[0], pool[1], pool[2]);
-                hipLaunchKernelGGL(k_mvs_finish, dim3(1), dim3(256), 0, s, B, q);
-                tm.end("k_dfs");
-                HIPCHK(hipGetLastError());
-                if (hcnt[3] & FLAG_NARROW_MATRIX) { // (a first column wider than the small matrix holds: once more on the reference's words)
-                    b->noSmallMatrix = true;
-                    continue;
-                }
-                if (hcnt[3] & FLAG_CAPACITY) return failWith(CMB_ERR_INTERNAL, "device search capacity exceeded (band width / descendants)");
-                if (hcnt[3] & (FLAG_BFS_Q | FLAG_BFS_EV | FLAG_BFS_F | FLAG_BFS_CTX | FLAG_BFS_ARENA | FLAG_FMOCC_OVERFLOW)) {
-                    if (hcnt[3] & FLAG_BFS_Q) b->qCap = std::max<size_t>(2 * b->qCap, (size_t)peakQ + peakQ / 4);
-                    if (hcnt[3] & FLAG_BFS_EV) b->evCap = std::max<size_t>(2 * b->evCap, (size_t)peakEv + peakEv / 4);
-                    if (hcnt[3] & FLAG_BFS_F) b->fCap = std::max<size_t>(2 * b->fCap, (size_t)pool[0] + pool[0] / 4);
-                    if (hcnt[3] & FLAG_BFS_CTX) b->cCap = std::max<size_t>(2 * b->cCap, (size_t)pool[1] + pool[1] / 4);
-                    if (hcnt[3] & FLAG_BFS_ARENA) b->aCap = std::max<size_t>(2 * b->aCap, (size_t)pool[2] + pool[2] / 4);
-                    if (hcnt[3] & FLAG_FMOCC_OVERFLOW) b->fm.alloc(std::max<size_t>(2 * b->fm.n, (size_t)hcnt[1] + hcnt[1] / 4 + 1024));
-                    continue;
-                }
-                if (!drained) return failWith(CMB_ERR_INTERNAL, "frontier search did not finish within its pass bound");
-            }
-            nFm = hcnt[1];
-            break;
+            bool again = false;
+            if ((rc = searchAttempt(c, again)) != CMB_OK) return rc;
+            if (!again) break;
         }
-        // ---- in-index occurrences: de-duplicate, locate, sort, filter
-        uint64_t totalPos = 0;
-        uint32_t nUniq = 0;
-        tm.begin();
-        if (nFm) {
-            if (b->keysA.n < nFm) {
-                const size_t c = (size_t)nFm + nFm / 4 + 256;
-                b->keysA.alloc(c), b->keysB.alloc(c), b->fmIdxA.alloc(c), b->fmIdxB.alloc(c), b->keep.alloc(c + 1), b->slot.alloc(c + 1), b->widths.alloc(c + 1);
-            }
-            hipLaunchKernelGGL(k_mvs_fm_keys, dim3(gridFor(nFm)), dim3(256), 0, s, b->fm.p, nFm, b->keysA.p, b->fmIdxA.p);
-            MV_COUNT_LIMIT((uint64_t)nFm + 1, "in-index occurrences of one slice"); // (2^31 records of 96 bytes would not fit the HBM)
-            sortPairs(b->sortTmp, b->keysA.p, b->keysB.p, b->fmIdxA.p, b->fmIdxB.p, nFm, 0, 64, s);
-            hipLaunchKernelGGL(k_mvs_fm_unique, dim3(gridFor(nFm)), dim3(256), 0, s, b->fm.p, b->fmIdxB.p, nFm, b->keep.p, b->widths.p);
-            HIPCHK(hipMemsetAsync(b->keep.p + nFm, 0, sizeof(uint32_t), s));
-            scanExclusive(b->sortTmp, b->keep.p, b->slot.p, (size_t)nFm + 1, s);
-            HIPCHK(hipMemcpyAsync(&nUniq, b->slot.p + nFm, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            if (nUniq) {
-                if (b->locRanges.n < nUniq) {
-                    const size_t c = (size_t)nUniq + nUniq / 4 + 256;
-                    b->locRanges.alloc(c), b->locMeta.alloc(c), b->locWidths.alloc(c + 1), b->locOff.alloc(c + 1);
-                }
-                hipLaunchKernelGGL(k_mvs_fm_compact, dim3(gridFor(nFm)), dim3(256), 0, s, b->fm.p, b->fmIdxB.p, b->keep.p, b->slot.p, nFm, b->locRanges.p,
-                                   b->locMeta.p, b->locWidths.p);
-                HIPCHK(hipMemsetAsync(b->locWidths.p + nUniq, 0, sizeof(uint64_t), s));
-                MV_COUNT_LIMIT((uint64_t)nUniq + 1, "distinct in-index occurrences of one slice"); // (nUniq <= nFm)
-                scanExclusive(b->sortTmp, b->locWidths.p, b->locOff.p, (size_t)nUniq + 1, s);
-                HIPCHK(hipMemcpyAsync(&totalPos, b->locOff.p + nUniq, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-                HIPCHK(hipStreamSynchronize(s));
-            }
-        }
-        tm.end("fm_unique");
-        if (totalPos >= (1ull << 31)) return failWith(CMB_ERR_UNSUPPORTED, "2^31 and more text positions in one b-move batch");
-        tm.begin();
-        if (totalPos) {
-            if (b->positions.n < totalPos) {
-                const size_t c = totalPos + totalPos / 4 + 256;
-                b->positions.alloc(c), b->keysA.alloc(std::max(c, b->keysA.n)), b->keysB.alloc(std::max(c, b->keysB.n)), b->vals.alloc(c), b->valsB.alloc(c);
-            }
-            if (b->keysA.n < totalPos) b->keysA.alloc(totalPos + 256), b->keysB.alloc(totalPos + 256);
-            HIPCHK(hipMemsetAsync(b->bad.p, 0, sizeof(uint32_t), s));
-            hipLaunchKernelGGL(k_move_locate, dim3(gridFor(nUniq)), dim3(256), 0, s, ix->d, b->locRanges.p, (uint64_t)nUniq, b->locOff.p, (uint64_t)0,
-                               b->positions.p, b->bad.p, true);
-        }
-        tm.end("locate");
-        tm.begin();
-        if (b->readCnt.n < (size_t)2 * nReads + 1) b->readCnt.alloc((size_t)2 * nReads + 1), b->readOff.alloc((size_t)2 * nReads + 1);
-        uint64_t nOut = 0, nNaiveKept = 0;
-        const uint32_t window = b->metric == CMB_METRIC_EDIT ? b->k : 0u;
-        const uint32_t uniqueOnly = b->metric == CMB_METRIC_EDIT ? 0u : 1u; // (getTextOccHamming, indexinterface.cpp:1331-1371: no redundancy filter)
-        auto sortAndFilter = [&](uint64_t nKeys, uint32_t nGroups, DevBuf<MoveOccOut>& dst, uint64_t& kept) -> int {
-            // (nKeys < 2^31: the refusals of 2^31 text positions per slice; nGroups <= 2^24: 2^23 reads per batch)
-            MV_COUNT_LIMIT(nKeys, "text occurrences of one slice");
-            MV_COUNT_LIMIT((uint64_t)nGroups + 1, "filter groups of one slice");
-            sortPairs(b->sortTmp, b->keysA.p, b->keysB.p, b->vals.p, b->valsB.p, (uint32_t)nKeys, 0, 64, s);
-            HIPCHK(hipMemsetAsync(b->readCnt.p, 0, ((size_t)nGroups + 1) * sizeof(uint64_t), s));
-            hipLaunchKernelGGL(k_mvs_filter<false>, dim3(gridFor(nGroups)), dim3(256), 0, s, b->keysB.p, b->valsB.p, nKeys, nGroups, window, b->readCnt.p,
-                               (const uint64_t*)nullptr, (MoveOccOut*)nullptr, uniqueOnly);
-            scanExclusive(b->sortTmp, b->readCnt.p, b->readOff.p, (size_t)nGroups + 1, s);
-            HIPCHK(hipMemcpyAsync(&kept, b->readOff.p + nGroups, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            if (dst.n < kept) dst.alloc(kept + kept / 4 + 256);
-            if (kept)
-                hipLaunchKernelGGL(k_mvs_filter<true>, dim3(gridFor(nGroups)), dim3(256), 0, s, b->keysB.p, b->valsB.p, nKeys, nGroups, window, b->readCnt.p,
-                                   b->readOff.p, dst.p, uniqueOnly);
-            return CMB_OK;
-        };
-        if (totalPos) {
-            if (hasNaive) { // the naive path's own filter pass, per read x strand (indexinterface.cpp:1137, :1205)
-                hipLaunchKernelGGL(k_mvs_text_keys, dim3(gridFor(totalPos)), dim3(256), 0, s, b->positions.p, b->locOff.p, nUniq, totalPos, b->locMeta.p,
-                                   b->keysA.p, b->vals.p, b->bad.p, (const uint8_t*)b->psel.p, 1);
-                if (const int rc = sortAndFilter(totalPos, 2 * nReads, b->naiveOut, nNaiveKept); rc != CMB_OK) return rc;
-                if (b->naiveOff.n < (size_t)2 * nReads + 1) b->naiveOff.alloc((size_t)2 * nReads + 1);
-                HIPCHK(hipMemcpyAsync(b->naiveOff.p, b->readOff.p, ((size_t)2 * nReads + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
-                const uint64_t need = totalPos + nNaiveKept;
-                if (need >= (1ull << 31)) return failWith(CMB_ERR_UNSUPPORTED, "2^31 and more text positions in one b-move batch");
-                if (b->keysA.n < need || b->vals.n < need) {
-                    HIPCHK(hipStreamSynchronize(s));
-                    b->keysA.alloc(need + 256), b->keysB.alloc(need + 256), b->vals.alloc(need + 256), b->valsB.alloc(need + 256);
-                }
-            }
-            const int perStrand = b->perStrand ? 1 : 0;
-            hipLaunchKernelGGL(k_mvs_text_keys, dim3(gridFor(totalPos)), dim3(256), 0, s, b->positions.p, b->locOff.p, nUniq, totalPos, b->locMeta.p, b->keysA.p,
-                               b->vals.p, b->bad.p, (const uint8_t*)b->psel.p, hasNaive ? 2 : 0, perStrand);
-            if (nNaiveKept)
-                hipLaunchKernelGGL(k_mvs_occ_keys, dim3(gridFor(2 * nReads)), dim3(256), 0, s, b->naiveOut.p, b->naiveOff.p, 2 * nReads, b->keysA.p + totalPos,
-                                   b->vals.p + totalPos, perStrand);
-            // (the previous slice's records may still be on their way out of b->out: this stream waits for them before the buffer is
-            // written or enlarged — sortAndFilter synchronises the stream before it allocates)
-            if (b->copyPending) HIPCHK(hipStreamWaitEvent(s, b->copyDone, 0));
-            if (const int rc = sortAndFilter(totalPos + nNaiveKept, perStrand ? 2 * nReads : nReads, b->out, nOut); rc != CMB_OK) return rc;
-            if (perStrand) { // per read again: the two strands of a read are neighbouring groups
-                if (b->rsOff.n < (size_t)2 * nReads + 1) b->rsOff.alloc((size_t)2 * nReads + 1);
-                HIPCHK(hipMemcpyAsync(b->rsOff.p, b->readOff.p, ((size_t)2 * nReads + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
-                hipLaunchKernelGGL(k_mvs_read_offsets, dim3(gridFor(nReads + 1)), dim3(256), 0, s, b->rsOff.p, nReads, b->readOff.p);
-            }
-        }
-        tm.end("filter");
-        HIPCHK(hipGetLastError());
-        if (b->wantAln && nOut) { // CIGAR and sequence of every final occurrence: findCIGAR on text[begin, end) (k_cigar)
-            tm.begin();
-            uint4* dOcc = nullptr;
-            AlnRec* dAln = nullptr;
-            uint16_t* dOps = nullptr;
-            if (b->keepLists) { // in place, behind the records of the slices before this one
-                b->keepReserve(b->keepN + nOut, s);
-                if (b->occRead.n < nOut) b->occRead.alloc(nOut + nOut / 4 + 256);
-                dOcc = b->keepOcc.p + b->keepN, dAln = b->keepAln.p + b->keepN, dOps = b->keepOps.p + b->keepN * b->alnStride;
-            } else {
-                if (b->occ32.n < nOut) {
-                    const size_t c = nOut + nOut / 4 + 256;
-                    b->occ32.alloc(c), b->alnRec.alloc(c), b->occRead.alloc(c), b->alnOps.alloc(c * b->alnStride);
-                }
-                dOcc = b->occ32.p, dAln = b->alnRec.p, dOps = b->alnOps.p;
-            }
-            hipLaunchKernelGGL(k_mvs_occ32, dim3(gridFor(nReads)), dim3(256), 0, s, b->out.p, b->readOff.p, nReads, dOcc, b->occRead.p);
-            uint32_t flagBefore = 0;
-            HIPCHK(hipMemcpyAsync(&flagBefore, b->cnt.p + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            const int rc = cmb::moveCigarsOnText(ix->textIndex, s, dOffs, b->G.p, b->gw, nReads, b->maxLen, b->k, b->metric == CMB_METRIC_EDIT ? 0 : 1,
-                                                 dOcc, b->occRead.p, nOut, dAln, dOps, b->alnStride, b->cnt.p + 3);
-            if (rc != CMB_OK) return rc;
-            const size_t base = b->hAlnRec.size();
-            b->hAlnRec.resize(base + nOut);
-            b->hAlnOps.resize((base + nOut) * b->alnStride);
-            HIPCHK(hipMemcpyAsync(b->hAlnRec.data() + base, dAln, nOut * sizeof(AlnRec), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(b->hAlnOps.data() + base * b->alnStride, dOps, nOut * b->alnStride * sizeof(uint16_t), hipMemcpyDeviceToHost, s));
-            uint32_t flagAfter = 0;
-            HIPCHK(hipMemcpyAsync(&flagAfter, b->cnt.p + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            tm.end("k_cigar");
-            if ((flagAfter & ~flagBefore) & FLAG_CAPACITY)
-                return failWith(CMB_ERR_INTERNAL, "a CIGAR traceback left the band or an occurrence is not an alignment within its distance");
-        }
-        if (b->keepLists) { // the slice's group offsets behind those of the slices before it
-            const uint32_t gs = b->keepStride;
-            const uint64_t* src = !totalPos ? nullptr : gs == 2 ? b->rsOff.p : b->readOff.p;
-            hipLaunchKernelGGL(k_mvs_keep_offsets, dim3(gridFor((uint64_t)gs * nReads + 1)), dim3(256), 0, s, src, (uint64_t)gs * nReads, b->keepN,
-                               b->keepOff.p + (size_t)gs * lo);
-            HIPCHK(hipGetLastError());
-            b->keepN += nOut;
-        }
-        uint32_t hb = 0;
-        HIPCHK(hipMemcpyAsync(&hb, b->bad.p, sizeof(hb), hipMemcpyDeviceToHost, s));
-        unsigned long long hc64[CMB_CNT_MAX];
-        HIPCHK(hipMemcpyAsync(hc64, b->counters.p, sizeof(hc64), hipMemcpyDeviceToHost, s));
-        static_assert(sizeof(cmb_move_occ) == sizeof(MoveOccOut), "cmb_move_occ layout");
-        const size_t occBase = b->occs.size();
-        if (occBase + nOut > b->occs.cap) b->waitForCopies(); // (the page-locked vector moves when it grows)
-        b->occs.resize(occBase + nOut);
-        std::vector<uint64_t> sliceOffs((size_t)nReads + 1, 0);
-        if (nOut) { // on the copy stream, behind everything this slice has queued: the next slice starts while the records travel
-            HIPCHK(hipEventRecord(b->outReady, s));
-            HIPCHK(hipStreamWaitEvent(b->copyStream, b->outReady, 0));
-            HIPCHK(hipMemcpyAsync(b->occs.data() + occBase, b->out.p, nOut * sizeof(MoveOccOut), hipMemcpyDeviceToHost, b->copyStream));
-            HIPCHK(hipEventRecord(b->copyDone, b->copyStream));
-            b->copyPending = true;
-        }
-        if (totalPos) HIPCHK(hipMemcpyAsync(sliceOffs.data(), b->readOff.p, ((size_t)nReads + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        for (uint32_t i = 0; i <= nReads; i++) b->occOffs[(size_t)lo + i] = occBase + sliceOffs[i];
-        if (totalPos && hb)
-            return failWith(CMB_ERR_INTERNAL, std::to_string(hb) + " occurrences whose phi chains do not have the width of their range, or whose "
-                                                                   "fields do not fit the filter keys");
-        for (int i = 0; i < CMB_CNT_MAX; i++) b->cnts[i] += hc64[i];
-        b->cnts[CMB_CNT_TOTAL_REPORTED] += totalPos + nNaiveKept; // (the naive path's survivors are reported again as text occurrences of the read)
-        b->cnts[CMB_CNT_LOCATED_ROWS] += totalPos;
-        return CMB_OK;
+        c.nFm = c.hcnt[1];
+        if ((rc = dedupFmOccurrences(c)) != CMB_OK) return rc;
+        locatePositions(c);
+        if ((rc = filterOccurrences(c)) != CMB_OK) return rc;
+        if ((rc = runCigar(c)) != CMB_OK) return rc;
+        appendKeptOffsets(c);
+        return downloadSlice(c);
     } catch (const std::exception& e) {
         return failWith(CMB_ERR_DEVICE, e.what());
     }

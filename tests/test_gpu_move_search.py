@@ -2,6 +2,7 @@
 cmb_move_match_batch against the oracle's restatement of the RUN_LENGTH_COMPRESSION flavour (oracle_move_search.hpp, itself
 tied to the FM-index restatement and to plain DP by tests/test_move_search_oracle.py), and against ground truth directly."""
 import os
+import re
 import sys
 
 import numpy as np
@@ -280,18 +281,96 @@ def test_bmove_frontier_code_paths(sworld, monkeypatch, env):
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and a[2] == b[2]
 
 
-def test_bmove_pool_growth(sworld):
+def _attempts(err):
+    """attempts of the search in a CMB_VERBOSE output: the prologue prints one `[grid] k_mvs_parts` line per attempt"""
+    return len(re.findall(r"\[grid\] k_mvs_parts ", err))
+
+
+def test_bmove_pool_growth(sworld, monkeypatch, capfd):
     """pools that start from almost nothing are grown and the search re-run: same lists"""
     ca = sworld["ca"]
     reads = _reads(sworld["g"], 4, 400, 150, seed=9)
     st = ca.SearchStrategy("multiple_opt", "edit", "dynamic")
     a = sworld["dev"].match_batch(st, 4, reads, kmer_size=8)
-    os.environ["CMB_TEST_SMALL_POOLS"] = "1"
-    try:
-        b = sworld["dev"].match_batch(st, 4, reads, kmer_size=8)
-    finally:
-        del os.environ["CMB_TEST_SMALL_POOLS"]
+    monkeypatch.setenv("CMB_TEST_SMALL_POOLS", "1")
+    monkeypatch.setenv("CMB_VERBOSE", "1")
+    capfd.readouterr()
+    b = sworld["dev"].match_batch(st, 4, reads, kmer_size=8)
+    assert _attempts(capfd.readouterr().err) > 1, "no pool overflowed: the run was not repeated"   # (one slice)
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and a[2] == b[2]
+
+
+def _haplotype_rich_reads(g, n, length, copies=16, base=40_000):
+    """n error-free reads from the pan-genome part of sworld's text, from the windows where the most DISTINCT haplotype strings lie
+    within two mismatches of one of them: a Hamming search at k = 2 follows all of those side by side (15 ... 13 at 150 bp)"""
+    H = g[:copies * base].reshape(copies, base)
+    cs = np.zeros((copies, copies, base + 1), np.int32)
+    cs[:, :, 1:] = np.cumsum(H[:, None, :] != H[None, :, :], axis=2)
+    d = cs[:, :, length:] - cs[:, :, :-length]     # [i, j, p]: mismatches of haplotypes i and j in the window at p
+    first = np.ones((copies, d.shape[2]), bool)    # haplotype j is the first with its string in the window
+    for j in range(1, copies):
+        first[j] = (d[:j, j] > 0).all(axis=0)
+    near = ((d <= 2) & first[None]).sum(axis=1)    # [i, p]: distinct strings within two mismatches of haplotype i's
+    best = np.argsort(-near.max(axis=0), kind="stable")[:n]
+    return [H[int(near[:, p].argmax()), p:p + length].tobytes() for p in sorted(best.tolist())]
+
+
+# Reads per case.  400 sampled reads leave the edit frontier's pools (64 records each with CMB_TEST_SMALL_POOLS) too small in every
+# slice.  The Hamming frontier starts from nTasks + 1024 nodes per slice whatever the setting, and more sampled reads add slices of
+# 64, not nodes to a slice: 400 ... 4 800 of them took as many attempts as slices (largest frontier of a pass 134 - 190 nodes for 97 -
+# 110 tasks; 540 for error-free reads of the pan-genome part).  So the count is raised by ONE slice, 7 x 64 = 448, whose last 64
+# reads are the 16 richest _haplotype_rich_reads, four times each: 192 tasks, room for 1 216 nodes — the capacity the six slices
+# before have left included —, and a frontier of 1 372 (printed by the test): 8 attempts in 7 slices.  Measured on the way: 400 rich
+# reads in slices of 58 reach 1 103 - 1 155 of 1 198 nodes, the 64 richest once each 1 196 of 1 216
+HAMMING_POOL_READS, HAMMING_RICH_READS = 448, 64
+
+
+@pytest.mark.parametrize("aligned", [False, True], ids=["lists", "alignments-per-strand"])
+@pytest.mark.parametrize("spec,metric,k,n", [("multiple_opt", "edit", 4, 400), ("kuch1", "hamming", 2, HAMMING_POOL_READS)])
+def test_bmove_pools_grow_in_a_later_slice(sworld, monkeypatch, capfd, spec, metric, k, n, aligned):
+    """The capacities of the pools (qCap ... aCap, nvQCap, the list of in-index occurrences) live in the batch across its slices: a
+    chunk matched in slices of 64 reads whose pools start from almost nothing — grown in one slice, met again by the next — leaves the
+    lists, offsets, counters and (on request, with every strand filtered by itself) alignments of the run with neither setting.
+    Guard: one `[grid] k_mvs_parts` line per attempt, more of them than slices.  In the Hamming cases it is the LAST slice that
+    overflows, on the capacity the slices before it have set."""
+    ca = sworld["ca"]
+    g = sworld["g"]
+    rich = HAMMING_RICH_READS if metric == "hamming" else 0
+    groups = [synth.sample_reads(g, (n - rich) // 4, length, seed=500 + k + j, n_frac=0.03, edit_choices=(0, 1, 2, k - 1, k, k, k + 1))
+              for j, length in enumerate((100, 117, 133, 150))]
+    reads = [r for quad in zip(*groups) for r in quad]   # (every slice holds every length)
+    if rich:
+        reads += _haplotype_rich_reads(g, rich // 4, 150) * 4   # (copies of a read reach their widest level in the same pass)
+    assert len(reads) == n
+    st = ca.SearchStrategy(spec, metric, "dynamic")
+    sworld["dev"].attach_text(sworld["text"], np.array([0, 250_000, 640_000, len(g)], dtype=np.uint64))
+
+    def run():
+        mb = ca.MoveBatch(sworld["dev"], st, k, reads=reads, kmer_size=8)
+        if aligned:
+            mb.filter_per_strand()
+            mb.want_alignments()
+        mb.run()
+        res = mb.results() + (mb.alignments() if aligned else ())
+        mb.close()
+        return res
+
+    a = run()
+    monkeypatch.setenv("CMB_MOVE_SLICE", "64")
+    monkeypatch.setenv("CMB_TEST_SMALL_POOLS", "1")
+    monkeypatch.setenv("CMB_VERBOSE", "1")
+    capfd.readouterr()
+    b = run()
+    err = capfd.readouterr().err
+    attempts = _attempts(err)
+    assert len(a[0]) > n // 2
+    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and a[2] == b[2]
+    if aligned:
+        assert np.array_equal(a[3], b[3]) and np.array_equal(a[4], b[4])
+    slices = -(-n // 64)
+    peak = max(int(m) for m in re.findall(r"\[grid\] k_mvs_(?:hbfs_)?pass (\d+) items", err))
+    print("%s %s k = %d, %d reads: %d attempts in %d slices, largest frontier of a pass %d nodes" % (spec, metric, k, n, attempts, slices, peak))
+    assert attempts > slices, "no pool overflowed: no slice was run again"
 
 
 @pytest.mark.parametrize("spec,metric,x,min_identity", [("columba", "edit", 0, 96), ("columba", "edit", 1, 96), ("multiple_opt", "edit", 0, 97),
