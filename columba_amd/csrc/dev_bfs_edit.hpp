@@ -336,6 +336,26 @@ __device__ __forceinline__ void blockAppend4(uint32_t* c0, uint32_t* c1, uint32_
     __syncthreads(); // sh may be reused by the next call
 }
 
+// The N <= 4 per-lane counters of a block of four wavefronts summed and added to the slots of block `bid` in blockCnt ([block][4], read
+// by the finish kernel): a shuffle sum, four wavefront partials in LDS, one lane per counter.  One writer per slot and launch,
+// launches are ordered.
+template <int N>
+__device__ __forceinline__ void blockAddCounters(unsigned long long (&v)[N], unsigned long long* blockCnt, uint32_t bid) {
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) v[j] += __shfl_xor(v[j], d);
+    }
+    __shared__ unsigned long long shc[4][N];
+    if ((threadIdx.x & 63u) == 0)
+        for (int j = 0; j < N; j++) shc[threadIdx.x >> 6][j] = v[j];
+    __syncthreads();
+    if (threadIdx.x < N) {
+        const unsigned long long t = shc[0][threadIdx.x] + shc[1][threadIdx.x] + shc[2][threadIdx.x] + shc[3][threadIdx.x];
+        if (t) blockCnt[(size_t)bid * 4 + threadIdx.x] += t;
+    }
+}
+
 // the two rank blocks an extension of `p` in `mode` needs: request (raw 16-byte chunks) and use
 __device__ __forceinline__ void issueRanks(const DevIndex& ix, int mode, const RangePair& p, uint4 v[4]) {
     DevBWT t = ix.fwd; // values, not references, are selected

@@ -1267,7 +1267,7 @@ static int runFrontierHamming(SliceCtx& c, bool& again) {
 // The pools of the edit-distance frontier as the kernels take them (move_search.hpp): grown to the capacities the batch asks for, their
 // cntWords counters (nodes and events per level, the pool sizes) zeroed on the stream, for a search of at most maxPass levels.
 // smallPos: text and run counts below 2^32 (the reference's default build of length_t) — the expanding blocks work on 32-bit positions
-// with the children in slots (mvExpandSlots; CMB_MOVE_POS64=1: the general 40-bit path)
+// with the children in slots (mvExpand<Geo, true>; CMB_MOVE_POS64=1: the general 40-bit path)
 static MvBufs frontierBufs(SliceCtx& c, uint32_t maxPass, size_t cntWords, bool smallPos) {
     cmb_move_batch* b = c.b;
     hipStream_t s = c.s;

@@ -88,7 +88,7 @@ struct MoveRangeRec {
 static_assert(sizeof(MoveRangeRec) == 80, "record layout");
 
 // (P: the type of a text position / run number — 64 bits in general; 32 bits for the frontier kernel's instance on indexes whose text and
-// run counts stay below 2^32, the reference's default build of length_t: move_search.hpp, mvExpand)
+// run counts stay below 2^32, the reference's default build of length_t: move_search.hpp, mvExpand<Geo, true>)
 template <typename P>
 struct MvRangeT {
     P begin, end, beginRun, endRun;

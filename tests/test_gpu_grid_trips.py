@@ -449,8 +449,13 @@ def test_wide_verification_slots_change_no_result(world, monkeypatch, capfd, env
     assert all(l == 256 for _, l in lines["k_verify_wide"]) and any(i >= 3 * l for i, l in lines["k_verify_wide"])
 
 
-@pytest.mark.parametrize("env", [{"CMB_MVS_GRID": "1"}, {"CMB_MVS_CHAIN": "1"}, {"CMB_MVS_CHAIN": "64"}], ids=_KNOB_ID)
+_MVS_KNOBS = [{"CMB_MVS_GRID": "1"}, {"CMB_MVS_CHAIN": "1"}, {"CMB_MVS_CHAIN": "64"}]
+
+
+@pytest.mark.parametrize("env", _MVS_KNOBS + [dict(e, CMB_MOVE_POS64="1") for e in _MVS_KNOBS], ids=_KNOB_ID)
 def test_bmove_knobs_change_no_result(world, monkeypatch, env):
+    """one block that makes many trips, no walk, and a walk that crosses blocks of match words: on both arms of the expansion (32-bit
+    positions with the children in slots, and with CMB_MOVE_POS64=1 the general 40-bit positions with one child per character)"""
     for n, v in env.items():
         monkeypatch.setenv(n, v)
     tms._compare(world["move"], "multiple_opt", "dynamic", 4, _mv(world, "k4"))

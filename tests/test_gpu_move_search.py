@@ -264,12 +264,13 @@ def test_bmove_alignments(sworld, spec, k, length):
     fm.close()
 
 
-@pytest.mark.parametrize("env", [{"CMB_MATRIX64": "1"}, {"CMB_TEST_NARROW_WV": "2"}, {"CMB_MOVE_POS64": "1"}])
+@pytest.mark.parametrize("env", [{"CMB_MATRIX64": "1"}, {"CMB_TEST_NARROW_WV": "2"}, {"CMB_MOVE_POS64": "1"},
+                                 {"CMB_MOVE_POS64": "1", "CMB_MATRIX64": "1"}])
 def test_bmove_frontier_code_paths(sworld, monkeypatch, env):
     """Round 4: up to 7 errors the frontier of this backend carries the in-index matrix on 32-bit words (GeoN32) and, on indexes below 2^32,
-    works on 32-bit positions with the children in slots (mvExpandSlots) — every test above runs on that.  Here the same lists and counters
-    on the reference's 64-bit matrix words, through the re-run a phase triggers that does not fit the small matrix (bound lowered by the
-    test hook), and on the general 40-bit positions."""
+    works on 32-bit positions with the children in slots (mvExpand<Geo, true>) — every test above runs on that.  Here the same lists and
+    counters on the reference's 64-bit matrix words, through the re-run a phase triggers that does not fit the small matrix (bound lowered
+    by the test hook), on the general 40-bit positions (mvExpand<Geo, false>), and on those with the 64-bit matrix words as well."""
     ca = sworld["ca"]
     reads = _reads(sworld["g"], 5, 600, 150, seed=77)
     st = ca.SearchStrategy("columba", "edit", "dynamic")
