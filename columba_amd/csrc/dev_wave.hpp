@@ -5,6 +5,19 @@
 
 namespace cmb {
 
+// the last of n >= 1 ascending offsets that is <= x (upper bound - 1; offsets[0] <= x is the caller's): which record, task or
+// sequence element x of a concatenation belongs to
+template <class T, class Idx>
+__device__ __forceinline__ Idx lastAtOrBelow(const T* __restrict__ offsets, Idx n, T x) {
+    Idx lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const Idx mid = (lo + hi) >> 1;
+        if (offsets[mid] <= x) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
 // Per-lane counters are summed over the wavefront first (all 64 lanes call this, at the end of a kernel):
 // one atomic per wavefront and counter instead of one per lane.
 __device__ __forceinline__ void flushCounters(const Queues& q, const uint32_t* local, const int* which, int n) {

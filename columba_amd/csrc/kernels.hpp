@@ -327,6 +327,7 @@ __device__ __forceinline__ void prepChunk(const uint8_t* __restrict__ rd, uint64
 #include "dev_bfs_edit.hpp"
 #include "dev_bfs_hamming.hpp"
 #include "dev_bfs_naive.hpp"
+#include "dev_trace.hpp" // the stored rows of the in-text matrices: formats, readers, the one walk over them, CigarRuns
 namespace cmb {
 
 // ---- the frontier kernels of the FM-index backend (the functions live in dev_bfs_edit.hpp, which the b-move translation
@@ -670,46 +671,15 @@ k_exact(DevIndex ix, const DevStrategyKT<MP>* __restrict__ stp, uint32_t nReads,
 // ------------------------------------------------------------------ locate + verification
 constexpr int VROWS = MAX_READ + 3 * 7 + 4; // rows of the longest in-text matrix (len + Wv, Wv = 3 k, k <= 7)
 __host__ __device__ inline uint32_t vRows(uint32_t maxLen) { return maxLen + 3u * 7u + 4u; } // ... of a batch
-
-// Row storage of the traceback pass, interleaved by slot so that the lanes of a wavefront (which
-// walk rows in lock step) write whole 512-byte lines: element (row, slot) lives at [row * nSlots + slot].
-// What the traceback reads of row i is bit (j - 32 b) + DIAG of HP and D0 with |i - j| inside the band, i.e.
-// at most 18 (= 3 k) bits below and 6 above the row's diagonal bit: both 32-bit windows starting 18 bits below
-// the diagonal are kept in ONE 64-bit word per row (low half HP, high half D0).
-// Layout: `lines` 64-byte lines per lane (slot), line-major (traceLine); line g = the packed rows 8 g + 1 .. 8 g + 8.  The forward pass
-// collects eight rows in registers and writes the line with four 16-byte stores; the traceback fetches a line
-// (and the eight text codes of its rows) whenever it crosses into the next group of eight rows.
-struct VPlanes {
-    uint64_t* W;
-    uint32_t nSlots, lines;
-};
-// line g of a lane's trace rows.  Line-major: the 64 lines a wavefront writes (or reads) for one group of rows are
-// 4 KB of consecutive memory instead of 64 lines `lines` x 64 bytes apart.
-__device__ __forceinline__ uint4* traceLine(const VPlanes& V, uint32_t slot, uint32_t line) {
-    return reinterpret_cast<uint4*>(V.W) + ((size_t)line * V.nSlots + slot) * 4;
-}
-constexpr uint32_t TB_BELOW = 18;  // narrow rows (32-bit matrix, maxED <= 4)
-constexpr uint32_t TBW_BELOW = 21; // wide rows (64-bit / 16-row-block matrix, maxED <= 7: Wv = 3 maxED <= 21, Wh <= 7)
-// low half: HP; high half: M | ~D0 — "the diagonal step is allowed" (bitparallelmatrix.h:559-562), folded in by the
-// forward pass, which has the row's match word at hand: the trace then needs neither the text nor match words.
-__device__ __forceinline__ uint64_t packTraceRow(uint32_t r, uint64_t HP, uint64_t diagOk) {
-    const uint32_t sh = (r % MXW_BLOCK) + MXW_DIAG - TBW_BELOW;
-    return (uint64_t)(uint32_t)(HP >> sh) | ((uint64_t)(uint32_t)(diagOk >> sh) << 32);
-}
-// NARROW rows (maxED <= 4): 16 + 16 bits per row, sixteen rows per 64-byte line — half the trace traffic.
-// A trace only visits cells whose value is at most maxED, i.e. cells of the band j - i in [-3 maxED, maxED]
-// (4 maxED + 1 <= 17 window bits, rel = j - i + TB_BELOW in [6, 22]); two of the 34 bits are never open:
-//  * HP at the band's left edge (rel = 6): "horizontal" would come from a cell outside the band, whose value
-//    exceeds maxED, so the bit is 0 wherever a trace reads it;
-//  * "diagonal allowed" at the band's right edge (rel = 22): the alternative, a vertical step, would come from a
-//    cell outside the band, so the bit is 1 wherever a trace (having read HP = 0) reads it.
-// Kept: HP for rel 7..22 (low half), diagonal for rel 6..21 (high half).  The wide kernel CHECKS both rules on
-// every step it takes (FLAG_CAPACITY if one is ever violated; CMB_TRACE_WIDE=1 selects it for any k).
-constexpr uint32_t TBN_HP_LO = 7, TBN_DG_LO = 6, TBN_REL_LO = 6, TBN_REL_HI = 22, TBN_MAX_ED = 4;
-// (HP and "diagonal allowed" of the 32-bit matrix: the diagonal of row r is bit r % 8 + MX32_DIAG)
-__device__ __forceinline__ uint32_t packTraceRowNarrow(uint32_t r, uint32_t HP, uint32_t diagOk) {
-    const uint32_t d = (r % MX32_BLOCK) + MX32_DIAG - TB_BELOW + 32u; // (+32: d itself would be negative)
-    return ((HP >> (d + TBN_HP_LO - 32u)) & 0xFFFFu) | ((diagOk >> (d + TBN_DG_LO - 32u)) << 16);
+// the in-text matrix of a read of `len` characters within maxED errors whose first column starts with nZeros zeros (1: a fixed start)
+__device__ __forceinline__ MatGeom inTextGeom(uint32_t len, uint32_t maxED, uint32_t nZeros) {
+    MatGeom g;
+    g.n = len + 1u;
+    g.maxED = maxED;
+    g.Wv = nZeros - 1u + maxED;
+    g.Wh = maxED;
+    g.m = max(g.Wv + g.n, g.Wv + g.Wh + 1u); // (bitparallelmatrix.cpp:98-103: reads shorter than the band)
+    return g;
 }
 
 // The device copy of the text holds CODES, one byte per character: A,C,G,T -> 0..3, anything else ('$',
@@ -1226,15 +1196,6 @@ struct WideRow { // the matrix state of one candidate, with the text codes and m
         return computeRowWide<WX::BLOCK, WX::DIAG>(g, r, M, HP, HN, D0, RAC, score);
     }
 };
-__device__ __forceinline__ MatGeom wideGeom(uint32_t len, uint32_t maxED, uint32_t nZeros) {
-    MatGeom g;
-    g.n = len + 1u;
-    g.maxED = maxED;
-    g.Wv = nZeros - 1u + maxED;
-    g.Wh = maxED;
-    g.m = max(g.Wv + g.n, g.Wv + g.Wh + 1u); // (bitparallelmatrix.cpp:98-103: reads shorter than the band)
-    return g;
-}
 
 template <class WX>
 __global__ void __launch_bounds__(256)
@@ -1284,7 +1245,7 @@ k_wide_filter(DevIndex ix, const uint64_t* __restrict__ offs, const uint32_t* __
                             const uint32_t nZeros = fixed ? 1u : 2u * maxED + 1u;
                             start = verifyKeyStart(key);
                             len = (uint32_t)(offs[(rs >> 1) + 1] - offs[rs >> 1]);
-                            g = wideGeom(len, maxED, nZeros);
+                            g = inTextGeom(len, maxED, nZeros);
                             const uint32_t maxEnd = ix.n - 1, hEnd = windowEnd(maxEnd, start, g.m);
                             size = hEnd > start ? hEnd - start : 0;
                             if (!g.inFinalColumn(size)) { // (indexhelpers.cpp:527): started, nothing computed
@@ -1401,7 +1362,7 @@ k_verify_wide(DevIndex ix, const uint64_t* __restrict__ offs, uint32_t maxLen, c
         const uint32_t len = active ? (uint32_t)(offs[(rs >> 1) + 1] - offs[rs >> 1]) : 0u;
         const uint8_t* rd = seq + (size_t)rs * maxLen;
         const uint32_t nZeros = fixed ? 1u : 2u * maxED + 1u;
-        const MatGeom g = wideGeom(len, maxED, nZeros);
+        const MatGeom g = inTextGeom(len, maxED, nZeros);
         const uint32_t sfc = g.sfc(), col = g.n - 1u, firstRow = (g.m - 1u) - sfc;
         // the values of the last column from row firstRow on (at most sfc + 1 <= 54 of them), four bits each: all that is asked of them
         // is how they compare with a value of at most maxED <= 13
@@ -1462,6 +1423,8 @@ k_verify_wide(DevIndex ix, const uint64_t* __restrict__ offs, uint32_t maxLen, c
                     if (betterThanAbove && betterThanBelow) {
                         nCentres++;
                         uint32_t ti = r, tj = col;
+                        // (a COPY of walkToColumn0, dev_trace.hpp, over the slab rows, as in k_cigar_wide: on the shared walk this kernel ran
+                        // 3 % longer and k_cigar_wide lost a register tier.  A change to the walk there belongs in both copies.)
                         while (tj > 0) {
                             const uint32_t bitIdx = (tj - (ti / WX::BLOCK) * WX::BLOCK) + WX::DIAG; // (:541-543; unsigned as there)
                             if (bitIdx >= 64u) {
@@ -1749,7 +1712,6 @@ k_verify_stage(DevIndex ix, const uint64_t* __restrict__ offs, MFull mf,
 // recomputed, this time keeping HP and D0, and every centre is traced back to its begin row
 // (bitparallelmatrix.h:531-586).  The traceback reads rows through an 8-row window staged in LDS, so
 // the dependent chain costs one memory round trip per 8 rows instead of three per row.
-constexpr int TBW = 8;
 template <bool NARROW, bool PACKED>
 __global__ void __launch_bounds__(256)
 k_traceback(DevIndex ix, const uint64_t* __restrict__ offs, MFull mf,
@@ -1764,7 +1726,6 @@ k_traceback(DevIndex ix, const uint64_t* __restrict__ offs, MFull mf,
     auto holeT = [&](uint32_t i) { q.text[i].rsId = 0xFFFFFFFFu; };
     const uint32_t stride = gridDim.x * blockDim.x;
     const uint32_t waveBase = slot & ~63u;
-    const uint64_t HP0 = (~0ull) << MXW_LEFT;
     for (uint32_t base = waveBase; base < nTasks; base += stride) { // wave-uniform trip count
         const uint32_t it = base + (tid & 63u);
         uint32_t rs = 0, start = 0, m = 0, firstRow = 0, len = 0, col = 0;
@@ -1779,12 +1740,7 @@ k_traceback(DevIndex ix, const uint64_t* __restrict__ offs, MFull mf,
             const uint32_t maxED = t.w & 15u, fixed = (t.w >> 4) & 1u;
             len = (uint32_t)(offs[(rs >> 1) + 1] - offs[rs >> 1]);
             const uint32_t nZeros = fixed ? 1u : 2u * maxED + 1u;
-            MatGeom g;
-            g.n = len + 1;
-            g.maxED = maxED;
-            g.Wv = nZeros - 1 + maxED;
-            g.Wh = maxED;
-            g.m = max(g.Wv + g.n, g.Wv + g.Wh + 1u); // (bitparallelmatrix.cpp:98-103: reads shorter than the band)
+            const MatGeom g = inTextGeom(len, maxED, nZeros);
             firstRow = (g.m - 1) - g.sfc();
             col = g.n - 1;
             relLeft = TBW_BELOW - g.Wv; // (the wide rows' window; used by the wide walk only)
@@ -1816,7 +1772,7 @@ k_traceback(DevIndex ix, const uint64_t* __restrict__ offs, MFull mf,
                 ti = ri;
                 tj = col;
             }
-            if (NARROW) {
+            if constexpr (NARROW) {
                 // The wavefront walks its traces ROW by row, downwards and in lock step (line g = rows 16 g + 1 ..
                 // 16 g + 16 sits in sixteen registers, row j of it is handled by every lane whose trace is in that
                 // row): per row, the run of horizontal steps is the run of HP bits below the current column (one
@@ -1874,41 +1830,13 @@ k_traceback(DevIndex ix, const uint64_t* __restrict__ offs, MFull mf,
                     tj = 0;
                 }
             } else if (have) {
-                uint32_t curG = 0xFFFFFFFFu; // the line (rows 8 g + 1 .. 8 g + 8) held in wW[.][tid]
-                while (tj > 0) {
-                    const uint32_t rel = tj + TBW_BELOW - ti; // bit of the row's windows
-                    uint64_t ww = packTraceRow(0, HP0, 0ull); // row 0 (never steps diagonally: ti > 0 below)
-                    if (ti > 0) {
-                        const uint32_t gq = (ti - 1) >> 3, jq = (ti - 1) & 7u;
-                        if (gq != curG) {
-                            curG = gq;
-                            const uint4* L = traceLine(V, slot, gq);
-#pragma unroll
-                            for (int h = 0; h < 4; h++) {
-                                const uint4 v = L[h];
-                                wW[2 * h][tid] = (uint64_t)v.x | ((uint64_t)v.y << 32);
-                                wW[2 * h + 1][tid] = (uint64_t)v.z | ((uint64_t)v.w << 32);
-                            }
-                        }
-                        ww = wW[jq][tid];
-                    }
-                    if (rel > 31u) { // outside the stored window: cannot happen inside the band (checked, not assumed)
-                        flags |= FLAG_CAPACITY;
-                        break;
-                    }
-                    const bool hpBit = ((uint32_t)ww >> rel) & 1u;
-                    const bool dgBit = ((uint32_t)(ww >> 32) >> rel) & 1u;
-                    // the two rules the narrow rows rely on (see packTraceRowNarrow), checked on every step
-                    if (rel < relLeft || rel > relRight || (rel == relLeft && hpBit) ||
-                        (rel == relRight && ti > 0 && !hpBit && !dgBit))
+                // the two rules the narrow rows rely on (see packTraceRowNarrow), checked on every step
+                auto rules = [&](uint32_t i, uint32_t j, bool hpBit, bool dgBit) {
+                    const uint32_t rel = j + TBW_BELOW - i;
+                    if (rel < relLeft || rel > relRight || (rel == relLeft && hpBit) || (rel == relRight && i > 0 && !hpBit && !dgBit))
                         flags |= FLAG_TRACE_RULE;
-                    if (hpBit) { // gap in horizontal (:553)
-                        --tj;
-                    } else {
-                        if (ti > 0 && dgBit) --tj; // diagonal (:559); else vertical
-                        --ti;
-                    }
-                }
+                };
+                walkToColumn0(WideLineRows{wW, V, slot, tid}, ti, tj, flags, [](uint32_t) {}, rules);
             }
             if (have) {
                 const uint32_t ed = bitIdx < 21u ? (uint32_t)((edPack >> (3u * bitIdx)) & 7ull)
@@ -2217,7 +2145,7 @@ k_filter_write(const unsigned long long* __restrict__ keys, uint32_t n, const ui
 // Output per occurrence: n runs of (length << 2 | op), op 0 M / 1 I / 2 D, stored END to BEGIN at ops[occ * stride + j].
 // Sequence assignment (IndexInterface::findSeqName, indexinterface.cpp:799-832): seq = the sequence `begin` lies in;
 // spans = the occurrence runs over its end (the host trims or drops those, :833-899) — AlnRec, host_util.hpp.
-constexpr uint32_t CIG_M = 0, CIG_I = 1, CIG_D = 2;
+// The walk, the run-length encoding and the sequence assignment are walkToColumn0, CigarRuns and assignSequence of dev_trace.hpp.
 constexpr uint32_t CIGAR_BLOCK_WORDS_MAX_ED = 9; // k_cigar up to this distance, k_cigar_wide beyond (see there)
 template <bool NARROW, bool PACKED>
 __global__ void __launch_bounds__(256)
@@ -2226,13 +2154,12 @@ k_cigar(DevIndex ix, const uint64_t* __restrict__ offs, MFull mf, const uint4* _
         uint16_t* __restrict__ ops, uint32_t stride, AlnRec* __restrict__ aln, uint32_t* __restrict__ flagWord,
         uint32_t gapless /* Hamming distance / exact matches: every CIGAR is <len>M (fmindex.cpp:367, indexinterface.cpp:988) */) {
     __shared__ uint64_t wW[NARROW ? 1 : TBW][256];
-    __shared__ uint32_t wN[NARROW ? 16 : 1][256];
+    __shared__ uint32_t wN[NARROW ? TBN : 1][256];
     __shared__ uint64_t Ml[ML_WORDS];
     const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t tid = threadIdx.x;
     uint32_t flags = 0, dummyRows = 0;
     const uint64_t strideT = (uint64_t)gridDim.x * blockDim.x;
-    const uint64_t HP0 = (~0ull) << MXW_LEFT;
     for (uint64_t base = slot & ~63u; base < nOcc; base += strideT) { // wave-uniform trip count
         const uint64_t it = base + (tid & 63u);
         uint4 o = make_uint4(0, 0, 0, 0);
@@ -2244,24 +2171,10 @@ k_cigar(DevIndex ix, const uint64_t* __restrict__ offs, MFull mf, const uint4* _
             len = (uint32_t)(offs[(rs >> 1) + 1] - offs[rs >> 1]);
             size = o.y - o.x;
             have = true;
-            // sequence of the occurrence: last start position <= begin (upper_bound - 1)
-            uint32_t lo = 0, hi = nSeqs; // seqStarts[0] == 0; seqStarts[nSeqs] = end of the last sequence
-            while (hi - lo > 1) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (seqStarts[mid] <= o.x) lo = mid;
-                else hi = mid;
-            }
-            aln[it].seqId = lo;
-            aln[it].seqBegin = o.x - seqStarts[lo];
-            aln[it].spans = o.y > seqStarts[lo + 1] ? 1u : 0u;
+            assignSequence(seqStarts, nSeqs, o.x, o.y, aln[it]);
         }
         const uint32_t maxED = o.z;
-        MatGeom g;
-        g.n = len + 1;
-        g.maxED = maxED;
-        g.Wv = maxED;
-        g.Wh = maxED;
-        g.m = max(g.Wv + g.n, g.Wv + g.Wh + 1u); // (bitparallelmatrix.cpp:98-103: reads shorter than the band)
+        const MatGeom g = inTextGeom(len, maxED, 1u);
         col = len;
         bool trace = have && maxED > 0 && size > 0 && !gapless;
         if (trace && NARROW && maxED > TBN_MAX_ED) { // (the host picks the wide kernel for k > 4)
@@ -2288,90 +2201,12 @@ k_cigar(DevIndex ix, const uint64_t* __restrict__ offs, MFull mf, const uint4* _
         }
         if (trace) {
             uint32_t ti = size, tj = col;
-            uint32_t curG = 0xFFFFFFFFu, state = 3u, run = 0;
-            auto emit = [&](uint32_t op) {
-                if (op != state) {
-                    if (run) {
-                        if (nOps < stride) myOps[nOps] = (uint16_t)((run << 2) | state);
-                        nOps++;
-                    }
-                    state = op;
-                    run = 0;
-                }
-                run++;
-            };
-            while (tj > 0) {
-                const uint32_t rel = tj + (NARROW ? TB_BELOW : TBW_BELOW) - ti;
-                bool hpBit, dgBit;
-                if (NARROW) {
-                    uint32_t wn = packTraceRowNarrow(0, (~0u) << MX32_LEFT, 0u);
-                    if (ti > 0) {
-                        const uint32_t gq = (ti - 1) >> 4, jq = (ti - 1) & 15u;
-                        if (gq != curG) {
-                            curG = gq;
-                            const uint4* L = traceLine(V, slot, gq);
-#pragma unroll
-                            for (int h = 0; h < 4; h++) {
-                                const uint4 v = L[h];
-                                wN[4 * h][tid] = v.x;
-                                wN[4 * h + 1][tid] = v.y;
-                                wN[4 * h + 2][tid] = v.z;
-                                wN[4 * h + 3][tid] = v.w;
-                            }
-                        }
-                        wn = wN[jq][tid];
-                    }
-                    if (rel < TBN_REL_LO || rel > TBN_REL_HI) {
-                        flags |= FLAG_CAPACITY;
-                        break;
-                    }
-                    hpBit = rel >= TBN_HP_LO && ((wn >> (rel - TBN_HP_LO)) & 1u);
-                    dgBit = rel == TBN_REL_HI || ((wn >> (16u + rel - TBN_DG_LO)) & 1u);
-                } else {
-                    uint64_t ww = packTraceRow(0, HP0, 0ull);
-                    if (ti > 0) {
-                        const uint32_t gq = (ti - 1) >> 3, jq = (ti - 1) & 7u;
-                        if (gq != curG) {
-                            curG = gq;
-                            const uint4* L = traceLine(V, slot, gq);
-#pragma unroll
-                            for (int h = 0; h < 4; h++) {
-                                const uint4 v = L[h];
-                                wW[2 * h][tid] = (uint64_t)v.x | ((uint64_t)v.y << 32);
-                                wW[2 * h + 1][tid] = (uint64_t)v.z | ((uint64_t)v.w << 32);
-                            }
-                        }
-                        ww = wW[jq][tid];
-                    }
-                    if (rel > 31u) {
-                        flags |= FLAG_CAPACITY;
-                        break;
-                    }
-                    hpBit = ((uint32_t)ww >> rel) & 1u;
-                    dgBit = ((uint32_t)(ww >> 32) >> rel) & 1u;
-                }
-                if (hpBit) { // gap in horizontal direction: insertion (:488-494)
-                    --tj;
-                    emit(CIG_I);
-                } else if (ti > 0 && dgBit) { // diagonal (:496-506)
-                    --tj;
-                    --ti;
-                    emit(CIG_M);
-                } else { // gap in vertical direction (:508-514)
-                    if (ti == 0) { // (cannot happen: row 0 only has horizontal steps)
-                        flags |= FLAG_CAPACITY;
-                        break;
-                    }
-                    --ti;
-                    emit(CIG_D);
-                }
-            }
-            for (; ti > 0; --ti) emit(CIG_D); // findCIGAR walks on to (0, 0): leading deletions
-            if (run) {
-                if (nOps < stride) myOps[nOps] = (uint16_t)((run << 2) | state);
-                nOps++;
-            }
-            if (nOps > stride) flags |= FLAG_CAPACITY;
+            CigarRuns runs{myOps, stride};
+            auto sink = [&](uint32_t op) { runs.emit(op); };
+            if constexpr (NARROW) walkToColumn0(NarrowLineRows{wN, V, slot, tid}, ti, tj, flags, sink);
+            else walkToColumn0(WideLineRows{wW, V, slot, tid}, ti, tj, flags, sink);
+            for (; ti > 0; --ti) runs.emit(CIG_D); // findCIGAR walks on to (0, 0): leading deletions
+            nOps = runs.finish(flags);
         }
         if (have) aln[it].nOps = nOps;
     }
@@ -2400,21 +2235,11 @@ k_cigar_wide(DevIndex ix, const uint64_t* __restrict__ offs, const uint32_t* __r
         const uint32_t rs = 2u * occRead[it] + (o.w & 1u);
         const uint32_t len = (uint32_t)(offs[(rs >> 1) + 1] - offs[rs >> 1]);
         const uint32_t size = o.y - o.x, maxED = o.z, col = len;
-        { // sequence of the occurrence: last start position <= begin (upper_bound - 1)
-            uint32_t lo = 0, hi = nSeqs; // seqStarts[0] == 0; seqStarts[nSeqs] = end of the last sequence
-            while (hi - lo > 1) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (seqStarts[mid] <= o.x) lo = mid;
-                else hi = mid;
-            }
-            aln[it].seqId = lo;
-            aln[it].seqBegin = o.x - seqStarts[lo];
-            aln[it].spans = o.y > seqStarts[lo + 1] ? 1u : 0u;
-        }
+        assignSequence(seqStarts, nSeqs, o.x, o.y, aln[it]);
         uint32_t nOps = 0;
         uint16_t* myOps = ops + it * stride;
         bool trace = maxED > 0 && size > 0 && !gapless;
-        const MatGeom g = wideGeom(len, maxED, 1u);
+        const MatGeom g = inTextGeom(len, maxED, 1u);
         if (trace && (g.Wv >= WX::LEFT || WX::DIAG + g.Wh + WX::BLOCK > 63u || (size + 1u) * VW_ROW_BYTES > slotBytes)) {
             flags |= FLAG_CAPACITY;
             trace = false;
@@ -2436,6 +2261,8 @@ k_cigar_wide(DevIndex ix, const uint64_t* __restrict__ offs, const uint32_t* __r
             rowBits[(size_t)r * 64u] = make_uint4((uint32_t)mx.HP, (uint32_t)(mx.HP >> 32), (uint32_t)md, (uint32_t)(md >> 32));
         }
         if (!ok) flags |= FLAG_CAPACITY; // (a row without a cell <= maxED: the occurrence is not an alignment within its distance)
+        // A COPY of walkToColumn0 (over the slab rows, as in k_verify_wide) feeding a copy of CigarRuns (dev_trace.hpp), kept written out: with
+        // either shared piece this kernel takes 76 registers instead of 68 (6 wavefronts per SIMD instead of 7).  A change there belongs here too.
         uint32_t ti = size, tj = col, state = 3u, run = 0;
         auto emit = [&](uint32_t op) {
             if (op != state) {

@@ -29,6 +29,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dev_wave.hpp" // (lastAtOrBelow)
 #include "move_row.hpp"
 
 namespace cmb {
@@ -555,12 +556,7 @@ static_assert(sizeof(MoveOccRec) == 24, "record layout");
 __global__ void k_move_occ(const uint64_t* __restrict__ positions, const uint64_t* __restrict__ taskOff, uint64_t nTasks, uint64_t total,
                            const uint64_t* __restrict__ readOff, MoveOccRec* __restrict__ out) {
     for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < total; j += (uint64_t)gridDim.x * blockDim.x) {
-        uint64_t lo = 0, hi = nTasks; // the last task whose offset is <= j
-        while (hi - lo > 1) {
-            const uint64_t mid = (lo + hi) >> 1;
-            if (taskOff[mid] <= j) lo = mid;
-            else hi = mid;
-        }
+        const uint64_t lo = lastAtOrBelow(taskOff, nTasks, j); // the last task whose offset is <= j
         const uint64_t rd = lo >> 1, len = readOff[rd + 1] - readOff[rd];
         out[j] = MoveOccRec{positions[j], positions[j] + len, 0u, (uint32_t)(lo & 1)};
     }

@@ -1483,13 +1483,7 @@ __global__ void k_mvs_text_keys(const uint64_t* __restrict__ positions, const ui
                                 const uint4* __restrict__ meta, unsigned long long* __restrict__ keys, uint32_t* __restrict__ vals,
                                 uint32_t* __restrict__ bad, const uint8_t* __restrict__ psel = nullptr, int which = 0, int perStrand = 0) {
     for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < total; j += (uint64_t)gridDim.x * blockDim.x) {
-        uint32_t lo = 0, hi = nRecs; // the last record whose offset is <= j
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (recOff[mid] <= j) lo = mid;
-            else hi = mid;
-        }
-        const uint4 m = meta[lo];
+        const uint4 m = meta[lastAtOrBelow(recOff, nRecs, j)]; // the last record whose offset is <= j
         const uint64_t begin = positions[j] + m.w;
         if (begin >> 40 || m.x >> 24 || m.y >= (1u << 19) || m.z >= 16u) atomicAdd(bad, 1u);
         const bool naive = which != 0 && (psel[m.x] & 0x80u) != 0u;

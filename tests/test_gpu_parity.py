@@ -500,10 +500,12 @@ def test_errors_are_loud(world):
 
 @pytest.mark.parametrize("spec,metric,k", [("multiple_opt", "edit", 4), ("columba", "edit", 6), ("kuch1", "edit", 2), ("columba", "edit", 9),
                                            ("kuch1", "hamming", 3), ("kuch1", "edit", 0), ("columba", "edit", 12)])
-def test_alignments_cigar_and_sequence(world, oracle_built, spec, metric, k):
+def test_alignments_cigar_and_sequence(world, oracle_built, monkeypatch, spec, metric, k):
     """SURVEY.md §8f rank 1 on the device: the CIGAR of every final occurrence (k_cigar) is what the reference's
     findCIGAR gives for (read on its strand, text[begin, end), distance) — asked of the oracle's restatement, which is
-    pinned to the reference's findCIGAR by the golden vectors — and the sequence assignment is findSeqName's."""
+    pinned to the reference's findCIGAR by the golden vectors — and the sequence assignment is findSeqName's.
+    Batches that take the narrow trace rows (edit distance, k <= 4) run once more on the wide rows (CMB_TRACE_WIDE=1: k_traceback<false>
+    and k_cigar<false>) and must give the same occurrences, CIGARs and sequence assignment."""
     g = world["genome"]
     reads = synth.sample_reads(g, 1500, 150, seed=700 + k, n_frac=0.01)
     # reads across sequence boundaries and with edits at their very ends
@@ -512,6 +514,23 @@ def test_alignments_cigar_and_sequence(world, oracle_built, spec, metric, k):
         reads.append(g[int(s) - 70:int(s) + 80].tobytes())
     reads += _edge_reads(g, 200, max(k, 1), seed=71)
     _check_alignments(world, oracle_built, spec, metric, k, reads, 1000 if k else 300)
+    if metric == "edit" and k in (2, 4):
+        runs = []
+        for wide_rows in (False, True):
+            if wide_rows:
+                monkeypatch.setenv("CMB_TRACE_WIDE", "1")
+            b = ca.Batch(world["dev"], ca.SearchStrategy(spec, metric, "dynamic"), k, reads)
+            b.want_alignments()
+            b.run()
+            occ, offs, _ = b.results()
+            aln, ops = b.alignments()
+            cigars = [ca.cigar_string(ops[int(a["cigar_off"]):int(a["cigar_off"]) + int(a["cigar_len"])]) for a in aln]
+            runs.append((occ.copy(), offs.copy(), aln["seq_id"].copy(), aln["seq_begin"].copy(), aln["spans"].copy(), cigars))
+            b.close()
+        monkeypatch.delenv("CMB_TRACE_WIDE")
+        for narrow, wide in zip(*runs):
+            assert np.array_equal(narrow, wide) if isinstance(narrow, np.ndarray) else narrow == wide
+        assert sum(("I" in c) or ("D" in c) for c in runs[0][5]) > 20
 
 
 def _check_alignments(world, oracle_built, spec, metric, k, reads, min_occ):
@@ -869,6 +888,44 @@ def test_cigars_along_the_right_edge_of_the_band(world, oracle_built):
             cases.append((base[:70] + ins[:n_ins] + base[70:150 - n_ins], 700_000, 700_000 + 150 - n_ins, d))
             cases.append((base[:150 - n_ins] + ins[:n_ins], 700_000, 700_000 + 150 - n_ins, d))
             cases.append((base[:60] + base[60 + n_ins:150 + n_ins], 700_000, 700_000 + 150 + n_ins, d))
+    cmds, got = [], []
+    for read, b, e, d in cases:
+        bb, ee, dd = np.array([b], np.uint32), np.array([e], np.uint32), np.array([d], np.uint32)
+        ops, nops = np.zeros(40, np.uint16), np.zeros(1, np.uint32)
+        rc = L.cmb_cigar_windows(world["dev"].h, read, len(read), bb.ctypes.data_as(C.c_void_p), ee.ctypes.data_as(C.c_void_p),
+                                 dd.ctypes.data_as(C.c_void_p), 1, ops.ctypes.data_as(C.c_void_p), 40, nops.ctypes.data_as(C.c_void_p))
+        assert rc == 0, (read, d, L.cmb_last_error())
+        got.append(ca.cigar_string(ops[:int(nops[0])]))
+        cmds.append(f"findcigar {read.decode()} {g[b:e].tobytes().decode()} {d}")
+    res = subprocess.run([os.path.join(oracle_built, "oracle_driver")], input="\n".join(cmds) + "\n", capture_output=True, text=True,
+                         check=True).stdout.splitlines()
+    assert res == got
+    assert sum("I" in c for c in got) > 50 and sum("D" in c for c in got) > 20
+
+
+@pytest.mark.parametrize("read_len", [150, 33, 16])
+def test_cigars_along_the_right_edge_of_the_band_small_distances(world, oracle_built, read_len):
+    """The four case shapes of test_cigars_along_the_right_edge_of_the_band at the distances of the other two instances
+    cmb_cigar_windows chooses from: up to 4 errors the narrow trace rows (k_cigar<true, .>, two bits per row implied at the band's
+    edges), 5 ... 9 errors the wide rows (k_cigar<false, .>); 1 ... 7 inserted or deleted characters at every distance from their
+    number to 7, and 9 errors for 5 and 7 of them.  Reads of 16 and 33 characters besides 150: a walk that ends inside its first line
+    of 8 or 16 stored rows, and one that crosses exactly one line boundary.  Against the oracle's findCIGAR."""
+    import ctypes as C
+    import os
+    import subprocess
+    g = world["genome"]
+    L = ca.lib()
+    base = g[700_000:700_200].tobytes()
+    ins = b"ACGTACGTACGTACG"
+    n, p_ins, p_del = read_len, (70 * read_len) // 150, (60 * read_len) // 150
+    cases = []
+    for n_ins in range(1, 8):
+        for d in list(range(n_ins, 8)) + ([9] if n_ins in (5, 7) else []):
+            cases.append((ins[:n_ins] + base[:n - n_ins], 700_000, 700_000 + n - n_ins, d))
+            cases.append((base[:p_ins] + ins[:n_ins] + base[p_ins:n - n_ins], 700_000, 700_000 + n - n_ins, d))
+            cases.append((base[:n - n_ins] + ins[:n_ins], 700_000, 700_000 + n - n_ins, d))
+            cases.append((base[:p_del] + base[p_del + n_ins:n + n_ins], 700_000, 700_000 + n + n_ins, d))
+    assert len(cases) == 120 and all(len(c[0]) == n for c in cases)
     cmds, got = [], []
     for read, b, e, d in cases:
         bb, ee, dd = np.array([b], np.uint32), np.array([e], np.uint32), np.array([d], np.uint32)
