@@ -204,6 +204,27 @@ int main() {
                 for (uint32_t j = fc; j <= lc; j++) os << ' ' << M.at(r, j);
                 if (!v) break;
             }
+        } else if (cmd == "matrix128i") { // the 128-bit matrix with a given first column, onlyVerticalGapsLeft included
+            string X, Y;
+            uint32_t maxED, nInit;
+            in >> X >> Y >> maxED >> nInit;
+            vector<uint32_t> init(nInit);
+            for (auto& v : init) in >> v;
+            BitParallelED128 M;
+            Substring sx(X.data(), (len_t)X.size(), 0, (len_t)X.size(), FORWARD);
+            M.setSequence(sx);
+            M.initializeMatrix(maxED, init);
+            os << M.getNumberOfRows() << ' ' << M.getNumberOfCols() << ' ' << M.getSizeOfFinalColumn();
+            for (uint32_t i = 0; i < Y.size() && i + 1 < M.getNumberOfRows(); i++) {
+                bool v = M.computeRow(i + 1, Y[i]);
+                uint32_t r = i + 1;
+                os << ' ' << v << ' ' << M.getFirstColumn(r) << ' ' << M.inFinalColumn(r) << ' ' << M.onlyVerticalGapsLeft(r);
+                uint32_t fc = M.getFirstColumn(r);
+                uint32_t lc = std::min(M.getNumberOfCols() - 1, r + (maxED - init[0]));
+                os << ' ' << (lc - fc + 1);
+                for (uint32_t j = fc; j <= lc; j++) os << ' ' << M.at(r, j);
+                if (!v) break;
+            }
         } else if (cmd == "search") {
             uint32_t n;
             in >> n;
