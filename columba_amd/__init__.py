@@ -58,6 +58,7 @@ EXPORTS = [
     "cmb_move_batch_alignments", "cmb_move_batch_filter_per_strand", "cmb_move_match_best",
     "cmb_move_batch_keep_device_lists", "cmb_move_batch_sam_device", "cmb_move_match_best_device",
     "cmb_pair_sam_device_classes", "cmb_move_pair_sam_device",
+    "cmb_batch_trim_on_device", "cmb_batch_trim_stats",
     "cmb_build_create", "cmb_build_destroy", "cmb_build_sizes_of", "cmb_build_bwt_arrays", "cmb_build_sparse_sa_sizes", "cmb_build_sparse_sa",
     "cmb_build_suffix_array", "cmb_build_index", "cmb_build_timings",
     "cmb_build_move_sizes_of", "cmb_build_move_arrays", "cmb_build_move_index", "cmb_build_pack_lfbp",
@@ -383,6 +384,8 @@ def lib():
         L.cmb_best_results.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp, vp, vp]
         L.cmb_best_destroy.argtypes = [vp]
         L.cmb_batch_want_alignments.argtypes = [vp, i32]
+        L.cmb_batch_trim_on_device.argtypes = [vp, i32]
+        L.cmb_batch_trim_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
         L.cmb_batch_alignments.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
         L.cmb_move_create.argtypes = [C.POINTER(_MoveDesc), i32, C.POINTER(vp)]
         L.cmb_move_destroy.argtypes = [vp]
@@ -1174,6 +1177,18 @@ class Batch:
     def want_alignments(self, on: bool = True):
         _chk(lib().cmb_batch_want_alignments(self.h, int(on)))
 
+    def trim_on_device(self, on: bool = True):
+        """the run trims or drops the occurrences over the end of their sequence itself (cmb_batch_trim_on_device): after it no
+        occurrence has spans == 1 — 2: trimmed in place, 4: dropped, no record — and sam_device() formats no read on the host.  After
+        want_alignments(), before run()."""
+        _chk(lib().cmb_batch_trim_on_device(self.h, int(on)))
+
+    def trim_stats(self) -> Dict[str, int]:
+        """occurrences over the end of their sequence in the last run, and how many of them were trimmed / dropped"""
+        v = [C.c_uint64() for _ in range(3)]
+        _chk(lib().cmb_batch_trim_stats(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("spanning", "trimmed", "dropped"), (int(x.value) for x in v)))
+
     def alignments(self):
         """(cmb_aln records parallel to the occurrences, pool of CIGAR run-length operations)"""
         n = C.c_uint64()
@@ -1215,9 +1230,9 @@ class Batch:
         return t.decode(), host
 
     def timings(self) -> Dict[str, float]:
-        names = (C.c_char_p * 16)()
-        ms = (C.c_float * 16)()
-        n = lib().cmb_batch_timings(self.h, names, ms, 16)
+        names = (C.c_char_p * 32)()
+        ms = (C.c_float * 32)()
+        n = lib().cmb_batch_timings(self.h, names, ms, 32)
         return {names[i].decode(): float(ms[i]) for i in range(n)}
 
     def close(self):

@@ -3,6 +3,7 @@
 #include "host_schemes.hpp"
 #include "host_util.hpp"
 #include "kernels.hpp"
+#include "dev_trim.hpp"
 #include "units.hpp"
 
 #include <chrono>
@@ -624,6 +625,17 @@ struct cmb_batch {
     uint32_t alnStride = 0;
     PinnedBuf<uint16_t> hAlnOps;
     PinnedBuf<AlnRec> hAlnRec;
+    // occurrences over the end of their sequence trimmed on the device (cmb_batch_trim_on_device; dev_trim.hpp): the direct items with their
+    // occurrences, the verification's records, counters and flags — its own, the search counters of the batch stay as the search left
+    // them —, the keys of the records, the survivors with their alignments
+    bool trimOn = false;
+    uint64_t trimStats[3] = {0, 0, 0}; // spanning, trimmed, dropped occurrences of the last run
+    DevBuf<uint4> trimItems, trimPickOcc;
+    DevBuf<uint32_t> trimItemOcc, trimPickRead, trimPickDst, trimCnt; // trimCnt: [0, 8) as Queues::cnt, [8] spanning, [9] items, [10] survivors
+    DevBuf<TextOccRec> trimText;
+    DevBuf<unsigned long long> trimKeysA, trimKeysB, trimCounters;
+    DevBuf<AlnRec> trimAln;
+    DevBuf<uint16_t> trimOps;
     SamBufs samBufs; // (what the SAM and pair drivers keep with this part: cmb_batch_sam_device, cmb_pair_sam_device, sam.hip)
     // cmb_verify_batch_staged: candidates given by the caller take the place of the search's in-text items, and the
     // raw text occurrences (before the filter) are what is handed back
@@ -924,8 +936,9 @@ static uint32_t traceLines(bool narrow, uint32_t rows) { return narrow ? (rows +
 // k_traceback over the nTb tasks of tbq (runTraceback, verifyDirect): the instance of the trace rows and of the text — packed or bytes;
 // the wide rows read either text through one instance
 static void launchTraceback(hipStream_t s, const DevIndex& d, bool narrow, const uint64_t* offs, MFull mf, const uint4* tbq, uint32_t nTb, VPlanes vp,
-                            Queues q, uint32_t rowMin) {
-    auto kTrace = withBools([](auto nrw, auto packed) { return k_traceback<nrw(), nrw() && packed()>; }, narrow, d.text2 != nullptr);
+                            Queues q, uint32_t rowMin, bool byItem = false /* the tasks of k_verify<false, true> (trimSpanning) */) {
+    auto kTrace = withBools([](auto nrw, auto packed, auto item) { return k_traceback<nrw(), nrw() && packed(), item()>; }, narrow,
+                            d.text2 != nullptr, byItem);
     hipLaunchKernelGGL(kTrace, dim3(vp.nSlots / 256), dim3(256), 0, s, d, offs, mf, tbq, nTb, vp, q, rowMin);
 }
 
@@ -1770,6 +1783,131 @@ static int runCigar(RunCtx& c, uint64_t total) {
     return CMB_OK;
 }
 
+// ---- on request (cmb_batch_trim_on_device): the final occurrences that run over the end of their sequence are trimmed to the sequence
+// they belong to, verified on the trimmed window and replaced by the minimal occurrence found there, or marked dropped — findSeqName
+// (indexinterface.cpp:828-897) for the whole sub-batch, dev_trim.hpp.  The verification writes into queues, counters and flags of its own
+static int trimSpanning(RunCtx& c, uint64_t total) {
+    cmb_batch* b = c.b;
+    memset(b->trimStats, 0, sizeof(b->trimStats));
+    if (!b->trimOn) return CMB_OK;
+    if (!b->wantAln) return fail(CMB_ERR_INVALID, "trimming on the device needs the alignments (cmb_batch_want_alignments)");
+    if (!total) return CMB_OK;
+    if (total >= 0xFFFFFFF0ull) return fail(CMB_ERR_UNSUPPORTED, "too many occurrences in one sub-batch");
+    cmb_index* ix = b->ix;
+    hipStream_t s = c.s;
+    const bool verbose = c.verbose;
+    // ---- plan: one item per spanning occurrence with a window (never more than occurrences)
+    c.tm.begin();
+    growTo(b->trimItems, total), growTo(b->trimItemOcc, total);
+    if (b->trimCnt.n < 16) b->trimCnt.alloc(16);
+    if (b->trimCounters.n < CMB_CNT_MAX) b->trimCounters.alloc(CMB_CNT_MAX);
+    HIPCHK(hipMemsetAsync(b->trimCnt.p, 0, 16 * sizeof(uint32_t), s));
+    const uint32_t pBlocks = capBlocks((uint32_t)std::min<uint64_t>((total + 255) / 256, 4096));
+    gridLine(verbose, "k_trim_plan", total, 256ull * pBlocks);
+    const uint32_t nSeqs = ix->seqStarts.size() >= 2 ? (uint32_t)ix->seqStarts.size() - 1u : 0u; // (none given: nothing can be trimmed)
+    hipLaunchKernelGGL(k_trim_plan, dim3(pBlocks), dim3(256), 0, s, b->fout.p, b->foutRead.p, b->alnRec.p, total, ix->seqStartsDev.p, nSeqs, b->k,
+                       b->metric == CMB_METRIC_HAMMING ? 1u : 0u, b->trimItems.p, b->trimItemOcc.p, b->trimCnt.p + 8);
+    HIPCHK(hipGetLastError());
+    uint32_t planned[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(planned, b->trimCnt.p + 8, sizeof(planned), hipMemcpyDeviceToHost, s));
+    c.tm.end("k_trim_plan"); // (waits for the stream)
+    const uint32_t nItems = planned[1];
+    b->trimStats[0] = planned[0], b->trimStats[2] = planned[0];
+    if (verbose) fprintf(stderr, "[trim] %llu occurrences, %u over the end of their sequence, %u windows to verify\n", (unsigned long long)total, planned[0], nItems);
+    if (!nItems) return CMB_OK;
+    if (nItems >= (1u << TRIM_ITEM_BITS)) return fail(CMB_ERR_UNSUPPORTED, "more trimmed windows in one sub-batch than the verification records number");
+    // ---- verification of the windows, as the hooks run it (verifyDirect): k_verify + k_traceback up to 7 errors, k_verify_wide beyond.
+    // The record queue is retried on overflow with the size the kernels asked for
+    c.tm.begin();
+    const bool dp = 3 * b->k + 1 > MXW_LEFT;
+    const uint32_t vSlots = std::min<uint32_t>(((nItems + 255) / 256) * 256, capSlots(256u * 1024u));
+    const uint32_t tSlots = std::min<uint32_t>(((nItems + 255) / 256) * 256, capSlots(512u * 1024u));
+    const uint32_t dSlots = std::min<uint32_t>(((nItems + 255) / 256) * 256, capSlots(envSlots("CMB_VW_SLOTS", 256u * 1536u)));
+    // (a record or two per window; every wavefront may leave a partly used chunk of 256 records, and up to 63 holes in a chunk it retires)
+    const size_t textNeed = c.smallPools ? 64 : (size_t)nItems * 3 + (size_t)((dp ? dSlots : vSlots + tSlots) / 64u + 2u) * 256u;
+    if (b->trimText.n < textNeed) b->trimText.alloc(textNeed);
+    const size_t tbNeed = (size_t)nItems + nItems / 2 + (size_t)(vSlots / 64u + 1u) * 256u;
+    if (!dp && b->tbq.n < tbNeed) b->tbq.alloc(tbNeed);
+    uint32_t hc[8] = {};
+    for (int attempt = 0;; attempt++) {
+        HIPCHK(hipMemsetAsync(b->trimCnt.p, 0, 8 * sizeof(uint32_t), s));
+        HIPCHK(hipMemsetAsync(b->trimCounters.p, 0, CMB_CNT_MAX * sizeof(unsigned long long), s));
+        Queues q{};
+        q.text = b->trimText.p, q.textCap = cap32(b->trimText.n), q.cnt = b->trimCnt.p, q.counters = b->trimCounters.p;
+        if (dp) {
+            const uint32_t slotBytes = (vwRows(b->maxLen) + 1u) * VW_ROW_BYTES;
+            if (b->dpSlab.n < (size_t)slotBytes * dSlots) b->dpSlab.alloc((size_t)slotBytes * dSlots);
+            gridLine(verbose, "k_verify_wide (trim)", nItems, dSlots);
+            auto kWide = k_verify_wide<false, WxTen, true>;
+            if (b->k > MX_MAX_ED) kWide = k_verify_wide<false, WxThirteen, true>;
+            hipLaunchKernelGGL(kWide, dim3(dSlots / 256), dim3(256), 0, s, ix->d, b->offs.p, b->maxLen, b->seq.p, b->G.p, b->gw, b->trimItems.p, nItems,
+                               (const unsigned long long*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, b->dpSlab.p,
+                               slotBytes, q);
+        } else {
+            gridLine(verbose, "k_verify (trim)", nItems, vSlots);
+            hipLaunchKernelGGL((k_verify<false, true>), dim3(vSlots / 256), dim3(256), 0, s, ix->d, b->offs.p, b->maxLen, b->gw, b->seq.p, c.mf, b->trimItems.p,
+                               nItems, b->tbq.p, cap32(b->tbq.n), (unsigned long long*)nullptr, q, 0u);
+            HIPCHK(hipMemcpyAsync(hc, b->trimCnt.p, sizeof(hc), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            if (hc[7] && !(hc[3] & FLAG_CAPACITY)) {
+                const bool narrow = b->k <= TBN_MAX_ED && !getenv("CMB_TRACE_WIDE");
+                const uint32_t slots = std::min<uint32_t>(((hc[7] + 255) / 256) * 256, tSlots);
+                const uint32_t tLines = traceLines(narrow, vRows(b->maxLen));
+                if (b->vW.n < (size_t)tLines * 8 * slots) b->vW.alloc((size_t)tLines * 8 * slots);
+                gridLine(verbose, "k_traceback (trim)", hc[7], slots);
+                launchTraceback(s, ix->d, narrow, b->offs.p, c.mf, b->tbq.p, hc[7], VPlanes{b->vW.p, slots, tLines}, q, 0u, true);
+            }
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(hc, b->trimCnt.p, sizeof(hc), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (!(hc[3] & FLAG_TEXT_OVERFLOW)) break;
+        if (attempt >= 3) return fail(CMB_ERR_INTERNAL, "the record queue of the trimmed windows keeps overflowing");
+        if (verbose) fprintf(stderr, "[retry] trim: %u verification records do not fit %zu\n", hc[2], b->trimText.n);
+        b->trimText.alloc((size_t)hc[2] + hc[2] / 8 + 1024);
+    }
+    c.tm.end("k_trim_verify");
+    if (hc[3] & (FLAG_CAPACITY | FLAG_TRACE_RULE)) return fail(CMB_ERR_INTERNAL, "the verification of a trimmed window left the band");
+    const uint32_t nText = hc[2];
+    if (!nText) return CMB_OK;
+    // ---- pick: the records sorted by (item, begin, distance, width); the first of every item survives
+    c.tm.begin();
+    growTo(b->trimKeysA, nText), growTo(b->trimKeysB, nText);
+    growTo(b->trimPickOcc, nItems), growTo(b->trimPickRead, nItems), growTo(b->trimPickDst, nItems);
+    const uint32_t kBlocks = capBlocks(std::min<uint32_t>((nText + 255) / 256, 4096u));
+    gridLine(verbose, "k_trim_keys", nText, 256ull * kBlocks);
+    hipLaunchKernelGGL(k_trim_keys, dim3(kBlocks), dim3(256), 0, s, b->trimText.p, nText, b->trimItems.p, nItems, b->trimKeysA.p, b->trimCnt.p + 3);
+    uint32_t itemBits = 1; // (nItems < 2^itemBits: the all-ones key of a hole sorts behind every item)
+    while ((1ull << itemBits) <= nItems) itemBits++;
+    sortKeys(b->sortTmp, b->trimKeysA.p, b->trimKeysB.p, nText, 0, TRIM_KEY_ITEM + itemBits, s);
+    gridLine(verbose, "k_trim_pick", nText, 256ull * kBlocks);
+    hipLaunchKernelGGL(k_trim_pick, dim3(kBlocks), dim3(256), 0, s, b->trimKeysB.p, nText, b->trimItems.p, b->trimItemOcc.p, b->trimPickOcc.p,
+                       b->trimPickRead.p, b->trimPickDst.p, b->trimCnt.p + 10);
+    HIPCHK(hipGetLastError());
+    uint32_t nPick = 0;
+    HIPCHK(hipMemcpyAsync(&nPick, b->trimCnt.p + 10, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    c.tm.end("k_trim_pick");
+    if (!nPick) return CMB_OK;
+    // ---- commit: the survivors' CIGARs from the matrix family of the batch's other occurrences (runCigar), then everything into place
+    c.tm.begin();
+    growTo(b->trimAln, nPick), growTo(b->trimOps, (size_t)nPick * b->alnStride);
+    const uint32_t cSlots = capSlots((uint32_t)std::min<uint64_t>(((nPick + 255ull) / 256) * 256, 512u * 1024u));
+    const CigarJob job{b->offs.p, b->G.p, b->gw, b->maxLen, c.mf, b->trimPickOcc.p, b->trimPickRead.p, (uint64_t)nPick, b->trimOps.p, b->alnStride,
+                       b->trimAln.p, b->trimCnt.p + 3, 0u};
+    launchCigar(ix, s, job, b->k > CIGAR_BLOCK_WORDS_MAX_ED, b->k <= TBN_MAX_ED && !getenv("CMB_TRACE_WIDE"), vRows(b->maxLen), cSlots, b->vW, b->dpSlab, verbose);
+    const uint32_t cBlocks = capBlocks(std::min<uint32_t>((nPick + 255) / 256, 4096u));
+    gridLine(verbose, "k_trim_commit", nPick, 256ull * cBlocks);
+    hipLaunchKernelGGL(k_trim_commit, dim3(cBlocks), dim3(256), 0, s, b->trimPickOcc.p, b->trimPickDst.p, b->trimAln.p, b->trimOps.p, nPick, b->alnStride,
+                       b->fout.p, b->alnRec.p, b->alnOps.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(hc, b->trimCnt.p, sizeof(hc), hipMemcpyDeviceToHost, s));
+    c.tm.end("k_trim_commit");
+    if (hc[3] & (FLAG_CAPACITY | FLAG_TRACE_RULE))
+        return fail(CMB_ERR_INTERNAL, "a trimmed occurrence does not fit its key or the CIGAR traceback of one left the band");
+    b->trimStats[1] = nPick, b->trimStats[2] = b->trimStats[0] - nPick;
+    return CMB_OK;
+}
+
 // the final occurrences, their offsets per group and (on request) their alignments in the page-locked buffers of the batch
 static int downloadResults(RunCtx& c, uint64_t total) {
     cmb_batch* b = c.b;
@@ -1872,6 +2010,7 @@ static int batchRunOne(cmb_batch* b) {
         if ((rc = filterFinal(c, total)) != CMB_OK) return rc;
         lap(c, "filter");
         if ((rc = runCigar(c, total)) != CMB_OK) return rc;
+        if ((rc = trimSpanning(c, total)) != CMB_OK) return rc;
         if ((rc = downloadResults(c, total)) != CMB_OK) return rc;
         b->done = true;
         return CMB_OK;
@@ -1911,6 +2050,7 @@ int batchListViews(cmb_batch* b, bool perStrand, std::vector<ListView>& out) {
         v.hAln = c->hAlnRec.data(), v.hOps = c->hAlnOps.data();
         v.cnts = c->cnts, v.times = &c->times;
         v.bufs = &c->samBufs, v.scanTmp = &c->scanTmp;
+        v.trimOnDevice = c->trimOn, v.trimDropped = c->trimStats[2];
         out.push_back(v);
     }
     return CMB_OK;
@@ -2004,6 +2144,26 @@ extern "C" int cmb_batch_want_alignments(cmb_batch* b, int on) {
     b->wantAln = on != 0;
     for (cmb_batch* c : b->subs) c->wantAln = on != 0;
     b->done = false;
+    return CMB_OK;
+}
+// the occurrences over the end of their sequence are trimmed or dropped by the run itself (trimSpanning); FM-index batches in ALL mode
+extern "C" int cmb_batch_trim_on_device(cmb_batch* b, int on) {
+    if (!b) return fail(CMB_ERR_INVALID, "null argument");
+    if (on && !b->wantAln) return fail(CMB_ERR_INVALID, "trimming on the device needs the alignments (cmb_batch_want_alignments)");
+    b->trimOn = on != 0;
+    for (cmb_batch* c : b->subs) c->trimOn = on != 0;
+    b->done = false;
+    return CMB_OK;
+}
+extern "C" int cmb_batch_trim_stats(const cmb_batch* b, uint64_t* spanning, uint64_t* trimmed, uint64_t* dropped) {
+    if (!b) return fail(CMB_ERR_INVALID, "null argument");
+    if (!b->done) return fail(CMB_ERR_INVALID, "batch has not been run");
+    uint64_t t[3] = {b->trimStats[0], b->trimStats[1], b->trimStats[2]};
+    for (const cmb_batch* c : b->subs)
+        for (int i = 0; i < 3; i++) t[i] += c->trimStats[i];
+    if (spanning) *spanning = t[0];
+    if (trimmed) *trimmed = t[1];
+    if (dropped) *dropped = t[2];
     return CMB_OK;
 }
 extern "C" int cmb_batch_alignments(const cmb_batch* b, cmb_aln* out, uint64_t cap, uint16_t* cigar_ops, uint64_t ops_cap,

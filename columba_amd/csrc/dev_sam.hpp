@@ -19,6 +19,7 @@
 //   k_sam_plan_best the same plan for the final lists of BEST mode: primary, minScore and nHits come from the strata bookkeeping,
 //                   the host-formatted reads from a flag per read
 //   k_sam_override  the lengths of the host-formatted reads, before the scan
+//   k_sam_keep_*    the lists of a part without the occurrences its run dropped (cmb_batch_trim_on_device), before the plan
 //   k_sam_write     a wavefront per SAM_READS_PER_WAVE consecutive reads, i.e. per contiguous piece of the text.  The piece is
 //                   cut into windows of SAM_WIN bytes aligned in the TEXT; a window is assembled in LDS and stored with 16-byte
 //                   words, single bytes only in the first and last word of the piece, which the wavefront shares with its
@@ -235,6 +236,38 @@ k_sam_plan_best(SamCtx cx, const uint32_t* __restrict__ best, const uint32_t* __
         plan[r] = pl;
         len[r] = total;
     }
+}
+
+// Lists with occurrences the run dropped (AlnRec::spans == 4: over the end of their sequence and not found again on the trimmed window,
+// cmb_batch_trim_on_device) are copied without those before the plan: no record is written for a dropped occurrence, it is no candidate
+// for the primary and counts in no tag, so the plan and write kernels see the lists findSeqName leaves on the host.
+//   k_sam_keep_flags  a lane per occurrence: 1 if it stays (one more element, 0, closes the scan)
+//   (rocPRIM)         exclusive scan: the new index of every occurrence
+//   k_sam_keep_copy   a lane per occurrence that stays: record, sequence assignment and CIGAR runs to their new index
+//   k_sam_keep_offs   a lane per group boundary: the new first occurrence of every filter group
+// All three are launched under the grid cap (host_grid.hpp) and loop.  The copy costs one more pass over the lists (32 bytes + the CIGAR
+// runs per occurrence) and a second set of list buffers per part; only parts that dropped something pay it.
+__global__ void k_sam_keep_flags(const AlnRec* __restrict__ aln, uint64_t n, uint32_t* __restrict__ keep) {
+    const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= n; i += step) keep[i] = i < n && aln[i].spans != 4u ? 1u : 0u;
+}
+__global__ void k_sam_keep_copy(const uint4* __restrict__ occ, const AlnRec* __restrict__ aln, const uint16_t* __restrict__ ops, uint32_t stride,
+                                uint64_t n, const uint64_t* __restrict__ pos, uint4* __restrict__ occOut, AlnRec* __restrict__ alnOut,
+                                uint16_t* __restrict__ opsOut) {
+    const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
+        if (pos[i + 1] == pos[i]) continue;
+        const uint64_t d = pos[i];
+        const AlnRec a = aln[i];
+        occOut[d] = occ[i];
+        alnOut[d] = a;
+        const uint32_t m = a.nOps < stride ? a.nOps : stride;
+        for (uint32_t j = 0; j < m; j++) opsOut[d * stride + j] = ops[i * stride + j];
+    }
+}
+__global__ void k_sam_keep_offs(const uint64_t* __restrict__ goffs, uint64_t nGroups, const uint64_t* __restrict__ pos, uint64_t* __restrict__ out) {
+    const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g <= nGroups; g += step) out[g] = pos[goffs[g]];
 }
 
 // the reads the host formatted (samOfRead): their lengths, and where their text lies in the side buffer

@@ -271,6 +271,12 @@ struct SamBufs {
     DevBuf<uint32_t> pairMapped;
     DevBuf<uint32_t> clsList, clsCount;
     DevBuf<uint64_t> clsLen, clsOffs;
+    // the lists of a part without its dropped occurrences (AlnRec::spans == 4; dev_sam.hpp: k_sam_keep_*), for the plan and write kernels
+    DevBuf<uint32_t> keepFlag;
+    DevBuf<uint64_t> keepPos, keepOffs;
+    DevBuf<uint4> keepOcc;
+    DevBuf<AlnRec> keepAln;
+    DevBuf<uint16_t> keepOps;
 };
 // The final lists a (sub-)batch of either backend holds in HBM for its whole chunk, as the SAM driver and the strata bookkeeping read
 // them (dev_sam.hpp: SamCtx; dev_best.hpp: k_best_scan / k_best_append), beside the host copies the host-formatted reads are taken
@@ -301,6 +307,10 @@ struct ListView {
     const std::vector<KernelTime>* times = nullptr;
     SamBufs* bufs = nullptr;
     DevBuf<uint8_t>* scanTmp = nullptr; // the part's scratch for the drivers' scans
+    // the run trimmed the occurrences over the end of their sequence itself (cmb_batch_trim_on_device): AlnRec::spans is 0, 2 (trimmed:
+    // an ordinary occurrence) or 4 (dropped: no record is written for it), never 1; how many of the part's occurrences are dropped
+    bool trimOnDevice = false;
+    uint64_t trimDropped = 0;
 };
 
 } // namespace cmb

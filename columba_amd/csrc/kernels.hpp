@@ -1001,7 +1001,9 @@ __device__ __forceinline__ uint32_t mismatch16(const uint4& t, const uint4& r, u
 // KEYS: edit-distance candidates only get their verification key (the batch path; the matrix runs in
 // k_verify_stage) — that instance carries no matrix code and keeps twice the wavefronts in flight for the locate (8 per SIMD: stated, as
 // hipcc's scalar registers alone would otherwise cost it one).
-template <bool KEYS>
+// BYITEM (dev_trim.hpp; no production instance): a traceback task carries the number of its item above its 5 bits of meta, so that
+// k_traceback<.., .., true> can name the ITEM in the records it writes — two items of one read x strand stay apart.
+template <bool KEYS, bool BYITEM = false>
 __global__ void __launch_bounds__(256, KEYS ? 8 : 1)
 k_verify(DevIndex ix, const uint64_t* __restrict__ offs, uint32_t maxLen, uint32_t gw,
          const uint8_t* __restrict__ seq, MFull mf, const uint4* __restrict__ items,
@@ -1113,6 +1115,7 @@ k_verify(DevIndex ix, const uint64_t* __restrict__ offs, uint32_t maxLen, uint32
                 } else if (verifyEdit(ix, offs, mf, rs, start, maxED, minED, fixed, 1u, cStarted, cRows, cText, cAbort,
                                       cCig, tbRec, Ml, direct ? a : 0u)) {
                     nTb = 1;
+                    if constexpr (BYITEM) tbRec.w |= it << 5;
                 }
             }
         }
@@ -1306,7 +1309,7 @@ k_wide_filter(DevIndex ix, const uint64_t* __restrict__ offs, const uint32_t* __
     if (flags) atomicOr(&q.cnt[3], flags);
 }
 
-template <bool KEYED, class WX>
+template <bool KEYED, class WX, bool BYITEM = false /* the records name the item, not its read x strand (dev_trim.hpp) */>
 __global__ void __launch_bounds__(256)
 k_verify_wide(DevIndex ix, const uint64_t* __restrict__ offs, uint32_t maxLen, const uint8_t* __restrict__ seq, const uint32_t* __restrict__ G,
               uint32_t gw, const uint4* __restrict__ items, uint32_t nItems, const unsigned long long* __restrict__ ukeys,
@@ -1447,7 +1450,7 @@ k_verify_wide(DevIndex ix, const uint64_t* __restrict__ offs, uint32_t maxLen, c
                         }
                         cCig += mult;
                         emit = true;
-                        rec = TextOccRec{rs, start + ti, start + r, ED};
+                        rec = TextOccRec{BYITEM ? it : rs, start + ti, start + r, ED};
                     }
                 }
             }
@@ -1712,7 +1715,7 @@ k_verify_stage(DevIndex ix, const uint64_t* __restrict__ offs, MFull mf,
 // recomputed, this time keeping HP and D0, and every centre is traced back to its begin row
 // (bitparallelmatrix.h:531-586).  The traceback reads rows through an 8-row window staged in LDS, so
 // the dependent chain costs one memory round trip per 8 rows instead of three per row.
-template <bool NARROW, bool PACKED>
+template <bool NARROW, bool PACKED, bool BYITEM = false /* the records name the item of the task (k_verify<false, true>) */>
 __global__ void __launch_bounds__(256)
 k_traceback(DevIndex ix, const uint64_t* __restrict__ offs, MFull mf,
             const uint4* __restrict__ tbq, uint32_t nTasks, VPlanes V, Queues q, uint32_t rowMin) {
@@ -1841,7 +1844,7 @@ k_traceback(DevIndex ix, const uint64_t* __restrict__ offs, MFull mf,
             if (have) {
                 const uint32_t ed = bitIdx < 21u ? (uint32_t)((edPack >> (3u * bitIdx)) & 7ull)
                                                  : (uint32_t)((edPackHi >> (3u * (bitIdx - 21u))) & 7ull);
-                rec = TextOccRec{rs, start + ti, start + ri, ed};
+                rec = TextOccRec{BYITEM ? t.w >> 5 : rs, start + ti, start + ri, ed};
             }
             const uint32_t o = chT.alloc(&q.cnt[2], q.textCap, have ? 1u : 0u, 256u, ovT, holeT);
             if (have && o != 0xFFFFFFFFu) q.text[o] = rec;

@@ -145,6 +145,7 @@ static void samOfRead(std::string& text, cmb_index* idx, uint32_t k, int metric,
     std::reverse(revQ.begin(), revQ.end());
     std::vector<SamHit> hits;
     for (BestOcc& o : occs) {
+        if (o.aln.spans == CMB_SPANS_DROPPED) continue; // NOT_FOUND, decided by the run (cmb_batch_trim_on_device)
         if (o.aln.spans == 1 && !trimOccurrence(idx, o.occ.strand ? revC : read, k, metric, o, nullptr)) continue; // NOT_FOUND
         hits.push_back(samHitOf(o, seq_names[o.aln.seq_id]));
     }
@@ -295,6 +296,24 @@ static std::vector<std::string> samNamesOf(const cmb_sam_inputs* in) {
 
 // the list fields of the context of one part
 static SamCtx samCtxOf(const ListView& v) { return SamCtx{v.reads, v.offs, v.goffs, v.groupStride, v.occ, v.aln, v.ops, v.stride}; }
+// ... of a part whose run dropped occurrences (AlnRec::spans == 4): the lists without those, in the part's driver buffers (k_sam_keep_*)
+static void samKeepLists(const ListView& v, SamCtx& cx, hipStream_t s) {
+    SamBufs& B = *v.bufs;
+    const uint64_t nGroups = (uint64_t)v.nReads * v.groupStride;
+    const uint64_t n = v.hOccOffs[nGroups]; // (a view of an FM-index batch: offsets per group)
+    growTo(B.keepFlag, n + 1), growTo(B.keepPos, n + 1), growTo(B.keepOffs, nGroups + 1);
+    growTo(B.keepOcc, n), growTo(B.keepAln, n), growTo(B.keepOps, n * v.stride);
+    const bool verbose = getenv("CMB_VERBOSE") != nullptr;
+    const dim3 perOcc(capBlocks((uint32_t)std::min<uint64_t>((n + 256) / 256, 4096))), perGroup(capBlocks((uint32_t)std::min<uint64_t>((nGroups + 256) / 256, 4096)));
+    gridLine(verbose, "k_sam_keep_copy", n, 256ull * perOcc.x);
+    gridLine(verbose, "k_sam_keep_offs", nGroups + 1, 256ull * perGroup.x);
+    hipLaunchKernelGGL(k_sam_keep_flags, perOcc, dim3(256), 0, s, v.aln, n, B.keepFlag.p);
+    scanExclusive(*v.scanTmp, B.keepFlag.p, B.keepPos.p, (size_t)n + 1, s);
+    hipLaunchKernelGGL(k_sam_keep_copy, perOcc, dim3(256), 0, s, v.occ, v.aln, v.ops, v.stride, n, B.keepPos.p, B.keepOcc.p, B.keepAln.p, B.keepOps.p);
+    hipLaunchKernelGGL(k_sam_keep_offs, perGroup, dim3(256), 0, s, v.goffs, nGroups, B.keepPos.p, B.keepOffs.p);
+    HIPCHK(hipGetLastError());
+    cx.foffs = B.keepOffs.p, cx.occ = B.keepOcc.p, cx.aln = B.keepAln.p, cx.ops = B.keepOps.p;
+}
 static bool samInputsOk(const cmb_sam_inputs* in) {
     return in && in->seqs && in->ids && in->id_offs && (!in->quals || in->qual_offs) && (!in->n_seqs || (in->seq_names && in->seq_name_offs));
 }
@@ -327,6 +346,7 @@ static int samDeviceOver(const std::vector<ListView>& parts, const cmb_sam_input
         if (!n) continue;
         hipStream_t s = c.stream;
         SamCtx& cx = ctx[j] = samCtxOf(c);
+        if (c.trimOnDevice && c.trimDropped) samKeepLists(c, cx, s);
         cx.unmapped = unmapped_records ? 1u : 0u, cx.xa = xa_tag ? 1u : 0u;
         if (int rc = samUpload(c.bufs->sam, in, readBase[j], n, s, cx)) return rc;
         growTo(c.bufs->hostList, (size_t)n + 1);
@@ -458,6 +478,10 @@ int pairArgsCheck(const void* mates1, const void* mates2, const cmb_pair_params*
 int pairDeviceOver(const std::vector<ListView>& subs1, const std::vector<ListView>& subs2, const cmb_pair_params* params, const cmb_sam_inputs* in1,
                    const cmb_sam_inputs* in2, uint32_t classes, const char** text, uint64_t* length, cmb_pair_class_stats* stats) {
     {
+        for (const std::vector<ListView>* subs : {&subs1, &subs2})
+            for (const ListView& v : *subs)
+                if (v.trimOnDevice)
+                    return failWith(CMB_ERR_INVALID, "a batch that trims on the device (cmb_batch_trim_on_device) cannot be paired: the pair drivers trim on the host");
         if (subs1[0].textIndex != subs2[0].textIndex || subs1[0].k != subs2[0].k || subs1[0].metric != subs2[0].metric)
             return failWith(CMB_ERR_INVALID, "the mates' batches differ in index, metric or maximal distance");
         uint64_t total1 = 0, total2 = 0;

@@ -288,7 +288,8 @@ int cmb_batch_results(const cmb_batch* b, cmb_occ* out, uint64_t out_cap, uint64
  *    (length << 2 | op), op 0 = M, 1 = I, 2 = D, from the begin of the alignment, at cigar_ops[cigar_off ...];
  *  - the reference sequence it lies in and its 0-based begin inside it (IndexInterface::findSeqName,
  *    indexinterface.cpp:799-832); spans != 0: the occurrence runs past the end of that sequence (the reference then
- *    trims and re-verifies, or drops it: :833-899 — the C++ adapter does that with cmb_verify_window). */
+ *    trims and re-verifies, or drops it: :833-899 — cmb_trim_occurrence per occurrence, or cmb_batch_trim_on_device for the whole
+ *    batch inside the run, after which spans is 0, CMB_SPANS_TRIMMED or CMB_SPANS_DROPPED). */
 typedef struct {
     uint32_t seq_id, seq_begin;
     uint64_t cigar_off;
@@ -298,6 +299,26 @@ typedef struct {
 int cmb_batch_want_alignments(cmb_batch* b, int on);
 int cmb_batch_alignments(const cmb_batch* b, cmb_aln* out, uint64_t cap, uint16_t* cigar_ops, uint64_t ops_cap,
                          uint64_t* n_ops);
+/* cmb_aln.spans */
+#define CMB_SPANS_OVER_END 1 /* runs over the end of its sequence: to be trimmed or dropped (cmb_trim_occurrence) */
+#define CMB_SPANS_TRIMMED 2  /* found with trimming: the record is the trimmed occurrence's (also in BEST-mode results) */
+#define CMB_SPANS_DROPPED 4  /* findSeqName's NOT_FOUND: no record is written for it */
+/* Opt-in, before cmb_batch_run, after cmb_batch_want_alignments(b, 1) (CMB_ERR_INVALID otherwise; FM-index batches in ALL mode): the
+ * run itself does what IndexInterface::findSeqName (indexinterface.cpp:828-897; cmb_trim_occurrence) does for every occurrence that runs
+ * over the end of its sequence, for the whole sub-batch in a fixed number of launches after the CIGAR step: the window is trimmed to
+ * the sequence (largest stratum = max_distance), verified with a fixed start (inTextVerificationOneString), and the minimal occurrence
+ * under (begin, distance, width) takes the place of the original — cmb_occ (begin, end, distance), cmb_aln (seq_id, seq_begin,
+ * cigar_len, spans = CMB_SPANS_TRIMMED) and CIGAR runs, at the same index of its read's list; the lists are neither sorted again nor
+ * deduplicated, as on the host.  An occurrence that cannot be trimmed or is not found again keeps its record and gets spans =
+ * CMB_SPANS_DROPPED (under Hamming distance: every one).  No occurrence is left with spans == 1, offsets and list lengths stay, and so
+ * do the search counters (cmb_trim_occurrence counts nothing either).  cmb_batch_sam, cmb_batch_sam_device and cmb_sam_chunk write no
+ * record for a dropped occurrence — a read left without any gets its unmapped record — and cmb_batch_sam_device reports 0 host reads;
+ * cmb_pair_sam_device[_classes] refuse such batches (CMB_ERR_INVALID: pairs are trimmed on the host).  A band or capacity flag raised
+ * by the stage fails the run with CMB_ERR_INTERNAL.  cmb_batch_trim_stats: occurrences over the end of their sequence in the last run,
+ * how many of them were trimmed and how many dropped (any pointer may be NULL).  cmb_batch_timings lists the stage as k_trim_plan,
+ * k_trim_verify, k_trim_pick and k_trim_commit. */
+int cmb_batch_trim_on_device(cmb_batch* b, int on);
+int cmb_batch_trim_stats(const cmb_batch* b, uint64_t* spanning, uint64_t* trimmed, uint64_t* dropped);
 /* every strand filtered by itself instead of the two strands of a read together (what one stratum of BEST mode needs:
  * mapRead works on one strand, src/searchstrategy.h:490-523); the result list of a read then holds the forward
  * strand's occurrences followed by the reverse-complement strand's */
@@ -503,7 +524,7 @@ int64_t cmb_batch_sam(const cmb_batch* b, const char* seqs, const char* const* r
  * cmb_batch_sam_device or cmb_batch_destroy on that batch.  *host_reads (may be NULL): how many reads were formatted by the host
  * path instead — exactly those with an occurrence that runs over the end of its sequence (cmb_aln.spans == 1), which
  * IndexInterface::findSeqName (src/indexinterface.cpp:833-899) trims, verifies again and may drop; their bytes are spliced into
- * the text at their place.  Preconditions and error codes as cmb_batch_sam (run, alignments requested).  Composite batches format
+ * the text at their place (none after cmb_batch_trim_on_device: the run has trimmed or dropped them).  Preconditions and error codes as cmb_batch_sam (run, alignments requested).  Composite batches format
  * every sub-batch on its own stream; the text is in read order.  MAPQ (TextOcc::getMapQ, src/indexhelpers.h:378-388) comes from
  * a table on the device: 60, 3, 2, then 1 up to nine and 0 from ten occurrences of minimal distance on.
  * ALL mode, single-end reads, FM-index batches: BEST mode has cmb_best_sam_device (below) on a result of cmb_match_best_device, the

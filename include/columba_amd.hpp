@@ -304,6 +304,12 @@ class SearchStrategy {
                                   qualOffs.data(), nameBuf.data(), nameOffs.data(), (uint32_t)(nameOffs.size() - 1)};
         }
     };
+    // CMB_TRIM_DEVICE=1: the run trims the occurrences over a sequence end itself (cmb_batch_trim_on_device) and the SAM writer formats no
+    // read on the host.  Opt-in: without it nothing changes.  The text is the same bytes either way
+    static int trimOnDevice() {
+        const char* e = getenv("CMB_TRIM_DEVICE");
+        return e && atoi(e) != 0 ? 1 : 0;
+    }
     // the SAM text of a chunk in ALL mode (matchApproxAllMap + generateOutputSingleEnd, searchstrategy.cpp:495-535, :1824-1902)
     std::string samOfChunkAll(const std::string& seqs, const std::vector<uint64_t>& offs, const std::vector<const char*>& ids,
                               const std::vector<const char*>& quals, const std::vector<const char*>& seqNames, length_t maxED,
@@ -315,6 +321,7 @@ class SearchStrategy {
             ~Guard() { cmb_batch_destroy(b); }
         } guard{b};
         check(cmb_batch_want_alignments(b, 1));
+        check(cmb_batch_trim_on_device(b, trimOnDevice()));
         check(cmb_batch_run(b));
         if (const char* e = getenv("CMB_SAM_HOST"); !e || atoi(e) == 0) { // the text is written on the device (cmb_batch_sam_device)
             const bool noQuals = quals.empty() || !quals.data();
@@ -355,6 +362,7 @@ class SearchStrategy {
             ~Guard() { cmb_batch_destroy(b); }
         } guard{b};
         check(cmb_batch_want_alignments(b, 1));
+        check(cmb_batch_trim_on_device(b, trimOnDevice()));
         check(cmb_batch_run(b));
         const SamPacked names(0, seqNames, [](size_t) { return ""; }, true, [](size_t) { return ""; });
         const cmb_sam_inputs in{c.seqs, c.ids, c.idOffs, c.quals, c.qualOffs, names.nameBuf.data(), names.nameOffs.data(), (uint32_t)seqNames.size()};
